@@ -20,6 +20,7 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+DUMP_BYTES = 64 << 20                                # --dump-outputs: the most it writes, over all ranks
 
 
 def parse_args(argv=None):
@@ -39,7 +40,32 @@ def parse_args(argv=None):
     ap.add_argument("--dry-run", action="store_true", help="no GPU work: exercise the launch / rendezvous / max-over-ranks path (gloo)")
     ap.add_argument("--e2e", action="store_true", help="configs[4] instead: end-to-end text -> mel -> wave, 8 utterances sharded over the GPUs (scripts/e2e_bench.py)")
     ap.add_argument("--e2e-frames", type=int, default=1000, help="mel frames per utterance handed to the vocoder with --e2e (1000 = the full 200-step decode)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (the generated samples) as DIR/<name>.npy, float32, "
+                         "at most %d MB in all" % (DUMP_BYTES >> 20))
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs is not None and (args.dry_run or args.e2e):
+        ap.error("--dump-outputs writes the headline path's outputs: not with --dry-run or --e2e")
+    return args
+
+
+def dump_outputs(directory, arrays, budget):
+    """arrays: {name: float32 / float64 ndarray} -> directory/<name>.npy.  An array larger than its share of `budget` is written as a
+    fixed seeded sample: <name>.npy holds the values at the flat (C-order) positions listed, ascending, in <name>_index.npy (float64)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    share = budget // len(arrays)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        if a.nbytes > share:
+            n = share // (a.itemsize + 8)
+            idx = np.sort(np.random.RandomState(0).choice(a.size, n, replace=False))
+            np.save(os.path.join(directory, name + "_index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def free_port():
@@ -271,6 +297,9 @@ def main():
     dt = time.perf_counter() - t0
     _lib.check(m._L.twv_wavenet_status(C.c_void_p(m._status.data_ptr()), None))
     samples = out.cpu().numpy()
+    if args.dump_outputs is not None:
+        # every rank generates its own batch (inputs seeded by rank): rank r > 0 writes samples_rank<r>
+        dump_outputs(args.dump_outputs, {"samples" if rank == 0 else "samples_rank%d" % rank: samples}, DUMP_BYTES // world)
     ok = bool(np.isfinite(samples).all() and np.abs(samples).max() <= 1.0)
     # the checker on THIS rank's timed output (after the timed region): the first 600 samples of every stream, bit for bit
     ncheck = min(T, 600)

@@ -1,19 +1,21 @@
-"""The config / CLI surface held to the reference's own source text -- build-container only (skipped where /root/reference is absent,
-i.e. on the GPU box): hparams.py:6-176,190-192 and the three argparse blocks (generate.py:51-79, synthesizer.py:371-380,
-train_vocoder.py:34-58) are `ast`-parsed -- nothing of the reference is imported or executed, no stand-in modules -- and every name,
-default, type and `required` flag is compared with this repo's.  The only differences allowed are the ones listed (and explained) here.
+"""The config / CLI surface held to the reference's own: hparams.py:6-176,190-192 and the three argparse blocks (generate.py:51-79,
+synthesizer.py:371-380, train_vocoder.py:34-58) of the reference were `ast`-parsed once into tests/golden/reference_surface.json
+(tests/golden/make_reference_surface.py: names and literal values, nothing of the reference imported or executed), and every
+name, default, type and `required` flag is compared with this repo's.  The only differences allowed are the ones listed (and
+explained) here.
 """
 import ast
+import json
 import os
 import sys
 
 import pytest
 
-REF = "/root/reference"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present (build container only)")
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "tacotron-wavenet-vocoder-korean_amd")
+SURFACE = os.path.join(ROOT, "tests", "golden", "reference_surface.json")
+CLI_FILES = ("generate.py", "synthesizer.py", "train_vocoder.py")
+RAISE_NAMES = ("gc_cardinality", "gc_id", "ArgumentTypeError")
 
 
 def _const(node, env=None):
@@ -68,33 +70,20 @@ def _argparse_surface(path):
     return out
 
 
-def _hparams_of_reference():
-    tree = _parse(os.path.join(REF, "hparams.py"))
-    values = None
-    derived = {}
-    for node in ast.walk(tree):
-        if isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr == "HParams":
-            values = {kw.arg: _const(kw.value) for kw in node.keywords}
-    assert values, "tf.contrib.training.HParams(...) call not found in the reference's hparams.py"
-    # hparams.py:190-192: the `else` branch of `if hparams.use_lws` (use_lws is False by default)
-    for node in ast.walk(tree):
-        if isinstance(node, ast.If) and isinstance(node.test, ast.Attribute) and node.test.attr == "use_lws":
-            for st in node.orelse:
-                if isinstance(st, ast.Assign) and isinstance(st.targets[0], ast.Attribute):
-                    derived[st.targets[0].attr] = st.value
-    return values, derived
+def _raises_of(path):
+    """source text of every `raise` statement in the file"""
+    return " ".join(ast.unparse(r) for r in ast.walk(_parse(path)) if isinstance(r, ast.Raise))
 
 
-def _eval_derived(expr, hp):
-    """hparams.py:190-192 right-hand sides: arithmetic over hparams.<name> and int(...)"""
-    if isinstance(expr, ast.Call) and isinstance(expr.func, ast.Name) and expr.func.id == "int":
-        return int(_eval_derived(expr.args[0], hp))
-    if isinstance(expr, ast.BinOp):
-        a, b = _eval_derived(expr.left, hp), _eval_derived(expr.right, hp)
-        return {ast.Add: a + b, ast.Sub: a - b, ast.Mult: a * b, ast.Div: a / b}[type(expr.op)]
-    if isinstance(expr, ast.Attribute):
-        return hp[expr.attr]
-    return _const(expr)
+def _reference():
+    """tests/golden/reference_surface.json; a flag's `type` (a callable, compared by its spelling) back as the ("name", id) pair"""
+    with open(SURFACE, encoding="utf-8") as fh:
+        ref = json.load(fh)
+    for flags in ref["cli"].values():
+        for spec in flags.values():
+            if spec["type"] is not None:
+                spec["type"] = tuple(spec["type"])
+    return ref
 
 
 def test_hparams_names_and_defaults_equal_the_reference():
@@ -102,7 +91,8 @@ def test_hparams_names_and_defaults_equal_the_reference():
     is defined; hparams.py:190-192: the derived values follow the reference's expressions."""
     sys.path.insert(0, ROOT)
     import twvk_amd
-    ref, derived = _hparams_of_reference()
+    surface = _reference()
+    ref, derived = surface["hparams"], surface["derived"]
     mine = twvk_amd.default_hparams().values()
     assert len(ref) >= 90
     missing = sorted(set(ref) - set(mine))
@@ -112,8 +102,7 @@ def test_hparams_names_and_defaults_equal_the_reference():
     wrong = {k: (ref[k], mine[k]) for k in ref if ref[k] != mine[k] or type(ref[k]) is not type(mine[k])}
     assert not wrong, "defaults that differ (reference, repo): %s" % wrong
     assert sorted(derived) == ["frame_length_ms", "frame_shift_ms", "num_freq"]
-    for name, expr in derived.items():
-        want = _eval_derived(expr, ref)
+    for name, want in derived.items():
         assert mine[name] == want and type(mine[name]) is type(want), (name, mine[name], want)
 
 
@@ -136,7 +125,7 @@ DEVIATIONS = {
 
 @pytest.mark.parametrize("fname,n_ref", [("generate.py", 9), ("synthesizer.py", 8), ("train_vocoder.py", 5)])
 def test_cli_flags_equal_the_reference(fname, n_ref):
-    ref = _argparse_surface(os.path.join(REF, fname))
+    ref = _reference()["cli"][fname]
     mine = _argparse_surface(os.path.join(PKG, fname))
     assert len(ref) == n_ref, sorted(ref)
     assert not (set(ref) - set(mine)), "flags of the reference's %s missing here: %s" % (fname, sorted(set(ref) - set(mine)))
@@ -155,9 +144,6 @@ def test_cli_post_parse_rules_of_the_reference():
     """generate.py:72-77: with hparams.gc_channels set, --gc_cardinality and --gc_id are mandatory (ValueError); generate.py:45-49: a
     negative temperature is refused by the argument type.  Both files must raise on the same conditions (compared as source text of the
     `raise` statements; nothing is executed)."""
-    def raises_of(path):
-        with open(path, encoding="utf-8") as fh:
-            return " ".join(ast.unparse(r) for r in ast.walk(ast.parse(fh.read())) if isinstance(r, ast.Raise))
-    for path in (os.path.join(REF, "generate.py"), os.path.join(PKG, "generate.py")):
-        msgs = raises_of(path)
-        assert "gc_cardinality" in msgs and "gc_id" in msgs and "ArgumentTypeError" in msgs, path
+    assert _reference()["generate_py_raises"] == list(RAISE_NAMES)
+    msgs = _raises_of(os.path.join(PKG, "generate.py"))
+    assert all(n in msgs for n in RAISE_NAMES), msgs

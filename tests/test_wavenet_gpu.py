@@ -703,7 +703,7 @@ def test_generate_cli(torch_cuda, tmp_path):
     rate, data = wavfile.read(paths[1])
     assert rate == 24000 and data.dtype == np.int16 and data.shape == (600,) and np.abs(data).max() == 32767
     with pytest.raises(ValueError):
-        main([str(ck), "--mel", str(tmp_path / "mel.npy"), "--random_init"])       # gc_cardinality required (generate.py:72-77)
+        main([str(ck), "--mel", str(tmp_path / "mel.npy"), "--random_init", "--logdir", str(tmp_path / "log")])   # gc_cardinality required (generate.py:72-77)
     # restore defaults for the other tests (hparams is a module singleton, like the reference's)
     d = twvk_amd.default_hparams()
     twvk_amd.hparams.__dict__.update(d.__dict__)
