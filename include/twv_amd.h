@@ -166,7 +166,8 @@ int twv_eval_elementwise64(int fn /*0 exp,1 log,2 exp for x <= 0 (the sampler's 
 /* ======================================= Tacotron text -> mel inference =======================================
  * Replaces the graph synthesizer.py:56 builds with Tacotron.initialize(inputs, input_lengths, num_speakers, speaker_id,
  * rnn_decoder_test_mode=True) (tacotron/tacotron.py:36-235) and runs in one sess.run (synthesizer.py:160); default
- * hparams path: model_type 'deepvoice' with num_speakers > 1, attention_type 'bah_mon_norm'.  Fields = hparams.py:126-165. */
+ * hparams path: model_type 'deepvoice' with num_speakers > 1, attention_type 'bah_mon_norm'; also model_type 'simple', a single speaker,
+ * and the attention types bah_mon, bah_norm, bah, luong, luong_scaled, loc_sen (not gmm, bah_mon_norm_hccho).  Fields = hparams.py:126-165. */
 typedef struct {
     int32_t n_symbols, embedding_size, num_speakers, speaker_embedding_size;
     int32_t enc_prenet_sizes[2], enc_bank_size, enc_bank_channel_size, enc_proj_sizes[2], enc_proj_width, enc_highway_depth, enc_rnn_size;
@@ -176,7 +177,13 @@ typedef struct {
     int32_t num_mels, reduction_factor, num_freq, max_iters;
     int32_t model_simple;   /* 0: hparams.model_type 'deepvoice' (hparams.py:123, the default); 1: 'simple' (tacotron.py:85-90: the speaker embedding is
                              * concatenated inside the decoder, rnn_wrappers.py:425-432 / 455-463); read only when num_speakers > 1 */
+    int32_t attention_type; /* hparams.attention_type (tacotron.py:127-144), TWV_ATT_*: 0 = 'bah_mon_norm' (hparams.py:145, the default).  The
+                             * others run on the split decoder kernel only (decoder_groups 0, 1, 2, 4, 8, 16); 'luong' / 'luong_scaled'
+                             * need attention_state_size == attention_size.  Appended last: callers of the older layout that zero the
+                             * struct get the default. */
 } twv_tacotron_dims;
+enum { TWV_ATT_BAH_MON_NORM = 0, TWV_ATT_BAH_MON = 1, TWV_ATT_BAH_NORM = 2, TWV_ATT_BAH = 3, TWV_ATT_LUONG = 4, TWV_ATT_LUONG_SCALED = 5,
+       TWV_ATT_LOC_SEN = 6 };
 typedef struct twv_tacotron twv_tacotron;
 
 int twv_tacotron_create(const twv_tacotron_dims* dims, twv_tacotron** out);          /* Tacotron(hparams) */
@@ -193,7 +200,7 @@ int twv_tacotron_infer(const twv_tacotron* h, const void* packed, const int32_t*
                        float* alignments, int32_t* status, void* stream);
 
 /* launch geometry (performance only, results are bit-identical): "decoder_groups" = 0 auto (the XCD-resident decoder kernel wherever it
- * fits -- batch <= 32, t_in <= 512, 256 CUs, decoder widths divisible by 4, not model_type 'simple' -- else the split kernel with 16 / 8 / 4
+ * fits -- batch <= 32, t_in <= 512, 256 CUs, decoder widths divisible by 4, not model_type 'simple', attention_type bah_mon_norm -- else the split kernel with 16 / 8 / 4
  * workgroups per utterance), 1/2/4/8/16 = the split kernel with that many workgroups per utterance, 32 = the XCD-resident kernel or an
  * error, -1 = the single-workgroup kernel.  "gemm_group" / "highway_stack" / "gemm_valu": 0 / 0 / 1 select the older launch forms of the
  * dense layers (one launch per problem, one per highway layer, the VALU kernel) for A/B runs and cross-checks. */
@@ -208,7 +215,8 @@ int twv_tacotron_set_profile_buffer(twv_tacotron* h, void* dev_u64);
  * and the launch count since then. */
 int twv_tacotron_gemm_stats(twv_tacotron* h, double* flop, double* ms, int64_t* launches);
 /* the decoder kernel twv_tacotron_infer launches for this (handle, batch, t_in, options) on the current device:
- * "tc_decoder_x_kernel" (XCD-resident), "tc_decoder_g_kernel" (split) or "tc_decoder_kernel" (static string; measurement label, bench.py) */
+ * "tc_decoder_x_kernel" (XCD-resident), "tc_decoder_g_kernel" (split) or "tc_decoder_kernel" (static string; measurement label, bench.py);
+ * "" where infer refuses the options (an attention_type other than bah_mon_norm with decoder_groups -1 or 32) */
 const char* twv_tacotron_decoder_kernel_name(const twv_tacotron* h, int batch, int t_in);
 
 /* ======================================= WaveNet teacher-forced training step =======================================

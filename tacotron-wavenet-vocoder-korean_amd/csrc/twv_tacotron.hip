@@ -1119,7 +1119,16 @@ struct DecGArgs {
     int* stab;                      // [workgroups][16 stages][16]: every workgroup's copy of its stage table (read with scalar loads)
     int split_all;                  // 1: the prenet and the query layer are split over the workgroups too (three more exchanges, 300 KB
                                     //    less weight traffic per workgroup and step); 0: every workgroup computes them whole
+    long long att_g;                // AK_LUONG: offset of the score scale (luong_scaled's attention_g, 1.0 for luong)
+    long long loc_f;                // AK_LOC: offset of the combined location filter [31 taps][A]
 };
+// attention kinds of tc_decoder_g_kernel (a compile-time parameter; which checkpoint tensors feed nv / ab / asb is decided at pack time):
+//   AK_MON   BahdanauMonotonicAttention (bah_mon_norm: nv = g v / |v|, ab = b; bah_mon: nv = v, ab = 0), sigmoid + monotonic recurrence
+//   AK_SOFT  BahdanauAttention (bah_norm: nv = g v / |v|, ab = b; bah: nv = v, ab = 0), masked softmax
+//   AK_LUONG LuongAttention: score = s * (query . keys), no query layer (s = attention_g for luong_scaled, 1 for luong), masked softmax
+//   AK_LOC   LocationSensitiveAttention: the Bahdanau score with location features of the cumulative alignments inside the tanh, softmax
+enum { AK_MON = 0, AK_SOFT = 1, AK_LUONG = 2, AK_LOC = 3 };
+constexpr int kLocTaps = 31;        // location_features_convolution kernel_size (rnn_wrappers.py:662)
 
 struct DecgPos { int m, ch; };
 __device__ __forceinline__ void decg_adv(DecgPos& p, int step, int nchunk)
@@ -1311,7 +1320,7 @@ __device__ __forceinline__ void decg_sload_geo(const int* p, i32x4s& lo, i32x4s&
 {
     asm volatile("s_load_dwordx4 %0, %2, 0x0\n\ts_load_dwordx4 %1, %2, 0x30\n\ts_waitcnt lgkmcnt(0)" : "=&s"(lo), "=&s"(hi) : "s"(p) : "memory");
 }
-template <bool PROF, bool DEF>
+template <bool PROF, bool DEF, int AK = AK_MON>
 __global__ void __launch_bounds__(512) tc_decoder_g_kernel(DecGArgs ga)
 {
     const DecArgs& a = ga.d;
@@ -1380,6 +1389,10 @@ __global__ void __launch_bounds__(512) tc_decoder_g_kernel(DecGArgs ga)
     const int o_cp = o; o += Tp;
     const int o_q = o; o += Tp;
     const int o_scp = o; o += Tp * 8;
+    // AK_LOC: the combined location filter, one skewed A-row per tap, and the cumulative alignments (the mechanism's state) between
+    // 16 zero words on either side -- the 'same' padding of the 31-tap convolution
+    const int o_lf = o; o += AK == AK_LOC ? kLocTaps * (A + A / 8) : 0;
+    const int o_cum = o; o += AK == AK_LOC ? Tp + 32 : 0;
     const bool kv = ga.kv_lds != 0;                       // this workgroup's key rows / memory columns held in LDS
     const int nt_all = T > g ? (T - g + G - 1) >> lg : 0;
     const int o_keys = o; o += kv ? ((T + G - 1) >> lg) * (A + A / 8) : 0;
@@ -1396,6 +1409,15 @@ __global__ void __launch_bounds__(512) tc_decoder_g_kernel(DecGArgs ga)
     for (int i = tid; i < Tp; i += 512) lds[o_al + i] = i == 0 ? 1.0f : 0.0f;
     if (tid < 4) LDSI(o_abort + tid) = 0;
     for (int i = tid; i < A; i += 512) { lds[o_nv + i + ((i >> 5) << 2)] = P[a.w.nv + i]; lds[o_ab + i + ((i >> 5) << 2)] = P[a.w.ab + i]; }
+    if constexpr (AK == AK_LOC) {
+        // every word of both regions is written here, the skew gaps and the pads included (the pads are read as the convolution's zeros)
+        const int rw = A + A / 8;
+        for (int i = tid; i < kLocTaps * rw; i += 512) {
+            const int k = i / rw, r = i - k * rw, c = r % 36, j = (r / 36) * 32 + c;
+            lds[o_lf + i] = c < 32 ? P[ga.loc_f + (long long)k * A + j] : 0.0f;
+        }
+        for (int i = tid; i < Tp + 32; i += 512) lds[o_cum + i] = 0.0f;     // LocationSensitiveAttention initial state: zeros
+    }
     if (kv) {
         // (every 32-word chunk of the attention tables is skewed by 4 words: the score's threads -- one per (t, chunk, chain) -- read
         // addresses 32 and 128 words apart, i.e. all in four of the 32 LDS banks without the skew: the phase was these reads)
@@ -1423,7 +1445,11 @@ __global__ void __launch_bounds__(512) tc_decoder_g_kernel(DecGArgs ga)
         put(a.w.aWg, a.w.abg, DE + ENC + AS, 2 * AS, o_cat2, o_vec, DA_SIGMOID, 1, DP_GATES, DE + ENC, AS, 0);
         put(a.w.aWc, a.w.abc, DE + ENC + AS, AS, o_cat2, o_cand, DA_TANH, 1, DP_CAND, AS, o_ha, -1);
         // attention query layer (redundant: 32 tiles), then score / recurrence / context
-        put(a.w.Wq, -1, AS, A, o_ha, o_pq, DA_NONE, ga.split_all, DP_QUERY, 0, 0, 0);
+        put(a.w.Wq, -1, AS, A, o_ha, o_pq, DA_NONE, AK == AK_LUONG ? 0 : ga.split_all, DP_QUERY, 0, 0, 0);
+        if (AK == AK_LUONG) {                             // LuongAttention has no query layer: a stage without tiles and without exchange
+            const int q = o_tab + (s - 1) * DS_STRIDE;
+            LDSI(q + DS_NTILE) = 0; LDSI(q + DS_GEO) = LDSI(q + DS_GEO) & ((1 << 13) - 1);
+        }
         // rnn_wrappers.py:463 concat(output, attention) -> OutputProjectionWrapper(dec_rnn)
         put(a.w.cW, a.w.cb, AS + ENC + SEc, DR, o_cat, o_y, DA_NONE, 1, DP_PROJ, 0, 0, 0);
         // tacotron.py:167 ResidualWrapper(GRUCell(dec_rnn)): y <- y + GRU(y, h_l)
@@ -1622,6 +1648,10 @@ __global__ void __launch_bounds__(512) tc_decoder_g_kernel(DecGArgs ga)
             } else if (post == DP_QUERY) {
                 // [RECALLED-TF BahdanauMonotonicAttention.__call__] score for the time steps t = g, g+G, ...: one (t, chunk) per thread
                 const int nt = T > g ? (T - g + G - 1) >> lg : 0;
+                if constexpr (AK == AK_LUONG) {           // [RECALLED-TF LuongAttention.__call__] the query is the cell output itself
+                    for (int j = tid; j < A; j += 512) lds[o_pq + j + ((j >> 5) << 2)] = lds[o_ha + j];
+                    __syncthreads();
+                }
                 // one thread per (t, chunk, chain k): s_k = fma chain over j = k, k+4, ..., k+28; the four chains of a chunk sit in
                 // adjacent lanes and are combined as (s0+s1)+(s2+s3)
                 for (int task0 = 0; task0 < nt * nAch * 4; task0 += 512) {
@@ -1633,12 +1663,37 @@ __global__ void __launch_bounds__(512) tc_decoder_g_kernel(DecGArgs ga)
                     const float* kr = keys + (long long)t * A + ch * 32 + k;
                     const int jb = ch * 32 + k, js = jb + 4 * ch, kl = o_keys + tl * A + jb + 4 * (tl * nAch + ch);      // js, kl: skewed
                     TWV_STAMP(54)
-                    if (kv) {
+                    if constexpr (AK == AK_LUONG) {       // [RECALLED-TF _luong_score] query . keys
+                        if (kv) {
 #pragma unroll
-                        for (int j = 0; j < 32; j += 4) sk = fma_(lds[o_nv + js + j], tanh_e((lds[kl + j] + lds[o_pq + js + j]) + lds[o_ab + js + j]), sk);
+                            for (int j = 0; j < 32; j += 4) sk = fma_(lds[o_pq + js + j], lds[kl + j], sk);
+                        } else {
+#pragma unroll
+                            for (int j = 0; j < 32; j += 4) sk = fma_(lds[o_pq + js + j], kr[j], sk);
+                        }
+                    } else if constexpr (AK == AK_LOC) {
+                        // rnn_wrappers.py:697-727: location features of the cumulative alignments, through the combined 31 x A filter
+                        // (loc_j = cdot_k F[k][j] * cum[t + k - 15], one fma chain in tap order), inside the tanh:
+                        // v . tanh(((keys + pq) + loc) + (attention_bias + the convolution bias through location_features_layer))
+                        float win[kLocTaps];
+#pragma unroll
+                        for (int k2 = 0; k2 < kLocTaps; ++k2) win[k2] = lds[o_cum + 1 + t + k2];
+#pragma unroll
+                        for (int j = 0; j < 32; j += 4) {
+                            float lv = 0.f;
+#pragma unroll
+                            for (int k2 = 0; k2 < kLocTaps; ++k2) lv = fma_(lds[o_lf + k2 * (A + A / 8) + js + j], win[k2], lv);
+                            const float kj = kv ? lds[kl + j] : kr[j];
+                            sk = fma_(lds[o_nv + js + j], tanh_e(((kj + lds[o_pq + js + j]) + lv) + lds[o_ab + js + j]), sk);
+                        }
                     } else {
+                        if (kv) {
 #pragma unroll
-                        for (int j = 0; j < 32; j += 4) sk = fma_(lds[o_nv + js + j], tanh_e((kr[j] + lds[o_pq + js + j]) + lds[o_ab + js + j]), sk);
+                            for (int j = 0; j < 32; j += 4) sk = fma_(lds[o_nv + js + j], tanh_e((lds[kl + j] + lds[o_pq + js + j]) + lds[o_ab + js + j]), sk);
+                        } else {
+#pragma unroll
+                            for (int j = 0; j < 32; j += 4) sk = fma_(lds[o_nv + js + j], tanh_e((kr[j] + lds[o_pq + js + j]) + lds[o_ab + js + j]), sk);
+                        }
                     }
                     TWV_STAMP(55)
                     const float s1 = __shfl_xor(sk, 1);
@@ -1656,8 +1711,14 @@ __global__ void __launch_bounds__(512) tc_decoder_g_kernel(DecGArgs ga)
                         const int t = (tl << lg) + g;
                         float sc = 0.0f;
                         for (int ch = 0; ch < nAch; ++ch) { const float c = lds[o_scp + tl * 8 + ch]; sc = ch == 0 ? c : sc + c; }
-                        sc = sc + P[a.w.asb];
-                        const float pv = t < len ? sigmoid_e(sc) : 0.0f;       // _maybe_mask_score(-inf) -> p = 0
+                        float pv;
+                        if constexpr (AK == AK_MON) {
+                            sc = sc + P[a.w.asb];
+                            pv = t < len ? sigmoid_e(sc) : 0.0f;               // _maybe_mask_score(-inf) -> p = 0
+                        } else {                                               // the masked score itself: the softmax follows
+                            if constexpr (AK == AK_LUONG) sc = P[ga.att_g] * sc;   // [RECALLED-TF _luong_score(scale=True)] g * score
+                            pv = t < len ? sc : -INFINITY;
+                        }
                         if (G == 1) lds[o_p + t] = pv; else decg_store(Xb + t, ep, pv, loc);
                     }
                     if (G > 1) decg_gather(Xb, T, ep, o_p, tid, o_abort);
@@ -1673,7 +1734,7 @@ __global__ void __launch_bounds__(512) tc_decoder_g_kernel(DecGArgs ga)
                 // 0, + block 1's own total, ... -- whether the blocks are scanned one after the other or their totals are summed
                 // afterwards.  (One wave walking the blocks: 1.02 us at T = 101, most of it the log / exp / division of block 2 waiting
                 // behind block 1's.)
-                {
+                if constexpr (AK == AK_MON) {
                     const int o_tot = o_scp;                               // block totals (the score chunk values are consumed)
                     float run = 0.0f, run2 = 0.0f;                         // totals in front of this round's first block
                     for (int base0 = 0; base0 < T; base0 += 512) {
@@ -1724,6 +1785,30 @@ __global__ void __launch_bounds__(512) tc_decoder_g_kernel(DecGArgs ga)
                             if (a.align && g == 0) a.align[((long long)n * T + t) * a.iters + it] = al;      // tacotron.py:223
                         }
                         __syncthreads();                                   // (the second totals have been read)
+                    }
+                    for (int t = T + tid; t < Tp; t += 512) lds[o_al + t] = 0.0f;
+                } else {
+                    // [RECALLED-TF _maybe_mask_score(-inf) + nn_ops.softmax] over the valid positions, wave 0 (redundant in every
+                    // workgroup): max, exp(s - max), sum, quotient.  Each lane sums its positions t = lane, lane + 64, ... in order, the
+                    // 64 lane sums meet in an xor butterfly (every lane ends with the same bits).  Past the length the alignments are 0.
+                    if (wave == 0) {
+                        const int lim = len < T ? len : T;
+                        float mx = -INFINITY;
+                        for (int t = lane; t < lim; t += 64) mx = fmaxf(mx, lds[o_p + t]);
+#pragma unroll
+                        for (int d = 32; d >= 1; d >>= 1) mx = fmaxf(mx, __shfl_xor(mx, d));
+                        float sm = 0.0f;
+                        for (int t = lane; t < lim; t += 64) { const float e = exp_e(lds[o_p + t] - mx); lds[o_cp + t] = e; sm = sm + e; }
+#pragma unroll
+                        for (int d = 32; d >= 1; d >>= 1) sm = sm + __shfl_xor(sm, d);
+                        for (int t = lane; t < T; t += 64) {
+                            const float al = t < lim ? div_(lds[o_cp + t], sm) : 0.0f;
+                            lds[o_al + t] = al;
+                            // LocationSensitiveAttention(cumulate_weights=True): next state = alignments + state; the alignments
+                            // themselves are what the wrapper emits and attends with (rnn_wrappers.py:718-725)
+                            if constexpr (AK == AK_LOC) lds[o_cum + 16 + t] = al + lds[o_cum + 16 + t];
+                            if (a.align && g == 0) a.align[((long long)n * T + t) * a.iters + it] = al;      // tacotron.py:223
+                        }
                     }
                     for (int t = T + tid; t < Tp; t += 512) lds[o_al + t] = 0.0f;
                 }
@@ -2450,6 +2535,9 @@ struct twv_tacotron {
     TMat rWg[4], rWc[4]; TVec rbg[4], rbc[4];
     TMat oW; TVec ob;
     TMat lW; TVec lb;
+    TMat lcK, lcL; TVec lcb;        // loc_sen: location_features_convolution kernel (31 x 32) / bias, location_features_layer (32 x A)
+    TVec zero, one, lf, lab;        // derived for the other attention types: zeros (ab / asb of the unnormalised ones), 1.0 (luong's
+                                    // scale), the combined location filter [31][A] and loc_sen's bias (attention_bias + conv bias . L)
     struct Item { int kind; long long src, dst; int K, N, r0, r1; };   // kind 0 = tiles of rows [r0,r1) of a (K,N) matrix, 1 = raw copy
     std::vector<Item> items;
 };
@@ -2510,8 +2598,17 @@ static void taco_build(twv_tacotron* h)
     }
     h->pW1 = mat(E, P0); h->pb1 = vec(P0); h->pW2 = mat(P0, P1); h->pb2 = vec(P1);
     cbhg(h->enc, P1, d.enc_bank_size, d.enc_bank_channel_size, d.enc_proj_sizes, d.enc_proj_width, d.enc_highway_depth, RN);
-    h->Wm = mat(ENC, A); h->Wq = mat(AS, A);
-    h->av = vec(A); h->ag = vec(1); h->ab = vec(A); h->asb = vec(1);
+    h->Wm = mat(ENC, A);
+    // the attention mechanism's own tensors (tacotron.tacotron_specs; tacotron.py:127-144)
+    const int at = d.attention_type;
+    if (at == TWV_ATT_BAH_MON_NORM) { h->Wq = mat(AS, A); h->av = vec(A); h->ag = vec(1); h->ab = vec(A); h->asb = vec(1); }
+    else if (at == TWV_ATT_BAH_MON) { h->Wq = mat(AS, A); h->av = vec(A); h->asb = vec(1); }
+    else if (at == TWV_ATT_BAH_NORM) { h->Wq = mat(AS, A); h->av = vec(A); h->ag = vec(1); h->ab = vec(A); }
+    else if (at == TWV_ATT_BAH) { h->Wq = mat(AS, A); h->av = vec(A); }
+    else if (at == TWV_ATT_LUONG_SCALED) { h->ag = vec(1); }
+    else if (at == TWV_ATT_LOC_SEN) {
+        h->Wq = mat(AS, A); h->lcK = raw(kLocTaps, 32); h->lcb = vec(32); h->lcL = raw(32, A); h->av = vec(A); h->ab = vec(A);
+    }
     h->dpW1 = mat(M, d.dec_prenet_sizes[0]); h->dpb1 = vec(d.dec_prenet_sizes[0]);
     h->dpW2 = mat(d.dec_prenet_sizes[0], d.dec_prenet_sizes[1]); h->dpb2 = vec(d.dec_prenet_sizes[1]);
     // model_type 'simple' (tacotron.py:85-90): only the speaker embedding, concatenated inside the decoder (rnn_wrappers.py:425-432, 455-463)
@@ -2527,6 +2624,11 @@ static void taco_build(twv_tacotron* h)
     h->blob_floats = src;
     h->nv = TVec{dst, A}; dst += (A + 3) / 4 * 4;      // derived: normed_v
     h->xt_off = dst; dst += 32LL * 8 * kXSlots * kTile;
+    if (at != TWV_ATT_BAH_MON_NORM) {                   // (the default type's packed layout is left as it was)
+        h->zero = TVec{dst, A}; dst += (A + 3) / 4 * 4;
+        h->one = TVec{dst, 1}; dst += 4;
+        if (at == TWV_ATT_LOC_SEN) { h->lf = TVec{dst, kLocTaps * A}; dst += ((long long)kLocTaps * A + 3) / 4 * 4; h->lab = TVec{dst, A}; dst += (A + 3) / 4 * 4; }
+    }
     h->packed_floats = dst;
 }
 
@@ -2551,6 +2653,10 @@ extern "C" int twv_tacotron_create(const twv_tacotron_dims* dims, twv_tacotron**
     if (d.enc_bank_size > 16 || d.post_bank_size > 16 || d.enc_highway_depth > 8 || d.post_highway_depth > 8) return twv_fail(TWV_E_UNSUPPORTED, "bank / highway depth out of range");
     if (d.num_speakers < 1) return twv_fail(TWV_E_INVALID, "num_speakers must be >= 1");
     if (d.num_speakers > 1 && d.speaker_embedding_size < 1) return twv_fail(TWV_E_INVALID, "speaker_embedding_size must be >= 1");
+    if (d.attention_type < TWV_ATT_BAH_MON_NORM || d.attention_type > TWV_ATT_LOC_SEN)
+        return twv_fail(TWV_E_INVALID, "attention_type must be 0 .. 6 (bah_mon_norm, bah_mon, bah_norm, bah, luong, luong_scaled, loc_sen)");
+    if ((d.attention_type == TWV_ATT_LUONG || d.attention_type == TWV_ATT_LUONG_SCALED) && d.attention_state_size != d.attention_size)
+        return twv_fail(TWV_E_INVALID, "luong attention scores the unprojected query against the keys: attention_state_size must equal attention_size");
     if (d.num_speakers > 1 && d.model_simple && d.speaker_embedding_size != 1) {
         // the embedding rides at the tail of the buffer the residual GRU inputs [y | h] share with the first projection's input
         if (2 * d.dec_rnn_size > d.attention_state_size + 2 * d.enc_rnn_size || d.speaker_embedding_size > 64)
@@ -2621,6 +2727,25 @@ __global__ void tc_normed_v_kernel(float* P, long long av, long long ag, long lo
     }
 }
 
+// the derived tensors of the other attention types: 1.0 (luong's unit scale); loc_sen: location_features_layer applied to the
+// convolution at pack time -- F[k][j] = cdot_c K[k][c] L[c][j] (one fma chain in c order) and lab[j] = attention_bias[j] + cdot_c
+// bias[c] L[c][j] -- so the decoder runs ONE 31-tap filter per attention column instead of 31 x 32 taps then a 32 x A layer
+__global__ void tc_attention_derive_kernel(float* P, int loc, long long one, long long cK, long long cb, long long cL, long long ab,
+                                           long long lf, long long lab, int A)
+{
+    const int j = blockIdx.x * 64 + threadIdx.x;
+    if (j == 0) P[one] = 1.0f;
+    if (!loc || j >= A) return;
+    for (int k = 0; k < kLocTaps; ++k) {
+        float f = 0.0f;
+        for (int c = 0; c < 32; ++c) f = fma_(P[cK + k * 32 + c], P[cL + (long long)c * A + j], f);
+        P[lf + (long long)k * A + j] = f;
+    }
+    float b = 0.0f;
+    for (int c = 0; c < 32; ++c) b = fma_(P[cb + c], P[cL + (long long)c * A + j], b);
+    P[lab + j] = P[ab + j] + b;
+}
+
 // the decoder step as a stage table (same order and operands as tc_decoder_g_kernel's): used by the XCD-local kernel and its pack
 static void taco_xstages(const twv_tacotron* h, XStageTab& t)
 {
@@ -2680,7 +2805,12 @@ extern "C" int twv_tacotron_pack(const twv_tacotron* h, const float* blob, void*
             twv_launch_pack_tiles(dst, blob, p, st);
         }
     }
-    hipLaunchKernelGGL(tc_normed_v_kernel, dim3(1), dim3(64), 0, st, dst, h->av.off, h->ag.off, h->nv.off, h->d.attention_size);
+    const int at = h->d.attention_type;
+    if (at == TWV_ATT_BAH_MON_NORM || at == TWV_ATT_BAH_NORM)
+        hipLaunchKernelGGL(tc_normed_v_kernel, dim3(1), dim3(64), 0, st, dst, h->av.off, h->ag.off, h->nv.off, h->d.attention_size);
+    if (at != TWV_ATT_BAH_MON_NORM)
+        hipLaunchKernelGGL(tc_attention_derive_kernel, dim3((h->d.attention_size + 63) / 64), dim3(64), 0, st, dst, at == TWV_ATT_LOC_SEN ? 1 : 0,
+                           h->one.off, h->lcK.off, h->lcb.off, h->lcL.off, h->ab.off, h->lf.off, h->lab.off, h->d.attention_size);
     {   // row tiles of the XCD-local decoder kernel, from the standard tiles just written
         XStageTab xt;
         taco_xstages(h, xt);
@@ -2960,6 +3090,15 @@ extern "C" int twv_tacotron_infer(const twv_tacotron* h, const void* packed, con
     da.w.dp1 = h->dpW1.off; da.w.dp1b = h->dpb1.off; da.w.dp2 = h->dpW2.off; da.w.dp2b = h->dpb2.off;
     da.w.aWg = h->aWgm.off; da.w.abg = h->abg.off; da.w.aWc = h->aWcm.off; da.w.abc = h->abc.off;
     da.w.Wq = h->Wq.off; da.w.nv = h->nv.off; da.w.ab = h->ab.off; da.w.asb = h->asb.off; da.w.cW = h->cW.off; da.w.cb = h->cb.off;
+    // the other attention types feed the same score slots (tc_decoder_g_kernel's AK_*): unnormalised Bahdanau scores read v itself and a
+    // zero bias, loc_sen its attention_variable and the combined bias; the softmax types never read the score bias
+    const int at = d.attention_type;
+    if (at == TWV_ATT_BAH_MON || at == TWV_ATT_BAH || at == TWV_ATT_LOC_SEN) da.w.nv = h->av.off;
+    if (at == TWV_ATT_BAH_MON || at == TWV_ATT_BAH) da.w.ab = h->zero.off;
+    if (at == TWV_ATT_LOC_SEN) da.w.ab = h->lab.off;
+    if (at != TWV_ATT_BAH_MON_NORM && at != TWV_ATT_BAH_MON) da.w.asb = h->zero.off;
+    const int ak = (at == TWV_ATT_BAH_MON_NORM || at == TWV_ATT_BAH_MON) ? AK_MON : (at == TWV_ATT_BAH_NORM || at == TWV_ATT_BAH) ? AK_SOFT
+                 : (at == TWV_ATT_LOC_SEN) ? AK_LOC : AK_LUONG;
     for (int i = 0; i < d.dec_layer_num; ++i) { da.w.rWg[i] = h->rWg[i].off; da.w.rbg[i] = h->rbg[i].off; da.w.rWc[i] = h->rWc[i].off; da.w.rbc[i] = h->rbc[i].off; }
     da.w.oW = h->oW.off; da.w.ob = h->ob.off;
     da.keys = keys; da.memo = memo; da.init = dinit; da.lengths = lengths;
@@ -2997,10 +3136,12 @@ extern "C" int twv_tacotron_infer(const twv_tacotron* h, const void* packed, con
         const bool xok = taco_xdec_ok(h, xt) && cus >= 256 && upx <= kXU && T <= 512 && xfl * 4 <= 160 * 1024 && !simple;
         if (simple && (h->dec_groups == -1 || h->dec_groups == 32))
             return twv_fail(TWV_E_UNSUPPORTED, "model_type 'simple' runs on the split decoder kernel only (decoder_groups 0, 1, 2, 4, 8 or 16)");
+        if (at != TWV_ATT_BAH_MON_NORM && (h->dec_groups == -1 || h->dec_groups == 32))
+            return twv_fail(TWV_E_UNSUPPORTED, "attention_type other than bah_mon_norm runs on the split decoder kernel only (decoder_groups 0, 1, 2, 4, 8 or 16)");
         // Which kernel (round 6, scripts/tacotron_bench.py --batch 8 / 16 / 24 / 32): the XCD-resident kernel is the default wherever it fits
         // (up to four utterances per XCD = batch 32); pass times against the split kernel are in profiles/r06_tacotron_decoder_ab.txt.
         // (Until its scratch spills and per-utterance branch chains were removed it tied the split kernel at four utterances per XCD.)
-        if (xok && (h->dec_groups == 32 || h->dec_groups == 0)) {
+        if (xok && at == TWV_ATT_BAH_MON_NORM && (h->dec_groups == 32 || h->dec_groups == 0)) {
             // XCD-local kernel: every XCD's 32 workgroups hold the decoder in registers and serve that XCD's utterances
             DecXArgs xa;
             xa.d = da; xa.tab = xt; xa.upx = upx; xa.xt_off = h->xt_off; xa.stab = reinterpret_cast<int*>(stabf);
@@ -3039,11 +3180,14 @@ extern "C" int twv_tacotron_infer(const twv_tacotron* h, const void* packed, con
             const int wgs = ga.local ? wgs_local : N * G;
             ga.split_all = h->dec_split_all < 0 ? ga.local : h->dec_split_all;
             ga.stab = reinterpret_cast<int*>(stabf);
+            ga.att_g = at == TWV_ATT_LUONG_SCALED ? h->ag.off : h->one.off;
+            ga.loc_f = h->lf.off;
             if (wgs > 512) return twv_fail(TWV_E_UNSUPPORTED, "more than 512 decoder workgroups");
             HIPCHK(hipMemsetAsync(exch, 0, (size_t)N * 2 * kExN * 8 + 64, st));
             ga.tickets = reinterpret_cast<int*>(exch + (long long)N * 2 * kExN * 2);
             long long fl = 1024 * 2 + (da.D1 + da.SEc + ENC + AS + 63) / 64 * 64 + 512 * 2 + AS + d.dec_layer_num * DR + (M + 31) / 32 * 32 + ENC + DR + (M * R + 63) / 64 * 64 + Tp * 4 + A +
                            Tp * 8 + 4 + 3 + 16 * 16 + 2 * A + 3 * (A / 8) + da.nbias + pmax;
+            if (ak == AK_LOC) fl += kLocTaps * (A + A / 8) + Tp + 32;        // the combined location filter, the cumulative alignments
             const long long kvf = (long long)((T + G - 1) / G) * (A + A / 8) + (long long)T * (ENC / G + 8);
             ga.kv_lds = (fl + kvf) * 4 <= 160 * 1024 ? 1 : 0;
             if (ga.kv_lds) fl += kvf;
@@ -3053,7 +3197,11 @@ extern "C" int twv_tacotron_infer(const twv_tacotron* h, const void* packed, con
             // the hparams-default sizes have an instantiation of their own (sizes folded: half the scalar-register spills); the
             // instrumented build (phase stamps) likewise
             const bool def = !simple && G == 8 && M == 80 && R == 5 && A == 256 && AS == 256 && ENC == 256 && DR == 256 && da.D0 == 256 && da.D1 == 128 && d.dec_layer_num == 2;
-            const void* kfn = da.prof ? (def ? (const void*)tc_decoder_g_kernel<true, true> : (const void*)tc_decoder_g_kernel<true, false>)
+            // (the other attention kinds have no instrumented build: a profile buffer is ignored there)
+            const void* kfn = ak == AK_SOFT ? (def ? (const void*)tc_decoder_g_kernel<false, true, AK_SOFT> : (const void*)tc_decoder_g_kernel<false, false, AK_SOFT>)
+                            : ak == AK_LUONG ? (def ? (const void*)tc_decoder_g_kernel<false, true, AK_LUONG> : (const void*)tc_decoder_g_kernel<false, false, AK_LUONG>)
+                            : ak == AK_LOC ? (def ? (const void*)tc_decoder_g_kernel<false, true, AK_LOC> : (const void*)tc_decoder_g_kernel<false, false, AK_LOC>)
+                            : da.prof ? (def ? (const void*)tc_decoder_g_kernel<true, true> : (const void*)tc_decoder_g_kernel<true, false>)
                                       : (def ? (const void*)tc_decoder_g_kernel<false, true> : (const void*)tc_decoder_g_kernel<false, false>);
             HIPCHK(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
             void* kargs[] = {&ga};
@@ -3076,6 +3224,8 @@ extern "C" const char* twv_tacotron_decoder_kernel_name(const twv_tacotron* h, i
 {
     if (!h || batch < 1 || t_in < 1) return "";
     const twv_tacotron_dims& d = h->d;
+    if (d.attention_type != TWV_ATT_BAH_MON_NORM)           // the split kernel only; -1 and 32 are refused
+        return h->dec_groups == -1 || h->dec_groups == 32 ? "" : "tc_decoder_g_kernel";
     if (h->dec_groups == -1) return "tc_decoder_kernel";
     int cus = 0, devid = 0;
     if (hipGetDevice(&devid) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, devid) != hipSuccess) return "";

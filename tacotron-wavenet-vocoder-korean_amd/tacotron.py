@@ -1,8 +1,8 @@
 """Host-side mirror of the reference's Tacotron inference surface (tacotron/tacotron.py `Tacotron.initialize(...,
 rnn_decoder_test_mode=True)` and synthesizer.py `Synthesizer.load / synthesize`) over the HIP C-ABI.
 
-Default hparams path (model_type 'deepvoice' with num_speakers > 1, or a single speaker; attention_type 'bah_mon_norm'); tokens in, mel /
-linear / alignments out.  Text -> token ids (text/*, jamo) and Griffin-Lim are host DSP outside this path."""
+Default hparams path (model_type 'deepvoice' with num_speakers > 1, or a single speaker; attention_type 'bah_mon_norm'), model_type
+'simple', and the attention types of ATTENTION_TYPES; tokens in, mel / linear / alignments out.  Text -> token ids (text/*, jamo) and Griffin-Lim are host DSP outside this path."""
 import ctypes as C
 import os
 
@@ -12,6 +12,10 @@ import torch
 from . import _lib
 
 BN_EPS = np.float32(1e-3)      # tf.layers.batch_normalization default epsilon
+# hparams.attention_type -> twv_tacotron_dims.attention_type (include/twv_amd.h TWV_ATT_*); tacotron.py:127-144.  'gmm' and
+# 'bah_mon_norm_hccho' are not built.
+ATTENTION_TYPES = {'bah_mon_norm': 0, 'bah_mon': 1, 'bah_norm': 2, 'bah': 3, 'luong': 4, 'luong_scaled': 5, 'loc_sen': 6}
+LOC_FILTERS, LOC_KERNEL = 32, 31      # rnn_wrappers.py:662-664 location_features_convolution (filters=32, kernel_size=31)
 
 
 def _cbhg_specs(scope, cin, bank, bch, proj, pw, depth, rnn):
@@ -34,6 +38,37 @@ def _cbhg_specs(scope, cin, bank, bch, proj, pw, depth, rnn):
         s += [(p + "gates/kernel", (2 * rnn, 2 * rnn)), (p + "gates/bias", (2 * rnn,)),
               (p + "candidate/kernel", (2 * rnn, rnn)), (p + "candidate/bias", (rnn,))]
     return s
+
+
+def _attention_specs(hp):
+    """the attention mechanism's tensors (tacotron.py:127-144) after memory_layer/kernel; TF scalars are (1,) here as everywhere"""
+    at = getattr(hp, "attention_type", "bah_mon_norm")
+    A, AS = hp.attention_size, hp.attention_state_size
+    if at == "bah_mon_norm":
+        p = "decoder/bahdanau_monotonic_attention/"
+        return [(p + "query_layer/kernel", (AS, A)), (p + "attention_v", (A,)), (p + "attention_g", (1,)), (p + "attention_b", (A,)),
+                (p + "attention_score_bias", (1,))]
+    if at == "bah_mon":            # BahdanauMonotonicAttention(normalize=False): no g, no b; the score bias stays
+        p = "decoder/bahdanau_monotonic_attention/"
+        return [(p + "query_layer/kernel", (AS, A)), (p + "attention_v", (A,)), (p + "attention_score_bias", (1,))]
+    if at == "bah_norm":           # BahdanauAttention(normalize=True)
+        p = "decoder/bahdanau_attention/"
+        return [(p + "query_layer/kernel", (AS, A)), (p + "attention_v", (A,)), (p + "attention_g", (1,)), (p + "attention_b", (A,))]
+    if at == "bah":
+        p = "decoder/bahdanau_attention/"
+        return [(p + "query_layer/kernel", (AS, A)), (p + "attention_v", (A,))]
+    if at in ("luong", "luong_scaled"):
+        # LuongAttention has no query layer: the (attention_state_size) cell output is dotted with the (attention_size) keys -- a
+        # graph with other sizes fails in TF's matmul
+        if AS != A:
+            raise ValueError("attention_type %r needs attention_state_size == attention_size (got %d and %d)" % (at, AS, A))
+        return [("decoder/luong_attention/attention_g", (1,))] if at == "luong_scaled" else []
+    if at == "loc_sen":            # rnn_wrappers.py:647-727 LocationSensitiveAttention
+        p = "decoder/Location_Sensitive_Attention/"
+        return [(p + "query_layer/kernel", (AS, A)), (p + "location_features_convolution/kernel", (LOC_KERNEL, 1, LOC_FILTERS)),
+                (p + "location_features_convolution/bias", (LOC_FILTERS,)), (p + "location_features_layer/kernel", (LOC_FILTERS, A)),
+                (p + "attention_variable", (A,)), (p + "attention_bias", (A,))]
+    raise NotImplementedError("attention_type %r is not built; built: %s" % (at, ", ".join(ATTENTION_TYPES)))
 
 
 def tacotron_specs(hp, num_speakers, n_symbols=80):
@@ -68,9 +103,7 @@ def tacotron_specs(hp, num_speakers, n_symbols=80):
     s += [("prenet/dense_1/kernel", (E, P0)), ("prenet/dense_1/bias", (P0,)), ("prenet/dense_2/kernel", (P0, P1)), ("prenet/dense_2/bias", (P1,))]
     s += _cbhg_specs("encoder_cbhg", P1, hp.enc_bank_size, hp.enc_bank_channel_size, tuple(hp.enc_proj_sizes), hp.enc_proj_width,
                      hp.enc_highway_depth, RN)
-    s += [("memory_layer/kernel", (ENC, A)), ("decoder/bahdanau_monotonic_attention/query_layer/kernel", (AS, A)),
-          ("decoder/bahdanau_monotonic_attention/attention_v", (A,)), ("decoder/bahdanau_monotonic_attention/attention_g", (1,)),
-          ("decoder/bahdanau_monotonic_attention/attention_b", (A,)), ("decoder/bahdanau_monotonic_attention/attention_score_bias", (1,))]
+    s += [("memory_layer/kernel", (ENC, A))] + _attention_specs(hp)
     D0, D1 = hp.dec_prenet_sizes
     s += [("decoder/decoder_prenet/dense_1/kernel", (M, D0)), ("decoder/decoder_prenet/dense_1/bias", (D0,)),
           ("decoder/decoder_prenet/dense_2/kernel", (D0, D1)), ("decoder/decoder_prenet/dense_2/bias", (D1,))]
@@ -125,8 +158,10 @@ class Tacotron(object):
 
     def __init__(self, hparams, num_speakers=2, n_symbols=80, device="cuda:0"):
         hp = self._hparams = hparams
-        if hp.attention_type != 'bah_mon_norm' or num_speakers < 1:
-            raise NotImplementedError("built: attention_type 'bah_mon_norm' (hparams.py:145, the default)")
+        if hp.attention_type not in ATTENTION_TYPES:
+            raise NotImplementedError("attention_type %r is not built; built: %s" % (hp.attention_type, ", ".join(ATTENTION_TYPES)))
+        if num_speakers < 1:
+            raise NotImplementedError("num_speakers must be >= 1")
         if num_speakers > 1 and hp.model_type not in ('deepvoice', 'simple'):
             raise Exception(" [!] Unkown multi-speaker model type: {}".format(hp.model_type))       # tacotron.py:92
         self.num_speakers = num_speakers
@@ -146,6 +181,7 @@ class Tacotron(object):
         d.post_proj_width, d.post_highway_depth, d.post_rnn_size = hp.post_proj_width, hp.post_highway_depth, hp.post_rnn_size
         d.num_mels, d.reduction_factor, d.num_freq, d.max_iters = hp.num_mels, hp.reduction_factor, hp.num_freq, hp.max_iters
         d.model_simple = 1 if (num_speakers > 1 and hp.model_type == 'simple') else 0
+        d.attention_type = ATTENTION_TYPES[hp.attention_type]
         self._dims = d
         self._L = _lib.lib()
         h = C.c_void_p()
