@@ -27,8 +27,8 @@ enum { TWV_OK = 0, TWV_E_INVALID = 1, TWV_E_UNSUPPORTED = 2, TWV_E_HIP = 3, TWV_
 typedef struct {
     int32_t n_layers;
     int32_t dilations[TWV_MAX_LAYERS];   /* hparams.dilations */
-    int32_t residual_channels;           /* R, must be 32 */
-    int32_t dilation_channels;           /* D, must be 32 */
+    int32_t residual_channels;           /* R: 32, 64 or 128 */
+    int32_t dilation_channels;           /* D: 32, 64 or 128 (independent of R) */
     int32_t skip_channels;               /* S, multiple of 64, <= 1024 */
     int32_t quantization_channels;       /* Q */
     int32_t out_channels;                /* MoL parameter count (3*nr_mix <= 63); ignored when !scalar_input */
@@ -107,7 +107,13 @@ int twv_wavenet_condition_mel(const twv_wavenet* h, const void* packed, const fl
  *   out         : (B, n_steps) float32 samples in [-1,1] (scalar_input) or int32 class ids.
  *   status      : device int32[4]; [0] = 0 on success, else an internal code (watchdogs; 31 = NaN class probabilities; checked by twv_wavenet_status).
  * State carries over between calls (n_steps=1 reproduces a single sess.run of generate.py:211).
- * cond must cover the same n_steps as this call (row t = frame pushed at step t). */
+ * cond must cover the same n_steps as this call (row t = frame pushed at step t).
+ *   debug       : optional, (B, debug_steps, NL*(D+R) + Opad) float32, Opad = out channels rounded up to 64: per step and layer the
+ *                 gated output z (D floats) then the layer output x (R floats), then the raw network outputs.  NL*64 + Opad at
+ *                 R = D = 32.
+ * Wide models ((R, D) != (32, 32)) run wn_wide_generate_kernel: one workgroup per stream, no condition on the batch size or on a free
+ * device, no watchdog codes (it contains no wait).  Their `cond` is [B][NL][2D] gc projections then [B][n_steps][NL][2D] lc
+ * projections (twv_wavenet_cond_bytes says so); twv_wavenet_fused_conditioning is 0 for them. */
 int twv_wavenet_generate(const twv_wavenet* h, const void* packed, void* state, const void* cond,
                          const void* first_input, const void* uniforms, double temperature,
                          int batch, int n_steps, void* out, int32_t* status, float* debug, int debug_steps,
@@ -132,7 +138,8 @@ int twv_wavenet_status(const int32_t* status, void* stream);
  * state and conditioning buffers.  "groups" = workgroups per stream of the generic kernel (0 auto; an explicit value also selects
  * the generic kernel), "workers" =
  * worker waves per stream workgroup (4 | 3), "helpers" = 1 (default: conv1d_1 and conv1d_2's chunk partials run in one helper
- * workgroup per stream slice when twice the workgroups are co-resident) | 2 (conv1d_1 only) | 0 (none). */
+ * workgroup per stream slice when twice the workgroups are co-resident) | 2 (conv1d_1 only) | 0 (none).
+ * On a wide model ((R, D) != (32, 32)) all of these are accepted and have no effect: wn_wide_generate_kernel has one geometry. */
 int twv_wavenet_set_option(twv_wavenet* h, const char* name, int value);
 
 /* optional in-kernel phase timestamps (tuning aid): device uint64[steps][80]; per step of stream 0's chain wave:

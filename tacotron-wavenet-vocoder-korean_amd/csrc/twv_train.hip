@@ -1868,7 +1868,7 @@ extern "C" int twv_wavenet_train_create(const twv_wavenet_dims* dims, int batch,
         if (fused_lc && (long long)batch * n_samples * 64 * 4 >= (1LL << 31))
             return twv_fail(TWV_E_UNSUPPORTED, "batch x samples too large: the fused layer kernels address a layer's activations with 32-bit byte offsets (batch * samples < 8.3 M)");
     }
-    if (d.residual_channels != 32 || d.dilation_channels != 32) return twv_fail(TWV_E_UNSUPPORTED, "residual/dilation channels must be 32");
+    if (d.residual_channels != 32 || d.dilation_channels != 32) return twv_fail(TWV_E_UNSUPPORTED, "training is built for residual_channels = dilation_channels = 32 only: training at other widths is not built");
     if (d.scalar_input && (d.out_channels % 3 || d.out_channels > 96)) return twv_fail(TWV_E_UNSUPPORTED, "out_channels must be 3*nr_mix <= 96");
     if (!d.scalar_input && (d.quantization_channels < 2 || d.quantization_channels > 512)) return twv_fail(TWV_E_UNSUPPORTED, "quantization_channels must be in [2, 512] for training");
     if (d.lc_channels != 80 || !d.gc_channels) return twv_fail(TWV_E_UNSUPPORTED, "the training step expects num_mels = 80 local and global conditioning (train_vocoder.py, hparams.py:30)");

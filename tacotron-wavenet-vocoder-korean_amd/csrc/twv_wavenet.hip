@@ -30,6 +30,7 @@
 #include "twv_dev.hpp"
 #include "twv_categorical.hpp"
 #include "twv_xcd.hpp"
+#include "twv_wide.hpp"
 
 using namespace twv;
 
@@ -1299,6 +1300,9 @@ struct twv_wavenet {
     int xcd_many;  // 0 = the library chooses (the many-streams form from batch 21 on), 1 = the many-streams form at every batch, 2 = never below batch 33
     unsigned long long* prof;
     int prof_steps;
+    int wide;      // (R, D) != (32, 32): every generation call goes to wn_wide_generate_kernel (twv_wavenet_wide.hip); the launch-geometry
+                   // options above are accepted and have no effect
+    WideLayout wl;
 };
 
 static thread_local std::string g_err;
@@ -1320,8 +1324,10 @@ static int build_layout(const twv_wavenet_dims& d, twv_wavenet* h)
     Layout& L = h->lay;
     memset(&L, 0, sizeof(L));
     if (d.n_layers < 1 || d.n_layers > kMaxLayers) return fail(TWV_E_INVALID, "n_layers must be in [1,64]");
-    if (d.residual_channels != 32 || d.dilation_channels != 32)
-        return fail(TWV_E_UNSUPPORTED, "residual_channels and dilation_channels must be 32 (hparams.py:71-72)");
+    if (!wide_width_ok(d.residual_channels) || !wide_width_ok(d.dilation_channels))
+        return fail(TWV_E_UNSUPPORTED, "residual_channels and dilation_channels must each be 32, 64 or 128 (hparams.py:71-72 has 32)");
+    const int R = d.residual_channels, D = d.dilation_channels;
+    h->wide = (R != 32 || D != 32) ? 1 : 0;
     if (d.skip_channels < 64 || d.skip_channels > 1024 || d.skip_channels % 64)
         return fail(TWV_E_UNSUPPORTED, "skip_channels must be a multiple of 64 in [64,1024]");
     if (d.gc_channels < 0 || d.gc_channels > 64) return fail(TWV_E_UNSUPPORTED, "gc_channels must be <= 64");
@@ -1346,7 +1352,7 @@ static int build_layout(const twv_wavenet_dims& d, twv_wavenet* h)
     int ro = 0;
     for (int i = 0; i < L.NL; ++i) {
         if (d.dilations[i] < 1) return fail(TWV_E_INVALID, "dilations must be >= 1");
-        h->dil[i] = d.dilations[i]; h->ring_off[i] = ro; ro += d.dilations[i] * 32;
+        h->dil[i] = d.dilations[i]; h->ring_off[i] = ro; ro += d.dilations[i] * R;
     }
     L.ring_floats = ro;
     // ---- packed layout
@@ -1365,11 +1371,11 @@ static int build_layout(const twv_wavenet_dims& d, twv_wavenet* h)
     L.off_gcemb = p; p += align_up((long long)L.gc_card * L.G, 4);
     for (int i = 0; i < L.n_up; ++i) { L.off_up[i] = p; p += align_up((long long)L.up[i] * 2, 4); }
     L.off_xl = 0; L.off_xc = 0;
-    if (xcd_model_ok(L)) { L.off_xl = p; p += (long long)kXcdXlFloats * L.NL; L.off_xc = p; p += kXcdXcFloats; }
+    if (!h->wide && xcd_model_ok(L)) { L.off_xl = p; p += (long long)kXcdXlFloats * L.NL; L.off_xc = p; p += kXcdXcFloats; }
     L.packed_floats = p;
+    if (h->wide) wide_build_packed_layout(L, h->wl, R, D);      // the wide kernel's own tiles; the shared fields keep their meaning
     // ---- canonical blob (must match DESIGN.md "canonical blob"; mirrored by the checker independently)
     long long c = 0;
-    const int R = 32, D = 32;
     L.c_causal = c; c += L.scalar ? (long long)L.ifw * R : (long long)2 * L.Q * R;
     L.c_gcemb = c; c += (long long)L.gc_card * L.G;
     L.c_layer0 = c;
@@ -1391,7 +1397,7 @@ static int build_layout(const twv_wavenet_dims& d, twv_wavenet* h)
     L.st_hist = s; s += 64;
     L.st_meta = s; s += 64;
     L.st_ringpos = s; s += 64;
-    L.st_lcprev = s; s += (long long)L.NL * 64;
+    L.st_lcprev = s; s += (long long)L.NL * 2 * D;
     L.st_ring = s; s += L.ring_floats;
     L.state_stride = align_up(s, 64);
     if (L.packed_floats * 4 > 0x7fffffffLL) return fail(TWV_E_UNSUPPORTED, "packed weights exceed 2 GiB");
@@ -1410,12 +1416,12 @@ static int device_cus()
 // the XCD-per-stream kernel: stream b on XCD b % 8 (8 x 32 CUs; up to four streams per XCD), explicit `groups` keeps the generic kernel
 static bool use_xcd(const twv_wavenet* h, int batch)
 {
-    return h->xcd != 0 && h->groups == 0 && h->lay.off_xl != 0 && batch >= 1 && batch <= xcd_max_streams(h->lay) && device_cus() >= 256;
+    return !h->wide && h->xcd != 0 && h->groups == 0 && h->lay.off_xl != 0 && batch >= 1 && batch <= xcd_max_streams(h->lay) && device_cus() >= 256;
 }
 static int resolve_groups(const twv_wavenet* h, int batch)
 {
     const int NSJ = h->lay.NSJ;
-    if (use_xcd(h, batch)) return 1;
+    if (h->wide || use_xcd(h, batch)) return 1;
     if (h->groups > 0) return (NSJ % h->groups == 0) ? h->groups : -1;
     const int cus = device_cus();
     for (int g = 8; g >= 1; g >>= 1)
@@ -1452,7 +1458,8 @@ extern "C" int twv_wavenet_create(const twv_wavenet_dims* dims, twv_wavenet** ou
     h->prof = nullptr; h->prof_steps = 0;
     const int rc = build_layout(*dims, h);
     if (rc != TWV_OK) { delete h; return rc; }
-    if (resolve_nslot(h->lay, 1) < 1) { delete h; return fail(TWV_E_UNSUPPORTED, "model does not fit the 160 KiB LDS budget"); }
+    if (h->wide && !wide_fits_lds(h->lay, h->wl.R, h->wl.D)) { delete h; return fail(TWV_E_UNSUPPORTED, "model does not fit the 160 KiB LDS budget"); }
+    if (!h->wide && resolve_nslot(h->lay, 1) < 1) { delete h; return fail(TWV_E_UNSUPPORTED, "model does not fit the 160 KiB LDS budget"); }
     *out = h;
     return TWV_OK;
 }
@@ -1475,6 +1482,7 @@ extern "C" size_t twv_wavenet_packed_bytes(const twv_wavenet* h) { return (size_
 extern "C" size_t twv_wavenet_state_bytes(const twv_wavenet* h, int batch)
 {
     // per (stream, workgroup) delay lines etc., then the all-gather granules [B][2][S] x 8 bytes
+    if (h->wide) return (size_t)h->lay.state_stride * 4 * (size_t)batch;      // one workgroup per stream, nothing exchanged
     int G = resolve_groups(h, batch);
     if (G < 1) G = 1;
     return (size_t)h->lay.state_stride * 4 * (size_t)batch * G + (size_t)batch * 2 * h->lay.S * 8 + (use_xcd(h, batch) ? xcd_exchange_bytes(batch) : 0);
@@ -1483,6 +1491,7 @@ extern "C" size_t twv_wavenet_cond_bytes(const twv_wavenet* h, int batch, int n_
 {
     // XCD path: header + gc projections + the rows of the (upsampled) condition; the lc projections are made inside the launch
     if (use_xcd(h, batch)) return ((size_t)XH_WORDS + (size_t)batch * h->lay.NL * 64 + (size_t)batch * (size_t)n_steps * h->lay.L) * 4;
+    if (h->wide) return ((size_t)batch * h->lay.NL + (size_t)batch * (size_t)n_steps * h->lay.NL) * 2 * h->wl.D * 4;   // [B][NL][2D], [B][T][NL][2D]
     return ((size_t)batch * h->lay.NL * 64 + (size_t)batch * (size_t)n_steps * h->lay.NL * 64) * 4;
 }
 extern "C" int twv_wavenet_set_profile_buffer(twv_wavenet* h, void* dev_u64, int steps)
@@ -1551,6 +1560,7 @@ extern "C" int twv_wavenet_pack(const twv_wavenet* h, const float* blob, void* p
     for (int i = 0; i < 64; ++i) { metah[i] = i < L.NL ? h->dil[i] : 1; metah[64 + i] = i < L.NL ? h->ring_off[i] : 0; }
     HIPCHK(hipMemcpyAsync(dst + L.off_meta, metah, sizeof(metah), hipMemcpyHostToDevice, st));
     HIPCHK(hipStreamSynchronize(st));   // metah is a stack buffer
+    if (h->wide) return wide_pack(dst, blob, L, h->wl, st);
     auto tiles = [&](long long dst_off, long long dst_gs, long long baseA, long long baseB, long long src_gs, int ng, int njb, int nch,
                      int K, int rowlen, int ncols, int halves, int lanes = 64) {
         PackTiles p{dst_off, dst_gs, baseA, baseB, src_gs, ng, njb, nch, K, rowlen, ncols, halves, lanes};
@@ -1654,6 +1664,7 @@ extern "C" int twv_wavenet_fused_conditioning(const twv_wavenet* h, int batch) {
 extern "C" const char* twv_wavenet_kernel_name(const twv_wavenet* h, int batch)
 {
     if (!h || batch < 1) return "";
+    if (h->wide) return "wn_wide_generate_kernel";
     if (!use_xcd(h, batch)) return "wn_generate_kernel";
     return xcd_uses_many(h->lay, batch, h->xcd_many) ? "wn_xcd_many_kernel" : "wn_xcd_generate_kernel";
 }
@@ -1677,6 +1688,7 @@ extern "C" int twv_wavenet_condition(const twv_wavenet* h, const void* packed, c
     const Layout& L = h->lay;
     hipStream_t st = (hipStream_t)stream;
     if (use_xcd(h, batch)) return xcd_condition(h, packed, upsampled, XLC_UPSAMPLED, gc_ids, batch, n_steps, cond, st);
+    if (h->wide) return wide_condition((const float*)packed, L, h->wl, upsampled, gc_ids, batch, n_steps, (float*)cond, st);
     const float* P = (const float*)packed;
     float* GCv = (float*)cond;
     float* LC = GCv + (size_t)batch * L.NL * 64;
@@ -1735,6 +1747,14 @@ static int generate_impl(const twv_wavenet* h, const void* packed, void* state, 
     a.uniforms = uniforms; a.out = out; a.status = status; a.dbg = debug; a.dbg_steps = debug ? debug_steps : 0;
     a.prof = h->prof; a.prof_steps = h->prof ? h->prof_steps : 0;
     a.B = batch; a.T = n_steps; a.temperature = (float)temperature; a.lay = L;
+    if (h->wide) {
+        // one workgroup per stream, no co-residency condition: any batch (twv_wavenet_wide.hip)
+        WideLaunch x;
+        x.P = a.P; x.state = a.state; x.cond = a.cond; x.first_input = first_input; x.forced = forced; x.uniforms = uniforms; x.out = out;
+        x.status = status; x.dbg = debug; x.dbg_steps = a.dbg_steps; x.B = batch; x.T = n_steps; x.temperature = (float)temperature;
+        x.lay = L; x.wl = h->wl;
+        return wide_launch(x, st);
+    }
     if (use_xcd(h, batch)) {
         // stream b on XCD b % 8, every weight register-resident across the XCD's CUs (twv_wavenet_xcd.hip)
         XcdLaunch x;

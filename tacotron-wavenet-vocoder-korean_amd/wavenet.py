@@ -305,7 +305,9 @@ class WaveNetModel(object):
             dbg = None
             if debug_steps:
                 opad = (((self.out_channels if self.scalar_input else self.quantization_channels) + 63) // 64) * 64
-                dbg = torch.zeros((B, debug_steps, len(self.dilations) * 64 + opad), dtype=torch.float32, device=self.device)
+                # per layer z (D floats) | x (R floats), then the raw outputs; 64 per layer at R = D = 32
+                dbg = torch.zeros((B, debug_steps, len(self.dilations) * (self.dilation_channels + self.residual_channels) + opad),
+                                  dtype=torch.float32, device=self.device)
             # TWV_E_BUSY (the persistent kernel's role workgroups were not all resident within ~50 ms: another kernel held CUs) means
             # NOTHING was done -- no sample written, state unchanged -- so the launch is simply repeated, a few times, with a pause
             for attempt in range(self.BUSY_RETRIES + 1):
@@ -369,7 +371,8 @@ class WaveNetModel(object):
             from .ops import eval_elementwise
             Q = self.quantization_channels
             _ids, dump = self.generate(lc, global_condition, np.asarray(waveform).reshape(B), np.full((B, 1), 0.5), debug_steps=1)
-            logits = dump[:, 0, len(self.dilations) * 64:len(self.dilations) * 64 + Q].to(torch.float64)
+            o_raw = len(self.dilations) * (self.dilation_channels + self.residual_channels)
+            logits = dump[:, 0, o_raw:o_raw + Q].to(torch.float64)
             e = eval_elementwise("exp64", logits - logits.max(dim=1, keepdim=True)[0], device=self.device)      # the kernel's own float64 exp
             return (e / e.sum(dim=1, keepdim=True)).to(torch.float32)
         if uniforms is None:
