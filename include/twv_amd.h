@@ -273,6 +273,37 @@ size_t twv_griffin_lim_workspace_bytes(const twv_griffin_lim* h);
  * in [0,1) replace np.random.rand of utils/audio.py:131; out (batch, samples).  iters = hparams.griffin_lim_iters. */
 int twv_inv_linear_spectrogram(twv_griffin_lim* h, const float* lin, const float* uniforms, int iters, double power, double ref_level_db,
                                double max_abs_value, double min_level_db, double preemphasis, void* workspace, float* out, void* stream);
+/* The same loop behind the general front of utils/audio.py:77-110.  spec (batch, n_frames, n_channels): n_channels = n_fft/2+1 with
+ * inv_basis NULL is inv_linear_spectrogram (:77-92); n_channels = n_mels with a device inv_basis (n_fft/2+1, n_mels) row-major
+ * (= np.linalg.pinv(mel basis)) is inv_mel_spectrogram (:95-110, _mel_to_linear :187-191: max(1e-10, inv_basis @ db_to_amp(D + ref))).
+ * norm_mode selects _denormalize (:222-234): 0 none (signal_normalization off), 1 clip + symmetric (the hparams default),
+ * 2 clip + asymmetric, 3 no clip + symmetric, 4 no clip + asymmetric.  uniforms (batch, n_frames, n_fft/2+1) in both cases. */
+int twv_inv_spectrogram(twv_griffin_lim* h, const float* spec, int n_channels, const float* inv_basis, const float* uniforms,
+                        int iters, double power, double ref_level_db, double max_abs_value, double min_level_db, int norm_mode,
+                        double preemphasis, void* workspace, float* out, void* stream);
+
+/* ======================================= waveform -> mel / linear spectrogram =======================================
+ * utils/audio.py:61-75 `linearspectrogram` / `melspectrogram` for a ragged batch, both from one FFT pass:
+ *   x = lfilter([1, -k], [1], wav) (:22-25);  D = librosa.stft(x, n_fft, hop, win_length) (:139-143: centre, reflect padding of
+ *   n_fft/2, periodic Hann zero-padded to n_fft, 1 + len / hop frames);  A = |D| or mel_basis @ |D| (:181-185);
+ *   S = 20 log10(max(min_level, A)) - ref_level_db, min_level = exp(min_level_db / 20 * ln 10) (:201-203);  _normalize(S) (:208-220).
+ * mel_basis_host (n_mels, n_fft/2+1) row-major HOST floats = librosa.filters.mel(...) (:199), an input: the library computes no
+ * basis.  Only each row's span first .. last non-zero is kept (a dense row keeps its whole width).  n_mels = 0: no mel output.
+ * create does no device work (the basis is copied on the host and uploaded by the first analyze). */
+typedef struct twv_spectrogram twv_spectrogram;
+int twv_spectrogram_create(int n_fft, int hop, int win_length, int n_mels, const float* mel_basis_host, int max_samples, int batch,
+                           twv_spectrogram** out);
+void twv_spectrogram_destroy(twv_spectrogram* h);
+int twv_spectrogram_frames(const twv_spectrogram* h);                  /* 1 + max_samples / hop: rows per utterance of the outputs */
+size_t twv_spectrogram_workspace_bytes(const twv_spectrogram* h);
+/* wav (batch, max_samples) device; lengths_host[batch] (HOST; NULL = every utterance has max_samples), each n_fft/2 < len <=
+ * max_samples.  mel_out (batch, frames, n_mels) and lin_out (batch, frames, n_fft/2+1), device, either may be NULL; rows past an
+ * utterance's 1 + len / hop frames are 0.  preemphasis = 0 when hparams.preemphasize is off.  norm_mode: 0 none, 1 clip +
+ * symmetric, 2 clip + asymmetric, 3 no clip + symmetric, 4 no clip + asymmetric (_normalize, :208-220).  minmax_out (device
+ * float[2], or NULL): min and max of S over every value written, for the assertion of :216 that the no-clip modes carry. */
+int twv_spectrogram_analyze(twv_spectrogram* h, const float* wav, const int32_t* lengths_host, double preemphasis, double ref_level_db,
+                            double min_level_db, double max_abs_value, int norm_mode, void* workspace, float* mel_out, float* lin_out,
+                            float* minmax_out, void* stream);
 
 /* cross-lane primitive self-test (device float[256]); used by the gpu tests to pin v_permlane32_swap / v_readlane semantics */
 int twv_selftest(float* out256, void* stream);

@@ -213,6 +213,12 @@ def lib():
     L.twv_griffin_lim_samples.argtypes = [vp]
     L.twv_griffin_lim_workspace_bytes.argtypes = [vp]; L.twv_griffin_lim_workspace_bytes.restype = C.c_size_t
     L.twv_inv_linear_spectrogram.argtypes = [vp, fp, fp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, vp, fp, vp]
+    L.twv_inv_spectrogram.argtypes = [vp, fp, C.c_int, fp, fp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_double, vp, fp, vp]
+    L.twv_spectrogram_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    L.twv_spectrogram_destroy.argtypes = [vp]; L.twv_spectrogram_destroy.restype = None
+    L.twv_spectrogram_frames.argtypes = [vp]
+    L.twv_spectrogram_workspace_bytes.argtypes = [vp]; L.twv_spectrogram_workspace_bytes.restype = C.c_size_t
+    L.twv_spectrogram_analyze.argtypes = [vp, fp, ip, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, vp, fp, fp, fp, vp]
     L.twv_wav_to_int16.argtypes = [fp, C.c_int, C.c_int64, vp, fp, vp]
     L.twv_eval_elementwise.argtypes = [C.c_int, fp, C.c_int64, fp, vp]
     L.twv_eval_elementwise64.argtypes = [C.c_int, dp, C.c_int64, dp, vp]
@@ -256,7 +262,8 @@ EXPORTS = ["twv_last_error", "twv_version", "twv_wavenet_create", "twv_wavenet_d
            "twv_wavenet_train_create", "twv_wavenet_train_destroy", "twv_wavenet_train_param_floats", "twv_wavenet_train_workspace_bytes",
            "twv_wavenet_train_output_width", "twv_wavenet_train_reset_workspace", "twv_wavenet_train_loss_grad", "twv_adam_ema_step", "twv_wavenet_train_l2",
            "twv_clip_by_global_norm", "twv_griffin_lim_create", "twv_griffin_lim_destroy", "twv_griffin_lim_samples",
-           "twv_griffin_lim_workspace_bytes", "twv_inv_linear_spectrogram", "twv_crc32c"]
+           "twv_griffin_lim_workspace_bytes", "twv_inv_linear_spectrogram", "twv_inv_spectrogram", "twv_spectrogram_create",
+           "twv_spectrogram_destroy", "twv_spectrogram_frames", "twv_spectrogram_workspace_bytes", "twv_spectrogram_analyze", "twv_crc32c"]
 
 
 class TacoDims(C.Structure):

@@ -1,10 +1,13 @@
-"""Host-side mirror of the reference's spectrogram -> waveform helpers (utils/audio.py) over the HIP C-ABI.
+"""Host-side mirror of the reference's audio helpers (utils/audio.py) over the HIP C-ABI, both directions.
 
+    mel, linear = spectrograms(wav, hparams)                      # utils/audio.py:61-75, both from one FFT pass on the GPU
+    mel = melspectrogram(wav, hparams); linear = linearspectrogram(wav, hparams)
     wav = inv_linear_spectrogram(linear, hparams, uniforms)      # utils/audio.py:77-92 (synthesizer.py:258), Griffin-Lim on the GPU
+    wav = inv_mel_spectrogram(mel, hparams, uniforms)            # utils/audio.py:95-110
     save_wav(wav, path, hparams.sample_rate)                      # utils/audio.py:14-17 (peak normalisation on the GPU)
 
-`linear` is the (B, T, num_freq) tensor Tacotron.infer returns (the reference transposes one utterance to (num_freq, T) first).
-PyTorch is used for device memory and streams only."""
+Spectrograms are (B, T, channels) throughout: what Tacotron.infer returns and what the npz examples hold (the reference works on one
+utterance at a time, transposed to (channels, T)).  PyTorch is used for device memory and streams only."""
 import ctypes as C
 
 import numpy as np
@@ -14,9 +17,189 @@ from . import _lib
 from .wavenet import _ptr, _stream
 
 
+def norm_mode(hparams):
+    """the C-ABI's norm_mode for _normalize / _denormalize (utils/audio.py:208-234)"""
+    if not hparams.signal_normalization:
+        return 0
+    if hparams.allow_clipping_in_normalization:
+        return 1 if hparams.symmetric_mels else 2
+    return 3 if hparams.symmetric_mels else 4
+
+
+def _hz_to_mel(f):
+    f = np.asarray(f, np.float64)
+    f_sp, min_log_hz, logstep = 200.0 / 3, 1000.0, np.log(6.4) / 27.0
+    return np.where(f >= min_log_hz, min_log_hz / f_sp + np.log(np.maximum(f, 1e-300) / min_log_hz) / logstep, f / f_sp)
+
+
+def _mel_to_hz(m):
+    m = np.asarray(m, np.float64)
+    f_sp, min_log_hz, logstep = 200.0 / 3, 1000.0, np.log(6.4) / 27.0
+    return np.where(m >= min_log_hz / f_sp, min_log_hz * np.exp(logstep * (m - min_log_hz / f_sp)), f_sp * m)
+
+
+def mel_basis(hparams):
+    """utils/audio.py:193-199 `librosa.filters.mel(sample_rate, fft_size, n_mels=num_mels)` -> float32 (num_mels, fft_size/2 + 1).
+    [RECALLED-LIBROSA <= 0.7]: fmin = 0, fmax = sr/2, Slaney's scale (200/3 Hz per mel below 1 kHz, log step ln(6.4)/27 above),
+    num_mels + 2 band edges equally spaced in mel, triangles min(rising, falling) clipped at 0 and scaled by 2 / (f[i+2] - f[i]).
+    Computed in float64 on the host; the kernels take any basis (twv_spectrogram_create), so librosa's own matrix can be passed."""
+    sr, n_fft, n_mels = float(hparams.sample_rate), int(hparams.fft_size), int(hparams.num_mels)
+    fft_f = np.linspace(0.0, sr / 2, 1 + n_fft // 2)
+    mel_f = _mel_to_hz(np.linspace(_hz_to_mel(0.0), _hz_to_mel(sr / 2), n_mels + 2))
+    fdiff = np.diff(mel_f)
+    ramps = mel_f[:, None] - fft_f[None, :]
+    lower = -ramps[:-2] / fdiff[:-1, None]
+    upper = ramps[2:] / fdiff[1:, None]
+    weights = np.maximum(0.0, np.minimum(lower, upper))
+    weights *= (2.0 / (mel_f[2:n_mels + 2] - mel_f[:n_mels]))[:, None]
+    return weights.astype(np.float32)
+
+
+_basis_cache = {}
+_analyzers = {}          # (device, n_fft, hop, win, basis key, max_samples, batch) -> [handle, workspace]: the FFT plan lives in the handle
+_MAX_ANALYZERS = 4
+
+
+def _default_basis(hparams):
+    key = (hparams.sample_rate, hparams.fft_size, hparams.num_mels)
+    if key not in _basis_cache:
+        _basis_cache[key] = mel_basis(hparams)
+    return key, _basis_cache[key]
+
+
+def _analyzer(L, hparams, basis_key, basis, max_samples, batch, device):
+    key = (str(device), hparams.fft_size, hparams.hop_size, hparams.win_size, basis_key, max_samples, batch)
+    hit = _analyzers.pop(key, None)
+    if hit is None:
+        h = C.c_void_p()
+        _lib.check(L.twv_spectrogram_create(hparams.fft_size, hparams.hop_size, hparams.win_size, basis.shape[0],
+                                            basis.ctypes.data_as(C.c_void_p), max_samples, batch, C.byref(h)))
+        hit = [h, torch.empty(L.twv_spectrogram_workspace_bytes(h) // 4 + 64, dtype=torch.float32, device=device)]
+        while len(_analyzers) >= _MAX_ANALYZERS:                 # oldest first (dicts keep insertion order)
+            old = _analyzers.pop(next(iter(_analyzers)))
+            torch.cuda.synchronize(device)
+            L.twv_spectrogram_destroy(old[0])
+    _analyzers[key] = hit
+    return hit
+
+
+def _as_batch(wav, lengths, device):
+    """(len,), (B, len), a list of 1-D arrays, or a device tensor -> ((B, max_len) float32 device tensor, int32 lengths, was 1-D)"""
+    if isinstance(wav, (list, tuple)) and len(wav) and np.ndim(wav[0]) == 1:
+        if lengths is not None:
+            raise ValueError("a list of utterances carries its own lengths")
+        lengths = np.asarray([len(w) for w in wav], np.int32)
+        host = np.zeros((len(wav), int(lengths.max())), np.float32)
+        for b, w in enumerate(wav):
+            host[b, :len(w)] = np.asarray(w, np.float32)
+        return torch.from_numpy(host).to(device), lengths, False
+    x = torch.as_tensor(wav, dtype=torch.float32, device=device)
+    single = x.dim() == 1
+    if single:
+        x = x[None]
+    if x.dim() != 2:
+        raise ValueError("wav must be (len,), (B, len) or a list of 1-D arrays")
+    x = x.contiguous()
+    if lengths is None:
+        lengths = np.full(x.shape[0], x.shape[1], np.int32)
+    lengths = np.ascontiguousarray(lengths, np.int32).reshape(-1)
+    if len(lengths) != x.shape[0]:
+        raise ValueError("lengths must have one entry per utterance")
+    return x, lengths, single
+
+
+def spectrograms(wav, hparams, lengths=None, mel_basis=None, device="cuda:0", mel=True, linear=True):
+    """utils/audio.py:61-75 for a ragged batch, both outputs from one FFT pass (twv_spectrogram_analyze):
+    -> (mel (B, frames, num_mels), linear (B, frames, fft_size/2 + 1)), frames = 1 + max(len) // hop_size; an utterance of `len`
+    samples fills its first 1 + len // hop_size rows, the rest are 0.  The reference returns (channels, frames) for one utterance.
+    wav: (len,) (then the outputs have no batch axis), (B, len) with optional `lengths`, or a list of 1-D arrays of different lengths;
+    a tensor already on the device is used in place.  mel_basis: (num_mels, fft_size/2 + 1), default mel_basis(hparams).
+    The no-clip normalisations raise AssertionError where utils/audio.py:216 does."""
+    if getattr(hparams, "use_lws", False):
+        raise NotImplementedError("use_lws=True (hparams.py:15 default False) is not built")
+    if not (mel or linear):
+        raise ValueError("neither output requested")
+    if isinstance(wav, torch.Tensor) and wav.is_cuda:
+        device = wav.device
+    x, lengths, single = _as_batch(wav, lengths, device)
+    B, n = x.shape
+    if mel_basis is None:
+        bkey, basis = _default_basis(hparams)
+    else:
+        basis = np.ascontiguousarray(mel_basis, np.float32)
+        if basis.shape != (hparams.num_mels, hparams.fft_size // 2 + 1):
+            raise ValueError("mel_basis must be (num_mels, fft_size/2 + 1) = %s" % ((hparams.num_mels, hparams.fft_size // 2 + 1),))
+        import hashlib
+        bkey = hashlib.sha1(basis.tobytes()).hexdigest()
+    mode = norm_mode(hparams)
+    L = _lib.lib()
+    with torch.cuda.device(x.device):
+        h, ws = _analyzer(L, hparams, bkey, basis, n, B, x.device)
+        T = L.twv_spectrogram_frames(h)
+        mel_out = torch.empty((B, T, basis.shape[0]), dtype=torch.float32, device=x.device) if mel else None
+        lin_out = torch.empty((B, T, hparams.fft_size // 2 + 1), dtype=torch.float32, device=x.device) if linear else None
+        mm = torch.empty(2, dtype=torch.float32, device=x.device) if mode in (3, 4) else None
+        _lib.check(L.twv_spectrogram_analyze(h, _ptr(x), lengths.ctypes.data_as(C.c_void_p),
+                                             float(hparams.preemphasis) if hparams.preemphasize else 0.0, float(hparams.ref_level_db),
+                                             float(hparams.min_level_db), float(hparams.max_abs_value), mode, _ptr(ws),
+                                             _ptr(mel_out) if mel else None, _ptr(lin_out) if linear else None,
+                                             _ptr(mm) if mm is not None else None, _stream()))
+        if mm is not None:
+            lo, hi = mm.tolist()
+            assert hi <= 0 and lo - hparams.min_level_db >= 0, \
+                "utils/audio.py:216: S.max() = %g, S.min() = %g outside [min_level_db, 0] without clipping" % (hi, lo)
+    if single:
+        mel_out = mel_out[0] if mel else None
+        lin_out = lin_out[0] if linear else None
+    return mel_out, lin_out
+
+
+def melspectrogram(wav, hparams, lengths=None, mel_basis=None, device="cuda:0"):
+    """utils/audio.py:69-75 -> (B, frames, num_mels); see spectrograms"""
+    return spectrograms(wav, hparams, lengths, mel_basis, device, linear=False)[0]
+
+
+def linearspectrogram(wav, hparams, lengths=None, device="cuda:0"):
+    """utils/audio.py:61-67 -> (B, frames, fft_size/2 + 1); see spectrograms"""
+    return spectrograms(wav, hparams, lengths, None, device, mel=False)[1]
+
+
+def _griffin_lim(spec, inv_basis, hparams, uniforms, seed, general):
+    B, T, _ = spec.shape
+    F = hparams.fft_size // 2 + 1
+    if uniforms is None:
+        uniforms = np.random.RandomState(seed).rand(B, T, F)
+    u = torch.as_tensor(uniforms, dtype=torch.float32, device=spec.device).contiguous()
+    if tuple(u.shape) != (B, T, F):
+        raise ValueError("uniforms must be %s" % ((B, T, F),))
+    L = _lib.lib()
+    h = C.c_void_p()
+    _lib.check(L.twv_griffin_lim_create(hparams.fft_size, hparams.hop_size, hparams.win_size, T, B, C.byref(h)))
+    try:
+        with torch.cuda.device(spec.device):
+            n = L.twv_griffin_lim_samples(h)
+            ws = torch.empty(L.twv_griffin_lim_workspace_bytes(h) // 4 + 64, dtype=torch.float32, device=spec.device)
+            out = torch.empty((B, n), dtype=torch.float32, device=spec.device)
+            k = float(hparams.preemphasis) if hparams.preemphasize else 0.0
+            if general:
+                _lib.check(L.twv_inv_spectrogram(h, _ptr(spec), spec.shape[2], _ptr(inv_basis) if inv_basis is not None else None, _ptr(u),
+                                                 int(hparams.griffin_lim_iters), float(hparams.power), float(hparams.ref_level_db),
+                                                 float(hparams.max_abs_value), float(hparams.min_level_db), norm_mode(hparams), k,
+                                                 _ptr(ws), _ptr(out), _stream()))
+            else:
+                _lib.check(L.twv_inv_linear_spectrogram(h, _ptr(spec), _ptr(u), int(hparams.griffin_lim_iters), float(hparams.power),
+                                                        float(hparams.ref_level_db), float(hparams.max_abs_value), float(hparams.min_level_db),
+                                                        k, _ptr(ws), _ptr(out), _stream()))
+            torch.cuda.current_stream().synchronize()
+    finally:
+        L.twv_griffin_lim_destroy(h)
+    return out
+
+
 def inv_linear_spectrogram(linear, hparams, uniforms=None, seed=None, device="cuda:0"):
     """(B, T, num_freq) normalised linear spectrograms -> (B, hop_size*(T-1)) waveforms.
-    uniforms (B, T, num_freq) in [0,1) replace utils/audio.py:131 np.random.rand; drawn from `seed` when absent."""
+    uniforms (B, T, num_freq) in [0,1) replace utils/audio.py:131 np.random.rand; drawn from `seed` when absent.
+    Every normalisation setting of _denormalize (utils/audio.py:222-234); the default one takes twv_inv_linear_spectrogram."""
     if getattr(hparams, "use_lws", False):
         raise NotImplementedError("use_lws=True (hparams.py:15 default False) is not built")
     lin = torch.as_tensor(linear, dtype=torch.float32, device=device).contiguous()
@@ -25,28 +208,23 @@ def inv_linear_spectrogram(linear, hparams, uniforms=None, seed=None, device="cu
     B, T, F = lin.shape
     if F != hparams.fft_size // 2 + 1:
         raise ValueError("last dimension must be fft_size/2 + 1 = %d, got %d" % (hparams.fft_size // 2 + 1, F))
-    if uniforms is None:
-        uniforms = np.random.RandomState(seed).rand(B, T, F)
-    u = torch.as_tensor(uniforms, dtype=torch.float32, device=device).contiguous()
-    if tuple(u.shape) != (B, T, F):
-        raise ValueError("uniforms must be %s" % ((B, T, F),))
-    if not hparams.signal_normalization or not hparams.allow_clipping_in_normalization or not hparams.symmetric_mels:
-        raise NotImplementedError("only the default normalisation (clipped, symmetric) is built")
-    L = _lib.lib()
-    h = C.c_void_p()
-    _lib.check(L.twv_griffin_lim_create(hparams.fft_size, hparams.hop_size, hparams.win_size, T, B, C.byref(h)))
-    try:
-        with torch.cuda.device(lin.device):
-            n = L.twv_griffin_lim_samples(h)
-            ws = torch.empty(L.twv_griffin_lim_workspace_bytes(h) // 4 + 64, dtype=torch.float32, device=lin.device)
-            out = torch.empty((B, n), dtype=torch.float32, device=lin.device)
-            _lib.check(L.twv_inv_linear_spectrogram(h, _ptr(lin), _ptr(u), int(hparams.griffin_lim_iters), float(hparams.power),
-                                                   float(hparams.ref_level_db), float(hparams.max_abs_value), float(hparams.min_level_db),
-                                                   float(hparams.preemphasis) if hparams.preemphasize else 0.0, _ptr(ws), _ptr(out), _stream()))
-            torch.cuda.current_stream().synchronize()
-    finally:
-        L.twv_griffin_lim_destroy(h)
-    return out
+    return _griffin_lim(lin, None, hparams, uniforms, seed, general=norm_mode(hparams) != 1)
+
+
+def inv_mel_spectrogram(mel, hparams, uniforms=None, seed=None, mel_basis=None, device="cuda:0"):
+    """utils/audio.py:95-110: (B, T, num_mels) normalised mel spectrograms -> (B, hop_size*(T-1)) waveforms through
+    _mel_to_linear (:187-191, inv_basis = np.linalg.pinv(mel basis), float64 on the host) and the same Griffin-Lim loop.
+    uniforms (B, T, fft_size/2 + 1) as in inv_linear_spectrogram."""
+    if getattr(hparams, "use_lws", False):
+        raise NotImplementedError("use_lws=True (hparams.py:15 default False) is not built")
+    m = torch.as_tensor(mel, dtype=torch.float32, device=device).contiguous()
+    if m.dim() == 2:
+        m = m[None]
+    basis = _default_basis(hparams)[1] if mel_basis is None else np.asarray(mel_basis)
+    if m.shape[2] != basis.shape[0] or basis.shape[1] != hparams.fft_size // 2 + 1:
+        raise ValueError("mel is (B, T, %d) but the basis is %s" % (m.shape[2], basis.shape))
+    inv = torch.as_tensor(np.linalg.pinv(basis.astype(np.float64)).astype(np.float32), device=m.device).contiguous()
+    return _griffin_lim(m, inv, hparams, uniforms, seed, general=True)
 
 
 def save_wav(wav, path, sr):

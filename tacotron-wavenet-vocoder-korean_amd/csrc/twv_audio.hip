@@ -5,6 +5,7 @@
 //   utils/audio.py:77-92   inv_linear_spectrogram: _denormalize (:222-227) -> _db_to_amp (:205-206) -> ** power -> _griffin_lim -> inv_preemphasis
 //   utils/audio.py:127-137 _griffin_lim: random initial phase, griffin_lim_iters x {librosa.stft -> unit phase -> librosa.istft}
 //   utils/audio.py:27-30   inv_preemphasis = lfilter([1], [1, -k])
+//   utils/audio.py:95-110  inv_mel_spectrogram (the same loop after _mel_to_linear, :187-191) and every _denormalize setting (:222-234)
 // The FFTs are plain library transforms (hipFFT, batched over every frame of every utterance); framing, windowing,
 // overlap-add with the window sum-of-squares normalisation, reflect padding, phase projection, magnitude shaping and the
 // de-emphasis recurrence are hand-written kernels.  The spectrogram stays in Tacotron's own (utterance, frame, bin) layout,
@@ -44,15 +45,39 @@ __device__ __forceinline__ float ga_window(int k, int n_fft, int win)
     if (j < 0 || j >= win) return 0.0f;
     return 0.5f - 0.5f * cospif(2.0f * (float)j / (float)win);
 }
-// utils/audio.py:222-227 + :205-206 + "** power": magnitude the Griffin-Lim iterations keep fixed
-__global__ void ga_mag_kernel(const float* lin, float* mag, long long n, float max_abs, float min_db, float ref_db, float power)
+// utils/audio.py:222-234 _denormalize.  mode: 0 none, 1 clip + symmetric, 2 clip + asymmetric, 3 symmetric, 4 asymmetric
+__device__ __forceinline__ float ga_denorm(float x, int mode, float max_abs, float min_db)
+{
+    if (mode == 0) return x;
+    if (mode == 1) x = x < -max_abs ? -max_abs : (x > max_abs ? max_abs : x);
+    if (mode == 2) x = x < 0.0f ? 0.0f : (x > max_abs ? max_abs : x);
+    if (mode == 1 || mode == 3) return ((x + max_abs) * -min_db / (2.0f * max_abs)) + min_db;
+    return (x * -min_db / max_abs) + min_db;
+}
+// _denormalize + :205-206 _db_to_amp + "** power": magnitude the Griffin-Lim iterations keep fixed
+__global__ void ga_mag_kernel(const float* lin, float* mag, long long n, int mode, float max_abs, float min_db, float ref_db, float power)
 {
     GA_STRIDE(i, n) {
-        float x = lin[i];
-        x = x < -max_abs ? -max_abs : (x > max_abs ? max_abs : x);
-        const float db = ((x + max_abs) * -min_db / (2.0f * max_abs)) + min_db;
+        const float db = ga_denorm(lin[i], mode, max_abs, min_db);
         const float s = powf(10.0f, (db + ref_db) * 0.05f);
         mag[i] = powf(s, power);
+    }
+}
+// utils/audio.py:95-110 with :187-191 _mel_to_linear: mag = max(1e-10, inv_basis @ db_to_amp(denormalize(mel) + ref)) ** power.
+// One workgroup per frame: the frame's n_mels amplitudes in LDS, one dot product per bin (inv_basis row-major (nbin, n_mels)).
+__global__ void ga_mel_mag_kernel(const float* mel, const float* inv_basis, float* mag, int n_mels, int nbin, int mode, float max_abs,
+                                  float min_db, float ref_db, float power)
+{
+    extern __shared__ float ga_amp[];
+    const long long row = blockIdx.x;
+    for (int m = threadIdx.x; m < n_mels; m += blockDim.x)
+        ga_amp[m] = powf(10.0f, (ga_denorm(mel[row * n_mels + m], mode, max_abs, min_db) + ref_db) * 0.05f);
+    __syncthreads();
+    for (int f = threadIdx.x; f < nbin; f += blockDim.x) {
+        const float* w = inv_basis + (long long)f * n_mels;
+        float acc = 0.0f;
+        for (int m = 0; m < n_mels; ++m) acc += w[m] * ga_amp[m];
+        mag[row * nbin + f] = powf(acc > 1e-10f ? acc : 1e-10f, power);
     }
 }
 // angles = exp(2j*pi*rand) (utils/audio.py:131): spec = mag * angles
@@ -156,12 +181,25 @@ extern "C" size_t twv_griffin_lim_workspace_bytes(const twv_griffin_lim* h)
     return (size_t)(bf * h->nbin * 4 + bf * h->nbin * 8 * 2 + bf * h->n_fft * 4 + (long long)h->batch * h->len * 4 + 4096);
 }
 
-extern "C" int twv_inv_linear_spectrogram(twv_griffin_lim* h, const float* lin, const float* uniforms, int iters, double power, double ref_level_db,
-                                          double max_abs_value, double min_level_db, double preemphasis, void* workspace, float* out, void* stream)
+// utils/audio.py:127-137 + :27-30 for magnitudes already in the workspace (ga_workspace): random initial phase, iters x {stft -> unit
+// phase -> istft}, inverse pre-emphasis.  Shared by both fronts below.
+struct ga_workspace { float* mag; float2* spec; float2* D; float* ft; float* y; };
+static ga_workspace ga_carve(const twv_griffin_lim* h, void* workspace)
 {
-    if (!h || !lin || !uniforms || !workspace || !out || iters < 0) return twv_fail(TWV_E_INVALID, "bad argument");
-    hipStream_t st = (hipStream_t)stream;
     const long long bf = (long long)h->batch * h->frames, nspec = bf * h->nbin;
+    ga_workspace p;
+    char* w = (char*)workspace;
+    p.mag = (float*)w; w += (nspec * 4 + 255) / 256 * 256;
+    p.spec = (float2*)w; w += (nspec * 8 + 255) / 256 * 256;
+    p.D = (float2*)w; w += (nspec * 8 + 255) / 256 * 256;
+    p.ft = (float*)w; w += (bf * h->n_fft * 4 + 255) / 256 * 256;
+    p.y = (float*)w;
+    return p;
+}
+static int ga_griffin_lim(twv_griffin_lim* h, const ga_workspace& p, const float* uniforms, int iters, double preemphasis, float* out, hipStream_t st)
+{
+    const long long bf = (long long)h->batch * h->frames, nspec = bf * h->nbin;
+    float* mag = p.mag; float2* spec = p.spec; float2* D = p.D; float* ft = p.ft; float* y = p.y;
     if (!h->have_plans) {
         int n[1] = {h->n_fft};
         FFTCHK(hipfftPlanMany(&h->c2r, 1, n, nullptr, 1, h->nbin, nullptr, 1, h->n_fft, HIPFFT_C2R, (int)bf));
@@ -170,14 +208,6 @@ extern "C" int twv_inv_linear_spectrogram(twv_griffin_lim* h, const float* lin, 
     }
     FFTCHK(hipfftSetStream(h->c2r, st));
     FFTCHK(hipfftSetStream(h->r2c, st));
-    char* w = (char*)workspace;
-    float* mag = (float*)w; w += (nspec * 4 + 255) / 256 * 256;
-    float2* spec = (float2*)w; w += (nspec * 8 + 255) / 256 * 256;
-    float2* D = (float2*)w; w += (nspec * 8 + 255) / 256 * 256;
-    float* ft = (float*)w; w += (bf * h->n_fft * 4 + 255) / 256 * 256;
-    float* y = (float*)w;
-    hipLaunchKernelGGL(ga_mag_kernel, dim3(ga_grid(nspec)), dim3(256), 0, st, lin, mag, nspec, (float)max_abs_value, (float)min_level_db,
-                       (float)ref_level_db, (float)power);
     hipLaunchKernelGGL(ga_phase_init_kernel, dim3(ga_grid(nspec)), dim3(256), 0, st, mag, uniforms, spec, nspec);
     for (int it = 0; it <= iters; ++it) {
         // librosa.istft: inverse FFT of every frame (the C2R transform may overwrite its input: spec is rebuilt each round), overlap-add
@@ -194,4 +224,36 @@ extern "C" int twv_inv_linear_spectrogram(twv_griffin_lim* h, const float* lin, 
     hipLaunchKernelGGL(ga_deemph_kernel, dim3(ga_grid((long long)h->batch * nchunk)), dim3(256), 0, st, y, out, h->batch, h->len, (float)preemphasis, 1024);
     HIPCHK(hipGetLastError());
     return TWV_OK;
+}
+
+extern "C" int twv_inv_linear_spectrogram(twv_griffin_lim* h, const float* lin, const float* uniforms, int iters, double power, double ref_level_db,
+                                          double max_abs_value, double min_level_db, double preemphasis, void* workspace, float* out, void* stream)
+{
+    if (!h || !lin || !uniforms || !workspace || !out || iters < 0) return twv_fail(TWV_E_INVALID, "bad argument");
+    hipStream_t st = (hipStream_t)stream;
+    const long long nspec = (long long)h->batch * h->frames * h->nbin;
+    const ga_workspace p = ga_carve(h, workspace);
+    hipLaunchKernelGGL(ga_mag_kernel, dim3(ga_grid(nspec)), dim3(256), 0, st, lin, p.mag, nspec, 1, (float)max_abs_value, (float)min_level_db,
+                       (float)ref_level_db, (float)power);
+    return ga_griffin_lim(h, p, uniforms, iters, preemphasis, out, st);
+}
+
+extern "C" int twv_inv_spectrogram(twv_griffin_lim* h, const float* spec, int n_channels, const float* inv_basis, const float* uniforms,
+                                   int iters, double power, double ref_level_db, double max_abs_value, double min_level_db, int norm_mode,
+                                   double preemphasis, void* workspace, float* out, void* stream)
+{
+    if (!h || !spec || !uniforms || !workspace || !out || iters < 0 || n_channels < 1 || norm_mode < 0 || norm_mode > 4)
+        return twv_fail(TWV_E_INVALID, "bad argument");
+    if (!inv_basis && n_channels != h->nbin) return twv_fail(TWV_E_INVALID, "a linear spectrogram has n_fft/2 + 1 channels; a mel spectrogram needs inv_basis");
+    if (inv_basis && n_channels > 12288) return twv_fail(TWV_E_INVALID, "n_channels too large");
+    hipStream_t st = (hipStream_t)stream;
+    const long long bf = (long long)h->batch * h->frames, nspec = bf * h->nbin;
+    const ga_workspace p = ga_carve(h, workspace);
+    if (inv_basis)
+        hipLaunchKernelGGL(ga_mel_mag_kernel, dim3((unsigned)bf), dim3(256), (size_t)n_channels * 4, st, spec, inv_basis, p.mag, n_channels, h->nbin,
+                           norm_mode, (float)max_abs_value, (float)min_level_db, (float)ref_level_db, (float)power);
+    else
+        hipLaunchKernelGGL(ga_mag_kernel, dim3(ga_grid(nspec)), dim3(256), 0, st, spec, p.mag, nspec, norm_mode, (float)max_abs_value,
+                           (float)min_level_db, (float)ref_level_db, (float)power);
+    return ga_griffin_lim(h, p, uniforms, iters, preemphasis, out, st);
 }

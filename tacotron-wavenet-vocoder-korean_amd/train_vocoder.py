@@ -7,8 +7,8 @@ forward/backward (twv_wavenet_train_loss_grad), the gradient all-reduce over RCC
 The feeder is datafeeder_wavenet.py's batch rule without its thread and TF queue: per data directory (= speaker) npz files with
 'audio' (T,) and 'mel' (T/hop, num_mels); every example is cut to `sample_size` (floored to a hop multiple) at a RANDOM FRAME
 offset, audio and mel in step (datafeeder_wavenet.py:153-156, which draws from the global np.random, not the feeder's rng).
-Dataset preparation and the text side of those npz files are out of scope; `--synthetic` trains on
-random data of the right shapes (no dataset exists in this image)."""
+Those npz files are written from wav files by preprocess.py (`python -m twvk_amd.preprocess --in_dir ... --out_dir ...`); their text side
+is out of scope.  `--synthetic` trains on random data of the right shapes."""
 import argparse
 import os
 import time
