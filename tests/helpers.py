@@ -1,12 +1,17 @@
 """shared builders for the parity tests: one config -> (oracle dims, oracle blob, product model)."""
 import numpy as np
 
+from sensitive_inputs import (assert_mol_inputs, assert_onehot_inputs, knife_edge_mol, knife_edge_onehot, narrow_logistic_uniforms,
+                              shift_mol_head)
+
 
 def make_case(O, dilations, scalar_input=True, S=512, Q=256, out_channels=30, ifw=32, use_bias=True, G=32, gc_card=2,
-              L=80, up=(5, 5, 12), seed=0, scale=0.05):
+              L=80, up=(5, 5, 12), seed=0, scale=0.05, shift=0.0):
     d = O.make_dims(dilations, R=32, D=32, S=S, Q=Q, out_channels=out_channels, scalar_input=scalar_input, ifw=ifw,
                     use_bias=use_bias, G=G, gc_card=gc_card, L=L, up=up)
     tensors = O.random_tensors(d, seed=seed, scale=scale)
+    if shift and scalar_input:
+        tensors = shift_mol_head(tensors, out_channels, by=shift)     # narrow components: the samples leave the clamp
     blob = O.blob_from_tensors(d, tensors)
     return d, tensors, blob
 
@@ -42,3 +47,29 @@ def first_mismatch(a, b):
     a = np.asarray(a); b = np.asarray(b)
     bad = np.argwhere(~((a == b) | (np.isnan(a) & np.isnan(b))))
     return None if bad.size == 0 else tuple(int(v) for v in bad[0])
+
+
+def builder_workers(d, B, T):
+    """processes for the knife-edge builders: placing an edge costs about as much host time as the oracle's step, so long
+    multi-stream cases deal their streams out (at most 16: the tests share a host)"""
+    return min(B, 16) if B > 1 and B * T * d.n_layers >= 200000 else 1
+
+
+def sensitive_mol(O, d, blob, U, gc, first_input, B, T, seed=2, prime=None):
+    """(uniforms, the oracle's samples) for a MoL case whose point is sample equality: mol_uniforms (the logistic draw narrowed
+    where the model has no bias to shift) with every mixture selection on its edge, and the conditions of
+    tests/sensitive_inputs.py asserted on the oracle's output"""
+    u0 = mol_uniforms(B, T, d.O // 3, seed)
+    if not d.use_bias:
+        u0 = narrow_logistic_uniforms(u0)
+    u, want, n = knife_edge_mol(O, d, blob, U, gc, first_input, u0, prime, builder_workers(d, B, T))
+    assert_mol_inputs(u, want, n)
+    return u, want
+
+
+def sensitive_onehot(O, d, blob, U, gc, first_input, u0, temperature=1.0, prime=None):
+    """the one-hot counterpart: the plain draws u0 moved onto the class boundaries, conditions asserted"""
+    B, T = np.shape(u0)
+    u, want, n = knife_edge_onehot(O, d, blob, U, gc, first_input, u0, temperature, prime, builder_workers(d, B, T))
+    assert_onehot_inputs(u, want, n, d.Q)
+    return u, want

@@ -1,8 +1,11 @@
-"""C5: text -> mel -> wave on the GPU equals the CPU oracle's Tacotron restatement chained into its WaveNet restatement."""
+"""C5: text -> mel -> wave on the GPU equals the CPU oracle's Tacotron restatement chained into its WaveNet restatement.
+
+The vocoder's inputs are those of tests/sensitive_inputs.py (shifted MoL head at weight scale 0.05, every mixture selection on its
+edge, conditions asserted on the oracle's output first): the oracle chain runs first, the uniforms it yields go to the device."""
 import numpy as np
 import pytest
 
-from helpers import first_mismatch, make_case, make_model, mol_uniforms
+from helpers import first_mismatch, make_case, make_model, sensitive_mol
 
 pytestmark = pytest.mark.gpu
 
@@ -17,20 +20,19 @@ def test_text_to_wave_matches_chained_oracles(oracle):
     tt = oracle.taco_random_tensors(td, seed=5)
     syn = Synthesizer(); syn.load(tt, num_speakers=2, hparams=hp)
     dil = [1, 2, 4, 8]
-    wd, wt, wblob = make_case(oracle, dil, S=64, scale=0.2)
+    wd, wt, wblob = make_case(oracle, dil, S=64, shift=5.0)
     voc = make_model(2, dil, wt, S=64)
     tokens = [[5, 9, 33, 12, 1], [7, 7, 1]]
     spk = np.array([1, 0], np.int32)
     n_frames = 4
     T = n_frames * 300
-    u = mol_uniforms(2, T, 10, seed=9)
-    out = text_to_wave(syn, voc, tokens, spk, u, n_frames=n_frames)
     # oracle chain: Tacotron restatement -> (mel hand-off, synthesizer.py:279 / generate.py:151-155) -> WaveNet restatement
     tok = np.array([[5, 9, 33, 12, 1], [7, 7, 1, 0, 0]], np.int32)
     mel_o, _, al_o = oracle.taco_infer(td, oracle.taco_blob(td, tt), tok, np.array([5, 3], np.int32), spk)
-    assert first_mismatch(out["mel"].cpu().numpy(), mel_o[:, :n_frames]) is None
     U = oracle.upsample(wd, wblob, mel_o[:, :n_frames])
-    ref = oracle.generate_mol(wd, wblob, oracle.State(wd, 2), U, spk, np.zeros(2, np.float32), u)
+    u, ref = sensitive_mol(oracle, wd, wblob, U, spk, np.zeros(2, np.float32), 2, T, seed=9)
+    out = text_to_wave(syn, voc, tokens, spk, u, n_frames=n_frames)
+    assert first_mismatch(out["mel"].cpu().numpy(), mel_o[:, :n_frames]) is None
     got = out["audio"].cpu().numpy()
     assert got.shape == (2, T)
     assert first_mismatch(got, ref) is None, first_mismatch(got, ref)
@@ -54,14 +56,13 @@ def test_text_to_wave_at_default_dims_on_the_xcd_kernel(oracle):
     tt = oracle.taco_random_tensors(td, seed=31)
     syn = Synthesizer(); syn.load(tt, num_speakers=2, hparams=hp)
     dil = [2 ** i for i in range(10)] * 3
-    wd, wt, wblob = make_case(oracle, dil, seed=7)
+    wd, wt, wblob = make_case(oracle, dil, seed=7, shift=5.0)
     B, n_frames = 8, 40                                                  # 40 of the 125 frames -> 12 000 samples per utterance
     T = n_frames * 300
     rng = np.random.RandomState(12)
     lengths = [40, 33, 40, 21, 37, 40, 9, 30]
     tokens = [list(rng.randint(2, 80, ln - 1)) + [1] for ln in lengths]
     spk = (np.arange(B) % 2).astype(np.int32)
-    u = mol_uniforms(B, T, 10, seed=13)
     # ---- oracle chain
     tok = np.zeros((B, 40), np.int32)
     for i, t in enumerate(tokens):
@@ -69,11 +70,7 @@ def test_text_to_wave_at_default_dims_on_the_xcd_kernel(oracle):
     mel_o, _, _ = oracle.taco_infer(td, oracle.taco_blob(td, tt), tok, np.asarray(lengths, np.int32), spk, want_linear=False)
     assert mel_o.shape == (B, 125, 80)
     U = oracle.upsample(wd, wblob, mel_o[:, :n_frames])
-    oracle.set_threads(min(B, oracle.set_threads(1)))
-    try:
-        ref = oracle.generate_mol(wd, wblob, oracle.State(wd, B), U, spk, np.zeros(B, np.float32), u)
-    finally:
-        oracle.set_threads(1)
+    u, ref = sensitive_mol(oracle, wd, wblob, U, spk, np.zeros(B, np.float32), B, T, seed=13)
     # ---- 8 utterances, one launch
     voc = make_model(B, dil, wt)
     assert voc.fused_conditioning(), "the 30-layer S=512 MoL vocoder must be served by the XCD-per-stream kernel"

@@ -3,14 +3,19 @@
 Input condition (so that sample equality cannot hide a wrong network): the MoL sampler clamps to +-1, and with plain random weights
 about half of the oracle's samples sit on the clamp.  Every MoL case that has biases therefore builds its weights with scale 0.05
 and lowers the log-scale third of wavenet/conv1d_2/bias by 5, and asserts on the ORACLE's output, before comparing, that at most 5 %
-of the samples are +-1.  use_bias=False variants cannot be shifted and are exempt, as is the scale-0.2 layer-dump case: the dumps
-compare z, x and the raw outputs directly."""
+of the samples are +-1.  The cases that go through run_mol / run_onehot also put every mixture selection / every one-hot draw on its
+edge (tests/sensitive_inputs.py: knife_edge_mol, knife_edge_onehot; use_bias=False variants get the narrowed logistic draw
+instead of the shift) and assert the edge count and the uniform range.  Exempt: the layer-dump cases (plain inputs; the MoL one at scale 0.2, the one-hot ones at 0.3: the dumps
+compare z, x and the raw outputs directly -- the peaked one-hot distribution of scale 0.3 is covered there and nowhere else),
+test_wide_keeps_the_clamp_covered (plain inputs on purpose), and test_wide_generate_cli_restores_a_bundle, whose uniforms are drawn
+by the command line tool from its --seed and cannot be injected: shifted head, clamp share asserted."""
 import json
 
 import numpy as np
 import pytest
 
-from helpers import first_mismatch, mol_uniforms
+from helpers import first_mismatch, mol_uniforms, sensitive_mol, sensitive_onehot
+from sensitive_inputs import assert_off_the_clamp, shift_mol_head
 
 pytestmark = pytest.mark.gpu
 
@@ -29,10 +34,8 @@ def make_case(O, dilations, R, D, scalar_input=True, S=512, Q=256, out_channels=
     d = O.make_dims(dilations, R=R, D=D, S=S, Q=Q, out_channels=out_channels, scalar_input=scalar_input, ifw=ifw, use_bias=use_bias,
                     G=G, gc_card=gc_card, L=L, up=up)
     tensors = dict(O.random_tensors(d, seed=seed, scale=scale))
-    if shift and scalar_input and use_bias:
-        b = tensors["wavenet/conv1d_2/bias"].copy()
-        b[2 * (out_channels // 3):] -= 5            # narrow mixture components: the samples leave the clamp
-        tensors["wavenet/conv1d_2/bias"] = b
+    if shift and scalar_input:
+        tensors = shift_mol_head(tensors, out_channels)      # narrow mixture components: the samples leave the clamp
     return d, tensors, O.blob_from_tensors(d, tensors)
 
 
@@ -48,11 +51,6 @@ def make_model(batch, dilations, tensors, R, D, scalar_input=True, S=512, Q=256,
         m.set_option(k, v)
     m.load_weights(tensors)
     return m
-
-
-def assert_off_the_clamp(want):
-    frac = float(np.mean(np.abs(want) == 1.0))
-    assert frac <= 0.05, "the oracle's own samples sit on the clamp: %.1f %%" % (100 * frac)
 
 
 def run_mol(O, dil, B, R, D, T=None, t_mel=1, debug_steps=0, options=(), seed=0, scale=0.05, shift=True, **kw):
@@ -72,15 +70,18 @@ def run_mol(O, dil, B, R, D, T=None, t_mel=1, debug_steps=0, options=(), seed=0,
         U_o = U_g = None
     gc = (np.arange(B) % 2).astype(np.int32) if G else None
     seed_in = (2 * rng.rand(B) - 1).astype(np.float32)
-    u = mol_uniforms(B, T, d.O // 3)
-    want = O.generate_mol(d, blob, O.State(d, B), U_o, gc, seed_in, u)
-    if shift and kw.get("use_bias", True):
-        assert_off_the_clamp(want)
+    if shift:
+        u, want = sensitive_mol(O, d, blob, U_o, gc, seed_in, B, T)
+    else:
+        u = mol_uniforms(B, T, d.O // 3)
+        want = O.generate_mol(d, blob, O.State(d, B), U_o, gc, seed_in, u)
     res = m.generate(U_g, gc, seed_in, u, debug_steps=debug_steps)
     return d, blob, m, want, res, (U_o, U_g, gc, seed_in, u)
 
 
-def run_onehot(O, dil, B, T, R, D, temperature=1.0, debug_steps=0, scale=0.3, **kw):
+def run_onehot(O, dil, B, T, R, D, temperature=1.0, debug_steps=0, scale=0.12, sensitive=True, **kw):
+    """scale 0.12: at 0.3 the distribution is so peaked that more than 10 % of the draws land in the last non-empty class, where
+    no edge exists; the layer-dump cases keep 0.3 and plain draws (sensitive=False)"""
     Q = kw.get("Q", 256)
     d, tensors, blob = make_case(O, dil, R, D, scalar_input=False, scale=scale, **kw)
     m = make_model(B, dil, tensors, R, D, scalar_input=False, **kw)
@@ -90,7 +91,10 @@ def run_onehot(O, dil, B, T, R, D, temperature=1.0, debug_steps=0, scale=0.3, **
     gc = (np.arange(B) % 2).astype(np.int32) if G else None
     seed_in = rng.randint(Q, size=B).astype(np.int32)
     u = rng.random_sample((B, T))
-    want = O.generate_mulaw(d, blob, O.State(d, B), U, gc, seed_in, u, temperature)
+    if sensitive:
+        u, want = sensitive_onehot(O, d, blob, U, gc, seed_in, u, temperature)
+    else:
+        want = O.generate_mulaw(d, blob, O.State(d, B), U, gc, seed_in, u, temperature)
     res = m.generate(U, gc, seed_in, u, temperature=temperature, debug_steps=debug_steps)
     return d, blob, m, want, res, (U, gc, seed_in, u)
 
@@ -126,13 +130,22 @@ def test_wide_layer_dumps(torch_cuda, oracle, R, D):
 def test_wide_onehot_layer_dumps(torch_cuda, oracle, R, D, temperature):
     dil = [1, 2, 4, 8, 1, 2, 4, 8]
     B, T, dbg = 2, 40, 3
-    d, blob, m, want, (got, dump), (U, gc, seed_in, u) = run_onehot(oracle, dil, B, T, R, D, S=128, temperature=temperature, debug_steps=dbg)
+    d, blob, m, want, (got, dump), (U, gc, seed_in, u) = run_onehot(oracle, dil, B, T, R, D, S=128, temperature=temperature, debug_steps=dbg,
+                                                                            scale=0.3, sensitive=False)
     check_dumps(oracle, d, blob, dump.cpu().numpy(), want, seed_in, U, gc, B, len(dil), dbg)
     assert np.array_equal(got.cpu().numpy(), want), first_mismatch(got.cpu().numpy(), want)
 
 
 # ---------------------------------------------------------------- 2. variants
 VARIANT_DIL = [1, 2, 4, 8, 16, 1, 2]
+
+
+def test_wide_keeps_the_clamp_covered(torch_cuda, oracle):
+    """the sampler's clamp to +-1 stays tested: plain inputs ON PURPOSE (unshifted head at scale 0.1, plain uniforms); the oracle's
+    samples must hold +1, -1 and values strictly inside"""
+    d, blob, m, want, got, _ = run_mol(oracle, VARIANT_DIL, 3, 64, 64, T=70, scale=0.1, shift=False)
+    assert (want == 1.0).any() and (want == -1.0).any() and (np.abs(want) < 1.0).any()
+    assert first_mismatch(got.cpu().numpy(), want) is None
 
 
 @pytest.mark.parametrize("kw", [dict(), dict(use_bias=False), dict(G=0), dict(L=0), dict(ifw=8), dict(S=64), dict(S=1024), dict(up=(3, 4))])
@@ -157,9 +170,7 @@ def test_wide_global_condition_passed_as_embedding(torch_cuda, oracle):
     rng = np.random.RandomState(6)
     mel = rng.uniform(-4, 4, (B, 1, 80)).astype(np.float32)
     seed_in = (2 * rng.rand(B) - 1).astype(np.float32)
-    u = mol_uniforms(B, T, 10)
-    want = oracle.generate_mol(d_id, blob_id, oracle.State(d_id, B), oracle.upsample(d_id, blob_id, mel)[:, :T].copy(), ids, seed_in, u)
-    assert_off_the_clamp(want)
+    u, want = sensitive_mol(oracle, d_id, blob_id, oracle.upsample(d_id, blob_id, mel)[:, :T].copy(), ids, seed_in, B, T)
     tensors_e = {k: v for k, v in tensors_id.items() if k != "wavenet/gc_embedding"}
     m = make_model(B, dil, tensors_e, 64, 64, gc_card=0)
     got = m.generate(m.create_upsample(mel)[:, :T].contiguous(), table[ids], seed_in, u).cpu().numpy()
@@ -237,17 +248,11 @@ def test_wide_priming_then_generation(torch_cuda, oracle, R, D, scalar):
     seedwave = rng.uniform(-1, 1, (B, rf)).astype(np.float32) if scalar else rng.randint(64, size=(B, rf)).astype(np.int32)
     U = rng.uniform(-4, 4, (B, T, 80)).astype(np.float32)
     gc = np.array([0, 1], np.int32)
-    st = oracle.State(d, B)
-    zeros = np.zeros((B, 80), np.float32)
-    for i in range(rf - 1):
-        oracle.step(d, blob, st, seedwave[:, i], zeros, gc)
     if scalar:
-        u = mol_uniforms(B, T, 10)
-        want = oracle.generate_mol(d, blob, st, U, gc, seedwave[:, -1], u)
-        assert_off_the_clamp(want)
+        u, want = sensitive_mol(oracle, d, blob, U, gc, seedwave[:, -1], B, T, prime=seedwave[:, :rf - 1])
     else:
-        u = np.random.RandomState(3).random_sample((B, T))
-        want = oracle.generate_mulaw(d, blob, st, U, gc, seedwave[:, -1], u, 1.0)
+        u, want = sensitive_onehot(oracle, d, blob, U, gc, seedwave[:, -1], np.random.RandomState(3).random_sample((B, T)), 1.0,
+                                   prime=seedwave[:, :rf - 1])
     m.prime(seedwave[:, :rf - 1], None, gc)
     got = m.generate(U, gc, seedwave[:, -1], u).cpu().numpy()
     assert first_mismatch(got, want) is None
@@ -277,9 +282,7 @@ def test_wide_conditioning_is_bounded(torch_cuda, oracle):
     mel = rng.uniform(-4, 4, (B, 3, 80)).astype(np.float32)
     gc = np.array([0, 1], np.int32)
     seed_in = (2 * rng.rand(B) - 1).astype(np.float32)
-    u = mol_uniforms(B, T, 10)
-    want = oracle.generate_mol(d, blob, oracle.State(d, B), oracle.upsample(d, blob, mel), gc, seed_in, u)
-    assert_off_the_clamp(want)
+    u, want = sensitive_mol(oracle, d, blob, oracle.upsample(d, blob, mel), gc, seed_in, B, T)
     m = make_model(B, dil, tensors, R, D, S=128)
     m.MAX_COND_BYTES = 4 * B * len(dil) * 2 * D * 450         # room for 450 steps -> one hop (300 steps) per call: three calls
     assert m._steps_per_call(T) == 300
