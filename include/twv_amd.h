@@ -243,6 +243,12 @@ size_t twv_wavenet_train_workspace_bytes(const twv_wavenet_trainer* h);
  * was freed and re-allocated (a caching allocator may hand out the same address) or written by anything else between two steps. */
 int twv_wavenet_train_reset_workspace(twv_wavenet_trainer* h);
 int twv_wavenet_train_output_width(const twv_wavenet_trainer* h);          /* n_samples - receptive_field (model.py:135) */
+/* host-only: which kernel families twv_wavenet_train_loss_grad runs for this trainer, as a string the handle owns:
+ *   "lc=<fused|staged> head=<skinny+c2bwd|skinny|gemm> loss=<mol<10>|mol<0>|softmax> nsplit=<n> carve_floats=<n>"
+ * lc: frame-rate lc projections inside the layer kernels, or the materialised upsampler; head: conv1d_2 as the skinny kernel (with or
+ * without its fused backward) or library GEMMs; nsplit: K slabs of the wide weight gradients; carve_floats: the floats loss_grad takes
+ * from the start of the workspace (workspace_bytes / 4 is at least that).  A label for tests and measurements. */
+const char* twv_wavenet_train_route(const twv_wavenet_trainer* h);
 /* loss (device float[1]) and d loss / d params (device float[param_floats], overwritten).
  * audio (B, n_samples) float in [-1,1]; lc (B, n_samples/hop, lc_channels); gc_ids (B) int32.
  * workspace: workspace_bytes of device memory that belongs to the trainer between calls (a pointer seen for the first time is

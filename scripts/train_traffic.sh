@@ -9,9 +9,9 @@ REPO=$PWD
 OUT=$PWD/gpurun_out/train_traffic_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-for C in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/pmc_$C -- python $REPO/scripts/train_bench.py --steps 1 --warmup 1 > $OUT/pmc_$C.log 2>&1
+for C in FETCH_SIZE WRITE_SIZE; do      # each pass under a limit of its own; a pass that fails ends the script (nothing more runs on the card)
+  timeout -k 10 300 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/pmc_$C -- python $REPO/scripts/train_bench.py --steps 1 --warmup 1 > $OUT/pmc_$C.log 2>&1 || { rc=$?; tail -5 $OUT/pmc_$C.log; exit $rc; }
 done
 cd $REPO
-python scripts/pmc_to_train_traffic.py "$OUT" "$TAG"
+python scripts/pmc_to_train_traffic.py "$OUT" "$TAG" || exit $?
 mkdir -p $REPO/gpurun_out && cp $REPO/profiles/traffic.json $REPO/gpurun_out/traffic.json

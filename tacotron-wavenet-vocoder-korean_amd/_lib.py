@@ -241,6 +241,7 @@ def lib():
     for n in ("twv_wavenet_train_param_floats", "twv_wavenet_train_workspace_bytes"):
         getattr(L, n).argtypes = [vp]; getattr(L, n).restype = C.c_size_t
     L.twv_wavenet_train_output_width.argtypes = [vp]
+    L.twv_wavenet_train_route.argtypes = [vp]; L.twv_wavenet_train_route.restype = C.c_char_p
     L.twv_wavenet_train_reset_workspace.argtypes = [vp]
     L.twv_wavenet_train_loss_grad.argtypes = [vp, fp, fp, fp, ip, vp, fp, fp, vp]
     L.twv_wavenet_train_l2.argtypes = [vp, fp, C.c_double, vp, fp, fp, vp]
@@ -260,7 +261,7 @@ EXPORTS = ["twv_last_error", "twv_version", "twv_wavenet_create", "twv_wavenet_d
            "twv_eval_elementwise64", "twv_sample_categorical", "twv_selftest", "twv_debug_occupy", "twv_tacotron_create", "twv_tacotron_destroy", "twv_tacotron_blob_floats",
            "twv_tacotron_packed_bytes", "twv_tacotron_workspace_bytes", "twv_tacotron_pack", "twv_tacotron_infer", "twv_tacotron_set_profile_buffer", "twv_tacotron_set_option", "twv_tacotron_gemm_stats", "twv_tacotron_decoder_kernel_name",
            "twv_wavenet_train_create", "twv_wavenet_train_destroy", "twv_wavenet_train_param_floats", "twv_wavenet_train_workspace_bytes",
-           "twv_wavenet_train_output_width", "twv_wavenet_train_reset_workspace", "twv_wavenet_train_loss_grad", "twv_adam_ema_step", "twv_wavenet_train_l2",
+           "twv_wavenet_train_output_width", "twv_wavenet_train_route", "twv_wavenet_train_reset_workspace", "twv_wavenet_train_loss_grad", "twv_adam_ema_step", "twv_wavenet_train_l2",
            "twv_clip_by_global_norm", "twv_griffin_lim_create", "twv_griffin_lim_destroy", "twv_griffin_lim_samples",
            "twv_griffin_lim_workspace_bytes", "twv_inv_linear_spectrogram", "twv_inv_spectrogram", "twv_spectrogram_create",
            "twv_spectrogram_destroy", "twv_spectrogram_frames", "twv_spectrogram_workspace_bytes", "twv_spectrogram_analyze", "twv_crc32c"]

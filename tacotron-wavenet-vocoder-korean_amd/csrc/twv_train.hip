@@ -49,6 +49,8 @@ struct twv_wavenet_trainer {
     long long ws_floats;
     long long l2_off;                     // twv_wavenet_train_l2's scratch inside the workspace (floats)
     const void* ws_clean;                 // the workspace that has been cleared (see twv_wavenet_train_loss_grad)
+    long long carve_floats;               // what tr_carve takes from the start of the workspace (l2_off == carve_floats)
+    std::string route;                    // twv_wavenet_train_route's answer
 };
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1852,22 +1854,108 @@ static rocblas_status gemm_tn_splitk(rocblas_handle h, hipStream_t st, int M, in
     return rocblas_status_success;
 }
 
+// Which kernel families twv_wavenet_train_loss_grad runs for (dims, batch, n_samples).  The ONE place these predicates are written:
+// create (the 32-bit addressing limit of the fused route), loss_grad (the dispatch) and twv_wavenet_train_route (the label a test
+// reads) all call it.
+enum { TR_LOSS_MOL10 = 0, TR_LOSS_MOLN = 1, TR_LOSS_SOFTMAX = 2 };
+struct TrainRoute {
+    bool fused_lc;      // tr_layer_fwdc / bwd1<true> / bwd2c on frame-rate lc projections; else the materialised upsampler + the <false> kernels
+    bool skinny;        // tr_skinny_nn_kernel for conv1d_2; else rocBLAS + tr_bias_add_kernel
+    bool fuse_c2;       // tr_conv2_bwd_kernel (dC1, db1, dW2 in one pass; conv1d_1's relu applied by its readers)
+    int loss;           // TR_LOSS_*
+    int nsplit;         // K slabs (whole batch entries) of the wide weight gradients
+};
+static TrainRoute tr_route(const twv_wavenet_dims& d, int batch, int n_samples)
+{
+    TrainRoute r;
+    int hop = 1;
+    for (int i = 0; i < d.n_upsample; ++i) hop *= d.upsample_factor[i];
+    r.fused_lc = d.n_upsample == 3 && hop >= 32 && hop <= 512 && d.lc_channels == 80;
+    int rf = (d.scalar_input ? d.initial_filter_width : 2);           // model.py:31-39
+    for (int l = 0; l < d.n_layers; ++l) rf += d.dilations[l];
+    const long long RO = (long long)batch * (n_samples - rf);
+    const int S = d.skip_channels, O = d.scalar_input ? d.out_channels : d.quantization_channels;
+    r.skinny = O <= 32 && (S & 63) == 0 && S * 32 * 4 <= 64 * 1024 && RO * S * 4 < (1LL << 31);
+    r.fuse_c2 = r.skinny && (S & 63) == 0 && 2048 % (S >> 6) == 0;      // (`part`: 2048 x 64 floats)
+    r.loss = !d.scalar_input ? TR_LOSS_SOFTMAX : (O / 3 == 10 ? TR_LOSS_MOL10 : TR_LOSS_MOLN);
+    r.nsplit = 1;
+    for (int c = 2; c <= 16 && c <= batch; ++c) if (batch % c == 0) r.nsplit = c;   // slabs of whole batch entries: RO = B * ow rows
+    return r;
+}
+
+// The workspace carve of twv_wavenet_train_loss_grad, each piece rounded up to 64 floats.  create runs it on a null base for the SIZE of
+// the workspace (no hand-kept estimate beside it), loss_grad for the pointers; returns the floats taken.
+struct TrainCarve {
+    float* ups[5]; long long upT[5];
+    float *dUa, *dUb, *xunf; int32_t* qin; float* ohpart;
+    float *X[TWV_MAX_LAYERS + 1], *TH[TWV_MAX_LAYERS], *SG[TWV_MAX_LAYERS];
+    float *ZC, *dZC, *PRE, *dXa, *dXb, *SK, *C1, *dS, *Y, *dY, *emb, *demb, *GCP, *dGCP, *WV, *WS, *GV, *GS, *part, *slabs, *zpage, *kpart, *wpart;
+    float *ctab, *melsh, *Qall, *Dbuf, *dctab, *PTall, *Rall, *tsum, *dGCPall, *bsum64;
+    long long vstride, slab_ls, q_ls, pt_ls, tsum_ls;
+};
+static long long tr_carve(const twv_wavenet_trainer* h, float* base, TrainCarve& c)
+{
+    const twv_wavenet_dims& d = h->d;
+    const int B = h->B, T = h->T, Tn = h->Tn, NL = h->NL, S = h->S, O = h->O, L = h->L, G = h->G, ow = h->ow;
+    const long long Rr = (long long)B * Tn, RT = (long long)B * T, RO = (long long)B * ow;
+    long long used = 0;
+    auto take = [&](long long n) { float* p = base ? base + used : nullptr; used += (n + 63) / 64 * 64; return p; };
+    c.upT[0] = T / h->hop;
+    for (int i = 0; i < d.n_upsample; ++i) c.upT[i + 1] = c.upT[i] * d.upsample_factor[i];
+    c.ups[0] = nullptr;                                      // (the caller's mel frames)
+    for (int i = 1; i <= d.n_upsample; ++i) c.ups[i] = take((long long)B * c.upT[i] * L);
+    c.dUa = take(RT * L); c.dUb = take(RT * L);
+    c.xunf = take(Rr * h->ifw);
+    c.qin = reinterpret_cast<int32_t*>(take(RT));
+    c.ohpart = take(d.scalar_input ? 0 : 256LL * 2 * d.quantization_channels * 32);
+    for (int l = 0; l <= NL; ++l) c.X[l] = take(Rr * 32);
+    for (int l = 0; l < NL; ++l) { c.TH[l] = take(Rr * 32); c.SG[l] = take(Rr * 32); }
+    const int ZW = NL * 32;                                  // stacked skip input: ZC[(b,p)][l*32 + j]
+    c.ZC = take(RO * ZW); c.dZC = take(RO * ZW);
+    c.PRE = take(Rr * 64);
+    c.dXa = take(Rr * 32); c.dXb = take(Rr * 32);
+    c.SK = take(RO * S); c.C1 = take(RO * S); c.dS = take(RO * S);
+    c.Y = take(RO * O); c.dY = take(RO * O);
+    c.emb = take((long long)B * G); c.demb = take((long long)B * G);
+    c.GCP = take((long long)B * 64 * NL); c.dGCP = take((long long)B * 64);
+    c.vstride = 64LL * (64 + L + G);
+    c.WV = take(c.vstride * NL); c.WS = take((long long)ZW * S);       // weight views
+    c.GV = take(c.vstride * NL); c.GS = take((long long)ZW * S);       // gradient views
+    c.part = take(512LL * 96 * 64 + 1024LL * 512);
+    c.slab_ls = 256LL * GQ_N * 1024;
+    c.slabs = take(c.slab_ls * NL);                          // every layer's gradient slabs: reduced in one launch after the layer loop
+    c.zpage = take(1024);
+    c.kpart = take(16LL * (ZW > S ? ZW : S) * S);            // split-K partials (dW1, dW2, stacked dWs)
+    c.wpart = take(2048LL * 64 * 32);                        // tr_conv2_bwd_kernel: [2048 / CG chunks][S][32] = 2048 x 64 x 32 whatever S is
+    const int F = T / h->hop;                                // mel frames per entry
+    c.ctab = take(4LL * 512);
+    c.melsh = take((long long)B * F * 4 * L);
+    c.q_ls = (long long)B * F * 4 * 64;
+    c.Qall = take((c.q_ls + 64) * NL);
+    c.Dbuf = take(RT * 4);                                   // sum over layers of dPRE . Q_j per U row (fused lc backward)
+    c.dctab = take(4LL * 512);
+    c.pt_ls = (long long)B * ((Tn + 31) / 32) * 512;
+    c.PTall = take((c.pt_ls + 64) * NL);
+    c.Rall = take((c.q_ls + 64) * NL);
+    c.tsum_ls = (long long)B * ((Tn + 31) / 32) * 96;        // layers back to back: the column sums treat (layer, batch entry) as segments
+    c.tsum = take(c.tsum_ls * NL);
+    c.dGCPall = take((long long)B * 64 * NL);
+    c.bsum64 = take(64LL * NL);
+    return used;
+}
+
 extern "C" int twv_wavenet_train_create(const twv_wavenet_dims* dims, int batch, int n_samples, twv_wavenet_trainer** out)
 {
     if (dims && dims->gc_channels > 0 && dims->gc_cardinality < 1)
         return twv_fail(TWV_E_UNSUPPORTED, "training needs global_condition_cardinality (the gc_embedding table is a trained variable; model.py:191-195)");
     if (!dims || !out || batch < 1) return twv_fail(TWV_E_INVALID, "bad argument");
     const twv_wavenet_dims& d = *dims;
-    {
-        // only the FUSED layer kernels (tr_layer_fwdc_kernel / tr_layer_bwd2c_kernel: three upsampling stages, 32 <= hop <= 512, 80 mel
-        // channels -- the same test as fused_lc in twv_wavenet_train_loss_grad) address a layer's activations with 32-bit byte offsets;
-        // the pointer kernels of every other model keep 64-bit addresses and take any size
-        int hop = 1;
-        for (int i = 0; i < d.n_upsample; ++i) hop *= d.upsample_factor[i];
-        const bool fused_lc = d.n_upsample == 3 && hop >= 32 && hop <= 512 && d.lc_channels == 80;
-        if (fused_lc && (long long)batch * n_samples * 64 * 4 >= (1LL << 31))
-            return twv_fail(TWV_E_UNSUPPORTED, "batch x samples too large: the fused layer kernels address a layer's activations with 32-bit byte offsets (batch * samples < 8.3 M)");
-    }
+    if (d.n_layers < 1 || d.n_layers > TWV_MAX_LAYERS || d.n_upsample < 0 || d.n_upsample > 4) return twv_fail(TWV_E_INVALID, "bad dims");
+    // only the FUSED layer kernels (tr_layer_fwdc_kernel / tr_layer_bwd2c_kernel: three upsampling stages, 32 <= hop <= 512, 80 mel
+    // channels: tr_route) address a layer's activations with 32-bit byte offsets; the pointer kernels of every other model keep 64-bit
+    // addresses and take any size
+    if (tr_route(d, batch, n_samples).fused_lc && (long long)batch * n_samples * 64 * 4 >= (1LL << 31))
+        return twv_fail(TWV_E_UNSUPPORTED, "batch x samples too large: the fused layer kernels address a layer's activations with 32-bit byte offsets (batch * samples < 8.3 M)");
     if (d.residual_channels != 32 || d.dilation_channels != 32) return twv_fail(TWV_E_UNSUPPORTED, "training is built for residual_channels = dilation_channels = 32 only: training at other widths is not built");
     if (d.scalar_input && (d.out_channels % 3 || d.out_channels > 96)) return twv_fail(TWV_E_UNSUPPORTED, "out_channels must be 3*nr_mix <= 96");
     if (!d.scalar_input && (d.quantization_channels < 2 || d.quantization_channels > 512)) return twv_fail(TWV_E_UNSUPPORTED, "quantization_channels must be in [2, 512] for training");
@@ -1903,36 +1991,21 @@ extern "C" int twv_wavenet_train_create(const twv_wavenet_dims* dims, int batch,
     h->nparams = c;
     h->blas = nullptr;
     h->ws_clean = nullptr;
-    // workspace (generous upper bound of what loss_grad carves, each piece rounded up to 64 floats)
-    const long long Rr = (long long)batch * h->Tn, RT = (long long)batch * n_samples, RO = (long long)batch * h->ow;
-    long long f = 0;
-    f += RT * h->L * 2;                         // upsample stages
-    f += RT * h->L * 2;                         // dU ping/pong
-    f += Rr * h->ifw + RT;                      // xunf / quantized input
-    f += d.scalar_input ? 0 : 256LL * 2 * d.quantization_channels * 32;   // one-hot causal gradient partial tables
-    f += Rr * 32 * (h->NL + 1);                 // X[l]
-    f += Rr * 32 * 3 * h->NL;                   // TH, SG, Z per layer
-    f += RO * 32 * h->NL * 2;                   // ZCall, dZCall
-    f += Rr * 64 + RT * 64;                     // PRE / dPRE, LCP / dLCP
-    f += Rr * 32 * 3;                           // dX ping/pong, dZ
-    f += RO * h->S * 3;                         // SK/H1, C1/H2, dC1
-    f += RO * h->O * 2;                         // Y, dY
-    f += (long long)batch * 64 * (h->NL + 2) + (long long)batch * h->G * 2;
-    f += 2 * ((long long)h->NL * (64LL * (64 + h->L + h->G) + 32LL * h->S));   // weight views + their gradients
-    f += 512LL * 96 * 64 + 1024LL * 512;        // reduction partials
-    f += (256LL * 11 * 1024 + 64 + (long long)batch * ((h->Tn + 31) / 32) * 96 + 64 + (long long)batch * 64 + 64 + 64) * h->NL + 1024 + 64;   // per layer: gradient slabs, per-tile column sums, dGCP
-    f += 16LL * ((long long)h->NL * 32 > h->S ? (long long)h->NL * 32 : h->S) * h->S;   // split-K partials of the wide weight gradients
-    f += RT * 4 + 64 + 4LL * 512 + 64;          // fused lc backward: per-row dot products, phase-table gradient
-    f += ((long long)batch * ((h->Tn + 31) / 32) * 512 + 64 + RT / h->hop * 256 + 64) * h->NL;   // per-tile / per-frame sums of ctab * dPRE (dW_lc)
-    f += 4LL * 512 + 64 + RT / h->hop * 4 * h->L + 64 + (RT / h->hop * 4 * 64 + 64) * h->NL;   // fused lc projection: tap table, shifted mel, per-layer frame projections
-    f += 2048LL * 64 * 32 + 64;                 // conv1d_2's fused backward: per-wave shares of dW2
-    f += 64 * 64;                               // rounding slack
+    // workspace: exactly what loss_grad carves (tr_carve on a null base), then twv_wavenet_train_l2's scratch
+    TrainCarve sizes;
+    long long f = h->carve_floats = tr_carve(h, nullptr, sizes);
     // twv_wavenet_train_l2's scratch (nparams squares + the partial sums) has a region of its OWN behind everything loss_grad carves: at
     // the start of the workspace it overwrote rows that the fused layer kernels rely on staying zero (the rows in front of a layer's
     // receptive offset are cleared once and never written again) -- harmless only while every gradient is finite
     h->l2_off = f;
     f += (h->nparams + 63) / 64 * 64 + 1024;
     h->ws_floats = f;
+    {
+        const TrainRoute r = tr_route(d, batch, n_samples);
+        h->route = std::string("lc=") + (r.fused_lc ? "fused" : "staged") + " head=" + (r.fuse_c2 ? "skinny+c2bwd" : r.skinny ? "skinny" : "gemm") +
+                   " loss=" + (r.loss == TR_LOSS_MOL10 ? "mol<10>" : r.loss == TR_LOSS_MOLN ? "mol<0>" : "softmax") + " nsplit=" + std::to_string(r.nsplit) +
+                   " carve_floats=" + std::to_string(h->carve_floats);
+    }
     *out = h;
     return TWV_OK;
 }
@@ -1950,6 +2023,7 @@ extern "C" int twv_wavenet_train_reset_workspace(twv_wavenet_trainer* h)
 extern "C" size_t twv_wavenet_train_param_floats(const twv_wavenet_trainer* h) { return (size_t)h->nparams; }
 extern "C" size_t twv_wavenet_train_workspace_bytes(const twv_wavenet_trainer* h) { return (size_t)h->ws_floats * 4; }
 extern "C" int twv_wavenet_train_output_width(const twv_wavenet_trainer* h) { return h->ow; }
+extern "C" const char* twv_wavenet_train_route(const twv_wavenet_trainer* h) { return h ? h->route.c_str() : ""; }
 
 extern "C" int twv_wavenet_train_loss_grad(twv_wavenet_trainer* h, const float* params, const float* audio, const float* lc,
                                            const int32_t* gc_ids, void* workspace, float* loss, float* grads, void* stream)
@@ -1966,6 +2040,13 @@ extern "C" int twv_wavenet_train_loss_grad(twv_wavenet_trainer* h, const float* 
     const bool ub = d.use_biases != 0;
     const float* P = params;
     float* Gd = grads;
+    // ---- workspace carve (tr_carve: the function create sized the workspace with), checked BEFORE the first device operation
+    TrainCarve cv;
+    if (tr_carve(h, (float*)workspace, cv) != h->carve_floats || h->carve_floats > h->l2_off || h->l2_off > h->ws_floats)
+        return twv_fail(TWV_E_INVALID, "internal: the workspace carve does not match the size twv_wavenet_train_create computed");
+    const TrainRoute route = tr_route(d, B, T);
+    const bool fused_lc = route.fused_lc;
+    const int nsplit = route.nsplit;
     HIPCHK(hipMemsetAsync(grads, 0, (size_t)h->nparams * 4, st));
     HIPCHK(hipMemsetAsync(loss, 0, 4, st));
     // A workspace seen for the first time is cleared once: the layer kernels do not walk the tiles in front of a layer's receptive offset,
@@ -1976,61 +2057,23 @@ extern "C" int twv_wavenet_train_loss_grad(twv_wavenet_trainer* h, const float* 
         HIPCHK(hipMemsetAsync(workspace, 0, (size_t)h->ws_floats * 4, st));
         h->ws_clean = workspace;
     }
-    // ---- workspace carve
-    float* w = (float*)workspace;
-    auto take = [&](long long n) { float* p = w; w += (n + 63) / 64 * 64; return p; };
-    float* ups[5]; long long upT[5];
-    upT[0] = T / h->hop;
-    for (int i = 0; i < d.n_upsample; ++i) upT[i + 1] = upT[i] * d.upsample_factor[i];
-    ups[0] = const_cast<float*>(lc);
-    for (int i = 1; i <= d.n_upsample; ++i) ups[i] = take((long long)B * upT[i] * L);
+    const long long* upT = cv.upT;
+    float* ups[5] = {const_cast<float*>(lc), cv.ups[1], cv.ups[2], cv.ups[3], cv.ups[4]};
     float* U = ups[d.n_upsample];
-    float* dUa = take(RT * L); float* dUb = take(RT * L);
-    float* xunf = take(Rr * h->ifw);
-    int32_t* qin = reinterpret_cast<int32_t*>(take(RT));
-    float* ohpart = take(d.scalar_input ? 0 : 256LL * 2 * d.quantization_channels * 32);
-    float** X = new float*[NL + 1];
-    float **TH = new float*[NL], **SG = new float*[NL];
-    for (int l = 0; l <= NL; ++l) X[l] = take(Rr * 32);
-    for (int l = 0; l < NL; ++l) { TH[l] = take(Rr * 32); SG[l] = take(Rr * 32); }
+    float *dUa = cv.dUa, *dUb = cv.dUb, *xunf = cv.xunf, *ohpart = cv.ohpart;
+    int32_t* qin = cv.qin;
+    float* const* X = cv.X; float* const* TH = cv.TH; float* const* SG = cv.SG;
     const int ZW = NL * 32;                                  // stacked skip input: ZC[(b,p)][l*32 + j]
-    float* ZC = take(RO * ZW); float* dZC = take(RO * ZW);
-    float* PRE = take(Rr * 64);
-    float* dXa = take(Rr * 32); float* dXb = take(Rr * 32);
-    float* SK = take(RO * S); float* C1 = take(RO * S); float* dS = take(RO * S);
-    float* Y = take(RO * O); float* dY = take(RO * O);
-    float* emb = take((long long)B * G); float* demb = take((long long)B * G);
-    float* GCP = take((long long)B * 64 * NL); float* dGCP = take((long long)B * 64);
-    const long long vstride = 64LL * (64 + L + G);
-    float* WV = take(vstride * NL); float* WS = take((long long)ZW * S);       // weight views
-    float* GV = take(vstride * NL); float* GS = take((long long)ZW * S);       // gradient views
-    float* part = take(512LL * 96 * 64 + 1024LL * 512);
-    const long long slab_ls = 256LL * GQ_N * 1024;
-    float* slabs = take(slab_ls * NL);                       // every layer's gradient slabs: reduced in one launch after the layer loop
-    float* zpage = take(1024);
-    float* kpart = take(16LL * (ZW > S ? ZW : S) * S);       // split-K partials (dW1, dW2, stacked dWs)
-    float* wpart = take(2048LL * 64 * 32);                   // tr_conv2_bwd_kernel: [2048 / CG chunks][S][32] = 2048 x 64 x 32 whatever S is
+    float *ZC = cv.ZC, *dZC = cv.dZC, *PRE = cv.PRE, *dXa = cv.dXa, *dXb = cv.dXb, *SK = cv.SK, *C1 = cv.C1, *dS = cv.dS, *Y = cv.Y, *dY = cv.dY;
+    float *emb = cv.emb, *demb = cv.demb, *GCP = cv.GCP, *WV = cv.WV, *WS = cv.WS, *GV = cv.GV, *GS = cv.GS, *part = cv.part, *slabs = cv.slabs;
+    float *zpage = cv.zpage, *kpart = cv.kpart, *wpart = cv.wpart, *ctab = cv.ctab, *melsh = cv.melsh, *Qall = cv.Qall, *Dbuf = cv.Dbuf, *dctab = cv.dctab;
+    float *PTall = cv.PTall, *Rall = cv.Rall, *tsum = cv.tsum, *dGCPall = cv.dGCPall, *bsum64 = cv.bsum64;
+    const long long vstride = cv.vstride, slab_ls = cv.slab_ls, q_ls = cv.q_ls, pt_ls = cv.pt_ls, tsum_ls = cv.tsum_ls;
     const int F = T / h->hop;                                // mel frames per entry
-    const bool fused_lc = d.n_upsample == 3 && h->hop >= 32 && h->hop <= 512 && L == 80;
-    float* ctab = take(4LL * 512);
-    float* melsh = take((long long)B * F * 4 * L);
-    const long long q_ls = (long long)B * F * 4 * 64;
-    float* Qall = take((q_ls + 64) * NL);
-    float* Dbuf = take(RT * 4);                              // sum over layers of dPRE . Q_j per U row (fused lc backward)
-    float* dctab = take(4LL * 512);
-    const long long pt_ls = (long long)B * ((Tn + 31) / 32) * 512;
-    float* PTall = take((pt_ls + 64) * NL);
-    float* Rall = take((q_ls + 64) * NL);
-    int nsplit = 1;
-    for (int c = 2; c <= 16 && c <= B; ++c) if (B % c == 0) nsplit = c;   // slabs of whole batch entries: RO = B * ow rows
     HIPCHK(hipMemsetAsync(zpage, 0, 4096, st));
     HIPCHK(hipFuncSetAttribute((const void*)tr_layer_bwd1_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * BS_FLOATS * 4));
     HIPCHK(hipFuncSetAttribute((const void*)tr_layer_bwd1_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (4 * BS_FLOATS + 2048) * 4));
     HIPCHK(hipFuncSetAttribute((const void*)tr_skinny_nn_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-    const long long tsum_ls = (long long)B * ((Tn + 31) / 32) * 96;     // layers back to back: the column sums below treat (layer, batch entry) as segments
-    float* tsum = take(tsum_ls * NL);
-    float* dGCPall = take((long long)B * 64 * NL);
-    float* bsum64 = take(64LL * NL);
     int rc = TWV_OK;
 #define K1(kern, n, ...) hipLaunchKernelGGL(kern, dim3(tg(n)), dim3(256), 0, st, __VA_ARGS__)
 #define LP(l) (P + h->c_layer0 + (long long)(l) * h->c_lstride)
@@ -2132,8 +2175,7 @@ extern "C" int twv_wavenet_train_loss_grad(twv_wavenet_trainer* h, const float* 
         if ((rc = gemm_rm(bl, false, false, (int)RO, S, S, 1.f, SK, S, P + h->c_w1, S, 0.f, C1, S))) break;
         // conv1d_1's activation: with the skinny output projection (MoL head) the relu(. + b1) pass over the (RO, S) array is never run --
         // its readers (the projection forward; conv1d_2's fused backward: mask of dC1 and operand of dW2) apply it to what they load
-        const bool skinny = O <= 32 && (S & 63) == 0 && S * 32 * 4 <= 64 * 1024 && RO * S * 4 < (1LL << 31);
-        const bool fuse_c2 = skinny && (S & 63) == 0 && 2048 % (S >> 6) == 0;   // (`part`: 2048 x 64 floats)
+        const bool skinny = route.skinny, fuse_c2 = route.fuse_c2;           // (tr_route)
         const bool c1_raw = fuse_c2;
         const float* b1p = ub ? P + h->c_b1 : nullptr;
         if (!c1_raw) {
@@ -2150,8 +2192,8 @@ extern "C" int twv_wavenet_train_loss_grad(twv_wavenet_trainer* h, const float* 
         // model.py:286-290 loss
         // per-row terms, then the same two-stage column sum as the bias gradients: the loss is bit-reproducible run to run
         float* row_loss = dS;                                       // (RO) scratch: dS is not written before the backward pass
-        if (d.scalar_input && nr == 10) K1(tr_mol_loss_kernel<10>, RO, Y, audio, B, T, ow, rf, nr, 1.0f / (float)RO, row_loss, dY);
-        else if (d.scalar_input) K1(tr_mol_loss_kernel<0>, RO, Y, audio, B, T, ow, rf, nr, 1.0f / (float)RO, row_loss, dY);
+        if (route.loss == TR_LOSS_MOL10) K1(tr_mol_loss_kernel<10>, RO, Y, audio, B, T, ow, rf, nr, 1.0f / (float)RO, row_loss, dY);
+        else if (route.loss == TR_LOSS_MOLN) K1(tr_mol_loss_kernel<0>, RO, Y, audio, B, T, ow, rf, nr, 1.0f / (float)RO, row_loss, dY);
         else hipLaunchKernelGGL(tr_softmax_ce_kernel, dim3(tg(RO * 64)), dim3(256), 0, st, Y, qin, B, T, ow, rf, O, 1.0f / (float)RO, row_loss, dY);
         colsum(row_loss, RO, 1, 1, 1, loss, 1);
         // ================= backward =================
@@ -2289,10 +2331,8 @@ extern "C" int twv_wavenet_train_loss_grad(twv_wavenet_trainer* h, const float* 
             }
         }
     } while (0);
-    delete[] X; delete[] TH; delete[] SG;
     if (rc) return twv_fail(TWV_E_HIP, "rocBLAS call failed with status " + std::to_string(rc));
     HIPCHK(hipGetLastError());
-    if ((long long)(w - (float*)workspace) > h->ws_floats) return twv_fail(TWV_E_INVALID, "internal: workspace overrun");
     return TWV_OK;
 }
 

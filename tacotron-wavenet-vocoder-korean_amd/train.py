@@ -174,6 +174,11 @@ class WaveNetTrainer(object):
     def gradients(self):
         return self._named(self.grads)
 
+    def route(self):
+        """which kernel families `loss_and_gradients` runs for this trainer (twv_wavenet_train_route), as a dict of strings:
+        lc (fused | staged), head (skinny+c2bwd | skinny | gemm), loss (mol<10> | mol<0> | softmax), nsplit, carve_floats"""
+        return dict(kv.split("=", 1) for kv in self._L.twv_wavenet_train_route(self._h).decode().split())
+
     def reset_workspace(self):
         """the next step clears the workspace again (twv_wavenet_train_reset_workspace): for a caller that let anything else write into
         `_ws`, or replaced it by a buffer a caching allocator may have handed out at the same address"""

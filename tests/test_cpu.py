@@ -370,6 +370,8 @@ def test_c_abi_exports_match_header():
     missing = [n for n in sorted(declared) if not hasattr(lib, n)]
     assert not missing, missing
     assert set(_lib.EXPORTS) <= declared
+    assert "twv_wavenet_train_route" in declared and "twv_wavenet_train_route" in _lib.EXPORTS
+    assert lib.twv_wavenet_train_route.restype is C.c_char_p
     nm = subprocess.check_output(["nm", "-D", "--defined-only", _lib.LIB_PATH]).decode()
     assert "wn_generate_kernel" in nm or "_Z18wn_generate_kernel" in nm, "gfx950 kernels must be in the library"
 

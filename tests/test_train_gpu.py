@@ -10,43 +10,12 @@ import torch
 
 import torch_train_ref as R
 from helpers import make_model
+from train_cases import DEFAULT_CASES, FLOOR, LOSS_FLOOR, RATIO, UP, _assert_against_float64, _case      # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-UP = (5, 5, 12)
-
-
-def _case(dil, B, Tm, S=64, seed=0, scale=0.05, ls_bias=None, clip_audio=False, use_bias=True, up=UP):
-    import twvk_amd  # noqa: F401
-    from twvk_amd import weights as W
-    from twvk_amd.train import WaveNetTrainer
-    specs = W.tensor_specs(len(dil), S=S, use_biases=use_bias, upsample_factor=up)
-    tensors = W.random_tensors(specs, seed=seed, scale=scale)
-    if ls_bias is not None:
-        tensors["wavenet/conv1d_2/bias"][20:30] = ls_bias          # log-scales: exercises the cdf_delta > 1e-5 branch
-    T = Tm * int(np.prod(up))
-    rng = np.random.RandomState(seed + 1)
-    audio = ((rng.rand(B, T) - 0.5) * 1.6).astype(np.float32)
-    if clip_audio:
-        audio = np.clip(audio * 1.5, -1.0, 1.0).astype(np.float32)  # some targets at +-1: the two edge branches
-    lc = (rng.randn(B, Tm, 80) * 0.5).astype(np.float32)
-    gc = rng.randint(0, 2, size=B).astype(np.int32)
-    net = make_model(B, dil, tensors, S=S, use_bias=use_bias, up=up)
-    tr = WaveNetTrainer(net, sample_size=T)
-    tr.load_weights(tensors)
-    cfg = dict(dilations=dil, initial_filter_width=32, use_biases=use_bias, upsample_factor=up)
-    return tr, tensors, cfg, audio, lc, gc
-
-
-# Bars, from the data of scripts/train_parity_report.py (profiles/r05_train_parity_report.txt: every geometry below, per tensor
-# e = max|g - g64| / max|g64| for the HIP gradients and for the float32 torch model, both against the float64 torch model):
-#   * wherever a float32 model has a measurable error of its own the HIP path was at most 4.1x further from float64 than the torch
-#     float32 model (16 x 3600: layer4 skip kernel; full size 2.1x; MoL-branch case 1.5x) -> asserted: 8x;
-#   * tensors the torch float32 model gets right to ~1e-7 (one ulp of the largest element) the HIP path gets right to 3.3e-6 at worst
-#     (chunked / split-K summation orders) -> absolute floor 5e-6 (rounds 1-4 carried 2e-3 here, which would have hidden a wrong
-#     bias-gradient term in a small tensor);
-#   * loss: at most 10x the float32 model's own distance from float64, floor 2e-6 relative (worst seen 3.7e-7).
-RATIO, FLOOR, LOSS_FLOOR = 8.0, 5e-6, 2e-6
+# (the case builder, the bars RATIO = 8, FLOOR = 5e-6, LOSS_FLOOR = 2e-6 and the data they come from: tests/train_cases.py)
+assert (RATIO, FLOOR, LOSS_FLOOR) == (8.0, 5e-6, 2e-6)
 
 
 def _check_grads(got, ref, rtol):
@@ -60,35 +29,7 @@ def _check_grads(got, ref, rtol):
         assert err <= rtol, "%s: max|diff| = %.3g of max|ref| %.3g" % (name, err, scale)
 
 
-def _assert_against_float64(label, loss, got, l64, g64, l32, g32):
-    assert abs(loss - l64) <= max(10 * abs(l32 - l64), LOSS_FLOOR * abs(l64)), (label, loss, l32, l64)
-    worst_e, worst_r = ("", 0.0, 0.0), ("", 0.0)
-    for k in g64:
-        scale = max(float(np.abs(g64[k]).max()), 1e-30)
-        e_hip = float(np.abs(got[k] - g64[k]).max()) / scale
-        e_t32 = float(np.abs(g32[k] - g64[k]).max()) / scale
-        assert np.isfinite(got[k]).all(), k
-        assert e_hip <= max(RATIO * e_t32, FLOOR), ("%s %s: HIP %.3g vs torch-f32 %.3g (relative to the tensor's max, against float64): ratio %.1f"
-                                                    % (label, k, e_hip, e_t32, e_hip / max(e_t32, 1e-30)))
-        if e_hip > worst_e[1]:
-            worst_e = (k, e_hip, e_t32)
-        if e_hip > FLOOR and e_hip / e_t32 > worst_r[1]:
-            worst_r = (k, e_hip / e_t32)
-    print("%s: loss %.7f (f64 %.7f, f32 %.7f); worst gradient tensor %s at %.2e of its max (torch f32: %.2e); worst e_hip / e_t32 above the floor: %.2f (%s)"
-          % (label, loss, l64, l32, worst_e[0], worst_e[1], worst_e[2], worst_r[1], worst_r[0] or "none above the floor"))
-    return worst_e, worst_r
-
-
-@pytest.mark.parametrize("kw", [
-    dict(dil=[1, 2, 4, 1, 2], B=2, Tm=3),
-    dict(dil=[1, 2, 4, 8, 16, 32, 64, 128, 256, 512], B=3, Tm=6, S=128),
-    dict(dil=[1, 2, 4, 1, 2], B=2, Tm=3, ls_bias=-4.0, clip_audio=True),
-    dict(dil=[1, 2, 4], B=1, Tm=2, use_bias=False),
-    dict(dil=[1, 2, 4, 8], B=2, Tm=21, up=(4, 4, 4)),          # hop 64: a 32-row tile of the fused layer kernels straddles a frame edge every other tile
-    dict(dil=[1, 2, 4], B=2, Tm=40, up=(2, 4, 4)),             # hop 32 = the tile height (the smallest hop the frame-rate lc path takes)
-    dict(dil=[1, 2, 4], B=2, Tm=5, S=128, use_bias=False),     # S % 128 == 0 takes the fused conv1d_2 backward; here without bias vectors
-    dict(dil=[1, 2], B=1, Tm=4, S=256),                        # two column groups of the fused conv1d_2 backward, a ragged last row tile
-], ids=["small", "one-cycle", "mol-branches", "no-bias", "hop64", "hop32", "no-bias-s128", "s256"])
+@pytest.mark.parametrize("kw", [kw for _, kw in DEFAULT_CASES], ids=[i for i, _ in DEFAULT_CASES])
 def test_loss_and_gradients_match_torch_fp32(kw, request):
     tr, tensors, cfg, audio, lc, gc = _case(**kw)
     loss = float(tr.loss_and_gradients(audio, lc, gc).item())

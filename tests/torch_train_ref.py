@@ -44,6 +44,37 @@ def mol_loss(y_hat, y, num_class=2 ** 16, log_scale_min=float(np.log(1e-14))):
     return -log_sum_exp(log_probs)
 
 
+def mol_branch_census(y_hat, y, num_class=2 ** 16, log_scale_min=float(np.log(1e-14))):
+    """which branch of `mol_loss` each (row, mixture) pair takes: counts of the four exclusive arms of the nested where (in its order)
+    and, independently, of the pairs whose log-scale is clamped.  Same arithmetic as mol_loss, on the same inputs."""
+    nr = y_hat.shape[-1] // 3
+    means = y_hat[:, :, nr:2 * nr]
+    raw = y_hat[:, :, 2 * nr:3 * nr]
+    log_scales = torch.clamp(raw, min=log_scale_min)
+    y = y.expand(-1, -1, nr)
+    inv_stdv = torch.exp(-log_scales)
+    cdf_delta = torch.sigmoid(inv_stdv * (y - means + 1.0 / (num_class - 1))) - torch.sigmoid(inv_stdv * (y - means - 1.0 / (num_class - 1)))
+    lo = y < -0.999
+    hi = ~lo & (y > 0.999)
+    delta = ~lo & ~hi & (cdf_delta > 1e-5)
+    mid = ~lo & ~hi & ~delta
+    clamped = raw < log_scale_min
+    return dict(lo_edge=int(lo.sum()), hi_edge=int(hi.sum()), cdf_delta=int(delta.sum()), mid_pdf=int(mid.sum()),
+                clamped=int(clamped.sum()), unclamped=int((~clamped).sum()), pairs=int(y.numel()))
+
+
+def branch_census(tensors, cfg, audio, lc, gc_ids):
+    """float64 forward pass of the scalar-input model -> mol_branch_census of its output against the targets"""
+    P = {k: torch.tensor(np.asarray(v), dtype=torch.float64) for k, v in tensors.items()}
+    a = torch.tensor(audio, dtype=torch.float64)
+    rf = receptive_field(cfg)
+    U = upsample(torch.tensor(lc, dtype=torch.float64), [P["wavenet/upsample%d/kernel" % i] for i in range(len(cfg["upsample_factor"]))],
+                 cfg["upsample_factor"])
+    with torch.no_grad():
+        y = network(P, cfg, a[:, None, :-1], U, torch.tensor(np.asarray(gc_ids)))
+        return mol_branch_census(y, a[:, rf:, None])
+
+
 def upsample(lc, kernels, factors):
     """conv2d_transpose(filters=1, kernel=(f,2), strides=(f,1), 'same'): out[t*f+a, m] = K[a,0] in[t,m] + K[a,1] in[t,m-1]"""
     x = lc                                                     # (B, T, L)
