@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """In-kernel phase timing of the XCD-per-stream generation kernel (tuning aid): s_memtime stamps of stream 0's workgroups
-(all on one XCD, one clock), averaged over the steps; prints the anatomy of a generation step in microseconds."""
+(all on one XCD, one clock), averaged over the steps; prints the anatomy of a generation step in microseconds.
+The chain is a relay of six waves with five layers each (waves 0..5); wave 7, the head, runs the causal layer and the sampler."""
 import argparse, ctypes as C, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -44,16 +45,16 @@ step = np.diff(p[:, 0]).mean()
 tick = args.ghz if args.ghz else step / (inst * 1e3)      # ticks per ns
 us = lambda a: a.mean() / tick / 1e3
 print("production build %.2f us/step, instrumented build %.2f us/step (events); %.3f ticks/ns" % (plain, inst, tick))
-print("step period (wave 7 head to head)     %.2f us" % us(np.diff(p[:, 0])))
+print("step period (head to head, wave 7)     %.2f us" % us(np.diff(p[:, 0])))
 print("causal layer (queue shift, dot, box)  %.2f" % us(p[:, 1] - p[:, 0]))
-nw = 8
+nw = 8                                                   # stamp slots 2 + w, 10 + w, 26 + w; the relay of six waves fills w = 0..5 (a build with eight layer waves: all)
 recv = [p[:, 2 + w] for w in range(nw)]; done = [p[:, 10 + w] for w in range(nw)]; pa = [p[:, 26 + w] for w in range(nw)]
-print("hand-off causal -> wave 0             %.2f" % us(recv[0] - p[:, 1]))
+print("hand-off causal (wave 7) -> wave 0    %.2f" % us(recv[0] - p[:, 1]))
 for w in range(nw):
     if done[w].any():
         print("wave %d: layers %.2f us%s" % (w, us(done[w] - recv[w]), ("   hand-off to wave %d %.2f" % (w + 1, us(recv[w + 1] - done[w]))) if w + 1 < nw and done[w + 1].any() else ""))
 last = max(w for w in range(nw) if done[w].any())
-print("residual stack total (wave 0 in -> last layer out)  %.2f" % us(done[last] - recv[0]))
+print("residual stack total (wave 0 in -> last layer out)  %.2f   (%d layer waves, %d hand-offs between them)" % (us(done[last] - recv[0]), last + 1, last))
 # round 6 (KF = 1): the skip workgroups serve layers 0 .. NL-2 and publish the RAW running sum; the conv1 workgroups poll the last layer's z
 # themselves, have its skip value ready when the sum arrives, and finish the sum + relu (stamp 22)
 print("post: last layer out -> the skip workgroup's summing wave has seen ITS last z (layer NL-2) %.2f" % us(p[:, 20] - done[last]))

@@ -10,7 +10,7 @@
 //     (bypass the reader's L1): 273 ns one way instead of the 590 ns of the agent-scope (write-through + memory-side) form
 //     (profiles/r02_xcd_chain_ubench.txt).
 //   * EVERY WEIGHT IS REGISTER-RESIDENT for the whole launch, spread over the XCD's CUs: nothing is re-streamed per step.
-//       chain workgroup   (1 per stream): 8 waves x 4 layers: tap-1 conv kernel + dense kernel of a layer = 48 VGPRs per lane
+//       chain workgroup   (1 per stream): 6 waves x 5 layers (tap-1 conv kernel in VGPRs, 32 per lane and layer; dense kernel in LDS), 1 head wave
 //       service workgroup (1 per stream): tap-0 conv kernels, the delay lines (model.py:49-64 queues; in the stream's state buffer)
 //       skip workgroups   (8 per XCD): slice g of the 30 skip kernels (model.py:94-96)
 //       conv1 workgroups  (8 per XCD): slice g of conv1d_1 and its two chunks of conv1d_2 (model.py:158-165)
@@ -23,7 +23,7 @@
 //     The skip / conv1 / lc workgroups hold weights only, so with more than 8 streams ONE set per XCD serves the XCD's streams in
 //     turn (2 ns + 16 + n_lc <= 28 of the 32 CUs for ns = 4): the streams settle a fraction of a microsecond apart, B = 16 keeps
 //     the single-stream step time (9.7 us), B = 32 runs at 10.8 us (2.97 M samples/s).
-//   * THE CHAIN IS A RELAY OF EIGHT WAVES.  A layer is 32 v_fmac_f32_dpp (row_newbcast feeds x[k] to the fma: no v_readlane,
+//   * THE CHAIN IS A RELAY OF SIX WAVES (+ the head wave: causal layer and sampler).  A layer is 32 v_fmac_f32_dpp (row_newbcast feeds x[k] to the fma: no v_readlane,
 //     no LDS operand reads) -> bias/conditioning adds -> rational tanh/sigmoid -> v_permlane32_swap -> 16 v_fmac_f32_dpp +
 //     v_permlane16_swap for the dense 1x1 (twv_dpp.hpp): 243 ns per layer in the product (200 for the arithmetic alone) against 654 ns
 //     in wn_generate_kernel.  A wave hands the residual vector to the next one through a tagged LDS granule (90 ns); nothing but
@@ -157,6 +157,58 @@ __device__ __forceinline__ int lane_of_x(int j) { return j < 16 ? j : 16 + j; }
 // chunk's chain 0 (AC-1b, twv_dpp.hpp: dense_bias_init).  Conv bias, gc and lc projections reach the chain inside the ADDEND the
 // service workgroup publishes.
 struct ChainRegs { float wc[32]; float bd; };
+// dot32_dpp_chain (twv_dpp.hpp) in its two blocks of 16, k = 0..15 | 16..31, for a caller that holds the halves of a tile apart: the
+// same instructions in the same order on the same chains
+__device__ __forceinline__ void dot32_dpp_chain_lo(const float (&w)[16], float xa, float init, float (&c)[4])
+{
+    float c0 = init, c1, c2, c3;
+    asm volatile(
+        "s_nop 1\n" TWV_ALIGN8
+        "v_fmac_f32_dpp %0, %4, %5 row_newbcast:0 row_mask:0xf bank_mask:0xf\n"
+        "v_mul_f32_dpp %1, %4, %6 row_newbcast:1 row_mask:0xf bank_mask:0xf\n"
+        "v_mul_f32_dpp %2, %4, %7 row_newbcast:2 row_mask:0xf bank_mask:0xf\n"
+        "v_mul_f32_dpp %3, %4, %8 row_newbcast:3 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %0, %4, %9 row_newbcast:4 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %1, %4, %10 row_newbcast:5 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %2, %4, %11 row_newbcast:6 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %3, %4, %12 row_newbcast:7 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %0, %4, %13 row_newbcast:8 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %1, %4, %14 row_newbcast:9 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %2, %4, %15 row_newbcast:10 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %3, %4, %16 row_newbcast:11 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %0, %4, %17 row_newbcast:12 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %1, %4, %18 row_newbcast:13 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %2, %4, %19 row_newbcast:14 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %3, %4, %20 row_newbcast:15 row_mask:0xf bank_mask:0xf"
+        : "+v"(c0), "=&v"(c1), "=&v"(c2), "=&v"(c3)
+        : "v"(xa), "v"(w[0]), "v"(w[1]), "v"(w[2]), "v"(w[3]), "v"(w[4]), "v"(w[5]), "v"(w[6]), "v"(w[7]), "v"(w[8]), "v"(w[9]), "v"(w[10]), "v"(w[11]), "v"(w[12]), "v"(w[13]), "v"(w[14]), "v"(w[15]));
+    c[0] = c0; c[1] = c1; c[2] = c2; c[3] = c3;
+}
+__device__ __forceinline__ float dot32_dpp_chain_hi(const float (&w)[16], float xb, const float (&c)[4])
+{
+    float c0 = c[0], c1 = c[1], c2 = c[2], c3 = c[3];
+    asm volatile(
+        TWV_ALIGN8
+        "v_fmac_f32_dpp %0, %4, %5 row_newbcast:0 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %1, %4, %6 row_newbcast:1 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %2, %4, %7 row_newbcast:2 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %3, %4, %8 row_newbcast:3 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %0, %4, %9 row_newbcast:4 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %1, %4, %10 row_newbcast:5 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %2, %4, %11 row_newbcast:6 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %3, %4, %12 row_newbcast:7 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %0, %4, %13 row_newbcast:8 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %1, %4, %14 row_newbcast:9 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %2, %4, %15 row_newbcast:10 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %3, %4, %16 row_newbcast:11 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %0, %4, %17 row_newbcast:12 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %1, %4, %18 row_newbcast:13 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %2, %4, %19 row_newbcast:14 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %3, %4, %20 row_newbcast:15 row_mask:0xf bank_mask:0xf"
+        : "+v"(c0), "+v"(c1), "+v"(c2), "+v"(c3)
+        : "v"(xb), "v"(w[0]), "v"(w[1]), "v"(w[2]), "v"(w[3]), "v"(w[4]), "v"(w[5]), "v"(w[6]), "v"(w[7]), "v"(w[8]), "v"(w[9]), "v"(w[10]), "v"(w[11]), "v"(w[12]), "v"(w[13]), "v"(w[14]), "v"(w[15]));
+    return (c0 + c1) + (c2 + c3);
+}
 
 // phase stamps (instrumented build only): lane 0 of stream 0's workgroups; s_memrealtime (100 MHz, ONE clock for the chip --
 // s_memtime counters of different CUs are offset against each other by milliseconds)
@@ -203,15 +255,17 @@ constexpr int kSkipLdsWords = 32 * 64;       // 8-byte LDS words per stream in a
 constexpr int kConvLdsFloats = 16 * 64 + 64; // LDS floats per stream in a conv1 workgroup
 
 // =====================================================================================================================
-//  CHAIN workgroup: model.py:41-46 causal layer (wave 0), model.py:66-101 residual layers (relay over the waves),
-//  mixture.py:84-114 sampler (wave 7)
+//  CHAIN workgroup: model.py:41-46 causal layer (wave 7), model.py:66-101 residual layers (relay over the waves),
+//  mixture.py:84-114 sampler (wave 7, the head, which also runs the causal layer)
 // =====================================================================================================================
 // ONEHOT (scalar_input False, the mu-law-256 model of generate.py:219-231): the head wave feeds the causal layer with two kernel ROWS
 // (model.py:41-46 over one-hot input: every AC-1 chunk holds at most one non-zero term, so the k = 2 conv is W0[q(t-1)] + W1[q(t)];
 // only the W1 row waits for the sample) and draws the next class with twv_categorical.hpp from the 256 logits the conv1 workgroups publish.
-// HW: 1 = this wave is the head (wave 7 of the first chain workgroup), 0 = it is not, -1 = decided at run time.  Known at compile time
-// the instantiations of waves 0..6 carry none of the head's code (causal layer, sampler) and may defer their granule stores (DEFER).
-template <int INSTR, bool ALL, bool FORCED, bool SEG1, bool TWOSEG, int NC, bool ONEHOT = false, int HW = -1>
+// HEAD: this wave is the head (wave 7 of the first chain workgroup: causal layer + sampler, no residual layer); the instantiations of the
+// layer waves carry none of the head's code and the head holds no layer tile: no instantiation has five tiles AND the causal kernel.
+// CONT: known at compile time that a later wave continues the stack: the wave may defer its granule stores (DEFER).
+constexpr int kChainLpw = 5;                                  // residual layers per chain wave (160 of a lane's 256 VGPRs hold tap-1 tiles)
+template <int INSTR, bool ALL, bool FORCED, bool SEG1, bool TWOSEG, int NC, bool ONEHOT = false, bool HEAD = false, bool CONT = false>
 __device__ __forceinline__ void chain_role(const XArgs& xa, int b, rsrc_t rs)
 {
     const XcdLaunch& a = xa.p;
@@ -219,21 +273,25 @@ __device__ __forceinline__ void chain_role(const XArgs& xa, int b, rsrc_t rs)
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int NL = L.NL, T = a.T;
     const bool use_bias = L.use_bias != 0, has_gc = L.G > 0, has_lc = L.L > 0;
-    constexpr bool forced = FORCED;                           // teacher-forced steps (twv_wavenet_prime): its own instantiation, the sampling loop carries none of it
-    // first chain workgroup: waves 0..5 hold four layers each, waves 6 and 7 three: wave 7 also runs the sampler and the causal
-    // layer (it HAS the new sample).  A model with more than 30 layers (hparams.py's default has 50) continues in a second chain
-    // workgroup (SEG1: four layers per wave from layer 30 on), one L2 hop away.
-    const int l0 = SEG1 ? kXcdSeg0Layers + 4 * w : (w < 6 ? 4 * w : 24 + 3 * (w - 6));
-    const int lw0 = SEG1 ? 4 * w : l0;                         // the wave's first layer, counted inside this workgroup (LDS copies)
-    const int cap = SEG1 ? 4 : (w < 6 ? 4 : 3);
+    constexpr bool forced = FORCED;                          // teacher-forced steps (twv_wavenet_prime): its own instantiation, the sampling loop carries none of it
+    // first chain workgroup: waves 0..5 hold five layers each (a relay of six waves), wave 6 has nothing to do, wave 7 runs the
+    // sampler and the causal layer (it HAS the new sample) and no residual layer.  A model with more than 30 layers (hparams.py's
+    // default has 50) continues in a second chain workgroup (SEG1: five layers per wave from layer 30 on), one L2 hop away.
+    // (Not built: the head running layers 0..4 itself, one hand-off fewer.  It would hold 144 tile registers beside the causal kernel's
+    // 32, the sampler's table (16) and its noise terms, with the causal kernel in LDS at best -- the layer waves sit at 245 of 256
+    // registers without any of that.)
+    constexpr int kLayerWaves = kXcdSeg0Layers / kChainLpw;    // 6
+    const int l0 = (SEG1 ? kXcdSeg0Layers : 0) + kChainLpw * w;
+    const int lw0 = kChainLpw * w;                             // the wave's first layer, counted inside this workgroup (LDS copies)
+    const int cap = (HEAD || w >= kLayerWaves) ? 0 : kChainLpw;
     int nl = NL - l0;
     nl = nl < 0 ? 0 : (nl > cap ? cap : nl);
-    // NC: the wave's layer count as a compile-time constant (4 or 3; -1: the run-time value) -- the step loop then carries no dispatch
-    // on the count (three compare-and-branch pairs on the wave-to-wave hand-off path)
+    // NC: the wave's layer count as a compile-time constant (5, the head: 0; -1: the run-time value) -- the step loop then carries no
+    // dispatch on the count (compare-and-branch pairs on the wave-to-wave hand-off path)
     const int nlc = NC >= 0 ? NC : nl;
     const bool next_has = (l0 + nl < NL);                      // a later wave continues the stack
-    const bool head = HW >= 0 ? (HW == 1) : (!SEG1 && (w == 7));      // sampler + causal layer
-    const bool to_seg1 = TWOSEG && !SEG1 && w == 7 && next_has;     // the stack goes on in the second chain workgroup
+    constexpr bool head = HEAD;                                // sampler + causal layer
+    const bool to_seg1 = TWOSEG && !SEG1 && w == kLayerWaves - 1 && next_has;     // the stack goes on in the second chain workgroup
     constexpr bool two_seg = TWOSEG;
     if (nl == 0 && !head) return;
     const int oc = dpp_conv_out(lane), od = dpp_dense_out(lane);
@@ -241,23 +299,34 @@ __device__ __forceinline__ void chain_role(const XArgs& xa, int b, rsrc_t rs)
     float* stb = a.state + (long long)b * L.state_stride;
     Poll pl{rs, a.status, 0, false};
     constexpr int O_WD = 2048;                                 // LDS floats: dense kernels [layer][4][64 lanes][4]
+    constexpr int O_WH = kXcdChainHalfTiles;                   // LDS floats: the waves' streamed half tiles [wave][4][64 lanes][4]
 
-    // ---- the wave's layers: tap-1 conv kernel register-resident for the whole launch, dense kernel LDS-resident
-    ChainRegs W[4];
+    // ---- the wave's layers: tap-1 conv kernel register-resident for the whole launch, dense kernel LDS-resident.
+    // Five whole tiles (160 registers) beside the activation's 15 coefficients, the addends, the deferred granules and a dense kernel in
+    // flight do not fit a lane's 256 registers, so the FIRST layer's terms k = 0..15 live in LDS: the wave fetches them every step
+    // before it waits for its input (it idles there anyway), their block of 16 fmas is the first thing the layer runs, and the
+    // layer's dense kernel is fetched behind that block into the registers it has freed -- nothing of it is on the sample path.
+    float wlo[kChainLpw - 1][16], whi[kChainLpw][16], bdi[kChainLpw];      // k = 0..15 of layers 1.., k = 16..31 of all, dense_bias_init
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        if (i < nl) {
+    for (int i = 0; i < kChainLpw; ++i) {
+        if (!HEAD && i < nl) {
             const f32x4* src = reinterpret_cast<const f32x4*>(a.P + L.off_xl + (long long)(l0 + i) * kXcdXlFloats) + lane;
 #pragma unroll
-            for (int q = 0; q < 8; ++q) { const f32x4 v = src[q * 64]; W[i].wc[4 * q] = v.x; W[i].wc[4 * q + 1] = v.y; W[i].wc[4 * q + 2] = v.z; W[i].wc[4 * q + 3] = v.w; }
+            for (int q = 0; q < 4; ++q) {
+                const f32x4 lo = src[q * 64], hi = src[(4 + q) * 64];
+                if (i == 0) LDS4((O_WH >> 2) + (w * 4 + q) * 64 + lane) = lo;
+                else { wlo[i > 0 ? i - 1 : 0][4 * q] = lo.x; wlo[i > 0 ? i - 1 : 0][4 * q + 1] = lo.y; wlo[i > 0 ? i - 1 : 0][4 * q + 2] = lo.z; wlo[i > 0 ? i - 1 : 0][4 * q + 3] = lo.w; }
+                whi[i][4 * q] = hi.x; whi[i][4 * q + 1] = hi.y; whi[i][4 * q + 2] = hi.z; whi[i][4 * q + 3] = hi.w;
+            }
 #pragma unroll
             for (int q = 0; q < 4; ++q) LDS4((O_WD >> 2) + ((lw0 + i) * 4 + q) * 64 + lane) = src[(8 + q) * 64];
             const f32x4 v = src[12 * 64];
-            W[i].bd = dense_bias_init(lane, use_bias ? v.y : 0.0f);
+            bdi[i] = dense_bias_init(lane, use_bias ? v.y : 0.0f);
         }
     }
-    // wave 7: causal kernel (model.py:41-46), every lane the 32 taps of ITS residual channel (X layout), in the registers of the
-    // fourth layer slot (wave 7 holds three layers); causal queue (model.py:52) as two row-broadcast registers:
+    float wcz[32];                                             // the head's causal kernel
+    // wave 7: causal kernel (model.py:41-46), every lane the 32 taps of ITS residual channel (X layout), (wave 7 holds no
+    // layer); causal queue (model.py:52) as two row-broadcast registers:
     // ha: every row hist[n], hb: every row hist[16+n]  (hist[31] = newest input)
     float ha = 0.0f, hb = 0.0f, first_in = 0.0f, b2v = 0.0f, s_lnl = 0.0f, s_tq = 0.0f, samp = 0.0f;
     float cp[4] = {0.0f, 0.0f, 0.0f, 0.0f};                   // the causal chunk without its newest term
@@ -274,7 +343,7 @@ __device__ __forceinline__ void chain_role(const XArgs& xa, int b, rsrc_t rs)
         const float b0 = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(hb), 0x150, 0xf, 0xf, true));   // row_newbcast:0
         ha = is15 ? b0 : t1;
         hb = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(hb), 0x101, 0xf, 0xf, true));
-        causal_partial_dpp(W[3].wc, ha, hb, cp);
+        causal_partial_dpp(wcz, ha, hb, cp);
     };
     auto noise = [&](int t) {
         // mixture.py:103 -log(-log u) per mixture lane; mixture.py:110-111 log u - log(1 - u) of the last draw
@@ -294,7 +363,7 @@ __device__ __forceinline__ void chain_role(const XArgs& xa, int b, rsrc_t rs)
         } else {
             const f32x4* src = reinterpret_cast<const f32x4*>(a.P + L.off_xc) + lane;
 #pragma unroll
-            for (int q = 0; q < 8; ++q) { const f32x4 v = src[q * 64]; W[3].wc[4 * q] = v.x; W[3].wc[4 * q + 1] = v.y; W[3].wc[4 * q + 2] = v.z; W[3].wc[4 * q + 3] = v.w; }
+            for (int q = 0; q < 8; ++q) { const f32x4 v = src[q * 64]; wcz[4 * q] = v.x; wcz[4 * q + 1] = v.y; wcz[4 * q + 2] = v.z; wcz[4 * q + 3] = v.w; }
             ha = stb[L.st_hist + (lane & 15)];
             hb = stb[L.st_hist + 16 + (lane & 15)];
             if (!forced) first_in = reinterpret_cast<const float*>(a.first_input)[b];
@@ -310,6 +379,7 @@ __device__ __forceinline__ void chain_role(const XArgs& xa, int b, rsrc_t rs)
 
     float X = 0.0f;
     unsigned long long t_in = 0, in_period = 0, now_in = 0;   // when this wave's input arrived in the previous step, the step period
+    unsigned long long t_tab = 0, tab_period = 0, now_tab = 0; // the head: the same for the conv1 workgroups' table (partials / logits)
     for (int t = 0; t < T && !pl.dead; ++t) {
         asm volatile(".p2align 6");                        // (XALIGN, see chain_many_role)
         const unsigned tag = (unsigned)t + 1u;
@@ -342,7 +412,7 @@ __device__ __forceinline__ void chain_role(const XArgs& xa, int b, rsrc_t rs)
                 if (sampler) u_next = reinterpret_cast<const double*>(a.uniforms)[(long long)b * T + t];      // generate.py:231's draw
             } else {
             const float s_in = forced ? reinterpret_cast<const float*>(a.forced)[(long long)b * T + t] : (t == 0 ? first_in : samp);
-            const float c3 = fma_(W[3].wc[31], s_in, cp[3]);            // k = 31, the last term of chain 3
+            const float c3 = fma_(wcz[31], s_in, cp[3]);            // k = 31, the last term of chain 3
             const float x0 = (cp[0] + cp[1]) + (cp[2] + c3);            // model.py:41-46: one AC-1 chunk, no bias; X layout
             LDSU64(0 * 64 + lane) = ((unsigned long long)tag << 32) | (unsigned long long)__float_as_uint(x0);
             XSTAMP(true, 1);
@@ -355,17 +425,23 @@ __device__ __forceinline__ void chain_role(const XArgs& xa, int b, rsrc_t rs)
             if (t + 1 < T) causal_prepare();
             if (sampler) noise(t);
             }
+            if (sampler) {                                         // the head's clock for its nap (off the sample path)
+                const unsigned long long d = now_tab - t_tab;
+                tab_period = (t_tab != 0 && d < (1ull << 18)) ? d : 0;
+                t_tab = now_tab;
+            }
             __builtin_amdgcn_s_setprio(0);
         }
         XMARK(SEG1 ? 30 : ROLE_CHAIN, 1);
         // ---- (A) this step's addends of the wave's layers: ((tap-0 chunk + bias) + gc) + lc (service workgroup; long since published)
-        float pre[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        float pre[kChainLpw] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+        float w0lo[16];                                        // k = 0..15 of the wave's first layer, this step's copy
         if (nlc > 0) {
             pl.it = 0;
             for (;;) {
                 bool ok = true;
 #pragma unroll
-                for (int i = 0; i < 4; ++i) {
+                for (int i = 0; i < kChainLpw; ++i) {
                     if (i < nlc) {
                         const unsigned long long qp = xb_load(rs, (int)XcdExch::PG + (l0 + i) * 64, oc);
                         ok = ok && g_tag(qp) == tag;
@@ -383,10 +459,16 @@ __device__ __forceinline__ void chain_role(const XArgs& xa, int b, rsrc_t rs)
             // through most of the step and polls only when its turn is near: a spinning wave takes issue slots from the wave that
             // shares its SIMD (waves w and w+4), and that one may be the wave carrying the chain right now.
             if (in_period) nap_until(t_in + in_period - (in_period >> 4));
+            asm volatile("" ::: "memory");                      // (a fetch per step: the registers are the point, see above)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const f32x4 v = LDS4((O_WH >> 2) + (w * 4 + k) * 64 + lane);
+                w0lo[4 * k] = v.x; w0lo[4 * k + 1] = v.y; w0lo[4 * k + 2] = v.z; w0lo[4 * k + 3] = v.w;
+            }
             unsigned long long q;
             pl.it = 0;
             if (SEG1 && w == 0) {
-                for (;;) {                                               // from wave 7 of the first chain workgroup: one L2 hop
+                for (;;) {                                               // from wave 5 of the first chain workgroup: one L2 hop
                     q = xb_load(rs, (int)XcdExch::SEG, lane);
                     if (__all(g_tag(q) == tag)) break;
                     if (!poll_tick(pl, 36)) break;
@@ -410,26 +492,34 @@ __device__ __forceinline__ void chain_role(const XArgs& xa, int b, rsrc_t rs)
         // DEFER (round 5): the granule store of a layer costs the wave ~40 issue cycles (tuple assembly, the 1 KB of store data, the
         // hazard wait: profiles/r05_chain_contract_ubench.txt, shape P against N) and nobody needs z / the layer input of an EARLY wave
         // at once -- the skip workgroups' sum only completes with the LAST layer, the service workgroup works a step ahead -- so the
-        // waves that are not the head (HW == 0: waves 0..6) keep {z, input} in registers and store their granules behind the hand-off
-        // to the next wave, off the sample-to-sample path.  The head wave (the stack's last layers) stores at once.
-        constexpr bool DEFER = ALL && !FORCED && !SEG1 && NC > 0 && HW == 0;
-        float zs[4] = {0.0f, 0.0f, 0.0f, 0.0f}, xs[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        // waves that a later wave follows (CONT: waves 0..4 of a 30-layer stack) keep {z, input} in registers and store their granules
+        // behind the hand-off to the next wave, off the sample-to-sample path.  The wave with the stack's last layers stores at once.
+        constexpr bool DEFER = ALL && !FORCED && !SEG1 && NC > 0 && CONT;
+        float zs[kChainLpw] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, xs[kChainLpw] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
         auto run_layers = [&](auto nc) {
             constexpr int N = decltype(nc)::value;
 #pragma unroll
             for (int i = 0; i < N; ++i) {
+                // layer_front_dpp (twv_dpp.hpp) with the dense kernel's fetch between the two blocks of the conv chunk: it is dead
+                // until layer_back_dpp and lands behind the second block and the activation
+                const auto xab = __builtin_amdgcn_permlane32_swap(__float_as_uint(X), __float_as_uint(X), false, false);
+                float cc[4];
+                dot32_dpp_chain_lo(i == 0 ? w0lo : wlo[i > 0 ? i - 1 : 0], __uint_as_float(xab[0]), pre[i], cc);
+                asm volatile("" ::: "memory");
                 float wd[16];
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     const f32x4 v = LDS4((O_WD >> 2) + ((lw0 + i) * 4 + q) * 64 + lane);
                     wd[4 * q] = v.x; wd[4 * q + 1] = v.y; wd[4 * q + 2] = v.z; wd[4 * q + 3] = v.w;
                 }
-                const float z = layer_front_dpp(W[i].wc, coef, X, pre[i]);
+                const float act = act_eval_pk_med3(coef, dot32_dpp_chain_hi(whi[i], __uint_as_float(xab[1]), cc));   // model.py:86: lanes 0-31 tanh, 32-63 logistic
+                const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(act), __float_as_uint(act), false, false);
+                const float z = __uint_as_float(sw[0]) * __uint_as_float(sw[1]);
                 // one 16-byte store, two self-tagged halves: {z, tag} -> skip workgroups, {layer input, tag} -> service workgroup
                 // (model.py:145: the queue takes the layer INPUT)
                 if (DEFER) { zs[i] = z; xs[i] = X; }
                 else xb_store2(rs, (int)XcdExch::ZX + (l0 + i) * 128, lane, tag, z, X);
-                layer_back_dpp(wd, W[i].bd, z, X);
+                layer_back_dpp(wd, bdi[i], z, X);
                 if ((INSTR & 2) && a.dbg != nullptr && t < a.dbg_steps) {
                     float* dp = a.dbg + ((long long)b * a.dbg_steps + t) * ((long long)NL * 64 + L.Opad) + (long long)(l0 + i) * 64;
                     if (lane < 32) dp[dpp_z_index(lane)] = z;
@@ -439,7 +529,8 @@ __device__ __forceinline__ void chain_role(const XArgs& xa, int b, rsrc_t rs)
         };
         if constexpr (NC > 0) run_layers(std::integral_constant<int, NC>{});
         else {
-            if (nl == 4) run_layers(std::integral_constant<int, 4>{});
+            if (nl == 5) run_layers(std::integral_constant<int, 5>{});
+            else if (nl == 4) run_layers(std::integral_constant<int, 4>{});
             else if (nl == 3) run_layers(std::integral_constant<int, 3>{});
             else if (nl == 2) run_layers(std::integral_constant<int, 2>{});
             else if (nl == 1) run_layers(std::integral_constant<int, 1>{});
@@ -468,6 +559,7 @@ __device__ __forceinline__ void chain_role(const XArgs& xa, int b, rsrc_t rs)
         // ---- sampler: conv1d_2's [16 chunks][32 lanes] partial table from the conv1 workgroups -> mixture.py:84-114
         if constexpr (ONEHOT) {
           if (sampler) {
+            if (tab_period) nap_until(t_tab + tab_period - (tab_period >> 3));      // (see the MoL head below)
             __builtin_amdgcn_s_setprio(3);
             // the 256 logits (conv1d_2 summed in chunk order + bias by the conv1 workgroups): class lane + 64 k in granule 4 lane + k,
             // two 16-byte loads per lane
@@ -479,6 +571,7 @@ __device__ __forceinline__ void chain_role(const XArgs& xa, int b, rsrc_t rs)
                 if (__all(d0.y == tag && d0.w == tag && d1.y == tag && d1.w == tag)) break;
                 if (!poll_tick(pl, 34)) break;
             }
+            now_tab = __builtin_amdgcn_s_memtime();
             XSTAMP(true, 18);
             XMARK(SEG1 ? 30 : ROLE_CHAIN, 5);
             const float y[4] = {__uint_as_float(d0.x), __uint_as_float(d0.z), __uint_as_float(d1.x), __uint_as_float(d1.z)};
@@ -496,6 +589,11 @@ __device__ __forceinline__ void chain_role(const XArgs& xa, int b, rsrc_t rs)
           }
         } else
         if (sampler) {
+            // The head has nothing to do between the causal layer and the table, almost a whole step: it sleeps through it like the
+            // layer waves in front of their input -- polling, it would send four L2 loads per round for ~8 us and take issue slots
+            // from wave 3 on its SIMD while that one carries the chain.  The table completes one step period after it did last time;
+            // the nap ends an eighth of a period (~1 us: the margin of the other L2 polls) before that.
+            if (tab_period) nap_until(t_tab + tab_period - (tab_period >> 3));
             __builtin_amdgcn_s_setprio(3);
             // the [8 chunk pairs][32 outputs][2] partial table, each granule once, FOUR 16-byte loads per round (every load in a polling
             // round adds to its round trip: 16 8-byte loads per lane were measured at +0.2 us on the hop over 8): lanes 0-31 chunks 0-7
@@ -516,6 +614,7 @@ __device__ __forceinline__ void chain_role(const XArgs& xa, int b, rsrc_t rs)
                 if (!poll_tick(pl, 34)) break;
             }
             // (a watchdog abort ends the loop at its head: an exit here would make the compiler thread state flags through the hand-off path)
+            now_tab = __builtin_amdgcn_s_memtime();                // (only read here, like now_in)
             XSTAMP(true, 18);
             XMARK(SEG1 ? 30 : ROLE_CHAIN, 5);
             float y = g_val(q[0]);                                     // chunk partials added in chunk order (AC-1)
@@ -1415,7 +1514,11 @@ __device__ __forceinline__ void lc_role(const XArgs& xa, const XStreams<NS>& sx,
                                 __builtin_amdgcn_s_sleep(8);
                             }
                         }
-                        (a.state + (long long)b * L.state_stride)[L.st_lcprev + l * 64 + lane] = r;
+                        // (BIG: the address is made HERE, on the last step -- hoisted out of the step loop, the 64-bit pairs of two streams x
+                        // two layers sat in VGPRs for the whole launch, and one of them went to scratch)
+                        int off = L.st_lcprev + l * 64 + lane;
+                        if constexpr (BIG) asm volatile("" : "+v"(off));
+                        (a.state + (long long)b * L.state_stride)[off] = r;
                     }
                 }
             }
@@ -1513,19 +1616,24 @@ __global__ void __launch_bounds__(512) wn_xcd_generate_kernel(XArgs xa)
             // (AC-1b: bias / gc / lc reach the chain inside the service workgroup's addend: the chain code does not depend on which of
             // them the model has, every model takes the instantiations with the layer count folded)
             if (ticket % nseg == 0) {
-                // the sampling chain of the hparams-default model once per layer count of a wave (first chain workgroup: 4 or 3)
+                // wave 7 is the head; waves 0..5 carry the layers (wave 6 has none): the sampling chain of a full wave once with a later
+                // wave behind it (granule stores deferred) and once as the stack's last wave, a short wave with the count at run time
                 const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-                const int nlw = a.lay.NL - (wv < 6 ? 4 * wv : 24 + 3 * (wv - 6));
-                if (forced) chain_role<INSTR, true, true, false, BIGK, -1, ONEHOT>(xa, b, rs);
-                else if (nlw >= 4 && wv < 6) chain_role<INSTR, true, false, false, BIGK, 4, ONEHOT, 0>(xa, b, rs);
-                else if (nlw >= 3 && wv == 6) chain_role<INSTR, true, false, false, BIGK, 3, ONEHOT, 0>(xa, b, rs);
-                else if (nlw >= 3 && wv == 7) chain_role<INSTR, true, false, false, BIGK, 3, ONEHOT, 1>(xa, b, rs);
+                const int nlw = a.lay.NL - kChainLpw * wv;      // layers from this wave's first one on
+                if (wv == 7) {
+                    if (forced) chain_role<INSTR, true, true, false, BIGK, 0, ONEHOT, true>(xa, b, rs);
+                    else chain_role<INSTR, true, false, false, BIGK, 0, ONEHOT, true>(xa, b, rs);
+                }
+                else if (wv >= kXcdSeg0Layers / kChainLpw || nlw <= 0) {}
+                else if (forced) chain_role<INSTR, true, true, false, BIGK, -1, ONEHOT>(xa, b, rs);
+                else if (nlw > kChainLpw) chain_role<INSTR, true, false, false, BIGK, kChainLpw, ONEHOT, false, true>(xa, b, rs);
+                else if (nlw == kChainLpw) chain_role<INSTR, true, false, false, BIGK, kChainLpw, ONEHOT, false, false>(xa, b, rs);
                 else chain_role<INSTR, true, false, false, BIGK, -1, ONEHOT>(xa, b, rs);
             } else if constexpr (BIGK) {
                 // (the second chain workgroup has no head: nothing of it depends on the input / output type)
                 const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
                 if (forced) chain_role<INSTR, true, true, true, true, -1>(xa, b, rs);
-                else if (a.lay.NL - kXcdSeg0Layers - 4 * wv >= 4) chain_role<INSTR, true, false, true, true, 4>(xa, b, rs);
+                else if (a.lay.NL - kXcdSeg0Layers - kChainLpw * wv >= kChainLpw) chain_role<INSTR, true, false, true, true, kChainLpw>(xa, b, rs);
                 else chain_role<INSTR, true, false, true, true, -1>(xa, b, rs);
             }
         }
@@ -2561,7 +2669,7 @@ int xcd_launch(const XcdLaunch& p, hipStream_t st)
     xa.p = p;
     xa.n_lc_wg = xcd_lc_workgroups(p.lay);
     xa.lc_lpw = lc_layers_per_wave(p.lay);
-    // chain workgroup: hand-off boxes + the dense kernels of its layers (136 KiB); more than 32 layers: the skip / service workgroups
+    // chain workgroup: hand-off boxes + the dense kernels of its layers + the waves' streamed half tiles (152 KiB); more than 30 layers: the skip / service workgroups
     // keep the tiles of layers 0 .. NL-41 in LDS next to their value slots (159 KiB of the CU's 160)
     const bool many = xcd_uses_many(p.lay, p.B, p.many);
     xa.total_roles = 0;
@@ -2570,7 +2678,7 @@ int xcd_launch(const XcdLaunch& p, hipStream_t st)
         if (many) xa.total_roles += 2 * ((ns + kMS - 1) / kMS) + 16 + xa.n_lc_wg;
         else xa.total_roles += ns * (p.lay.NL > kXcdSeg0Layers ? 2 : 1) + ns + 16 + xa.n_lc_wg;
     }
-    const size_t shm = many ? (size_t)kManyLds * 4 : p.lay.NL > kXcdSeg0Layers ? (size_t)159 * 1024 : (size_t)(2048 + 32 * 1024) * 4;
+    const size_t shm = many ? (size_t)kManyLds * 4 : p.lay.NL > kXcdSeg0Layers ? (size_t)159 * 1024 : (size_t)kXcdChainLdsFloats * 4;
     int dev = 0, cus = 256;
     hipDeviceProp_t prop;
     if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;

@@ -7,7 +7,9 @@
 
 namespace twv {
 
-constexpr int kXcdSeg0Layers = 30;     // first chain workgroup: waves 0..5 four layers each, waves 6 and 7 three (wave 7 also runs the causal layer + sampler)
+constexpr int kXcdChainHalfTiles = 2048 + 30 * 1024;      // chain workgroup LDS (floats): behind the boxes and 30 dense kernels, 6 half tiles of 1024
+constexpr int kXcdChainLdsFloats = kXcdChainHalfTiles + 6 * 1024;      // 152 KiB
+constexpr int kXcdSeg0Layers = 30;     // first chain workgroup: waves 0..5 five layers each, wave 7 the causal layer + sampler
 constexpr int kXcdMaxLayers = 50;      // a second chain workgroup takes layers 30.. (hparams.py has 50); limit: LDS of the service workgroup (tiles of layers 0 .. NL-33) and of the skip workgroups (value slots of two streams + tiles of layers 0 .. NL-41)
 constexpr int kXcdLs = 64;             // layer slots of the per-layer exchange arrays
 constexpr int kXcdStreams = 32;        // up to four streams per XCD (stream b runs on XCD b % 8), each with its own chain workgroup
