@@ -23,11 +23,6 @@
 #include "twv_dev.hpp"
 #include "twv_dpp.hpp"
 
-// the GEMM options of the pass in flight on this thread: copied from the HANDLE at the top of twv_tacotron_infer (they are per-handle
-// options -- one model's A/B toggle must not change another model's launches in the same process)
-static thread_local int g_gemm_valu = 0;            // "gemm_valu" option: 1 = the VALU kernel (cross-check of the MFMA one)
-static thread_local int g_gemm_group = 1;           // "gemm_group" option: 0 = one launch per GEMM, separate highway kernels (A/B runs, cross-check)
-static thread_local int g_hw_stack = 1;             // "highway_stack" option: 0 = one launch per highway layer (the form before round 6: A/B runs, cross-check)
 // "gemm_timing" option (measurement aid, bench.py's `tacotron.roofline`): every GEMM launch is bracketed by a pair of HIP events on
 // its stream and its useful FLOPs (2 * rows * K * N, unpadded) are counted; twv_tacotron_gemm_stats sums both since the option was set.
 // PROCESS-WIDE and single-threaded by design (one bench process, one model): the option set through any handle counts the launches of
@@ -846,8 +841,41 @@ struct DecArgs {
     unsigned long long* prof;   // optional [iters][16] s_memtime stamps of workgroup 0 (tuning aid)
     int nbias;                  // total bias floats over the decoder stages
 };
-// LDS map of the decoder (float offsets)
-struct DecLds { int cat, vec, h[5], frame, ctx, part, sc, p, cp, lg, al, q; };
+// GEMV chunk partials of the split and the single-workgroup decoder (floats): one area, as large as the stage that needs most of it
+__host__ __device__ __forceinline__ int dec_partials(int M, int R, int D1, int SEc, int ENC, int AS, int DR, int T)
+{
+    const int kmax = (D1 + SEc + ENC + AS) > 2 * DR ? (D1 + SEc + ENC + AS) : 2 * DR, umax = AS > DR ? AS : DR;
+    const int part = ((kmax + 31) / 32) * ((2 * umax + 63) / 64) * 64;      // a GRU's gates: the deepest contraction x the widest output
+    const int part2 = ((DR + 31) / 32) * ((M * R + 63) / 64) * 64;          // the output projection: dec_rnn_size deep, num_mels * r wide
+    const int part3 = ((T + 31) / 32) * ENC;                                // the context: 32-step chunk values of every memory column
+    const int p12 = part > part2 ? part : part2;
+    return p12 > part3 ? p12 : part3;
+}
+// LDS carve of tc_decoder_kernel, shared by the kernel and the host's size check (float offsets, all multiples of 4 floats).  The kernel
+// reads the offsets only and passes 0 for the partials size; the host passes dec_partials(...) and reads `total`.
+struct Dec1Carve { int cat, vec, ha, frame, ctx, y, Tp, al, p, cp, q, pq, scp, part, total; };
+__host__ __device__ __forceinline__ Dec1Carve dec1_carve(int M, int ENC, int AS, int layers, int DR, int A, int T, int partials, int (&hr)[4])
+{
+    Dec1Carve c;
+    int o = 0;
+    c.cat = o; o += 1024;                                 // concatenated GEMV input
+    c.vec = o; o += 1024;                                 // scratch vector (kept h | u, prenet outputs, ...)
+    c.ha = o; o += AS;                                    // attention GRU state
+    for (int i = 0; i < layers; ++i) { hr[i] = o; o += DR; }  // residual GRU states
+    c.frame = o; o += ((M + 31) / 32) * 32;               // padded to whole chunks (pad stays zero)
+    c.ctx = o; o += ENC;
+    c.y = o; o += DR;
+    c.Tp = ((T + 3) / 4) * 4;
+    c.al = o; o += c.Tp;                                  // alignments of the previous step
+    c.p = o; o += c.Tp;
+    c.cp = o; o += c.Tp;
+    c.q = o; o += c.Tp;
+    c.pq = o; o += A;
+    c.scp = o; o += c.Tp * 8;                             // score chunk values [t][A/32]
+    c.part = o; o += partials;                            // GEMV chunk partials (dec_partials)
+    c.total = o;
+    return c;
+}
 
 // y_part[(nb*nchunk + ch)*64 + lane] = chunk(nb, ch) of W (tiles at wt) applied to the LDS vector at xo; tiles round-robin over
 // the 8 waves, two named buffers so that the next tile travels while the current one is used
@@ -921,24 +949,11 @@ __global__ void __launch_bounds__(512) tc_decoder_kernel(DecArgs a)
     const rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.P), 0, (int)a.packed_bytes, 0x00020000);
     const float* keys = a.keys + (long long)n * T * A;
     const float* memo = a.memo + (long long)n * T * ENC;
-    // ---- LDS carve (all multiples of 4 floats)
-    int o = 0;
-    const int o_cat = o; o += 1024;                       // concatenated GEMV input
-    const int o_vec = o; o += 1024;                       // scratch vector (kept h | u, prenet outputs, ...)
-    const int o_ha = o; o += AS;                          // attention GRU state
+    // ---- LDS carve
     int o_hr[4];
-    for (int i = 0; i < a.layers; ++i) { o_hr[i] = o; o += DR; }
-    const int o_frame = o; o += ((M + 31) / 32) * 32;     // padded to whole chunks (pad stays zero)
-    const int o_ctx = o; o += ENC;
-    const int o_y = o; o += DR;
-    const int Tp = ((T + 3) / 4) * 4;
-    const int o_al = o; o += Tp;                          // alignments of the previous step
-    const int o_p = o; o += Tp;
-    const int o_cp = o; o += Tp;
-    const int o_q = o; o += Tp;
-    const int o_pq = o; o += A;
-    const int o_scp = o; o += Tp * 8;                     // score chunk values [t][A/32]
-    const int o_part = o;                                 // GEMV chunk partials (largest: (nin+U)/32 chunks x 2U/64 blocks x 64)
+    const Dec1Carve cv = dec1_carve(M, ENC, AS, a.layers, DR, A, T, 0, o_hr);
+    const int o_cat = cv.cat, o_vec = cv.vec, o_ha = cv.ha, o_frame = cv.frame, o_ctx = cv.ctx, o_y = cv.y, Tp = cv.Tp;
+    const int o_al = cv.al, o_p = cv.p, o_cp = cv.cp, o_q = cv.q, o_pq = cv.pq, o_scp = cv.scp, o_part = cv.part;
 
     // ---- initial state (tacotron.py:184-195, AttentionWrapper.zero_state, helpers.py:90-92)
     const float* init = a.init + (long long)n * (AS + a.layers * DR);
@@ -1320,6 +1335,57 @@ __device__ __forceinline__ void decg_sload_geo(const int* p, i32x4s& lo, i32x4s&
 {
     asm volatile("s_load_dwordx4 %0, %2, 0x0\n\ts_load_dwordx4 %1, %2, 0x30\n\ts_waitcnt lgkmcnt(0)" : "=&s"(lo), "=&s"(hi) : "s"(p) : "memory");
 }
+// LDS carve of tc_decoder_g_kernel, shared by the kernel and the host's size check (float offsets).  The sizes come by value and the
+// function is inlined: in the DEF instantiations they are constants and the offsets in front of the input-length areas fold.  The kernel
+// reads the offsets only and passes 0 for the partials size; the host passes dec_partials(...) and reads `total`.
+struct DecgCarve {
+    int cat, cat2, vec, cand, keep, ha, hr0, frame, ctx, y, out, pq, abort, tab, nv, ab, bias, Tp, al, p, cp, q, scp, lf, cum, keys, memo, part, total;
+};
+__host__ __device__ __forceinline__ DecgCarve decg_carve(int M, int R, int D1, int SEc, int ENC, int AS, int NL, int DR, int A, int T, int Tp, int lg, int ak,
+                                                         bool kv, int nbias, int partials)
+{
+    DecgCarve c;
+    const int G = 1 << lg, DE = D1 + SEc;
+    int o = 0;
+    c.cat = o; o += 1024;
+    // the attention GRU's input [prenet_out | attention | ha] has a buffer of its own: its three parts are written where they are
+    // produced (the prenet's epilogue, the context's gather of the PREVIOUS step, the attention cell's update), not copied together
+    // behind a barrier at the start of every step
+    c.cat2 = o; o += ((DE + ENC + AS + 63) / 64) * 64;
+    c.vec = o; o += 1024;                                 // gathered gates (r | u), prenet hidden
+    c.cand = o; o += 512;
+    c.keep = o; o += 512;                                 // h before the update
+    c.ha = o; o += AS;
+    c.hr0 = o; o += NL * DR;                              // residual GRU states, layer l at hr0 + l*DR
+    c.frame = o; o += ((M + 31) / 32) * 32;
+    c.ctx = o; o += ENC;
+    c.y = o; o += DR;
+    c.out = o; o += ((M * R + 63) / 64) * 64;
+    // (areas whose size does not depend on the input length first: with the default sizes folded in, their offsets are constants)
+    c.pq = o; o += A + A / 8;                             // attention tables are skewed by 4 words per 32 (see the score phase)
+    c.abort = o; o += 4;
+    o = (o + 3) & ~3;
+    c.tab = o; o += 16 * DS_STRIDE;                       // stage table (16-byte aligned records)
+    c.nv = o; o += A + A / 8;                             // normed_v, attention bias
+    c.ab = o; o += A + A / 8;
+    c.bias = o; o += nbias;                               // every stage's bias vector, in stage order
+    c.Tp = Tp;                                            // T rounded up to a multiple of 4
+    c.al = o; o += c.Tp;
+    c.p = o; o += c.Tp;
+    c.cp = o; o += c.Tp;
+    c.q = o; o += c.Tp;
+    c.scp = o; o += c.Tp * 8;
+    // AK_LOC: the combined location filter, one skewed A-row per tap, and the cumulative alignments (the mechanism's state) between
+    // 16 zero words on either side -- the 'same' padding of the 31-tap convolution
+    c.lf = o; o += ak == AK_LOC ? kLocTaps * (A + A / 8) : 0;
+    c.cum = o; o += ak == AK_LOC ? c.Tp + 32 : 0;
+    // kv: this workgroup's key rows / memory columns held in LDS
+    c.keys = o; o += kv ? ((T + G - 1) >> lg) * (A + A / 8) : 0;
+    c.memo = o; o += kv ? T * ((ENC >> lg) + 8) : 0;      // rows 8 words apart in the banks: the context's chains k = t mod 4 read four rows at once
+    c.part = o; o += partials;                            // GEMV chunk partials (dec_partials)
+    c.total = o + 3;                                      // (+ 3: the most c.tab's alignment can take; the launch has always asked for it)
+    return c;
+}
 template <bool PROF, bool DEF, int AK = AK_MON>
 __global__ void __launch_bounds__(512) tc_decoder_g_kernel(DecGArgs ga)
 {
@@ -1360,44 +1426,13 @@ __global__ void __launch_bounds__(512) tc_decoder_g_kernel(DecGArgs ga)
     const float* memo = a.memo + (long long)n * T * ENC;
     unsigned long long* X = ga.exch + (long long)n * 2 * kExN;
     // ---- LDS carve
-    int o = 0;
-    const int o_cat = o; o += 1024;
-    // the attention GRU's input [prenet_out | attention | ha] has a buffer of its own: its three parts are written where they are
-    // produced (the prenet's epilogue, the context's gather of the PREVIOUS step, the attention cell's update), not copied together
-    // behind a barrier at the start of every step
-    const int o_cat2 = o; o += ((DE + ENC + AS + 63) / 64) * 64;
-    const int o_vec = o; o += 1024;                       // gathered gates (r | u), prenet hidden
-    const int o_cand = o; o += 512;
-    const int o_keep = o; o += 512;                       // h before the update
-    const int o_ha = o; o += AS;
-    const int o_hr0 = o; o += NL * DR;              // residual GRU states, layer l at o_hr0 + l*DR
-    const int o_frame = o; o += ((M + 31) / 32) * 32;
-    const int o_ctx = o; o += ENC;
-    const int o_y = o; o += DR;
-    const int o_out = o; o += ((M * R + 63) / 64) * 64;
-    // (areas whose size does not depend on the input length first: with the default sizes folded in, their offsets are constants)
-    const int o_pq = o; o += A + A / 8;                   // attention tables are skewed by 4 words per 32 (see the score phase)
-    const int o_abort = o; o += 4;
-    o = (o + 3) & ~3;
-    const int o_tab = o; o += 16 * DS_STRIDE;             // stage table (16-byte aligned records)
-    const int o_nv = o; o += A + A / 8;                   // normed_v, attention bias
-    const int o_ab = o; o += A + A / 8;
-    const int o_bias = o; o += DEF ? 256 + 128 + 3 * 256 + 256 + 2 * 3 * 256 + 400 : a.nbias;   // every stage's bias vector, in stage order
-    const int Tp = ((T + 3) / 4) * 4;
-    const int o_al = o; o += Tp;
-    const int o_p = o; o += Tp;
-    const int o_cp = o; o += Tp;
-    const int o_q = o; o += Tp;
-    const int o_scp = o; o += Tp * 8;
-    // AK_LOC: the combined location filter, one skewed A-row per tap, and the cumulative alignments (the mechanism's state) between
-    // 16 zero words on either side -- the 'same' padding of the 31-tap convolution
-    const int o_lf = o; o += AK == AK_LOC ? kLocTaps * (A + A / 8) : 0;
-    const int o_cum = o; o += AK == AK_LOC ? Tp + 32 : 0;
     const bool kv = ga.kv_lds != 0;                       // this workgroup's key rows / memory columns held in LDS
+    const DecgCarve cv = decg_carve(M, R, D1, SEc, ENC, AS, NL, DR, A, T, ((T + 3) / 4) * 4, lg, AK, kv, DEF ? 256 + 128 + 3 * 256 + 256 + 2 * 3 * 256 + 400 : a.nbias, 0);
+    const int o_cat = cv.cat, o_cat2 = cv.cat2, o_vec = cv.vec, o_cand = cv.cand, o_keep = cv.keep, o_ha = cv.ha, o_hr0 = cv.hr0, o_frame = cv.frame;
+    const int o_ctx = cv.ctx, o_y = cv.y, o_out = cv.out, o_pq = cv.pq, o_abort = cv.abort, o_tab = cv.tab, o_nv = cv.nv, o_ab = cv.ab, o_bias = cv.bias;
+    const int Tp = cv.Tp, o_al = cv.al, o_p = cv.p, o_cp = cv.cp, o_q = cv.q, o_scp = cv.scp, o_lf = cv.lf, o_cum = cv.cum;
+    const int o_keys = cv.keys, o_memo = cv.memo, o_part = cv.part;
     const int nt_all = T > g ? (T - g + G - 1) >> lg : 0;
-    const int o_keys = o; o += kv ? ((T + G - 1) >> lg) * (A + A / 8) : 0;
-    const int o_memo = o; o += kv ? T * ((ENC >> lg) + 8) : 0;   // rows 8 words apart in the banks: the context's chains k = t mod 4 read four rows at once
-    const int o_part = o;
 
     const float* init = a.init + (long long)n * (AS + NL * DR);
     for (int i = tid; i < AS; i += 512) lds[o_ha + i] = init[i];
@@ -2519,8 +2554,7 @@ struct twv_tacotron {
     int dec_groups = 0;             // 0 auto (16, halved until N*G fits the CUs), -1 single-workgroup kernel
     int dec_split_all = -1;         // prenet + query layer split over the workgroups: -1 = when the exchanges are L2-local, 0 / 1
     int dec_local = 1;              // split kernel: 1 = an utterance's workgroups on one XCD (exchanges through its L2), 0 = spread over the XCDs
-    int gemm_valu = 0, gemm_group = 1;   // see g_gemm_valu / g_gemm_group
-    int hw_stack = 1;                    // see g_hw_stack
+    int gemm_valu = 0, gemm_group = 1, hw_stack = 1;   // "gemm_valu", "gemm_group", "highway_stack": see TacoLaunch
     long long blob_floats, packed_floats;
     long long xt_off = 0;           // row tiles of the XCD-local decoder kernel [32 slices][8 waves][kXSlots][2048]
     TMat emb, semb;                 // raw tables (K rows x N)
@@ -2820,41 +2854,60 @@ extern "C" int twv_tacotron_pack(const twv_tacotron* h, const float* blob, void*
     return TWV_OK;
 }
 
-// workspace (floats) for N utterances of T tokens
-static long long taco_ws_floats(const twv_tacotron* h, int N, int T)
+// ---- the workspace of N utterances of T tokens: ONE carve, which also sizes it (twv_tacotron_workspace_bytes is the carve on a null base)
+struct TacoCarve {
+    float *bankbuf, *poolbuf, *ra, *rb, *rc, *rd, *gx, *cx;     // CBHG row buffers (shared by the encoder and the post net)
+    float *memo, *keys, *postout;                               // encoder output [N][T][ENC], keys [N][T][A], post CBHG output
+    float *semb, *sv[8], *dinit;                                // speaker embedding rows, one piece per dense output, the decoder's initial states
+    float *exch, *xexch, *stabf;    // exchange granules of the split ([N][2][kExN]) and the XCD-local ([8][2][kXU * 512]) decoder; stage tables
+    int *tickets, *xtickets; long long exch_floats, xexch_floats;    // the role tickets behind either area; granules + tickets: what a launch clears
+};
+static long long taco_carve(const twv_tacotron* h, int N, int T, float* base, TacoCarve& c)
 {
     const twv_tacotron_dims& d = h->d;
-    const long long rowsE = (long long)N * T, rowsP = (long long)N * d.max_iters * d.reduction_factor;
-    const long long rows = rowsE > rowsP ? rowsE : rowsP;
-    const int CBe = d.enc_bank_size * d.enc_bank_channel_size, CBp = d.post_bank_size * d.post_bank_channel_size;
-    const int CB = CBe > CBp ? CBe : CBp;
-    long long f = 0;
-    f += rows * CB * 2;                 // bank output + maxpool output
-    f += rows * 512 * 4;                // generic row buffers (<= 512 wide): a, b, c, d
-    f += rows * 256 * 3;                // Gx (2 dirs x 256), Cx (2 x 128) -> 768 per row
-    f += rowsE * 256 * 2;               // encoder output (memory), keys
-    f += (long long)N * 4096;           // speaker-dependent vectors
-    f += rowsP * 256;                   // post CBHG output
-    f += (long long)N * 4096 + 16;      // decoder exchange granules + the local mode's role tickets
-    f += 512 * 256;                     // split decoder: stage tables
-    f += 8LL * 2 * kXU * 512 * 2 + 64;  // XCD-local decoder: exchange granules per XCD + role tickets
-    return f + 1024;
+    const long long rowsE = (long long)N * T, rowsP = (long long)N * d.max_iters * d.reduction_factor, rmax = rowsE > rowsP ? rowsE : rowsP;
+    const int CBe = d.enc_bank_size * d.enc_bank_channel_size, CBp = d.post_bank_size * d.post_bank_channel_size, CB = CBe > CBp ? CBe : CBp;
+    long long used = 0;
+    // (pieces start on multiples of four floats: the GEMM epilogues store single floats, hipMemcpy2DAsync and the gathers need no more)
+    auto take = [&](long long n) { float* p = base ? base + used : nullptr; used += (n + 3) / 4 * 4; return p; };
+    c.bankbuf = take(rmax * CB); c.poolbuf = take(rmax * CB);                           // bank output, maxpool output
+    c.ra = take(rmax * 512); c.rb = take(rmax * 512); c.rc = take(rmax * 512); c.rd = take(rmax * 512);      // generic row buffers (<= 512 wide)
+    c.gx = take(rmax * 512); c.cx = take(rmax * 256);                                   // Gx (2 dirs x 256), Cx (2 x 128)
+    c.memo = take(rowsE * 2 * d.enc_rnn_size); c.keys = take(rowsE * 256);              // (attention_size <= 256)
+    // speaker-dependent vectors: every piece has its real size.  The three areas are never smaller than the N * 64, N * 1984 and N * 2048
+    // floats they had as fixed offsets of one N * 4096 block, so a model that fit those has the workspace size it always had.
+    const long long SE = d.num_speakers > 1 ? d.speaker_embedding_size : 0, ninit = d.attention_state_size + (long long)d.dec_layer_num * d.dec_rnn_size;
+    c.semb = take(N * (SE > 64 ? SE : 64));
+    long long dsum = 0;
+    for (int i = 0; i < 8; ++i) { c.sv[i] = i < h->ndense ? take((long long)N * h->dn[i]) : nullptr; dsum += i < h->ndense ? h->dn[i] : 0; }
+    if (dsum < 1984) take(N * (1984 - dsum));
+    c.dinit = take(N * (ninit > 2048 ? ninit : 2048));
+    c.postout = take(rowsP * 2 * d.post_rnn_size);
+    c.exch_floats = (long long)N * 2 * kExN * 2 + 16; c.xexch_floats = 8LL * 2 * kXU * 512 * 2 + 64;   // 8-byte granules + 8 (16 words) / 64 tickets
+    c.exch = take(c.exch_floats); c.tickets = base ? reinterpret_cast<int*>(c.exch + (c.exch_floats - 16)) : nullptr;
+    c.stabf = take(512 * 256);                                                          // up to 512 workgroups
+    c.xexch = take(c.xexch_floats); c.xtickets = base ? reinterpret_cast<int*>(c.xexch + (c.xexch_floats - 64)) : nullptr;
+    return used;
 }
-extern "C" size_t twv_tacotron_workspace_bytes(const twv_tacotron* h, int batch, int t_in) { return (size_t)taco_ws_floats(h, batch, t_in) * 4; }
+extern "C" size_t twv_tacotron_workspace_bytes(const twv_tacotron* h, int batch, int t_in) { TacoCarve c; return (size_t)taco_carve(h, batch, t_in, nullptr, c) * 4; }
 
 static inline int tgrid(long long n) { long long g = (n + 255) / 256; return (int)(g < 1 ? 1 : (g > 16384 ? 16384 : g)); }
 
-static GemmArgs gemm_args(const float* P, const float* X, int ldx, int rows, int T, int Cin, int kw, const TMat& W,
-                          const TVec* bias, int act, const TVec* inv, const TVec* shift, const float* add1, int ld1, const float* add2,
-                          int ld2, float* Y, int ldy, int col0)
+// what the launch helpers of one twv_tacotron_infer call share: the stream, the packed weights and the handle's GEMM options (per-handle
+// options -- one model's A/B toggle must not change another model's launches in the same process)
+struct TacoLaunch {
+    hipStream_t st; const float* P;
+    int gemm_valu;      // "gemm_valu" option: 1 = the VALU kernel (cross-check of the MFMA one)
+    int gemm_group;     // "gemm_group" option: 0 = one launch per GEMM, separate highway kernels (A/B runs, cross-check)
+    int hw_stack;       // "highway_stack" option: 0 = one launch per highway layer (the form before round 6: A/B runs, cross-check)
+    const float* at(const TVec& v) const { return P + v.off; }
+};
+// a plain GEMM Y[:, col0 ..] = X' . W; the optional epilogue terms (bias + act, bn_inv / bn_shift, add1 / add2) are set by name on the result
+static GemmArgs gemm_args(const TacoLaunch& L, const float* X, int ldx, int rows, int T, int Cin, int kw, const TMat& W, float* Y, int ldy, int col0)
 {
-    GemmArgs a;
+    GemmArgs a = {};                    // bias, bn_inv, bn_shift, add1, add2, bias2 null; act TACT_NONE, ld1, ld2, mode 0
     a.X = X; a.ldx = ldx; a.rows = rows; a.T = T; a.Cin = Cin; a.kw = kw; a.pl = (kw - 1) / 2;
-    a.Wt = P + W.off; a.K = W.K; a.N = W.N;
-    a.bias = bias ? P + bias->off : nullptr; a.act = act;
-    a.bn_inv = inv ? P + inv->off : nullptr; a.bn_shift = shift ? P + shift->off : nullptr;
-    a.add1 = add1; a.ld1 = ld1; a.add2 = add2; a.ld2 = ld2; a.Y = Y; a.ldy = ldy; a.col0 = col0;
-    a.bias2 = nullptr; a.mode = 0;
+    a.Wt = L.P + W.off; a.K = W.K; a.N = W.N; a.Y = Y; a.ldy = ldy; a.col0 = col0;
     return a;
 }
 // "gemm_timing": a pair of events around the launch(es) of one call, useful FLOPs counted per problem
@@ -2879,35 +2932,29 @@ struct GemmTimed {
     }
     ~GemmTimed() { if (e1) (void)hipEventRecord(e1, st); }
 };
-static void launch_gemm_args(hipStream_t st, const GemmArgs& a)
+static void launch_gemm_args(const TacoLaunch& L, const GemmArgs& a)
 {
     // mode 1 (highway pair): N counts H and T columns, each useful once
-    GemmTimed tm(st, 2.0 * (double)a.rows * (double)a.K * (double)a.N, 1);
-    if (g_gemm_valu)
-        hipLaunchKernelGGL(tc_gemm_kernel, dim3((a.rows + kGemmRows - 1) / kGemmRows), dim3(256), kGemmRows * kGemmKS * 4, st, a);
+    GemmTimed tm(L.st, 2.0 * (double)a.rows * (double)a.K * (double)a.N, 1);
+    if (L.gemm_valu)
+        hipLaunchKernelGGL(tc_gemm_kernel, dim3((a.rows + kGemmRows - 1) / kGemmRows), dim3(256), kGemmRows * kGemmKS * 4, L.st, a);
     else {
         const int nchunk_ = (a.K + 31) / 32;
         const long long wgs = (long long)((a.rows + kMmRows - 1) / kMmRows) * ((a.N + 127) / 128);
         if (a.mode == 1)
-            hipLaunchKernelGGL(tc_gemm_mfma_highway_kernel, dim3((a.rows + kMmRows - 1) / kMmRows, (a.N + 127) / 128), dim3(256), 0, st, a);
+            hipLaunchKernelGGL(tc_gemm_mfma_highway_kernel, dim3((a.rows + kMmRows - 1) / kMmRows, (a.N + 127) / 128), dim3(256), 0, L.st, a);
         else if (wgs < 192 && nchunk_ >= 8)      // too few tiles for the chip and a deep contraction: chunk-parallel waves
-            hipLaunchKernelGGL(tc_gemm_mfma_ck_kernel, dim3((a.rows + 31) / 32, (a.N + 63) / 64), dim3(256), 0, st, a);
+            hipLaunchKernelGGL(tc_gemm_mfma_ck_kernel, dim3((a.rows + 31) / 32, (a.N + 63) / 64), dim3(256), 0, L.st, a);
         else
-            hipLaunchKernelGGL(tc_gemm_mfma_kernel, dim3((a.rows + kMmRows - 1) / kMmRows, (a.N + 127) / 128), dim3(256), 0, st, a);
+            hipLaunchKernelGGL(tc_gemm_mfma_kernel, dim3((a.rows + kMmRows - 1) / kMmRows, (a.N + 127) / 128), dim3(256), 0, L.st, a);
     }
-}
-static void launch_gemm(hipStream_t st, const float* P, const float* X, int ldx, int rows, int T, int Cin, int kw, const TMat& W,
-                        const TVec* bias, int act, const TVec* inv, const TVec* shift, const float* add1, int ld1, const float* add2,
-                        int ld2, float* Y, int ldy, int col0)
-{
-    launch_gemm_args(st, gemm_args(P, X, ldx, rows, T, Cin, kw, W, bias, act, inv, shift, add1, ld1, add2, ld2, Y, ldy, col0));
 }
 // independent problems as ONE grid (tc_gemm_mfma_group_kernel), deepest contraction first; with the "gemm_valu" cross-check option, or when
 // grouping is switched off ("gemm_group" = 0: A/B runs), one launch per problem as before
-static void launch_gemm_group(hipStream_t st, std::vector<GemmArgs> v)
+static void launch_gemm_group(const TacoLaunch& L, std::vector<GemmArgs> v)
 {
     if (v.empty()) return;
-    if (g_gemm_valu || !g_gemm_group || v.size() == 1) { for (const auto& a : v) launch_gemm_args(st, a); return; }
+    if (L.gemm_valu || !L.gemm_group || v.size() == 1) { for (const auto& a : v) launch_gemm_args(L, a); return; }
     std::stable_sort(v.begin(), v.end(), [](const GemmArgs& x, const GemmArgs& y) { return x.K > y.K; });
     for (size_t i0 = 0; i0 < v.size(); i0 += kGroupMax) {
         GemmGroup g;
@@ -2924,82 +2971,184 @@ static void launch_gemm_group(hipStream_t st, std::vector<GemmArgs> v)
         }
         for (int p = g.n; p <= kGroupMax; ++p) g.start[p] = wg;
         for (int p = g.n; p < kGroupMax; ++p) { g.nby[p] = 1; g.a[p] = v[i0]; }
-        GemmTimed tm(st, flop, 1);
-        hipLaunchKernelGGL(tc_gemm_mfma_group_kernel, dim3(wg), dim3(256), 0, st, g);
+        GemmTimed tm(L.st, flop, 1);
+        hipLaunchKernelGGL(tc_gemm_mfma_group_kernel, dim3(wg), dim3(256), 0, L.st, g);
     }
 }
 
 // modules.py:25-74 for `rows` = N*T rows
-static void run_cbhg(hipStream_t st, const twv_tacotron* h, const float* P, const TCbhg& c, const float* in, int Cin, int N, int T,
-                     int bank, int bch, const int32_t* proj, int pw, int depth, const float* before_hw, const float* init,
-                     const int32_t* lengths, float* bankbuf, float* poolbuf, float* ra, float* rb, float* rc, float* gx, float* cx, float* out)
+static void run_cbhg(const TacoLaunch& L, const TCbhg& c, const float* in, int Cin, int N, int T, int bank, int bch, const int32_t* proj, int pw,
+                     int depth, const float* before_hw, const float* init, const int32_t* lengths, const TacoCarve& w, float* out)
 {
+    hipStream_t st = L.st;
+    const float *P = L.P; float *ra = w.ra, *rb = w.rb, *rc = w.rc;
+    GemmArgs a;                         // (the problem in hand: gemm_args, then its optional terms by name)
+    std::vector<GemmArgs> v;
     const int rows = N * T, CB = bank * bch, rnn = 128;
-    {                                   // conv bank -> concatenated channels: `bank` independent GEMMs, one grid
-        std::vector<GemmArgs> v;
-        for (int k = 1; k <= bank; ++k)
-            v.push_back(gemm_args(P, in, Cin, rows, T, Cin, k, c.W[k], &c.b[k], TACT_RELU, &c.inv[k], &c.shift[k], nullptr, 0, nullptr, 0, bankbuf, CB, (k - 1) * bch));
-        launch_gemm_group(st, v);
+    for (int k = 1; k <= bank; ++k) {   // conv bank -> concatenated channels: `bank` independent GEMMs, one grid
+        a = gemm_args(L, in, Cin, rows, T, Cin, k, c.W[k], w.bankbuf, CB, (k - 1) * bch);
+        a.bias = L.at(c.b[k]); a.act = TACT_RELU; a.bn_inv = L.at(c.inv[k]); a.bn_shift = L.at(c.shift[k]);
+        v.push_back(a);
     }
-    if (CB % 4 == 0) hipLaunchKernelGGL(tc_maxpool2_kernel, dim3(tgrid((long long)rows * (CB / 4))), dim3(256), 0, st, bankbuf, rows, T, CB, poolbuf);
-    else hipLaunchKernelGGL(tc_maxpool2_scalar_kernel, dim3(tgrid((long long)rows * CB)), dim3(256), 0, st, bankbuf, rows, T, CB, poolbuf);
-    launch_gemm(st, P, poolbuf, CB, rows, T, CB, pw, c.pW[0], &c.pb[0], TACT_RELU, &c.pinv[0], &c.pshift[0], nullptr, 0, nullptr, 0, ra, proj[0], 0);
+    launch_gemm_group(L, v);
+    if (CB % 4 == 0) hipLaunchKernelGGL(tc_maxpool2_kernel, dim3(tgrid((long long)rows * (CB / 4))), dim3(256), 0, st, w.bankbuf, rows, T, CB, w.poolbuf);
+    else hipLaunchKernelGGL(tc_maxpool2_scalar_kernel, dim3(tgrid((long long)rows * CB)), dim3(256), 0, st, w.bankbuf, rows, T, CB, w.poolbuf);
+    a = gemm_args(L, w.poolbuf, CB, rows, T, CB, pw, c.pW[0], ra, proj[0], 0);
+    a.bias = L.at(c.pb[0]); a.act = TACT_RELU; a.bn_inv = L.at(c.pinv[0]); a.bn_shift = L.at(c.pshift[0]);
+    launch_gemm_args(L, a);
     // second projection + residual: (proj + inputs) + before_highway
-    launch_gemm(st, P, ra, proj[0], rows, T, proj[0], pw, c.pW[1], &c.pb[1], TACT_NONE, &c.pinv[1], &c.pshift[1], in, Cin, before_hw, before_hw ? rnn : 0, rb, proj[1], 0);
+    a = gemm_args(L, ra, proj[0], rows, T, proj[0], pw, c.pW[1], rb, proj[1], 0);
+    a.bias = L.at(c.pb[1]); a.bn_inv = L.at(c.pinv[1]); a.bn_shift = L.at(c.pshift[1]);
+    a.add1 = in; a.ld1 = Cin; a.add2 = before_hw; a.ld2 = before_hw ? rnn : 0;
+    launch_gemm_args(L, a);
     float* hw = rb;
-    if (c.has_dense) { launch_gemm(st, P, rb, proj[1], rows, T, proj[1], 1, c.dW, &c.db, TACT_NONE, nullptr, nullptr, nullptr, 0, nullptr, 0, rc, rnn, 0); hw = rc; }
-    float* hH = ra;
-    float* hT = (hw == rc) ? rb : rc;
-    if (!g_gemm_valu && g_gemm_group && g_hw_stack && depth >= 1 && depth <= kHwMaxDepth) {
+    if (c.has_dense) {
+        a = gemm_args(L, rb, proj[1], rows, T, proj[1], 1, c.dW, rc, rnn, 0);
+        a.bias = L.at(c.db);
+        launch_gemm_args(L, a);
+        hw = rc;
+    }
+    float *hH = ra, *hT = (hw == rc) ? rb : rc;
+    if (!L.gemm_valu && L.gemm_group && L.hw_stack && depth >= 1 && depth <= kHwMaxDepth) {
         // the whole stack in one launch: rows stay in LDS between the layers
         HwStackArgs ha;
         ha.X = hw; ha.ldx = rnn; ha.rows = rows; ha.depth = depth;
         for (int i = 0; i < depth; ++i) { ha.Wt[i] = P + c.hHT[i].off; ha.bh[i] = P + c.hHb[i].off; ha.bt[i] = P + c.hTb[i].off; }
-        ha.Y = hH; ha.ldy = rnn;
-        {
-            GemmTimed tm(st, 2.0 * (double)rows * (double)rnn * (double)(2 * rnn) * depth, 1);
-            if ((rows + 63) / 64 >= 256) {
-                const size_t shm = (size_t)2 * 64 * kHwPitch * 4;
-                (void)hipFuncSetAttribute((const void*)tc_highway_stack_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-                hipLaunchKernelGGL(tc_highway_stack_kernel<2>, dim3((rows + 63) / 64), dim3(256), shm, st, ha);
-            } else {
-                const size_t shm = (size_t)2 * 32 * kHwPitch * 4;
-                hipLaunchKernelGGL(tc_highway_stack_kernel<1>, dim3((rows + 31) / 32), dim3(256), shm, st, ha);
-            }
+        ha.Y = hw = hH; ha.ldy = rnn;
+        GemmTimed tm(st, 2.0 * (double)rows * (double)rnn * (double)(2 * rnn) * depth, 1);
+        if ((rows + 63) / 64 >= 256) {
+            const size_t shm = (size_t)2 * 64 * kHwPitch * 4;
+            (void)hipFuncSetAttribute((const void*)tc_highway_stack_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+            hipLaunchKernelGGL(tc_highway_stack_kernel<2>, dim3((rows + 63) / 64), dim3(256), shm, st, ha);
+        } else {
+            const size_t shm = (size_t)2 * 32 * kHwPitch * 4;
+            hipLaunchKernelGGL(tc_highway_stack_kernel<1>, dim3((rows + 31) / 32), dim3(256), shm, st, ha);
         }
-        hw = hH;
     } else
     for (int i = 0; i < depth; ++i) {
-        if (!g_gemm_valu && g_gemm_group) {
+        if (!L.gemm_valu && L.gemm_group) {
             // the whole highway layer in one launch (mm_body, mode 1): H and T columns interleaved in the tiles, output to the other buffer
-            GemmArgs a = gemm_args(P, hw, rnn, rows, T, rnn, 1, c.hHT[i], &c.hHb[i], TACT_NONE, nullptr, nullptr, hw, rnn, nullptr, 0, hH, rnn, 0);
-            a.bias2 = P + c.hTb[i].off; a.mode = 1;
-            launch_gemm_args(st, a);
+            a = gemm_args(L, hw, rnn, rows, T, rnn, 1, c.hHT[i], hH, rnn, 0);
+            a.bias = L.at(c.hHb[i]); a.add1 = hw; a.ld1 = rnn; a.bias2 = L.at(c.hTb[i]); a.mode = 1;
+            launch_gemm_args(L, a);
             float* t = hw; hw = hH; hH = t;
             if (hT == hw) hT = hH;
             continue;
         }
-        launch_gemm(st, P, hw, rnn, rows, T, rnn, 1, c.hH[i], &c.hHb[i], TACT_RELU, nullptr, nullptr, nullptr, 0, nullptr, 0, hH, rnn, 0);
-        launch_gemm(st, P, hw, rnn, rows, T, rnn, 1, c.hT[i], &c.hTb[i], TACT_SIGMOID, nullptr, nullptr, nullptr, 0, nullptr, 0, hT, rnn, 0);
+        a = gemm_args(L, hw, rnn, rows, T, rnn, 1, c.hH[i], hH, rnn, 0);
+        a.bias = L.at(c.hHb[i]); a.act = TACT_RELU;
+        launch_gemm_args(L, a);
+        a = gemm_args(L, hw, rnn, rows, T, rnn, 1, c.hT[i], hT, rnn, 0);
+        a.bias = L.at(c.hTb[i]); a.act = TACT_SIGMOID;
+        launch_gemm_args(L, a);
         hipLaunchKernelGGL(tc_highway_kernel, dim3(tgrid((long long)rows * rnn)), dim3(256), 0, st, hH, hT, hw, (long long)rows * rnn);
     }
     // biGRU: hoisted x halves (four GEMMs over the same rows: one grid), then the recurrent kernel
-    {
-        std::vector<GemmArgs> v;
-        for (int dr = 0; dr < 2; ++dr) {
-            v.push_back(gemm_args(P, hw, rnn, rows, T, rnn, 1, c.gWgx[dr], nullptr, TACT_NONE, nullptr, nullptr, nullptr, 0, nullptr, 0, gx + (long long)dr * rows * 2 * rnn, 2 * rnn, 0));
-            v.push_back(gemm_args(P, hw, rnn, rows, T, rnn, 1, c.gWcx[dr], nullptr, TACT_NONE, nullptr, nullptr, nullptr, 0, nullptr, 0, cx + (long long)dr * rows * rnn, rnn, 0));
-        }
-        launch_gemm_group(st, v);
+    v.clear();
+    for (int dr = 0; dr < 2; ++dr) {
+        v.push_back(gemm_args(L, hw, rnn, rows, T, rnn, 1, c.gWgx[dr], w.gx + (long long)dr * rows * 2 * rnn, 2 * rnn, 0));
+        v.push_back(gemm_args(L, hw, rnn, rows, T, rnn, 1, c.gWcx[dr], w.cx + (long long)dr * rows * rnn, rnn, 0));
     }
+    launch_gemm_group(L, v);
     // (rows past an utterance's length are not written by the recurrent kernel: zeros; without lengths every row is)
     if (lengths) hipLaunchKernelGGL(tc_zero_kernel, dim3(tgrid((long long)rows * 2 * rnn)), dim3(256), 0, st, out, (long long)rows * 2 * rnn);
     GruSeqArgs g;
-    g.Gx = gx; g.Cx = cx; g.gx_dstride = (long long)rows * 2 * rnn; g.cx_dstride = (long long)rows * rnn;
+    g.Gx = w.gx; g.Cx = w.cx; g.gx_dstride = (long long)rows * 2 * rnn; g.cx_dstride = (long long)rows * rnn;
     for (int dr = 0; dr < 2; ++dr) { g.Wgh[dr] = P + c.gWgh[dr].off; g.Wch[dr] = P + c.gWch[dr].off; g.bg[dr] = P + c.gbg[dr].off; g.bc[dr] = P + c.gbc[dr].off; }
     g.init = init; g.lengths = lengths; g.T = T; g.out = out;
     hipLaunchKernelGGL(tc_gru_seq_kernel, dim3(N * 2), dim3(512), 384 * 4, st, g);
-    (void)h;
+}
+
+static int taco_cus() { int cus = 0, dev = 0; return hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess ? cus : -1; }
+// ---- which decoder kernel serves (handle, batch, t_in, options) on a device of `cus` compute units, and with what launch geometry: the
+// one statement of it, read by twv_tacotron_infer (which launches) and twv_tacotron_decoder_kernel_name (which labels measurements)
+constexpr long long kLdsBudget = 160 * 1024;    // bytes of LDS one workgroup may ask for (gfx950)
+enum { TK_NONE = 0, TK_X, TK_G, TK_ONE };       // nothing, tc_decoder_x_kernel (XCD-resident), tc_decoder_g_kernel (split), tc_decoder_kernel
+struct TacoRoute {
+    int kind;                           // the kernel that serves the call -- and, when `err` refuses it, the one that would serve it
+    int err; const char* msg;           // TWV_OK, or the code and message twv_tacotron_infer fails with
+    bool simple; int ak, nbias;         // model_type 'simple'; attention kind (AK_*); total bias floats over the decoder stages
+    XStageTab xt;                       // the decoder step as a stage table
+    int G, local, split_all, kv_lds;    // TK_G: workgroups per utterance, placement, which stages are split, keys / memory in LDS
+    int upx; bool mm;                   // TK_X: utterances per XCD; the tasks run on the matrix core
+    bool def;                           // TK_X / TK_G: the instantiation with the hparams-default sizes folded in
+    long long lds_floats; int wgs;      // dynamic LDS and workgroups of the launch
+};
+static TacoRoute taco_route(const twv_tacotron* h, int N, int T, int cus)
+{
+    const twv_tacotron_dims& d = h->d;
+    const int M = d.num_mels, R = d.reduction_factor, D0 = d.dec_prenet_sizes[0], D1 = d.dec_prenet_sizes[1], A = d.attention_size,
+              AS = d.attention_state_size, DR = d.dec_rnn_size, NL = d.dec_layer_num, ENC = 2 * d.enc_rnn_size, at = d.attention_type;
+    TacoRoute r = {};
+    r.simple = d.num_speakers > 1 && d.model_simple && d.speaker_embedding_size != 1; r.nbias = D0 + D1 + 3 * AS + DR + NL * 3 * DR + M * R;
+    r.ak = (at == TWV_ATT_BAH_MON_NORM || at == TWV_ATT_BAH_MON) ? AK_MON : (at == TWV_ATT_BAH_NORM || at == TWV_ATT_BAH) ? AK_SOFT
+         : (at == TWV_ATT_LOC_SEN) ? AK_LOC : AK_LUONG;
+    taco_xstages(h, r.xt);
+    const int SEc = r.simple ? d.speaker_embedding_size : 0;
+    auto refuse = [&](const char* msg) { r.err = TWV_E_UNSUPPORTED; r.msg = msg; return r; };
+    // Which kernel (round 6, scripts/tacotron_bench.py --batch 8 / 16 / 24 / 32): the XCD-resident kernel is the default wherever it fits
+    // (up to four utterances per XCD = batch 32); pass times against the split kernel are in profiles/r06_tacotron_decoder_ab.txt.
+    // (Until its scratch spills and per-utterance branch chains were removed it tied the split kernel at four utterances per XCD.)
+    r.upx = (N + 7) / 8;
+    const int nu = r.upx < N ? r.upx : N;
+    const long long xfl = xdec_carve(M, D1, ENC, AS, NL, DR, A, T, nu < 1 ? 1 : nu, r.xt.nst).total + 64;
+    const bool xok = taco_xdec_ok(h, r.xt) && cus >= 256 && r.upx <= kXU && T <= 512 && xfl * 4 <= kLdsBudget && !r.simple;
+    const bool one_or_x = h->dec_groups == -1 || h->dec_groups == 32, other_att = at != TWV_ATT_BAH_MON_NORM;
+    r.kind = other_att && one_or_x ? TK_NONE : h->dec_groups == -1 ? TK_ONE
+           : xok && !other_att && (h->dec_groups == 32 || h->dec_groups == 0) ? TK_X : TK_G;
+    if (r.simple && one_or_x) return refuse("model_type 'simple' runs on the split decoder kernel only (decoder_groups 0, 1, 2, 4, 8 or 16)");
+    if (other_att && one_or_x) return refuse("attention_type other than bah_mon_norm runs on the split decoder kernel only (decoder_groups 0, 1, 2, 4, 8 or 16)");
+    if (h->dec_groups == 32 && r.kind != TK_X)
+        return refuse("decoder_groups = 32 (XCD-local decoder) needs 256 CUs, batch <= 32, t_in <= 512 and the default decoder sizes");
+    if (r.kind == TK_X) {
+        // every XCD's 32 workgroups hold the decoder in registers and serve that XCD's utterances
+        r.lds_floats = xfl; r.wgs = 2 * cus; r.mm = r.upx > 2;
+        r.def = M == 80 && R == 5 && A == 256 && AS == 256 && ENC == 256 && DR == 256 && D1 == 128 && NL == 2 && r.xt.nst == 11;
+    } else if (r.kind == TK_ONE) {      // the single-workgroup kernel (kept as a cross-check of the split one)
+        int hr[4];
+        r.lds_floats = dec1_carve(M, ENC, AS, NL, DR, A, T, dec_partials(M, R, D1, 0, ENC, AS, DR, T), hr).total; r.wgs = N;
+    } else {
+        // G workgroups per utterance, all N*G co-resident (they exchange through polled granules)
+        int G = h->dec_groups > 0 ? h->dec_groups : 16;        // 16 workgroups per utterance up to batch 16, 8 up to 32, 4 up to 64, ...
+        while (G > 1 && (long long)N * G > cus) G >>= 1;
+        if (2 * (AS > DR ? AS : DR) > kExN || M * R > kExN || T > kExN || ENC > kExN) G = 1;
+        while (G > 1 && ENC % G) G >>= 1;
+        const int wgs_local = 8 * G * ((N + 7) / 8);
+        // 'local' maps workgroup -> (utterance, slice) by per-XCD tickets and assumes EIGHT XCDs that each receive G * ceil(N / 8)
+        // of the launch's workgroups: true of the 256-CU part in SPX mode (the same guard as the WaveNet XCD kernels, use_xcd).  On a
+        // part / partition with fewer XCDs or CUs (6-XCD devices, CPX) utterances whose n % 8 names a missing XCD would get no
+        // workgroup at all and their outputs would stay unwritten -- there the spread mapping is used.
+        r.local = (h->dec_local && G > 1 && wgs_local <= cus && cus >= 256) ? 1 : 0;
+        r.wgs = r.local ? wgs_local : N * G;
+        r.split_all = h->dec_split_all < 0 ? r.local : h->dec_split_all;
+        if (r.wgs > 512) return refuse("more than 512 decoder workgroups");
+        int lg = 0;
+        while ((1 << lg) < G) ++lg;                            // (G is a power of two)
+        r.G = G;
+        const int Tp = (T + 3) / 4 * 4, part = dec_partials(M, R, D1, SEc, ENC, AS, DR, T);
+        r.kv_lds = (long long)decg_carve(M, R, D1, SEc, ENC, AS, NL, DR, A, T, Tp, lg, r.ak, true, r.nbias, part).total * 4 <= kLdsBudget ? 1 : 0;
+        r.lds_floats = decg_carve(M, R, D1, SEc, ENC, AS, NL, DR, A, T, Tp, lg, r.ak, r.kv_lds != 0, r.nbias, part).total;
+        // the hparams-default sizes have an instantiation of their own (sizes folded: half the scalar-register spills)
+        r.def = !r.simple && G == 8 && M == 80 && R == 5 && A == 256 && AS == 256 && ENC == 256 && DR == 256 && D0 == 256 && D1 == 128 && NL == 2;
+    }
+    if (r.kind != TK_X && r.lds_floats * 4 > kLdsBudget) return refuse("decoder LDS footprint exceeds 160 KiB (t_in too large)");
+    return r;
+}
+// a route's instantiation: <PROF, DEF, MM> / <PROF, DEF, AK> (the other attention kinds have no instrumented build: a profile buffer is ignored there)
+static const void* taco_decoder_fn(const TacoRoute& r, bool prof)
+{
+    const bool def = r.def, mm = r.mm;
+    if (r.kind == TK_ONE) return (const void*)tc_decoder_kernel;
+    if (r.kind == TK_X)
+        return prof ? (def ? (mm ? (const void*)tc_decoder_x_kernel<true, true, true> : (const void*)tc_decoder_x_kernel<true, true, false>)
+                           : (mm ? (const void*)tc_decoder_x_kernel<true, false, true> : (const void*)tc_decoder_x_kernel<true, false, false>))
+                    : (def ? (mm ? (const void*)tc_decoder_x_kernel<false, true, true> : (const void*)tc_decoder_x_kernel<false, true, false>)
+                           : (mm ? (const void*)tc_decoder_x_kernel<false, false, true> : (const void*)tc_decoder_x_kernel<false, false, false>));
+    return r.ak == AK_SOFT ? (def ? (const void*)tc_decoder_g_kernel<false, true, AK_SOFT> : (const void*)tc_decoder_g_kernel<false, false, AK_SOFT>)
+         : r.ak == AK_LUONG ? (def ? (const void*)tc_decoder_g_kernel<false, true, AK_LUONG> : (const void*)tc_decoder_g_kernel<false, false, AK_LUONG>)
+         : r.ak == AK_LOC ? (def ? (const void*)tc_decoder_g_kernel<false, true, AK_LOC> : (const void*)tc_decoder_g_kernel<false, false, AK_LOC>)
+         : prof ? (def ? (const void*)tc_decoder_g_kernel<true, true> : (const void*)tc_decoder_g_kernel<true, false>)
+                : (def ? (const void*)tc_decoder_g_kernel<false, true> : (const void*)tc_decoder_g_kernel<false, false>);
 }
 
 extern "C" int twv_tacotron_infer(const twv_tacotron* h, const void* packed, const int32_t* tokens, const int32_t* lengths,
@@ -3009,85 +3158,62 @@ extern "C" int twv_tacotron_infer(const twv_tacotron* h, const void* packed, con
     if (!h || !packed || !tokens || !lengths || !workspace || !mel || !status) return twv_fail(TWV_E_INVALID, "null argument");
     if (!speaker_ids && h->d.num_speakers > 1) return twv_fail(TWV_E_INVALID, "speaker_ids is required for a multi-speaker model");
     if (batch < 1 || t_in < 1 || t_in > 1024) return twv_fail(TWV_E_INVALID, "batch >= 1 and 1 <= t_in <= 1024 required");
-    g_gemm_valu = h->gemm_valu; g_gemm_group = h->gemm_group; g_hw_stack = h->hw_stack;
     const twv_tacotron_dims& d = h->d;
-    hipStream_t st = (hipStream_t)stream;
-    const float* P = (const float*)packed;
+    hipStream_t st = (hipStream_t)stream; const float* P = (const float*)packed;
+    const TacoLaunch L{st, P, h->gemm_valu, h->gemm_group, h->hw_stack};
     const int N = batch, T = t_in, rows = N * T;
-    const int E = d.embedding_size, SE = d.speaker_embedding_size, P0 = d.enc_prenet_sizes[0], P1 = d.enc_prenet_sizes[1], RN = 128,
-              A = d.attention_size, AS = d.attention_state_size, DR = d.dec_rnn_size, M = d.num_mels, R = d.reduction_factor, ENC = 256;
-    const int TO = d.max_iters * R, rowsP = N * TO;
-    const long long rmax = rows > rowsP ? rows : rowsP;
-    const int CBe = d.enc_bank_size * d.enc_bank_channel_size, CBp = d.post_bank_size * d.post_bank_channel_size, CB = CBe > CBp ? CBe : CBp;
+    const int E = d.embedding_size, SE = d.speaker_embedding_size, P0 = d.enc_prenet_sizes[0], P1 = d.enc_prenet_sizes[1],
+              A = d.attention_size, AS = d.attention_state_size, DR = d.dec_rnn_size, M = d.num_mels, R = d.reduction_factor, ENC = 2 * d.enc_rnn_size;
+    const int TO = d.max_iters * R, rowsP = N * TO, dstride = AS + d.dec_layer_num * DR;
+    // the decoder kernel of this call, or its refusal -- before anything is launched
+    const int cus = taco_cus();
+    if (cus < 0) return twv_fail(TWV_E_HIP, "hipDeviceGetAttribute(hipDeviceAttributeMultiprocessorCount) failed");
+    const TacoRoute r = taco_route(h, N, T, cus);
+    if (r.err) return twv_fail(r.err, r.msg);
     HIPCHK(hipMemsetAsync(status, 0, 16, st));
-    // ---- workspace carve
-    float* w = (float*)workspace;
-    float* bankbuf = w; w += rmax * CB;
-    float* poolbuf = w; w += rmax * CB;
-    float* ra = w; w += rmax * 512;
-    float* rb = w; w += rmax * 512;
-    float* rc = w; w += rmax * 512;
-    float* rd = w; w += rmax * 512;
-    float* gx = w; w += rmax * 512;
-    float* cx = w; w += rmax * 256;
-    float* memo = w; w += (long long)rows * 256;
-    float* keys = w; w += (long long)rows * 256;
-    float* spk = w; w += (long long)N * 4096;
-    float* postout = w; w += (long long)rowsP * 256;
-    float* exch = w; w += (long long)N * 2 * kExN * 2 + 16; // decoder exchange granules (8 bytes each) + 8 role tickets
-    float* stabf = w; w += 512 * 256;                       // the split decoder's per-workgroup stage tables (up to 512 workgroups)
-    float* xexch = w; w += 8LL * 2 * kXU * 512 * 2 + 64;    // XCD-local decoder: granules [8][2][kXU*512] + tickets
+    TacoCarve w;
+    taco_carve(h, N, T, (float*)workspace, w);
     // ---- tacotron.py:51-60 embedding, :67-82 speaker embedding + deep_dense (softsign)
-    hipLaunchKernelGGL(tc_embed_kernel, dim3(tgrid((long long)rows * E)), dim3(256), 0, st, P + h->emb.off, tokens, rows, E, ra);
-    const bool multi = d.num_speakers > 1;
-    const bool simple = multi && d.model_simple && SE != 1;     // tacotron.py:85-90: no speaker-dependent states, the embedding goes into the decoder
-    // spk layout: [N][SE] at 0, then per dense i a [N][dn_i] block
-    float* sv[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    // decoder initial states gathered as [N][AS + layers*DR]
-    float* dinit = spk + (long long)N * 2048;
-    if (simple) {
-        hipLaunchKernelGGL(tc_gather_rows_kernel, dim3(tgrid((long long)N * SE)), dim3(256), 0, st, P + h->semb.off, speaker_ids, N, SE, spk);
-        HIPCHK(hipMemsetAsync(dinit, 0, (size_t)N * (AS + d.dec_layer_num * DR) * 4, st));
-    } else if (multi) {
-        { float* q = spk + (long long)N * 64; for (int i = 0; i < h->ndense; ++i) { sv[i] = q; q += (long long)N * h->dn[i]; } }
-        if (SE == 1) {
-            // tacotron.py:69-75 get_embed: tf.nn.embedding_lookup of five tables by speaker id
-            for (int i = 0; i < h->ndense; ++i)
-                hipLaunchKernelGGL(tc_gather_rows_kernel, dim3(tgrid((long long)N * h->dn[i])), dim3(256), 0, st, P + h->stab[i].off, speaker_ids, N, h->dn[i], sv[i]);
-        } else {
-            hipLaunchKernelGGL(tc_gather_rows_kernel, dim3(tgrid((long long)N * SE)), dim3(256), 0, st, P + h->semb.off, speaker_ids, N, SE, spk);
-            // (the decoder's initial states -- dense layers 2 .. -- are written where the decoder reads them: [N][AS + layers * DR])
-            std::vector<GemmArgs> v;
-            const int dstride = AS + d.dec_layer_num * DR;
-            for (int i = 0; i < h->ndense; ++i) {
-                if (i >= 2 && i < 3 + d.dec_layer_num)
-                    v.push_back(gemm_args(P, spk, SE, N, 1, SE, 1, h->dW[i], &h->db[i], TACT_SOFTSIGN, nullptr, nullptr, nullptr, 0, nullptr, 0, dinit, dstride,
-                                          i == 2 ? 0 : AS + (i - 3) * DR));
-                else
-                    v.push_back(gemm_args(P, spk, SE, N, 1, SE, 1, h->dW[i], &h->db[i], TACT_SOFTSIGN, nullptr, nullptr, nullptr, 0, nullptr, 0, sv[i], h->dn[i], 0));
-            }
-            launch_gemm_group(st, v);
-        }
-        for (int i = 0; SE == 1 && i < 1 + d.dec_layer_num; ++i) {
-            const int wdt = i == 0 ? AS : DR;
-            HIPCHK(hipMemcpy2DAsync(dinit + (i == 0 ? 0 : AS + (i - 1) * DR), (size_t)(AS + d.dec_layer_num * DR) * 4, sv[2 + i], (size_t)wdt * 4,
-                                    (size_t)wdt * 4, N, hipMemcpyDeviceToDevice, st));
-        }
+    hipLaunchKernelGGL(tc_embed_kernel, dim3(tgrid((long long)rows * E)), dim3(256), 0, st, P + h->emb.off, tokens, rows, E, w.ra);
+    const bool multi = d.num_speakers > 1, simple = r.simple;   // 'simple' (tacotron.py:85-90): no speaker-dependent states, the embedding goes into the decoder
+    float *const *sv = w.sv, *dinit = w.dinit;      // a [N][dn_i] block per dense output; the decoder's initial states [N][AS + layers * DR]
+    if (multi && SE != 1)       // the speaker embedding rows ('simple' and deepvoice)
+        hipLaunchKernelGGL(tc_gather_rows_kernel, dim3(tgrid((long long)N * SE)), dim3(256), 0, st, P + h->semb.off, speaker_ids, N, SE, w.semb);
+    if (simple || !multi) {
+        // tacotron.py:97-104: no before_highway (sv[0] is null: the residual is proj + inputs), zero GRU / attention-cell states
+        HIPCHK(hipMemsetAsync(dinit, 0, (size_t)N * dstride * 4, st));
+    } else if (SE == 1) {
+        // tacotron.py:69-75 get_embed: tf.nn.embedding_lookup of five tables by speaker id; the state tables then go where the decoder reads them
+        for (int i = 0; i < h->ndense; ++i)
+            hipLaunchKernelGGL(tc_gather_rows_kernel, dim3(tgrid((long long)N * h->dn[i])), dim3(256), 0, st, P + h->stab[i].off, speaker_ids, N, h->dn[i], sv[i]);
+        for (int i = 0; i < 1 + d.dec_layer_num; ++i)
+            HIPCHK(hipMemcpy2DAsync(dinit + (i == 0 ? 0 : AS + (i - 1) * DR), (size_t)dstride * 4, sv[2 + i], (size_t)(i == 0 ? AS : DR) * 4,
+                                    (size_t)(i == 0 ? AS : DR) * 4, N, hipMemcpyDeviceToDevice, st));
     } else {
-        // tacotron.py:97-104: no before_highway (sv[0] stays null: the residual is proj + inputs), zero GRU / attention-cell states
-        HIPCHK(hipMemsetAsync(dinit, 0, (size_t)N * (AS + d.dec_layer_num * DR) * 4, st));
+        // (the decoder's initial states -- dense layers 2 .. -- are written where the decoder reads them: [N][AS + layers * DR])
+        std::vector<GemmArgs> v;
+        for (int i = 0; i < h->ndense; ++i) {
+            const bool state = i >= 2 && i < 3 + d.dec_layer_num;
+            v.push_back(state ? gemm_args(L, w.semb, SE, N, 1, SE, 1, h->dW[i], dinit, dstride, i == 2 ? 0 : AS + (i - 3) * DR)
+                              : gemm_args(L, w.semb, SE, N, 1, SE, 1, h->dW[i], sv[i], h->dn[i], 0));
+            v.back().bias = L.at(h->db[i]); v.back().act = TACT_SOFTSIGN;
+        }
+        launch_gemm_group(L, v);
     }
     // ---- tacotron.py:108 prenet, :113 encoder CBHG
-    launch_gemm(st, P, ra, E, rows, T, E, 1, h->pW1, &h->pb1, TACT_RELU, nullptr, nullptr, nullptr, 0, nullptr, 0, rb, P0, 0);
-    launch_gemm(st, P, rb, P0, rows, T, P0, 1, h->pW2, &h->pb2, TACT_RELU, nullptr, nullptr, nullptr, 0, nullptr, 0, rd, P1, 0);
-    run_cbhg(st, h, P, h->enc, rd, P1, N, T, d.enc_bank_size, d.enc_bank_channel_size, d.enc_proj_sizes, d.enc_proj_width, d.enc_highway_depth,
-             sv[0], sv[1], lengths, bankbuf, poolbuf, ra, rb, rc, gx, cx, memo);
+    GemmArgs a = gemm_args(L, w.ra, E, rows, T, E, 1, h->pW1, w.rb, P0, 0);
+    a.bias = L.at(h->pb1); a.act = TACT_RELU;
+    launch_gemm_args(L, a);
+    a = gemm_args(L, w.rb, P0, rows, T, P0, 1, h->pW2, w.rd, P1, 0);
+    a.bias = L.at(h->pb2); a.act = TACT_RELU;
+    launch_gemm_args(L, a);
+    run_cbhg(L, h->enc, w.rd, P1, N, T, d.enc_bank_size, d.enc_bank_channel_size, d.enc_proj_sizes, d.enc_proj_width, d.enc_highway_depth,
+             sv[0], sv[1], lengths, w, w.memo);
     // memory is already zero past the lengths (pre-zeroed GRU output); keys = memory_layer(memory)
-    launch_gemm(st, P, memo, ENC, rows, T, ENC, 1, h->Wm, nullptr, TACT_NONE, nullptr, nullptr, nullptr, 0, nullptr, 0, keys, A, 0);
+    launch_gemm_args(L, gemm_args(L, w.memo, ENC, rows, T, ENC, 1, h->Wm, w.keys, A, 0));
     // ---- decoder
     DecArgs da;
-    da.P = P;
-    da.w.dp1 = h->dpW1.off; da.w.dp1b = h->dpb1.off; da.w.dp2 = h->dpW2.off; da.w.dp2b = h->dpb2.off;
+    da.P = P; da.w.dp1 = h->dpW1.off; da.w.dp1b = h->dpb1.off; da.w.dp2 = h->dpW2.off; da.w.dp2b = h->dpb2.off;
     da.w.aWg = h->aWgm.off; da.w.abg = h->abg.off; da.w.aWc = h->aWcm.off; da.w.abc = h->abc.off;
     da.w.Wq = h->Wq.off; da.w.nv = h->nv.off; da.w.ab = h->ab.off; da.w.asb = h->asb.off; da.w.cW = h->cW.off; da.w.cb = h->cb.off;
     // the other attention types feed the same score slots (tc_decoder_g_kernel's AK_*): unnormalised Bahdanau scores read v itself and a
@@ -3097,144 +3223,51 @@ extern "C" int twv_tacotron_infer(const twv_tacotron* h, const void* packed, con
     if (at == TWV_ATT_BAH_MON || at == TWV_ATT_BAH) da.w.ab = h->zero.off;
     if (at == TWV_ATT_LOC_SEN) da.w.ab = h->lab.off;
     if (at != TWV_ATT_BAH_MON_NORM && at != TWV_ATT_BAH_MON) da.w.asb = h->zero.off;
-    const int ak = (at == TWV_ATT_BAH_MON_NORM || at == TWV_ATT_BAH_MON) ? AK_MON : (at == TWV_ATT_BAH_NORM || at == TWV_ATT_BAH) ? AK_SOFT
-                 : (at == TWV_ATT_LOC_SEN) ? AK_LOC : AK_LUONG;
     for (int i = 0; i < d.dec_layer_num; ++i) { da.w.rWg[i] = h->rWg[i].off; da.w.rbg[i] = h->rbg[i].off; da.w.rWc[i] = h->rWc[i].off; da.w.rbc[i] = h->rbc[i].off; }
-    da.w.oW = h->oW.off; da.w.ob = h->ob.off;
-    da.keys = keys; da.memo = memo; da.init = dinit; da.lengths = lengths;
+    da.w.oW = h->oW.off; da.w.ob = h->ob.off; da.keys = w.keys; da.memo = w.memo; da.init = dinit; da.lengths = lengths;
     da.N = N; da.T = T; da.M = M; da.R = R; da.D0 = d.dec_prenet_sizes[0]; da.D1 = d.dec_prenet_sizes[1]; da.A = A; da.AS = AS; da.ENC = ENC;
     da.DR = DR; da.layers = d.dec_layer_num; da.iters = d.max_iters; da.mel = mel; da.align = alignments; da.status = status;
-    da.SEc = simple ? SE : 0; da.semb = simple ? spk : nullptr;
-    da.packed_bytes = (long long)h->packed_floats * 4;
-    da.prof = h->prof;
-    da.nbias = da.D0 + da.D1 + 3 * AS + DR + d.dec_layer_num * 3 * DR + M * R;
-    {
-        const int Tp = (T + 3) / 4 * 4;
-        const int ain = da.D1 + da.SEc + ENC;
-        const int kmax = (ain + AS) > 2 * DR ? (ain + AS) : 2 * DR;
-        const long long part = (long long)((kmax + 31) / 32) * ((2 * (AS > DR ? AS : DR) + 63) / 64) * 64;
-        const long long part2 = (long long)((DR + 31) / 32) * ((M * R + 63) / 64) * 64;
-        const long long part3 = (long long)((T + 31) / 32) * ENC;
-        long long pmax = part > part2 ? part : part2;
-        pmax = pmax > part3 ? pmax : part3;
-        // G workgroups per utterance, all N*G co-resident (they exchange through polled granules)
-        int cus = 0, devid = 0;
-        HIPCHK(hipGetDevice(&devid));
-        HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, devid));
-        int G = h->dec_groups > 0 ? h->dec_groups : 16;        // 16 workgroups per utterance up to batch 16, 8 up to 32, 4 up to 64, ...
-        while (G > 1 && (long long)N * G > cus) G >>= 1;
-        if (2 * (AS > DR ? AS : DR) > kExN || M * R > kExN || T > kExN || ENC > kExN) G = 1;
-        while (G > 1 && ENC % G) G >>= 1;
-        XStageTab xt;
-        taco_xstages(h, xt);
-        const int upx = (N + 7) / 8;
-        long long xfl = 0;
-        {   // LDS of tc_decoder_x_kernel (the kernel's own carve)
-            const int nu = upx < N ? upx : N;
-            xfl = xdec_carve(M, da.D1, ENC, AS, d.dec_layer_num, DR, A, T, nu < 1 ? 1 : nu, xt.nst).total + 64;
-        }
-        const bool xok = taco_xdec_ok(h, xt) && cus >= 256 && upx <= kXU && T <= 512 && xfl * 4 <= 160 * 1024 && !simple;
-        if (simple && (h->dec_groups == -1 || h->dec_groups == 32))
-            return twv_fail(TWV_E_UNSUPPORTED, "model_type 'simple' runs on the split decoder kernel only (decoder_groups 0, 1, 2, 4, 8 or 16)");
-        if (at != TWV_ATT_BAH_MON_NORM && (h->dec_groups == -1 || h->dec_groups == 32))
-            return twv_fail(TWV_E_UNSUPPORTED, "attention_type other than bah_mon_norm runs on the split decoder kernel only (decoder_groups 0, 1, 2, 4, 8 or 16)");
-        // Which kernel (round 6, scripts/tacotron_bench.py --batch 8 / 16 / 24 / 32): the XCD-resident kernel is the default wherever it fits
-        // (up to four utterances per XCD = batch 32); pass times against the split kernel are in profiles/r06_tacotron_decoder_ab.txt.
-        // (Until its scratch spills and per-utterance branch chains were removed it tied the split kernel at four utterances per XCD.)
-        if (xok && at == TWV_ATT_BAH_MON_NORM && (h->dec_groups == 32 || h->dec_groups == 0)) {
-            // XCD-local kernel: every XCD's 32 workgroups hold the decoder in registers and serve that XCD's utterances
-            DecXArgs xa;
-            xa.d = da; xa.tab = xt; xa.upx = upx; xa.xt_off = h->xt_off; xa.stab = reinterpret_cast<int*>(stabf);
-            xa.nap_idle = h->xdec_nap_idle; xa.nap_owner = h->xdec_nap_owner; xa.nap_round = h->xdec_nap_round; xa.nap_w0 = h->xdec_nap_w0;
-            xa.exch = reinterpret_cast<unsigned long long*>(xexch);
-            xa.tickets = reinterpret_cast<int*>(xexch + 8LL * 2 * kXU * 512 * 2);
-            HIPCHK(hipMemsetAsync(xexch, 0, (size_t)(8LL * 2 * kXU * 512 * 2 + 64) * 4, st));
-            const size_t shm = (size_t)xfl * 4;
-            const bool xdef = M == 80 && R == 5 && A == 256 && AS == 256 && ENC == 256 && DR == 256 && da.D1 == 128 && d.dec_layer_num == 2 && xt.nst == 11;
-            const bool mm = upx > 2;
-            const void* kfn = da.prof ? (xdef ? (mm ? (const void*)tc_decoder_x_kernel<true, true, true> : (const void*)tc_decoder_x_kernel<true, true, false>)
-                                              : (mm ? (const void*)tc_decoder_x_kernel<true, false, true> : (const void*)tc_decoder_x_kernel<true, false, false>))
-                                      : (xdef ? (mm ? (const void*)tc_decoder_x_kernel<false, true, true> : (const void*)tc_decoder_x_kernel<false, true, false>)
-                                              : (mm ? (const void*)tc_decoder_x_kernel<false, false, true> : (const void*)tc_decoder_x_kernel<false, false, false>));
-            HIPCHK(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-            void* kargs[] = {&xa};
-            HIPCHK(hipLaunchKernel(kfn, dim3(2 * cus), dim3(512), kargs, shm, st));
-        } else if (h->dec_groups == 32) {
-            return twv_fail(TWV_E_UNSUPPORTED, "decoder_groups = 32 (XCD-local decoder) needs 256 CUs, batch <= 32, t_in <= 512 and the default decoder sizes");
-        } else
-        if (h->dec_groups == -1) {       // the single-workgroup kernel (kept as a cross-check of the split one)
-            const long long fl = 2048 + AS + d.dec_layer_num * DR + (M + 31) / 32 * 32 + ENC + DR + Tp * 4 + A + Tp * 8 + pmax;
-            const size_t shm = (size_t)fl * 4;
-            if (shm > 160 * 1024) return twv_fail(TWV_E_UNSUPPORTED, "decoder LDS footprint exceeds 160 KiB (t_in too large)");
-            HIPCHK(hipFuncSetAttribute((const void*)tc_decoder_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-            hipLaunchKernelGGL(tc_decoder_kernel, dim3(N), dim3(512), shm, st, da);
-        } else {
-            DecGArgs ga;
-            ga.d = da; ga.G = G; ga.exch = reinterpret_cast<unsigned long long*>(exch);
-            const int wgs_local = 8 * G * ((N + 7) / 8);
-            // 'local' maps workgroup -> (utterance, slice) by per-XCD tickets and assumes EIGHT XCDs that each receive G * ceil(N / 8)
-            // of the launch's workgroups: true of the 256-CU part in SPX mode (the same guard as the WaveNet XCD kernels, use_xcd).  On a
-            // part / partition with fewer XCDs or CUs (6-XCD devices, CPX) utterances whose n % 8 names a missing XCD would get no
-            // workgroup at all and their outputs would stay unwritten -- there the spread mapping is used.
-            ga.local = (h->dec_local && G > 1 && wgs_local <= cus && cus >= 256) ? 1 : 0;
-            const int wgs = ga.local ? wgs_local : N * G;
-            ga.split_all = h->dec_split_all < 0 ? ga.local : h->dec_split_all;
-            ga.stab = reinterpret_cast<int*>(stabf);
-            ga.att_g = at == TWV_ATT_LUONG_SCALED ? h->ag.off : h->one.off;
-            ga.loc_f = h->lf.off;
-            if (wgs > 512) return twv_fail(TWV_E_UNSUPPORTED, "more than 512 decoder workgroups");
-            HIPCHK(hipMemsetAsync(exch, 0, (size_t)N * 2 * kExN * 8 + 64, st));
-            ga.tickets = reinterpret_cast<int*>(exch + (long long)N * 2 * kExN * 2);
-            long long fl = 1024 * 2 + (da.D1 + da.SEc + ENC + AS + 63) / 64 * 64 + 512 * 2 + AS + d.dec_layer_num * DR + (M + 31) / 32 * 32 + ENC + DR + (M * R + 63) / 64 * 64 + Tp * 4 + A +
-                           Tp * 8 + 4 + 3 + 16 * 16 + 2 * A + 3 * (A / 8) + da.nbias + pmax;
-            if (ak == AK_LOC) fl += kLocTaps * (A + A / 8) + Tp + 32;        // the combined location filter, the cumulative alignments
-            const long long kvf = (long long)((T + G - 1) / G) * (A + A / 8) + (long long)T * (ENC / G + 8);
-            ga.kv_lds = (fl + kvf) * 4 <= 160 * 1024 ? 1 : 0;
-            if (ga.kv_lds) fl += kvf;
-            const size_t shm = (size_t)fl * 4;
-            if (shm > 160 * 1024) return twv_fail(TWV_E_UNSUPPORTED, "decoder LDS footprint exceeds 160 KiB (t_in too large)");
-            // plain launch (N * G <= CU count is enforced above); a cooperative launch was measured and dropped, see twv_wavenet.hip
-            // the hparams-default sizes have an instantiation of their own (sizes folded: half the scalar-register spills); the
-            // instrumented build (phase stamps) likewise
-            const bool def = !simple && G == 8 && M == 80 && R == 5 && A == 256 && AS == 256 && ENC == 256 && DR == 256 && da.D0 == 256 && da.D1 == 128 && d.dec_layer_num == 2;
-            // (the other attention kinds have no instrumented build: a profile buffer is ignored there)
-            const void* kfn = ak == AK_SOFT ? (def ? (const void*)tc_decoder_g_kernel<false, true, AK_SOFT> : (const void*)tc_decoder_g_kernel<false, false, AK_SOFT>)
-                            : ak == AK_LUONG ? (def ? (const void*)tc_decoder_g_kernel<false, true, AK_LUONG> : (const void*)tc_decoder_g_kernel<false, false, AK_LUONG>)
-                            : ak == AK_LOC ? (def ? (const void*)tc_decoder_g_kernel<false, true, AK_LOC> : (const void*)tc_decoder_g_kernel<false, false, AK_LOC>)
-                            : da.prof ? (def ? (const void*)tc_decoder_g_kernel<true, true> : (const void*)tc_decoder_g_kernel<true, false>)
-                                      : (def ? (const void*)tc_decoder_g_kernel<false, true> : (const void*)tc_decoder_g_kernel<false, false>);
-            HIPCHK(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-            void* kargs[] = {&ga};
-            HIPCHK(hipLaunchKernel(kfn, dim3(wgs), dim3(512), kargs, shm, st));
-        }
+    da.SEc = simple ? SE : 0; da.semb = simple ? w.semb : nullptr;
+    da.packed_bytes = (long long)h->packed_floats * 4; da.prof = h->prof; da.nbias = r.nbias;
+    DecXArgs xa; DecGArgs ga; void* kargs[1] = {&da};
+    if (r.kind == TK_X) {
+        xa.d = da; xa.tab = r.xt; xa.upx = r.upx; xa.xt_off = h->xt_off; xa.stab = reinterpret_cast<int*>(w.stabf);
+        xa.nap_idle = h->xdec_nap_idle; xa.nap_owner = h->xdec_nap_owner; xa.nap_round = h->xdec_nap_round; xa.nap_w0 = h->xdec_nap_w0;
+        xa.exch = reinterpret_cast<unsigned long long*>(w.xexch); xa.tickets = w.xtickets;
+        HIPCHK(hipMemsetAsync(w.xexch, 0, (size_t)w.xexch_floats * 4, st));
+        kargs[0] = &xa;
+    } else if (r.kind == TK_G) {
+        ga.d = da; ga.G = r.G; ga.local = r.local; ga.split_all = r.split_all; ga.kv_lds = r.kv_lds;
+        ga.exch = reinterpret_cast<unsigned long long*>(w.exch); ga.tickets = w.tickets; ga.stab = reinterpret_cast<int*>(w.stabf);
+        ga.att_g = at == TWV_ATT_LUONG_SCALED ? h->ag.off : h->one.off; ga.loc_f = h->lf.off;
+        HIPCHK(hipMemsetAsync(w.exch, 0, (size_t)w.exch_floats * 4, st));
+        kargs[0] = &ga;
     }
+    // plain launch (the route keeps the workgroups of the split and the resident kernel co-resident); a cooperative launch was measured and
+    // dropped, see twv_wavenet.hip
+    const void* kfn = taco_decoder_fn(r, da.prof != nullptr);
+    HIPCHK(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(r.lds_floats * 4)));
+    HIPCHK(hipLaunchKernel(kfn, dim3(r.wgs), dim3(512), kargs, (size_t)r.lds_floats * 4, st));
     // ---- tacotron.py:209 post CBHG (no lengths, zero init), :219 linear projection
     if (linear) {
-        run_cbhg(st, h, P, h->post, mel, M, N, TO, d.post_bank_size, d.post_bank_channel_size, d.post_proj_sizes, d.post_proj_width,
-                 d.post_highway_depth, nullptr, nullptr, nullptr, bankbuf, poolbuf, ra, rb, rc, gx, cx, postout);
-        launch_gemm(st, P, postout, 256, rowsP, TO, 256, 1, h->lW, &h->lb, TACT_NONE, nullptr, nullptr, nullptr, 0, nullptr, 0, linear, d.num_freq, 0);
+        run_cbhg(L, h->post, mel, M, N, TO, d.post_bank_size, d.post_bank_channel_size, d.post_proj_sizes, d.post_proj_width,
+                 d.post_highway_depth, nullptr, nullptr, nullptr, w, w.postout);
+        a = gemm_args(L, w.postout, 2 * d.post_rnn_size, rowsP, TO, 2 * d.post_rnn_size, 1, h->lW, linear, d.num_freq, 0);
+        a.bias = L.at(h->lb);
+        launch_gemm_args(L, a);
     }
     HIPCHK(hipGetLastError());
     return TWV_OK;
 }
 
-// the decoder kernel twv_tacotron_infer launches for this (handle, batch, t_in, options) on the current device -- the rules of the
-// launch code above restated for a measurement label (bench.py's `tacotron.roofline.kernel`, `batch_sweep`); static strings
+// taco_route's answer for (handle, batch, t_in, options) on the current device as a measurement label (bench.py's `tacotron.roofline.kernel`,
+// `batch_sweep`; static strings).  Where infer refuses the call: the kernel that would serve it, "" where there is none.
 extern "C" const char* twv_tacotron_decoder_kernel_name(const twv_tacotron* h, int batch, int t_in)
 {
     if (!h || batch < 1 || t_in < 1) return "";
-    const twv_tacotron_dims& d = h->d;
-    if (d.attention_type != TWV_ATT_BAH_MON_NORM)           // the split kernel only; -1 and 32 are refused
-        return h->dec_groups == -1 || h->dec_groups == 32 ? "" : "tc_decoder_g_kernel";
-    if (h->dec_groups == -1) return "tc_decoder_kernel";
-    int cus = 0, devid = 0;
-    if (hipGetDevice(&devid) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, devid) != hipSuccess) return "";
-    const bool simple = d.num_speakers > 1 && d.model_simple && d.speaker_embedding_size != 1;
-    XStageTab xt;
-    taco_xstages(h, xt);
-    const int upx = (batch + 7) / 8, nu = upx < batch ? upx : batch;
-    const long long xfl = xdec_carve(d.num_mels, d.dec_prenet_sizes[1], 256, d.attention_state_size, d.dec_layer_num, d.dec_rnn_size, d.attention_size, t_in,
-                                     nu < 1 ? 1 : nu, xt.nst).total + 64;
-    const bool xok = taco_xdec_ok(h, xt) && cus >= 256 && upx <= kXU && t_in <= 512 && xfl * 4 <= 160 * 1024 && !simple;
-    return xok && (h->dec_groups == 32 || h->dec_groups == 0) ? "tc_decoder_x_kernel" : "tc_decoder_g_kernel";
+    const int cus = taco_cus();
+    const TacoRoute r = taco_route(h, batch, t_in, cus);
+    // (without a device only the choices that do not look at it are answered: the other attention types, the single-workgroup kernel)
+    if (cus < 0 && h->d.attention_type == TWV_ATT_BAH_MON_NORM && r.kind != TK_ONE) return "";
+    return r.kind == TK_X ? "tc_decoder_x_kernel" : r.kind == TK_G ? "tc_decoder_g_kernel" : r.kind == TK_ONE ? "tc_decoder_kernel" : "";
 }

@@ -376,6 +376,38 @@ def test_c_abi_exports_match_header():
     assert "wn_generate_kernel" in nm or "_Z18wn_generate_kernel" in nm, "gfx950 kernels must be in the library"
 
 
+def test_tacotron_workspace_is_sized_by_its_carve():
+    """twv_tacotron_workspace_bytes is taco_carve on a null base (host-only).  Against the hand-kept sum it replaced: never larger, and
+    smaller by no more than that sum's 1024-float slack plus 16 bytes of alignment per carved piece; a speaker embedding wider than
+    the 64 floats the old layout held gets its real size; the size never falls as batch or t_in grow."""
+    import twvk_amd
+    from twvk_amd.tacotron import Tacotron
+    cases = ((1, 1), (8, 45), (32, 101), (32, 512), (64, 1024))
+    # what the parent commit's taco_ws_floats gave for these (batch, t_in) at the hparams-default dims -- it looked at neither
+    # dec_layer_num nor the speaker settings, so one row serves the whole sweep
+    parent = (29497664, 231166272, 925962560, 952897856, 2014581056)
+    pieces = 24          # 8 CBHG row buffers, memory, keys, embedding rows, <= 7 dense outputs + their pad, initial states, post output, 3 decoder areas
+
+    def sizes(layers, se, speakers):
+        hp = twvk_amd.default_hparams()
+        hp.dec_layer_num, hp.speaker_embedding_size = layers, se
+        m = Tacotron(hp, num_speakers=speakers)
+        return m, [int(m._L.twv_tacotron_workspace_bytes(m._h, n, t)) for n, t in cases]
+    for layers in (1, 4):
+        for se, speakers in ((1, 2), (16, 2), (64, 2), (16, 1)):
+            m, got = sizes(layers, se, speakers)
+            for (n, t), g, p in zip(cases, got, parent):
+                assert p - 4096 - 16 * pieces <= g <= p, (layers, se, speakers, n, t, g, p)
+            if se == 64:
+                _, wide = sizes(layers, 96, speakers)
+                for (n, t), g, w in zip(cases, got, wide):
+                    assert w >= g + n * 32 * 4, (layers, n, t, g, w)
+            ws = lambda n, t: int(m._L.twv_tacotron_workspace_bytes(m._h, n, t))
+            for n, t in cases:
+                assert ws(n + 1, t) >= ws(n, t) and ws(n, min(t + 1, 1024)) >= ws(n, t), (layers, se, speakers, n, t)
+            assert all(a <= b for a, b in zip(got, got[1:]))
+
+
 def test_create_rejects_unsupported_dims():
     import twvk_amd
     from twvk_amd.wavenet import WaveNetModel

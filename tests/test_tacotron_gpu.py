@@ -30,7 +30,7 @@ def _case(oracle, hp, N, T, lengths, seed=0, num_speakers=2):
     from twvk_amd.tacotron import Tacotron
     d = oracle.taco_dims(enc_bank=hp.enc_bank_size, post_bank=hp.post_bank_size, enc_hw_depth=hp.enc_highway_depth,
                          post_hw_depth=hp.post_highway_depth, dec_layers=hp.dec_layer_num, max_iters=hp.max_iters, num_freq=hp.num_freq,
-                         r=hp.reduction_factor, n_speakers=num_speakers)
+                         r=hp.reduction_factor, n_speakers=num_speakers, spk_emb=hp.speaker_embedding_size)
     tensors = oracle.taco_random_tensors(d, seed=seed)
     blob = oracle.taco_blob(d, tensors)
     rng = np.random.RandomState(seed + 1)
@@ -325,6 +325,29 @@ def test_speaker_embedding_size_one_uses_embedding_tables(torch_cuda, oracle):
     # a different speaker gives a different utterance (the tables are really read)
     mel2, _, _ = m.infer(tok, ln_, np.array([0, 0, 1, 2], np.int32), want_linear=False, want_alignments=False)
     assert first_mismatch(mel2.cpu().numpy()[0], mel_o[0]) is not None and first_mismatch(mel2.cpu().numpy()[1:], mel_o[1:]) is None
+
+
+@pytest.mark.parametrize("gemm_group", [1, 0])
+@pytest.mark.parametrize("groups", [0, 8])
+@pytest.mark.parametrize("width", [64, 96])
+def test_wide_speaker_embedding_has_workspace_of_its_own(torch_cuda, oracle, width, groups, gemm_group):
+    """deepvoice multi-speaker with speaker_embedding_size 64 and 96: the gathered embedding rows [N][SE] and the deep_dense outputs are
+    separate pieces of the workspace carve (taco_carve), each of its real size.  The layout before the carve put the first dense
+    output N * 64 floats behind the rows: three rows of 96 reached past it, and the grouped dense launch read the rows while it wrote
+    that output.  64 is the last width that layout held.  Mel, linear and alignments bit for bit against the checker, ragged lengths,
+    on the resident and the split decoder, two passes each.  As one grouped launch the dense layers have read their rows before any
+    of them writes (at this size), so the overlap showed only with one launch per layer ("gemm_group" 0): both are run."""
+    hp = _hp(max_iters=4, enc_bank_size=3, post_bank_size=2, num_freq=65, speaker_embedding_size=width)
+    d, blob, tok, ln, spk, m = _case(oracle, hp, 3, 13, [13, 8, 3], seed=60)
+    assert d.spk_emb == width and dict(m.specs)["speaker_embedding"] == (2, width)
+    mel_o, lin_o, al_o = oracle.taco_infer(d, blob, tok, ln, spk)
+    m.set_option("decoder_groups", groups)
+    m.set_option("gemm_group", gemm_group)
+    for _ in range(2):
+        mel, lin, al = m.infer(tok, ln, spk)
+        assert first_mismatch(al.cpu().numpy(), al_o) is None, ("alignments", first_mismatch(al.cpu().numpy(), al_o))
+        assert first_mismatch(mel.cpu().numpy(), mel_o) is None, ("mel", first_mismatch(mel.cpu().numpy(), mel_o))
+        assert first_mismatch(lin.cpu().numpy(), lin_o) is None, ("linear", first_mismatch(lin.cpu().numpy(), lin_o))
 
 
 @pytest.mark.parametrize("N,groups", [(3, 0), (5, 4), (32, 8)])
