@@ -311,6 +311,34 @@ int twv_spectrogram_analyze(twv_spectrogram* h, const float* wav, const int32_t*
                             double min_level_db, double max_abs_value, int norm_mode, void* workspace, float* mel_out, float* lin_out,
                             float* minmax_out, void* stream);
 
+/* ======================================= resampling (any wav rate -> the model's) =======================================
+ * utils/audio.py:11-12 `librosa.core.load(path, sr=sr)` (and generate.py:90 for --wav_seed): channels averaged, then a band-limited
+ * rational resampler, for a ragged batch.  The arithmetic is this project's contract ("Resampling"):
+ *   g = gcd(sr_in, sr_out), L = sr_out / g, M = sr_in / g, s = min(1, L / M);  n_out = ceil(n_in * L / M) in integers;
+ *   y[t] = sum_n x[n] * s * h(s * (t * M / L - n)), x zero outside [0, n_in), position exact: q = (t M) div L, p = (t M) mod L;
+ *   h(u) = r sinc(r u) I0(beta sqrt(1 - (u / Z)^2)) / I0(beta) for |u| < Z, else 0;
+ *   Z = 64, r = 0.9475937167399596, beta = 14.769656459379492   [RECALLED: resampy's kaiser_best; unpinned against librosa].
+ * create does host work only: the L x taps table c[p][k] = s h(s (k - taps/2 + p / L)), y[t] = sum_k c[p][k] x[q + taps/2 - k],
+ * taps = 2 * (ceil(Z / s) rounded up to a multiple of 4), computed in double and rounded once to float32.  It refuses rates <= 0,
+ * equal rates (TWV_E_INVALID) and, with TWV_E_UNSUPPORTED, a ratio whose table exceeds 2^20 floats (every pair among 8000, 11025,
+ * 16000, 22050, 24000, 32000, 44100, 48000, 96000 Hz is far below: at most 1280 x 128, or 147 x 1120) or whose tile does not fit LDS. */
+typedef struct twv_resampler twv_resampler;
+int twv_resample_create(int sr_in, int sr_out, int max_samples_in, int batch, twv_resampler** out);
+void twv_resample_destroy(twv_resampler* h);
+int twv_resample_phases(const twv_resampler* h);                        /* L */
+int twv_resample_taps(const twv_resampler* h);                          /* columns of the table */
+int64_t twv_resample_out_samples(const twv_resampler* h, int64_t n_in); /* ceil(n_in * L / M); -1 for a negative n_in */
+size_t twv_resample_workspace_bytes(const twv_resampler* h);
+int twv_resample_filter_host(const twv_resampler* h, float* out);       /* HOST float[phases * taps]: the table, row-major */
+const char* twv_resample_kernel_name(const twv_resampler* h);           /* which instantiation twv_resample launches (the handle owns it) */
+/* in (batch, max_samples_in[, channels]) device: in_format 0 = float32, 1 = int16 (scaled by 1 / 32768); channels 1, or 2 interleaved
+ * and averaged (librosa.load's mono=True) -- both happen while the input is staged, there is no separate pass.  lengths_host[batch]
+ * (HOST; NULL = every utterance has max_samples_in), 0 <= len <= max_samples_in.  out (batch, out_samples(max_samples_in)) float32
+ * device; a row is 0 past its utterance's out_samples(len).  workspace: workspace_bytes of device memory, 256-byte aligned, that
+ * belongs to the handle between calls (the table is uploaded into a workspace the handle sees for the first time). */
+int twv_resample(twv_resampler* h, const void* in, int in_format, int channels, const int32_t* lengths_host, void* workspace, float* out,
+                 void* stream);
+
 /* cross-lane primitive self-test (device float[256]); used by the gpu tests to pin v_permlane32_swap / v_readlane semantics */
 int twv_selftest(float* out256, void* stream);
 /* test aid: `blocks` workgroups that each hold `lds_bytes` of LDS and spin for `milliseconds` on `stream` -- stands in for "another

@@ -219,6 +219,15 @@ def lib():
     L.twv_spectrogram_frames.argtypes = [vp]
     L.twv_spectrogram_workspace_bytes.argtypes = [vp]; L.twv_spectrogram_workspace_bytes.restype = C.c_size_t
     L.twv_spectrogram_analyze.argtypes = [vp, fp, ip, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, vp, fp, fp, fp, vp]
+    L.twv_resample_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    L.twv_resample_destroy.argtypes = [vp]; L.twv_resample_destroy.restype = None
+    L.twv_resample_phases.argtypes = [vp]
+    L.twv_resample_taps.argtypes = [vp]
+    L.twv_resample_out_samples.argtypes = [vp, C.c_int64]; L.twv_resample_out_samples.restype = C.c_int64
+    L.twv_resample_workspace_bytes.argtypes = [vp]; L.twv_resample_workspace_bytes.restype = C.c_size_t
+    L.twv_resample_filter_host.argtypes = [vp, fp]
+    L.twv_resample_kernel_name.argtypes = [vp]; L.twv_resample_kernel_name.restype = C.c_char_p
+    L.twv_resample.argtypes = [vp, vp, C.c_int, C.c_int, ip, vp, fp, vp]
     L.twv_wav_to_int16.argtypes = [fp, C.c_int, C.c_int64, vp, fp, vp]
     L.twv_eval_elementwise.argtypes = [C.c_int, fp, C.c_int64, fp, vp]
     L.twv_eval_elementwise64.argtypes = [C.c_int, dp, C.c_int64, dp, vp]
@@ -264,7 +273,9 @@ EXPORTS = ["twv_last_error", "twv_version", "twv_wavenet_create", "twv_wavenet_d
            "twv_wavenet_train_output_width", "twv_wavenet_train_route", "twv_wavenet_train_reset_workspace", "twv_wavenet_train_loss_grad", "twv_adam_ema_step", "twv_wavenet_train_l2",
            "twv_clip_by_global_norm", "twv_griffin_lim_create", "twv_griffin_lim_destroy", "twv_griffin_lim_samples",
            "twv_griffin_lim_workspace_bytes", "twv_inv_linear_spectrogram", "twv_inv_spectrogram", "twv_spectrogram_create",
-           "twv_spectrogram_destroy", "twv_spectrogram_frames", "twv_spectrogram_workspace_bytes", "twv_spectrogram_analyze", "twv_crc32c"]
+           "twv_spectrogram_destroy", "twv_spectrogram_frames", "twv_spectrogram_workspace_bytes", "twv_spectrogram_analyze", "twv_crc32c",
+           "twv_resample_create", "twv_resample_destroy", "twv_resample_phases", "twv_resample_taps", "twv_resample_out_samples",
+           "twv_resample_workspace_bytes", "twv_resample_filter_host", "twv_resample_kernel_name", "twv_resample"]
 
 
 class TacoDims(C.Structure):

@@ -5,6 +5,8 @@
     wav = inv_linear_spectrogram(linear, hparams, uniforms)      # utils/audio.py:77-92 (synthesizer.py:258), Griffin-Lim on the GPU
     wav = inv_mel_spectrogram(mel, hparams, uniforms)            # utils/audio.py:95-110
     save_wav(wav, path, hparams.sample_rate)                      # utils/audio.py:14-17 (peak normalisation on the GPU)
+    wav = load_wav(path, hparams.sample_rate)                     # utils/audio.py:11-12: any rate, resampled on the GPU
+    out, lengths = resample(wavs, 44100, 24000)                   # the resampler behind it, for a ragged batch
 
 Spectrograms are (B, T, channels) throughout: what Tacotron.infer returns and what the npz examples hold (the reference works on one
 utterance at a time, transposed to (channels, T)).  PyTorch is used for device memory and streams only."""
@@ -162,6 +164,120 @@ def melspectrogram(wav, hparams, lengths=None, mel_basis=None, device="cuda:0"):
 def linearspectrogram(wav, hparams, lengths=None, device="cuda:0"):
     """utils/audio.py:61-67 -> (B, frames, fft_size/2 + 1); see spectrograms"""
     return spectrograms(wav, hparams, lengths, None, device, mel=False)[1]
+
+
+_resamplers = {}         # (device, orig_sr, target_sr, max_samples_in, batch) -> [handle, workspace]: the table lives in the workspace
+_MAX_RESAMPLERS = 4
+
+
+def _resampler(L, orig_sr, target_sr, max_in, batch, device):
+    key = (str(device), orig_sr, target_sr, max_in, batch)
+    hit = _resamplers.pop(key, None)
+    if hit is None:
+        h = C.c_void_p()
+        _lib.check(L.twv_resample_create(orig_sr, target_sr, max_in, batch, C.byref(h)))
+        hit = [h, torch.empty(L.twv_resample_workspace_bytes(h) // 4 + 64, dtype=torch.float32, device=device)]
+        while len(_resamplers) >= _MAX_RESAMPLERS:               # oldest first
+            old = _resamplers.pop(next(iter(_resamplers)))
+            torch.cuda.synchronize(device)
+            L.twv_resample_destroy(old[0])
+    _resamplers[key] = hit
+    return hit
+
+
+def _as_frames(wav, lengths, device):
+    """-> ((B, max_len[, 2]) int16 or float32 device tensor, int32 lengths).  A list holds utterances, (len,) or (len, 2) each;
+    an array or tensor is (len,), (B, len) or (B, len, 2) -- one stereo utterance is passed as [x] or x[None]."""
+    if isinstance(wav, (list, tuple)):
+        if lengths is not None:
+            raise ValueError("a list of utterances carries its own lengths")
+        if not len(wav):
+            raise ValueError("no utterances")
+        arrs = [w.cpu().numpy() if isinstance(w, torch.Tensor) else np.asarray(w) for w in wav]
+        tail = arrs[0].shape[1:]
+        if any(a.ndim not in (1, 2) or a.shape[1:] != tail for a in arrs) or tail not in ((), (2,)):
+            raise ValueError("utterances must all be (len,) or all be (len, 2)")
+        dt = np.int16 if all(a.dtype == np.int16 for a in arrs) else np.float32
+        if dt is np.float32 and any(a.dtype.kind != "f" for a in arrs):
+            raise ValueError("utterances must all be int16 or all be floating point")
+        lengths = np.asarray([len(a) for a in arrs], np.int32)
+        host = np.zeros((len(arrs), max(1, int(lengths.max()))) + tail, dt)
+        for b, a in enumerate(arrs):
+            host[b, :len(a)] = a
+        return torch.from_numpy(host).to(device), lengths
+    x = wav if isinstance(wav, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(wav))
+    if x.dtype != torch.int16:
+        if not x.dtype.is_floating_point:
+            raise ValueError("samples must be int16 or floating point, got %s" % (x.dtype,))
+        x = x.to(torch.float32)
+    x = x.to(device)
+    if x.dim() == 1:
+        x = x[None]
+    if x.dim() not in (2, 3) or (x.dim() == 3 and x.shape[2] != 2) or x.shape[1] < 1:
+        raise ValueError("wav must be (len,), (B, len), (B, len, 2) or a list of utterances")
+    x = x.contiguous()
+    if lengths is None:
+        lengths = np.full(x.shape[0], x.shape[1], np.int32)
+    lengths = np.ascontiguousarray(lengths, np.int32).reshape(-1)
+    if len(lengths) != x.shape[0]:
+        raise ValueError("lengths must have one entry per utterance")
+    return x, lengths
+
+
+def resample(wav, orig_sr, target_sr, lengths=None, device="cuda:0"):
+    """What librosa.core.load does after reading (utils/audio.py:11-12): channels averaged, then band-limited resampling
+    orig_sr -> target_sr, for a ragged batch in one kernel (twv_resample; the arithmetic is DESIGN.md's "Resampling" contract,
+    [RECALLED] resampy's kaiser_best parameters, unpinned against librosa).
+    wav: what `spectrograms` accepts -- (len,), (B, len) with optional `lengths`, a list of 1-D arrays, a device tensor -- and also
+    int16 samples (scaled by 1 / 32768 on the device) and interleaved stereo as (B, len, 2) or a list of (len, 2) arrays.
+    -> ((B, max_out) float32 device tensor, zero past each utterance's end, [out length per utterance]),
+    out length = ceil(len * target_sr / orig_sr).  Equal rates: (wav, lengths) come back as given, nothing is launched."""
+    orig_sr, target_sr = int(orig_sr), int(target_sr)
+    if orig_sr == target_sr:
+        return wav, lengths
+    if isinstance(wav, torch.Tensor) and wav.is_cuda:
+        device = wav.device
+    x, lengths = _as_frames(wav, lengths, device)
+    B, n = x.shape[0], x.shape[1]
+    L = _lib.lib()
+    with torch.cuda.device(x.device):
+        h, ws = _resampler(L, orig_sr, target_sr, n, B, x.device)
+        out = torch.empty((B, L.twv_resample_out_samples(h, n)), dtype=torch.float32, device=x.device)
+        _lib.check(L.twv_resample(h, _ptr(x), 1 if x.dtype == torch.int16 else 0, 2 if x.dim() == 3 else 1,
+                                  lengths.ctypes.data_as(C.c_void_p), _ptr(ws), _ptr(out), _stream()))
+        out_lengths = [int(L.twv_resample_out_samples(h, int(v))) for v in lengths]
+    return out, out_lengths
+
+
+def wav_samples(data):
+    """what scipy.io.wavfile.read returns -> what `resample` takes: int16 as it is (the device scales it by 1 / 32768), every other
+    format as float32 in [-1, 1); one or two channels are kept, more are averaged here"""
+    if data.dtype == np.int32:
+        data = (data.astype(np.float64) / 2147483648.0).astype(np.float32)
+    elif data.dtype == np.float64:
+        data = data.astype(np.float32)
+    elif data.dtype == np.uint8:
+        data = (data.astype(np.float32) - 128.0) / 128.0
+    elif data.dtype not in (np.int16, np.float32):
+        raise ValueError("unsupported sample format %s (uint8, int16, int32 and float wavs are read)" % (data.dtype,))
+    if data.ndim == 2 and data.shape[1] == 1:
+        data = data[:, 0]
+    if data.ndim == 2 and data.shape[1] > 2:
+        data = (data.astype(np.float32) / 32768.0 if data.dtype == np.int16 else data).mean(axis=1)
+    return data
+
+
+def load_wav(path, sr, device="cuda:0"):
+    """utils/audio.py:11-12 `librosa.core.load(path, sr=sr)[0]`: float32 numpy at `sr`, channels averaged; a file of another rate
+    is resampled on the GPU (`resample`)."""
+    from scipy.io import wavfile
+    rate, data = wavfile.read(path)
+    x = wav_samples(data)
+    if rate == sr:
+        x = x.astype(np.float32) / 32768.0 if x.dtype == np.int16 else x
+        return x.mean(axis=1) if x.ndim == 2 else x
+    out, n = resample([x], rate, sr, device=device)
+    return out[0, :n[0]].cpu().numpy()
 
 
 def _griffin_lim(spec, inv_basis, hparams, uniforms, seed, general):

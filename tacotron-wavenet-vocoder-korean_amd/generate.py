@@ -5,8 +5,8 @@ kernel launch.
 Differences that are deliberate and visible: the checkpoint is the `model.ckpt-N` bundle the directory's `checkpoint`
 file names (read by checkpoint.py without TensorFlow; unpinned against a TF-written file) or, without one,
 `<checkpoint_dir>/wavenet_weights.npz` (numpy arrays keyed by the TF variable names of wavenet/model.py); `--wav_seed` takes
-a wav at the model's sample rate or a .npy (no librosa resampling / silence trimming, both are host DSP outside the
-path); `--seed` makes the sampler's uniforms reproducible (the reference is unseeded)."""
+a wav of any rate (one of another rate is resampled on the GPU, audio.load_wav) or a .npy, without the reference's silence
+trimming; `--seed` makes the sampler's uniforms reproducible (the reference is unseeded)."""
 import argparse
 import os
 import time
@@ -50,8 +50,9 @@ def _load_seed(path, sr):
         return np.load(path).astype(np.float32)
     from scipy.io import wavfile
     rate, data = wavfile.read(path)
-    if rate != sr:
-        raise ValueError('seed wav is %d Hz, the model runs at %d Hz (no resampling on this path)' % (rate, sr))
+    if rate != sr:                                                                     # generate.py:90 librosa.load(path, sr)
+        from .audio import load_wav
+        return load_wav(path, sr)
     data = data.astype(np.float32)
     if data.ndim > 1:
         data = data.mean(axis=1)

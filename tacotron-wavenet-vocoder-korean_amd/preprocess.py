@@ -2,6 +2,8 @@
 
     python -m twvk_amd.preprocess --in_dir wavs/ --out_dir data/moon        # one <name>.npz per <name>.wav
 
+Files are read at their own rate; those not at hparams.sample_rate are resampled on the GPU first (read_chunk, audio.resample: what
+librosa.load(path, sr) does in utils/audio.py:11-12), a chunk's files of one rate in one pass.
 Per utterance: rescale (moon.py:80-81), trim leading / trailing silence (:84-85, utils/audio.py:46-52), mel and linear spectrogram
 (:113,120 -- both from one FFT pass on the GPU, audio.spectrograms), the length rule (:116-117), and the audio reflect-padded by
 fft_size // 2 and cut to mel_frames * hop_size (:135-147) so that audio and mel stay in step for the transposed-convolution
@@ -104,6 +106,30 @@ def process_batch(wavs, hparams, device="cuda:0"):
     return out
 
 
+def read_chunk(paths, sample_rate, device="cuda:0"):
+    """the utterances of `paths` at `sample_rate`: a file already at that rate goes through read_wav; the others are read at their
+    own rate and resampled on the GPU (audio.resample), the files that share a rate and a sample layout in one device pass"""
+    from scipy.io import wavfile
+    from .audio import resample, wav_samples
+    out, groups = [None] * len(paths), {}
+    for i, p in enumerate(paths):
+        sr, data = wavfile.read(p, mmap=True)
+        if sr == sample_rate:
+            out[i] = read_wav(p, sample_rate)
+            continue
+        try:
+            x = wav_samples(np.asarray(data))
+        except ValueError as e:
+            raise ValueError("%s: %s" % (p, e))
+        groups.setdefault((sr, x.dtype.str, x.ndim), []).append((i, x))
+    for (sr, _, _), members in groups.items():
+        y, n = resample([x for _, x in members], sr, sample_rate, device=device)
+        y = y.cpu().numpy()
+        for row, (i, _) in enumerate(members):
+            out[i] = y[row, :n[row]].copy()
+    return out
+
+
 def get_arguments(argv=None):
     parser = argparse.ArgumentParser(description="wav files -> npz examples for train_vocoder.py")
     parser.add_argument("--in_dir", required=True, help="directory of .wav files (one speaker)")
@@ -126,7 +152,7 @@ def main(argv=None, log=print):
     written, skipped = [], []
     for i in range(0, len(paths), max(1, args.batch_size)):
         chunk = paths[i:i + max(1, args.batch_size)]
-        examples = process_batch([read_wav(p, hp.sample_rate) for p in chunk], hp, device=args.device)
+        examples = process_batch(read_chunk(chunk, hp.sample_rate, device=args.device), hp, device=args.device)
         for p, ex in zip(chunk, examples):
             if ex is None:
                 skipped.append(p)
