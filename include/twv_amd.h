@@ -69,6 +69,34 @@ int twv_wavenet_pack(const twv_wavenet* h, const float* blob, void* packed, void
 /* net.queue_initializer (model.py:64, generate.py:163): zero every delay line of every stream. */
 int twv_wavenet_reset_state(const twv_wavenet* h, void* state, int batch, void* stream);
 
+/* The same for the streams b with flags[b] != 0 alone (flags: DEVICE int32 (batch)): stream b's part of `state` -- causal queue,
+ * previous lc frame, delay lines and their positions, of every workgroup that serves the stream -- becomes what
+ * twv_wavenet_reset_state leaves; every other stream's state stays bit for bit.  One launch, no host synchronisation.  Right for
+ * every state layout twv_wavenet_state_bytes selects (generic kernel at any "groups", both XCD kernels, the wide kernel); the
+ * exchange areas behind the per-stream blocks are per launch (zeroed by every generate / prime call) and are not touched. */
+int twv_wavenet_reset_streams(const twv_wavenet* h, void* state, int batch, const int32_t* flags, void* stream);
+
+/* Utterance queue (DESIGN.md "Utterance queue"): a list of utterances of any lengths on `batch` stream slots, refilled at chunk
+ * boundaries.  table: DEVICE int32 (n_chunks, batch, 4) = {utterance index or -1 for an idle slot, first frame of the piece, valid
+ * frames (<= chunk_frames), 1 where the utterance starts in this chunk}; frame_off: DEVICE int64 (n_utterances + 1) prefix sums of
+ * the lengths in mel frames.  Packed inputs, utterances back to back: mels (sum frames, lc) float32; uniforms (sum frames * hop,
+ * nr_mix + 1) float32 or (sum frames * hop) float64 (one-hot); seeds (n_utterances) float32 | int32; gc_ids (n_utterances) int32
+ * or NULL.
+ *   twv_wavenet_queue_stage   writes chunk `chunk`'s inputs: mel_chunk (batch, chunk_frames, lc), zeros past an utterance's end
+ *                             and in idle slots; u_chunk (batch, chunk_frames * hop, ...), 0.5 there; gc_chunk (batch) (0 when
+ *                             idle; NULL allowed); first_input (batch): the utterance's seed where it starts here, else the last
+ *                             sample of prev_out (batch, chunk_frames * hop), the previous chunk's output, read on the device
+ *                             (NULL for chunk 0); reset_flags (batch) for twv_wavenet_reset_streams.
+ *   twv_wavenet_queue_collect copies every slot's valid prefix of out_chunk (batch, chunk_frames * hop) into result, the packed
+ *                             (sum frames * hop) float32 samples | int32 class ids.
+ * Per chunk: stage, reset_streams, condition(_mel), generate for chunk_frames * hop steps, collect. */
+int twv_wavenet_queue_stage(const twv_wavenet* h, const int32_t* table, int chunk, int batch, int chunk_frames,
+                            const int64_t* frame_off, const float* mels, const void* uniforms, const void* seeds,
+                            const int32_t* gc_ids, const void* prev_out, float* mel_chunk, void* u_chunk, int32_t* gc_chunk,
+                            void* first_input, int32_t* reset_flags, void* stream);
+int twv_wavenet_queue_collect(const twv_wavenet* h, const int32_t* table, int chunk, int batch, int chunk_frames,
+                              const int64_t* frame_off, const void* out_chunk, void* result, void* stream);
+
 /* WaveNetModel.create_upsample (model.py:102-111): mel (B, T_mel, lc) -> out (B, T_mel*hop, lc).
  * scratch: device buffer of at least the output size (ping-pong for the transposed-conv stages). */
 int twv_wavenet_upsample(const twv_wavenet* h, const void* packed, const float* mel, int batch, int t_mel,

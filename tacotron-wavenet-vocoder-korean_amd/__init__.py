@@ -17,9 +17,9 @@ def __getattr__(name):
     if name in ("WaveNetTrainer",):
         from .train import WaveNetTrainer
         return WaveNetTrainer
-    if name in ("text_to_wave",):
-        from .e2e import text_to_wave
-        return text_to_wave
+    if name in ("text_to_wave", "texts_to_waves"):
+        from . import e2e
+        return getattr(e2e, name)
     if name in ("mu_law_encode", "mu_law_decode", "mu_law_expand"):
         from . import ops
         return getattr(ops, name)

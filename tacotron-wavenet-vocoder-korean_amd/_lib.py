@@ -194,6 +194,9 @@ def lib():
     L.twv_wavenet_cond_bytes.argtypes = [vp, C.c_int, C.c_int]; L.twv_wavenet_cond_bytes.restype = C.c_size_t
     L.twv_wavenet_pack.argtypes = [vp, fp, vp, vp]
     L.twv_wavenet_reset_state.argtypes = [vp, vp, C.c_int, vp]
+    L.twv_wavenet_reset_streams.argtypes = [vp, vp, C.c_int, ip, vp]
+    L.twv_wavenet_queue_stage.argtypes = [vp, ip, C.c_int, C.c_int, C.c_int, vp, fp, vp, vp, ip, vp, fp, vp, ip, vp, ip, vp]
+    L.twv_wavenet_queue_collect.argtypes = [vp, ip, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
     L.twv_wavenet_upsample.argtypes = [vp, vp, fp, C.c_int, C.c_int, fp, fp, vp]
     L.twv_wavenet_condition.argtypes = [vp, vp, fp, ip, C.c_int, C.c_int, vp, vp]
     L.twv_wavenet_fused_conditioning.argtypes = [vp, C.c_int]
@@ -264,7 +267,7 @@ def lib():
 
 EXPORTS = ["twv_last_error", "twv_version", "twv_wavenet_create", "twv_wavenet_destroy", "twv_wavenet_receptive_field",
            "twv_wavenet_hop_size", "twv_wavenet_blob_floats", "twv_wavenet_packed_bytes", "twv_wavenet_state_bytes",
-           "twv_wavenet_cond_bytes", "twv_wavenet_pack", "twv_wavenet_reset_state", "twv_wavenet_upsample",
+           "twv_wavenet_cond_bytes", "twv_wavenet_pack", "twv_wavenet_reset_state", "twv_wavenet_reset_streams", "twv_wavenet_queue_stage", "twv_wavenet_queue_collect", "twv_wavenet_upsample",
            "twv_wavenet_condition", "twv_wavenet_fused_conditioning", "twv_wavenet_kernel_name", "twv_wavenet_cond_bytes_mel", "twv_wavenet_condition_mel", "twv_wavenet_generate", "twv_wavenet_prime", "twv_wavenet_status", "twv_wavenet_set_option", "twv_wavenet_set_profile_buffer",
            "twv_mu_law_encode", "twv_mu_law_decode", "twv_mu_law_expand", "twv_wav_to_int16", "twv_eval_elementwise",
            "twv_eval_elementwise64", "twv_sample_categorical", "twv_selftest", "twv_debug_occupy", "twv_tacotron_create", "twv_tacotron_destroy", "twv_tacotron_blob_floats",

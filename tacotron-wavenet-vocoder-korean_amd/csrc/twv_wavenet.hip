@@ -1610,6 +1610,33 @@ extern "C" int twv_wavenet_reset_state(const twv_wavenet* h, void* state, int ba
     return TWV_OK;
 }
 
+// One stream's part of the state buffer is the contiguous block [b * G * state_stride, (b + 1) * G * state_stride) floats in every
+// kernel family (G = 1 on the XCD, many-streams and wide kernels, the workgroups per stream on the generic one).  Everything behind
+// those blocks -- the generic kernel's all-gather granules, the XCD kernels' exchange area and role tickets -- is zeroed by every
+// generate / prime call before its launch and carries nothing from one launch to the next: nothing of it belongs to a stream between
+// launches, so a per-stream reset leaves it alone.
+__global__ void __launch_bounds__(256) wn_reset_streams_kernel(float4* state, long long vec_per_stream, const int32_t* flags)
+{
+    const int b = blockIdx.y;
+    if (flags[b] == 0) return;
+    float4* s = state + (long long)b * vec_per_stream;
+    const float4 z = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < vec_per_stream; i += (long long)gridDim.x * blockDim.x) s[i] = z;
+}
+extern "C" int twv_wavenet_reset_streams(const twv_wavenet* h, void* state, int batch, const int32_t* flags, void* stream)
+{
+    if (!h || !state || !flags || batch < 1) return fail(TWV_E_INVALID, "bad argument");
+    int G = resolve_groups(h, batch);
+    if (G < 1) return fail(TWV_E_INVALID, "groups option does not divide skip_channels/64");
+    const long long vec = (long long)h->lay.state_stride * G / 4;        // state_stride is a multiple of 64 floats
+    hipLaunchKernelGGL(wn_reset_streams_kernel, dim3((unsigned)grid_for(vec, 256) > 64u ? 64u : (unsigned)grid_for(vec, 256), (unsigned)batch), dim3(256), 0,
+                       (hipStream_t)stream, (float4*)state, vec, flags);
+    HIPCHK(hipGetLastError());
+    return TWV_OK;
+}
+// what twv_wavenet_queue.hip needs of the handle
+const twv::Layout* twv_wavenet_layout_of(const twv_wavenet* h) { return h ? &h->lay : nullptr; }
+
 extern "C" int twv_wavenet_upsample(const twv_wavenet* h, const void* packed, const float* mel, int batch, int t_mel,
                                     float* out, float* scratch, void* stream)
 {

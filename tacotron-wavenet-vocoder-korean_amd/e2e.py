@@ -47,6 +47,39 @@ def text_to_wave(synthesizer, vocoder, tokens, speaker_ids, uniforms, n_frames=N
     return {"mel": mel, "alignments": out["alignments"], "input_lengths": out["input_lengths"], "audio": audio}
 
 
+def texts_to_waves(synthesizer, vocoder, tokens, speaker_ids, uniforms, attention_trim=True, **queue_kw):
+    """Any number of utterances, each vocoded at its own length (the reference never pads: synthesizer.py:232-256 trims every
+    utterance to where its attention ends, generate.py:151-155 vocodes one mel of its own length per run).  tokens: list of
+    token-id lists -- its length need not equal vocoder.batch_size; Tacotron runs in batches of vocoder.batch_size
+    utterances, each batch padded to its longest as synthesizer.py does.  Utterance i keeps
+    attention_trim_frames(its alignment, its padded length, r) frames when attention_trim (the slice of synthesizer.py:255-256,
+    so at most max_iters*r), else all frames; the mel slices go to WaveNetModel.generate_list without leaving HBM.
+    uniforms: callable(i, n_frames) -> the draws of utterance i, or a list of arrays with at least n_frames*hop rows (the first
+    n_frames*hop are used).  queue_kw: chunk_frames, order, check of generate_list.
+    Returns dict(mel, alignments, audio, frames, input_lengths): per-utterance lists in input order."""
+    n = len(tokens)
+    tb = vocoder.batch_size
+    spk = np.zeros(n, np.int32) if speaker_ids is None else np.asarray(speaker_ids, np.int32)
+    r = synthesizer.hparams.reduction_factor
+    mels, aligns, frames, in_lens = [], [], [], []
+    for p in range(0, n, tb):
+        out = synthesizer.infer(tokens[p:p + tb], speaker_ids=spk[p:p + tb], want_linear=False)
+        al = out["alignments"].cpu().numpy() if attention_trim else None
+        for j in range(len(out["input_lengths"])):
+            total = out["mel"].shape[1]
+            keep = min(attention_trim_frames(al[j], len(out["sequences"][j]), r), total) if attention_trim else total
+            mels.append(out["mel"][j, :keep])
+            aligns.append(out["alignments"][j])
+            frames.append(int(keep))
+            in_lens.append(out["input_lengths"][j])
+    hop = vocoder.hop_size
+    us = [uniforms(i, frames[i]) if callable(uniforms) else uniforms[i][:frames[i] * hop] for i in range(n)]
+    first_inputs = np.zeros(n, np.float32 if vocoder.scalar_input else np.int32)          # generate.py:192
+    gc = spk if vocoder.global_condition_channels else None
+    audio = vocoder.generate_list(mels, gc, first_inputs, us, **queue_kw)
+    return {"mel": mels, "alignments": aligns, "audio": audio, "frames": frames, "input_lengths": in_lens}
+
+
 def shard_utterances(n_utterances, world_size, rank):
     """contiguous shard of the utterance list for this rank (configs[4]: 8 utterances over 8 GPUs -> one each)"""
     return shard_range(n_utterances, world_size, rank)

@@ -324,6 +324,110 @@ class WaveNetModel(object):
                 break
         return (out, dbg) if debug_steps else out
 
+    # ---- a list of utterances of any lengths on the batch_size stream slots (queue.py; DESIGN.md "Utterance queue") ----
+    DEFAULT_CHUNK_FRAMES = 4         # frames per launch between two refills: the best delivered samples/s of profiles/utterance_queue_bench.txt (4 and 8 tie within the spread)
+
+    def _pack_list(self, items, dtype, row_shape, rows, what):
+        """the per-utterance arrays back to back on the device: item i must hold rows[i] rows of shape row_shape"""
+        parts = []
+        for i, (x, r) in enumerate(zip(items, rows)):
+            t = torch.as_tensor(x if torch.is_tensor(x) else np.asarray(x), dtype=dtype, device=self.device)
+            if tuple(t.shape) != (r,) + tuple(row_shape):
+                raise ValueError("%s[%d] has shape %s, expected %s" % (what, i, tuple(t.shape), (r,) + tuple(row_shape)))
+            parts.append(t)
+        return torch.cat(parts, dim=0).contiguous()
+
+    def generate_list(self, mels, global_condition, first_inputs, uniforms, temperature=1.0, chunk_frames=None,
+                      order="longest_first", check=True):
+        """generate.py:151-233 for a LIST of utterances, each at its own length: mels[i] (T_i, lc) arrays or device tensors;
+        global_condition: n ids | None; first_inputs: n seeds; uniforms[i]: (T_i*hop, nr_mix+1) float32 (scalar_input) or (T_i*hop,)
+        float64.  Returns the n (T_i*hop,) device tensors (float32 samples | int32 class ids) in input order, each what a freshly
+        initialised one-stream model generates for that utterance alone.
+        All streams are reset first (queue_initializer), then queue.plan's schedule runs: per chunk of `chunk_frames` frames one
+        staging launch (twv_wavenet_queue_stage), the per-stream reset of the slots that take a new utterance, the conditioning and
+        generation launches `generate` uses, and one collecting launch; the refill costs no host round trip.  check=True reads the
+        status after every chunk and repeats a launch that found the device busy, as `generate` does; check=False enqueues
+        everything and ends with status(): a busy launch then raises and nothing is returned."""
+        from . import queue as Q
+        if not self.local_condition_channels:
+            raise ValueError("generate_list needs a model with local conditioning: the utterances' lengths are those of their mels")
+        if self.global_condition_channels and not self.global_condition_cardinality:
+            raise ValueError("generate_list takes global-condition ids (a model with a gc_embedding table)")
+        n = len(mels)
+        if n < 1 or len(first_inputs) != n or len(uniforms) != n or (global_condition is not None and len(global_condition) != n):
+            raise ValueError("mels, global_condition, first_inputs and uniforms must list the same utterances, at least one")
+        if self.global_condition_channels and global_condition is None:
+            raise ValueError("global_condition ids required (generate.py:72-77)")
+        B, hop, lc = self.batch_size, self.hop_size, self.local_condition_channels
+        k = int(chunk_frames) if chunk_frames is not None else self.DEFAULT_CHUNK_FRAMES
+        lengths = [int(m.shape[0]) for m in mels]
+        plan = Q.plan(lengths, B, k, order)
+        steps = k * hop
+        fused = self.fused_conditioning()
+        if not fused and int(self._L.twv_wavenet_cond_bytes(self._h, B, steps)) > self.MAX_COND_BYTES:
+            raise ValueError("chunk_frames %d needs a conditioning table above MAX_COND_BYTES on this kernel: choose a smaller chunk" % k)
+        sdt = torch.float32 if self.scalar_input else torch.int32
+        with torch.cuda.device(self.device):
+            dev = self.device
+            mel_p = self._pack_list(mels, torch.float32, (lc,), lengths, "mels")
+            if self.scalar_input:
+                u_p = self._pack_list(uniforms, torch.float32, (self.out_channels // 3 + 1,), [t * hop for t in lengths], "uniforms")
+                u_c = torch.empty((B, steps, self.out_channels // 3 + 1), dtype=torch.float32, device=dev)
+            else:
+                u_p = self._pack_list(uniforms, torch.float64, (), [t * hop for t in lengths], "uniforms")
+                u_c = torch.empty((B, steps), dtype=torch.float64, device=dev)
+            seeds = torch.as_tensor(np.asarray(first_inputs, dtype=np.float32 if self.scalar_input else np.int32).reshape(n), device=dev)
+            gc_p = gc_c = None
+            if self.global_condition_channels:
+                gc_p = torch.as_tensor(np.asarray(global_condition, dtype=np.int32).reshape(n), device=dev)
+                gc_c = torch.empty(B, dtype=torch.int32, device=dev)
+            off = np.zeros(n + 1, np.int64)
+            off[1:] = np.cumsum(lengths)
+            frame_off = torch.from_numpy(off).to(dev)
+            table = torch.from_numpy(plan.table).to(dev).contiguous()           # the whole schedule, uploaded once
+            result = torch.empty(int(off[-1]) * hop, dtype=sdt, device=dev)
+            mel_c = torch.empty((B, k, lc), dtype=torch.float32, device=dev)
+            fi = torch.empty(B, dtype=sdt, device=dev)
+            flags = torch.empty(B, dtype=torch.int32, device=dev)
+            out = torch.zeros((B, steps), dtype=sdt, device=dev)
+            if fused:
+                cond = torch.empty(self._L.twv_wavenet_cond_bytes_mel(self._h, B, k) // 4, dtype=torch.float32, device=dev)
+            else:
+                cond = torch.empty(self._L.twv_wavenet_cond_bytes(self._h, B, steps) // 4, dtype=torch.float32, device=dev)
+                up = torch.empty((B, steps, lc), dtype=torch.float32, device=dev)
+                scratch = torch.empty_like(up)
+            self.queue_initializer()
+            # check=False: one status word per chunk (every launch zeroes the word it is given), read together at the end
+            stat = self._status.reshape(1, 4) if check else torch.zeros((plan.makespan, 4), dtype=torch.int32, device=dev)
+            L, h, st = self._L, self._h, _stream()
+            for c in range(plan.makespan):
+                _lib.check(L.twv_wavenet_queue_stage(h, _ptr(table), c, B, k, _ptr(frame_off), _ptr(mel_p), _ptr(u_p), _ptr(seeds), _ptr(gc_p),
+                                                     _ptr(out) if c else None, _ptr(mel_c), _ptr(u_c), _ptr(gc_c), _ptr(fi), _ptr(flags), st))
+                _lib.check(L.twv_wavenet_reset_streams(h, _ptr(self._state), B, _ptr(flags), st))
+                if fused:
+                    _lib.check(L.twv_wavenet_condition_mel(h, _ptr(self._packed), _ptr(mel_c), _ptr(gc_c), B, k, _ptr(cond), st))
+                else:
+                    _lib.check(L.twv_wavenet_upsample(h, _ptr(self._packed), _ptr(mel_c), B, k, _ptr(up), _ptr(scratch), st))
+                    _lib.check(L.twv_wavenet_condition(h, _ptr(self._packed), _ptr(up), _ptr(gc_c), B, steps, _ptr(cond), st))
+                word = stat[0 if check else c]
+                for attempt in range(self.BUSY_RETRIES + 1):
+                    _lib.check(L.twv_wavenet_generate(h, _ptr(self._packed), _ptr(self._state), _ptr(cond), _ptr(fi), _ptr(u_c),
+                                                      float(temperature), B, steps, _ptr(out), _ptr(word), None, 0, st))
+                    if not check:
+                        break
+                    rc = L.twv_wavenet_status(_ptr(word), st)
+                    if rc == _lib.TWV_E_BUSY and attempt < self.BUSY_RETRIES:
+                        time.sleep(0.05 * (attempt + 1))
+                        continue
+                    _lib.check(rc)
+                    break
+                _lib.check(L.twv_wavenet_queue_collect(h, _ptr(table), c, B, k, _ptr(frame_off), _ptr(out), _ptr(result), st))
+            if not check:
+                bad = torch.nonzero(stat[:, 0]).reshape(-1)            # (waits for the stream)
+                self._status.copy_(stat[int(bad[0])] if bad.numel() else stat[-1])
+                self.status()
+        return [result[int(off[i]) * hop:int(off[i + 1]) * hop] for i in range(n)]
+
     def status(self):
         """The status word of the launches issued so far on this model (generate / prime with check=False return without reading it):
         waits for the stream, raises TwvError for a watchdog abort, a launch that found the device busy (nothing was written: the
