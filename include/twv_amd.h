@@ -304,7 +304,11 @@ void twv_griffin_lim_destroy(twv_griffin_lim* h);
 int twv_griffin_lim_samples(const twv_griffin_lim* h);                 /* hop * (n_frames - 1) samples per utterance */
 size_t twv_griffin_lim_workspace_bytes(const twv_griffin_lim* h);
 /* lin (batch, n_frames, n_fft/2+1): the normalised linear spectrogram exactly as twv_tacotron_infer emits it; uniforms (same shape)
- * in [0,1) replace np.random.rand of utils/audio.py:131; out (batch, samples).  iters = hparams.griffin_lim_iters. */
+ * in [0,1) replace np.random.rand of utils/audio.py:131; out (batch, samples).  iters = hparams.griffin_lim_iters.
+ * preemphasis = k of the inverse pre-emphasis lfilter([1], [1, -k]) (:27-30), 0 when hparams.preemphasize is off: computed as the
+ * exact recurrence y[n] = x[n] + k*y[n-1] over the whole utterance (float32, the state carried across the kernel's chunks) for every
+ * k in [-1, 1]; any other k (|k| > 1: an unstable filter; NaN) is TWV_E_INVALID before anything is launched -- in
+ * twv_inv_spectrogram too. */
 int twv_inv_linear_spectrogram(twv_griffin_lim* h, const float* lin, const float* uniforms, int iters, double power, double ref_level_db,
                                double max_abs_value, double min_level_db, double preemphasis, void* workspace, float* out, void* stream);
 /* The same loop behind the general front of utils/audio.py:77-110.  spec (batch, n_frames, n_channels): n_channels = n_fft/2+1 with

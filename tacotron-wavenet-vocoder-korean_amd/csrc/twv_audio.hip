@@ -139,23 +139,42 @@ __global__ void ga_frame_kernel(const float* y, float* fr, int batch, int frames
         fr[idx] = v;
     }
 }
-// utils/audio.py:27-30 lfilter([1], [1, -k]): y[n] = x[n] + k*y[n-1].  The impulse response k^m is below 1e-13 after 1024 samples
-// (k = 0.97), so each thread restarts the recurrence 1024 samples before its 2048-sample chunk with a zero state.
-__global__ void ga_deemph_kernel(const float* x, float* y, int batch, int len, float k, int warm)
+// utils/audio.py:27-30 lfilter([1], [1, -k]): y[n] = x[n] + k*y[n-1], exact for the k it is given (any |k| <= 1; the fronts refuse the
+// rest).  One thread per 2048-sample chunk, the state carried from chunk to chunk: ga_deemph_ends_kernel leaves each chunk's
+// zero-state end value; ga_deemph_kernel chains the ends of the chunks before its own (end_c = local_c + k^2048 * end_{c-1}, every
+// chunk before the last is full; at most ~150 steps for 300 k samples) into y[n0 - 1] and runs the recurrence on from there.
+// (A zero-state warm-up of any fixed length m leaves k^m of the state out -- after 1024 samples 3e-14 at k = 0.97 but 0.36 at
+// 0.999 -- hence the carried state.)
+#define GA_DEEMPH_CHUNK 2048
+__global__ void ga_deemph_ends_kernel(const float* x, float* ends, int batch, int len, float k)
 {
-    const int chunk = 2048;
-    const int nchunk = (len + chunk - 1) / chunk;
+    const int nchunk = (len + GA_DEEMPH_CHUNK - 1) / GA_DEEMPH_CHUNK;
     const long long total = (long long)batch * nchunk;
     GA_STRIDE(idx, total) {
         const int b = (int)(idx / nchunk), c = (int)(idx - (long long)b * nchunk);
         const float* xs = x + (long long)b * len;
-        float* ys = y + (long long)b * len;
-        const int n0 = c * chunk, n1 = n0 + chunk < len ? n0 + chunk : len;
+        const int n0 = c * GA_DEEMPH_CHUNK, n1 = n0 + GA_DEEMPH_CHUNK < len ? n0 + GA_DEEMPH_CHUNK : len;
         float acc = 0.0f;
-        for (int n = n0 - warm > 0 ? n0 - warm : 0; n < n0; ++n) acc = xs[n] + k * acc;
+        for (int n = n0; n < n1; ++n) acc = xs[n] + k * acc;
+        ends[idx] = acc;
+    }
+}
+__global__ void ga_deemph_kernel(const float* x, const float* ends, float* y, int batch, int len, float k, float k_chunk)
+{
+    const int nchunk = (len + GA_DEEMPH_CHUNK - 1) / GA_DEEMPH_CHUNK;
+    const long long total = (long long)batch * nchunk;
+    GA_STRIDE(idx, total) {
+        const int b = (int)(idx / nchunk), c = (int)(idx - (long long)b * nchunk);
+        const float* xs = x + (long long)b * len;
+        const float* es = ends + (long long)b * nchunk;
+        float* ys = y + (long long)b * len;
+        const int n0 = c * GA_DEEMPH_CHUNK, n1 = n0 + GA_DEEMPH_CHUNK < len ? n0 + GA_DEEMPH_CHUNK : len;
+        float acc = 0.0f;
+        for (int j = 0; j < c; ++j) acc = es[j] + k_chunk * acc;          // = y[n0 - 1]
         for (int n = n0; n < n1; ++n) { acc = xs[n] + k * acc; ys[n] = acc; }
     }
 }
+static bool ga_preemphasis_ok(double k) { return k >= -1.0 && k <= 1.0; }      // false for NaN
 
 extern "C" int twv_griffin_lim_create(int n_fft, int hop, int win_length, int n_frames, int batch, twv_griffin_lim** out)
 {
@@ -178,12 +197,13 @@ extern "C" int twv_griffin_lim_samples(const twv_griffin_lim* h) { return h->len
 extern "C" size_t twv_griffin_lim_workspace_bytes(const twv_griffin_lim* h)
 {
     const long long bf = (long long)h->batch * h->frames;
-    return (size_t)(bf * h->nbin * 4 + bf * h->nbin * 8 * 2 + bf * h->n_fft * 4 + (long long)h->batch * h->len * 4 + 4096);
+    const long long nchunk = (h->len + GA_DEEMPH_CHUNK - 1) / GA_DEEMPH_CHUNK;
+    return (size_t)(bf * h->nbin * 4 + bf * h->nbin * 8 * 2 + bf * h->n_fft * 4 + (long long)h->batch * h->len * 4 + h->batch * nchunk * 4 + 4096);
 }
 
 // utils/audio.py:127-137 + :27-30 for magnitudes already in the workspace (ga_workspace): random initial phase, iters x {stft -> unit
 // phase -> istft}, inverse pre-emphasis.  Shared by both fronts below.
-struct ga_workspace { float* mag; float2* spec; float2* D; float* ft; float* y; };
+struct ga_workspace { float* mag; float2* spec; float2* D; float* ft; float* y; float* ends; };
 static ga_workspace ga_carve(const twv_griffin_lim* h, void* workspace)
 {
     const long long bf = (long long)h->batch * h->frames, nspec = bf * h->nbin;
@@ -193,7 +213,8 @@ static ga_workspace ga_carve(const twv_griffin_lim* h, void* workspace)
     p.spec = (float2*)w; w += (nspec * 8 + 255) / 256 * 256;
     p.D = (float2*)w; w += (nspec * 8 + 255) / 256 * 256;
     p.ft = (float*)w; w += (bf * h->n_fft * 4 + 255) / 256 * 256;
-    p.y = (float*)w;
+    p.y = (float*)w; w += ((long long)h->batch * h->len * 4 + 255) / 256 * 256;
+    p.ends = (float*)w;                                    // batch * ceil(len / 2048) chunk ends of the de-emphasis
     return p;
 }
 static int ga_griffin_lim(twv_griffin_lim* h, const ga_workspace& p, const float* uniforms, int iters, double preemphasis, float* out, hipStream_t st)
@@ -220,8 +241,12 @@ static int ga_griffin_lim(twv_griffin_lim* h, const ga_workspace& p, const float
         FFTCHK(hipfftExecR2C(h->r2c, ft, (hipfftComplex*)D));
         hipLaunchKernelGGL(ga_phase_kernel, dim3(ga_grid(nspec)), dim3(256), 0, st, mag, D, spec, nspec);
     }
-    const int nchunk = (h->len + 2047) / 2048;
-    hipLaunchKernelGGL(ga_deemph_kernel, dim3(ga_grid((long long)h->batch * nchunk)), dim3(256), 0, st, y, out, h->batch, h->len, (float)preemphasis, 1024);
+    const int nchunk = (h->len + GA_DEEMPH_CHUNK - 1) / GA_DEEMPH_CHUNK;
+    const dim3 dgrid(ga_grid((long long)h->batch * nchunk));
+    if (nchunk > 1)
+        hipLaunchKernelGGL(ga_deemph_ends_kernel, dgrid, dim3(256), 0, st, y, p.ends, h->batch, h->len, (float)preemphasis);
+    hipLaunchKernelGGL(ga_deemph_kernel, dgrid, dim3(256), 0, st, y, p.ends, out, h->batch, h->len, (float)preemphasis,
+                       (float)pow(preemphasis, (double)GA_DEEMPH_CHUNK));
     HIPCHK(hipGetLastError());
     return TWV_OK;
 }
@@ -229,6 +254,7 @@ static int ga_griffin_lim(twv_griffin_lim* h, const ga_workspace& p, const float
 extern "C" int twv_inv_linear_spectrogram(twv_griffin_lim* h, const float* lin, const float* uniforms, int iters, double power, double ref_level_db,
                                           double max_abs_value, double min_level_db, double preemphasis, void* workspace, float* out, void* stream)
 {
+    if (!ga_preemphasis_ok(preemphasis)) return twv_fail(TWV_E_INVALID, "preemphasis must be in [-1, 1]");
     if (!h || !lin || !uniforms || !workspace || !out || iters < 0) return twv_fail(TWV_E_INVALID, "bad argument");
     hipStream_t st = (hipStream_t)stream;
     const long long nspec = (long long)h->batch * h->frames * h->nbin;
@@ -242,6 +268,7 @@ extern "C" int twv_inv_spectrogram(twv_griffin_lim* h, const float* spec, int n_
                                    int iters, double power, double ref_level_db, double max_abs_value, double min_level_db, int norm_mode,
                                    double preemphasis, void* workspace, float* out, void* stream)
 {
+    if (!ga_preemphasis_ok(preemphasis)) return twv_fail(TWV_E_INVALID, "preemphasis must be in [-1, 1]");
     if (!h || !spec || !uniforms || !workspace || !out || iters < 0 || n_channels < 1 || norm_mode < 0 || norm_mode > 4)
         return twv_fail(TWV_E_INVALID, "bad argument");
     if (!inv_basis && n_channels != h->nbin) return twv_fail(TWV_E_INVALID, "a linear spectrogram has n_fft/2 + 1 channels; a mel spectrogram needs inv_basis");

@@ -5,7 +5,8 @@ oracle.audio_np's librosa.stft restatement (window, centring, framing).  Float64
 float32 (numpy >= 2 keeps float32 through np.fft.rfft): the measure of what a float32 implementation can reach, which the GPU tests
 scale their tolerance by.  The functions pinned to the reference's own code by tests/golden/reference_numpy_audio.npz are
 preemphasis, amp_to_db, normalize and denormalize; the mel basis [RECALLED-LIBROSA <= 0.7], written here independently of
-twvk_amd.audio.mel_basis, and the STFT conventions are restated from recall."""
+twvk_amd.audio.mel_basis, and the STFT conventions are restated from recall.  inv_spectrogram_f32 is the inverse path with every stage,
+the Griffin-Lim loop and the de-emphasis included, in float32 / complex64 (scipy.fft): the yardstick of the Griffin-Lim tests."""
 import numpy as np
 
 from oracle import audio_np as A
@@ -134,6 +135,80 @@ def inv_spectrogram(spec, uniforms, hp, iters, inv_basis=None, dtype=np.float64)
     mag = (S ** dt(hp.power)).astype(np.float64)
     y = A.griffin_lim(mag.T, np.asarray(uniforms, np.float64).T, iters, hp.fft_size, hp.hop_size, hp.win_size)
     return A.inv_preemphasis(y, hp.preemphasis) if hp.preemphasize else y
+
+
+def inv_preemphasis_f32(wav, k):
+    """y[n] = x[n] + k * y[n-1], one sample after the other, every product and sum rounded to float32"""
+    wav = np.asarray(wav, np.float32)
+    y = np.empty_like(wav)
+    k, acc = np.float32(k), np.float32(0.0)
+    for i, x in enumerate(wav):
+        acc = x + k * acc
+        y[i] = acc
+    return y
+
+
+def _stft_f32(y, w, n_fft, hop):
+    from scipy import fft as sfft                      # scipy.fft keeps single precision (numpy.fft does not promise to)
+    yp = np.pad(y, n_fft // 2, mode="reflect")
+    n_frames = 1 + (len(yp) - n_fft) // hop
+    frames = np.stack([yp[i * hop:i * hop + n_fft] * w for i in range(n_frames)], axis=1)
+    D = sfft.rfft(frames, axis=0)
+    assert D.dtype == np.complex64
+    return D
+
+
+def _istft_f32(D, w, hop):
+    from scipy import fft as sfft
+    n_fft = 2 * (D.shape[0] - 1)
+    n_frames = D.shape[1]
+    fr = sfft.irfft(D, n_fft, axis=0)
+    assert fr.dtype == np.float32
+    y = np.zeros(n_fft + hop * (n_frames - 1), np.float32)
+    wss = np.zeros_like(y)
+    for i in range(n_frames):
+        y[i * hop:i * hop + n_fft] += w * fr[:, i]
+        wss[i * hop:i * hop + n_fft] += w * w
+    nz = wss > np.finfo(np.float32).tiny
+    y[nz] /= wss[nz]
+    return y[n_fft // 2:len(y) - n_fft // 2]
+
+
+def inv_spectrogram_f32(spec, uniforms, hp, iters, inv_basis=None):
+    """inv_spectrogram with EVERY stage in float32 / complex64 -- denormalise, dB -> amplitude, (inverse basis, max(1e-10, .)),
+    ** power, initial phase, istft / stft with a float32 window, unit phase, a sequential float32 de-emphasis: what a float32
+    implementation of the same lines reaches, the yardstick of the Griffin-Lim tests.  Restated from oracle/audio_np.py's lines."""
+    f = np.float32
+    D = denormalize(np.asarray(spec, f), mode_of(hp), f(hp.max_abs_value), f(hp.min_level_db))
+    S = np.power(f(10.0), (D + f(hp.ref_level_db)) * f(0.05))
+    if inv_basis is not None:
+        S = np.maximum(f(1e-10), S @ np.asarray(inv_basis, f).T)
+    mag = (S ** f(hp.power)).T
+    ph = f(2.0 * np.pi) * np.asarray(uniforms, f).T
+    Sc = mag.astype(np.complex64)
+    w = A.hann_padded(hp.win_size, hp.fft_size).astype(f)
+    y = _istft_f32(Sc * (np.cos(ph) + 1j * np.sin(ph)).astype(np.complex64), w, hp.hop_size)
+    for _ in range(iters):
+        ang = np.angle(_stft_f32(y, w, hp.fft_size, hp.hop_size))
+        y = _istft_f32(Sc * (np.cos(ang) + 1j * np.sin(ang)).astype(np.complex64), w, hp.hop_size)
+    assert mag.dtype == f and y.dtype == f
+    return inv_preemphasis_f32(y, hp.preemphasis) if hp.preemphasize else y
+
+
+def chunked_deemphasis_model(x, k, chunk=2048, warm=1024):
+    """numpy model (float64) of a de-emphasis that restarts the recurrence from a zero state `warm` samples before each `chunk`:
+    what ga_deemph_kernel did before it carried the state.  The sensitivity test applies it to show that the Griffin-Lim bars see
+    the truncation at k near 1."""
+    x = np.asarray(x, np.float64)
+    y = np.empty_like(x)
+    for n0 in range(0, len(x), chunk):
+        acc = 0.0
+        for n in range(max(0, n0 - warm), n0):
+            acc = x[n] + k * acc
+        for n in range(n0, min(n0 + chunk, len(x))):
+            acc = x[n] + k * acc
+            y[n] = acc
+    return y
 
 
 def parity_signals(sample_rate=24000):
