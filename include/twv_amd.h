@@ -303,6 +303,25 @@ int twv_griffin_lim_create(int n_fft, int hop, int win_length, int n_frames, int
 void twv_griffin_lim_destroy(twv_griffin_lim* h);
 int twv_griffin_lim_samples(const twv_griffin_lim* h);                 /* hop * (n_frames - 1) samples per utterance */
 size_t twv_griffin_lim_workspace_bytes(const twv_griffin_lim* h);
+/* Utterances of unequal lengths in one call: n_frames_host[b] >= 2 frames of utterance b (HOST int32, read here and not kept).
+ * create's rules hold for every utterance (hop * (n_frames[b] - 1) > n_fft / 2); a violation is TWV_E_INVALID and the message
+ * names the utterance's index.  Host work only.  Totals that do not fit hipFFT's `int` batch count are refused.
+ * Packed layout of a ragged handle -- utterances concatenated, no padding rows:
+ *   spec (total_frames, n_channels), uniforms (total_frames, n_fft/2+1), out (total_samples);
+ *   utterance b owns frames [frame_offsets[b], frame_offsets[b+1]) and samples [sample_offsets[b], sample_offsets[b+1]),
+ *   sample_offsets[b] = hop * (frame_offsets[b] - b): hop * (n_frames[b] - 1) samples each.
+ * twv_inv_linear_spectrogram and twv_inv_spectrogram take a ragged handle with these layouts and are otherwise unchanged (every
+ * norm_mode, the mel front, the [-1, 1] rule of preemphasis).  Overlap-add, reflect padding and the de-emphasis state stop at each
+ * utterance's own ends: utterance b comes out as it does from a handle of its own.  The number of launches of a call depends
+ * neither on batch nor on the lengths.  twv_griffin_lim_samples of a ragged handle is the LONGEST utterance's sample count;
+ * workspace_bytes includes the per-utterance offset table the kernels read (copied into the workspace in stream order by each call). */
+int twv_griffin_lim_create_ragged(int n_fft, int hop, int win_length, const int32_t* n_frames_host, int batch, twv_griffin_lim** out);
+/* Sums over the batch; on a handle of twv_griffin_lim_create batch * n_frames and batch * samples. */
+int64_t twv_griffin_lim_total_frames(const twv_griffin_lim* h);
+int64_t twv_griffin_lim_total_samples(const twv_griffin_lim* h);
+/* batch + 1 HOST entries each (the last ones are the totals); either pointer may be NULL.  A uniform handle answers b * n_frames
+ * and b * samples. */
+int twv_griffin_lim_offsets(const twv_griffin_lim* h, int64_t* frame_offsets_host, int64_t* sample_offsets_host);
 /* lin (batch, n_frames, n_fft/2+1): the normalised linear spectrogram exactly as twv_tacotron_infer emits it; uniforms (same shape)
  * in [0,1) replace np.random.rand of utils/audio.py:131; out (batch, samples).  iters = hparams.griffin_lim_iters.
  * preemphasis = k of the inverse pre-emphasis lfilter([1], [1, -k]) (:27-30), 0 when hparams.preemphasize is off: computed as the

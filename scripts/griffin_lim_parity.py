@@ -4,6 +4,9 @@ the grid-stride regime -- device vs float64 checker beside the float32 run of th
 profiles/griffin_lim_parity.txt.  Needs the GPU.
 
     python scripts/griffin_lim_parity.py [out.txt [timing.txt]]      # timing.txt: the A/B record to keep below the parity rows
+    python scripts/griffin_lim_parity.py --ragged [out.txt]          # APPENDS the rows of tests/test_griffin_lim_ragged_gpu.py (utterances of
+                                                                     # unequal lengths in one call), same columns, and whether each ragged
+                                                                     # utterance is bit-equal to its B = 1 call
     python scripts/griffin_lim_parity.py --time [reps]               # one number: ms of inv_linear_spectrogram at B = 32 x 1000 frames
                                                                      # x 60 iterations (median of reps), for scripts/ab_two_builds.sh
 """
@@ -71,8 +74,25 @@ def main(out=os.path.join(ROOT, "profiles", "griffin_lim_parity.txt"), timing=No
     print("\n".join(lines))
 
 
+def ragged(out=os.path.join(ROOT, "profiles", "griffin_lim_parity.txt")):
+    import torch
+    import twvk_amd
+    from test_griffin_lim_ragged_gpu import ragged_parity_report
+    lines = ["", "Utterances of unequal lengths in one call (twv_griffin_lim_create_ragged; tests/griffin_lim_ragged_cases.py); library %s on %s"
+             % (twvk_amd._lib.lib().twv_version().decode(), torch.cuda.get_device_name(0)),
+             "same columns; the float64 checker runs on each utterance alone, at its own length"]
+    rows, equal = ragged_parity_report(log=lines.append)
+    lines.append("%d rows, worst e_gpu / e_f32 = %.2f, worst e_gpu / bar = %.3f, all within the bar: %s"
+                 % (len(rows), max(r[2] / r[3] for r in rows if r[3]), max(r[2] / r[4] for r in rows), all(r[2] <= r[4] for r in rows)))
+    with open(out, "a") as fh:
+        fh.write("\n".join(lines) + "\n")
+    print("\n".join(lines))
+
+
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "--time":
+    if len(sys.argv) > 1 and sys.argv[1] == "--ragged":
+        ragged(*sys.argv[2:3])
+    elif len(sys.argv) > 1 and sys.argv[1] == "--time":
         med, ms = time_default(*[int(a) for a in sys.argv[2:3]])
         print("%.3f" % med)
         sys.stderr.write("runs (ms): %s\n" % " ".join("%.3f" % m for m in ms))

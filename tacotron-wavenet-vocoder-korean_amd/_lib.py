@@ -215,6 +215,10 @@ def lib():
     L.twv_griffin_lim_destroy.argtypes = [vp]; L.twv_griffin_lim_destroy.restype = None
     L.twv_griffin_lim_samples.argtypes = [vp]
     L.twv_griffin_lim_workspace_bytes.argtypes = [vp]; L.twv_griffin_lim_workspace_bytes.restype = C.c_size_t
+    L.twv_griffin_lim_create_ragged.argtypes = [C.c_int, C.c_int, C.c_int, ip, C.c_int, C.POINTER(C.c_void_p)]
+    for n in ("twv_griffin_lim_total_frames", "twv_griffin_lim_total_samples"):
+        getattr(L, n).argtypes = [vp]; getattr(L, n).restype = C.c_int64
+    L.twv_griffin_lim_offsets.argtypes = [vp, ip, ip]
     L.twv_inv_linear_spectrogram.argtypes = [vp, fp, fp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, vp, fp, vp]
     L.twv_inv_spectrogram.argtypes = [vp, fp, C.c_int, fp, fp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_double, vp, fp, vp]
     L.twv_spectrogram_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
@@ -278,7 +282,8 @@ EXPORTS = ["twv_last_error", "twv_version", "twv_wavenet_create", "twv_wavenet_d
            "twv_griffin_lim_workspace_bytes", "twv_inv_linear_spectrogram", "twv_inv_spectrogram", "twv_spectrogram_create",
            "twv_spectrogram_destroy", "twv_spectrogram_frames", "twv_spectrogram_workspace_bytes", "twv_spectrogram_analyze", "twv_crc32c",
            "twv_resample_create", "twv_resample_destroy", "twv_resample_phases", "twv_resample_taps", "twv_resample_out_samples",
-           "twv_resample_workspace_bytes", "twv_resample_filter_host", "twv_resample_kernel_name", "twv_resample"]
+           "twv_resample_workspace_bytes", "twv_resample_filter_host", "twv_resample_kernel_name", "twv_resample",
+           "twv_griffin_lim_create_ragged", "twv_griffin_lim_total_frames", "twv_griffin_lim_total_samples", "twv_griffin_lim_offsets"]
 
 
 class TacoDims(C.Structure):

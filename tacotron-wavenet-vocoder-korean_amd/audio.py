@@ -4,6 +4,7 @@
     mel = melspectrogram(wav, hparams); linear = linearspectrogram(wav, hparams)
     wav = inv_linear_spectrogram(linear, hparams, uniforms)      # utils/audio.py:77-92 (synthesizer.py:258), Griffin-Lim on the GPU
     wav = inv_mel_spectrogram(mel, hparams, uniforms)            # utils/audio.py:95-110
+    wavs = inv_linear_spectrogram_list([lin_0, lin_1, ...], hparams)   # utterances of unequal lengths in one call (also inv_mel_..._list)
     save_wav(wav, path, hparams.sample_rate)                      # utils/audio.py:14-17 (peak normalisation on the GPU)
     wav = load_wav(path, hparams.sample_rate)                     # utils/audio.py:11-12: any rate, resampled on the GPU
     out, lengths = resample(wavs, 44100, 24000)                   # the resampler behind it, for a ragged batch
@@ -341,6 +342,95 @@ def inv_mel_spectrogram(mel, hparams, uniforms=None, seed=None, mel_basis=None, 
         raise ValueError("mel is (B, T, %d) but the basis is %s" % (m.shape[2], basis.shape))
     inv = torch.as_tensor(np.linalg.pinv(basis.astype(np.float64)).astype(np.float32), device=m.device).contiguous()
     return _griffin_lim(m, inv, hparams, uniforms, seed, general=True)
+
+
+def _shape(x):
+    return tuple(x.shape) if hasattr(x, "shape") else np.shape(x)
+
+
+def _packed(arrays, device):
+    """a list of (T_i, C) arrays or tensors -> one contiguous (sum T_i, C) float32 device tensor"""
+    if not any(isinstance(a, torch.Tensor) for a in arrays):
+        return torch.from_numpy(np.concatenate([np.asarray(a, np.float32) for a in arrays], axis=0)).to(device)
+    return torch.cat([torch.as_tensor(a, dtype=torch.float32, device=device) for a in arrays], dim=0).contiguous()
+
+
+def _griffin_lim_list(specs, channels, basis, hparams, uniforms, seed, general, device):
+    """the list fronts below: every argument is checked on the host first (ValueError, no device work), then ONE ragged handle
+    (twv_griffin_lim_create_ragged) runs all utterances packed end to end -> 1-D views of one (total_samples,) tensor"""
+    if getattr(hparams, "use_lws", False):
+        raise ValueError("use_lws=True (hparams.py:15 default False) is not built")
+    if not isinstance(specs, (list, tuple)) or not len(specs):
+        raise ValueError("a non-empty list of (T_i, %d) spectrograms is required" % channels)
+    F = hparams.fft_size // 2 + 1
+    Ts = []
+    for i, s in enumerate(specs):
+        shp = _shape(s)
+        if len(shp) != 2 or shp[1] != channels:
+            raise ValueError("utterance %d must be (T, %d), got %s" % (i, channels, shp))
+        if shp[0] < 2 or hparams.hop_size * (shp[0] - 1) <= hparams.fft_size // 2:
+            raise ValueError("utterance %d: %d frames are %d samples, not more than the reflect padding (fft_size/2 = %d)"
+                             % (i, shp[0], hparams.hop_size * max(shp[0] - 1, 0), hparams.fft_size // 2))
+        Ts.append(int(shp[0]))
+    if uniforms is None:
+        rs = np.random.RandomState(seed)
+        uniforms = [rs.rand(T, F) for T in Ts]                   # a list of one: the stream of rand(1, T, F)
+    elif not isinstance(uniforms, (list, tuple)) or [_shape(u) for u in uniforms] != [(T, F) for T in Ts]:
+        raise ValueError("uniforms must be a list of %s" % ([(T, F) for T in Ts],))
+    device = torch.device(device)
+    for t in list(specs) + list(uniforms):
+        if isinstance(t, torch.Tensor) and t.is_cuda:
+            device = t.device
+            break
+    L = _lib.lib()
+    h = C.c_void_p()
+    n_frames = np.asarray(Ts, np.int32)
+    _lib.check(L.twv_griffin_lim_create_ragged(hparams.fft_size, hparams.hop_size, hparams.win_size, n_frames.ctypes.data_as(C.c_void_p),
+                                               len(Ts), C.byref(h)))
+    try:
+        with torch.cuda.device(device):
+            spec = _packed(specs, device)
+            u = _packed(uniforms, device)
+            inv_basis = None
+            if basis is not None:                                # utils/audio.py:187-191 _mel_to_linear, as inv_mel_spectrogram does
+                inv_basis = torch.as_tensor(np.linalg.pinv(basis.astype(np.float64)).astype(np.float32), device=device).contiguous()
+            s_off = (C.c_int64 * (len(Ts) + 1))()
+            _lib.check(L.twv_griffin_lim_offsets(h, None, C.cast(s_off, C.c_void_p)))
+            ws = torch.empty(L.twv_griffin_lim_workspace_bytes(h) // 4 + 64, dtype=torch.float32, device=device)
+            out = torch.empty(L.twv_griffin_lim_total_samples(h), dtype=torch.float32, device=device)
+            k = float(hparams.preemphasis) if hparams.preemphasize else 0.0
+            if general:
+                _lib.check(L.twv_inv_spectrogram(h, _ptr(spec), channels, _ptr(inv_basis) if inv_basis is not None else None, _ptr(u),
+                                                 int(hparams.griffin_lim_iters), float(hparams.power), float(hparams.ref_level_db),
+                                                 float(hparams.max_abs_value), float(hparams.min_level_db), norm_mode(hparams), k,
+                                                 _ptr(ws), _ptr(out), _stream()))
+            else:
+                _lib.check(L.twv_inv_linear_spectrogram(h, _ptr(spec), _ptr(u), int(hparams.griffin_lim_iters), float(hparams.power),
+                                                        float(hparams.ref_level_db), float(hparams.max_abs_value), float(hparams.min_level_db),
+                                                        k, _ptr(ws), _ptr(out), _stream()))
+            torch.cuda.current_stream().synchronize()
+    finally:
+        L.twv_griffin_lim_destroy(h)
+    return [out[s_off[b]:s_off[b + 1]] for b in range(len(Ts))]
+
+
+def inv_linear_spectrogram_list(linears, hparams, uniforms=None, seed=None, device="cuda:0"):
+    """inv_linear_spectrogram for utterances of unequal lengths in ONE call: linears is a list of (T_i, num_freq) arrays or tensors
+    -> a list of 1-D tensors of hop_size * (T_i - 1) samples, views of one packed buffer.  Every utterance comes out as from a call
+    of its own (overlap-add, reflect padding and the de-emphasis state stop at its ends); the number of kernel launches does not
+    depend on the list.  uniforms: a list of (T_i, num_freq); without it `rs = RandomState(seed); [rs.rand(T_i, num_freq) ...]`.
+    ValueError before any device work: an empty list, a wrong channel count, uniforms of other shapes, an utterance not longer
+    than the reflect padding (hop_size * (T_i - 1) <= fft_size / 2), use_lws."""
+    return _griffin_lim_list(linears, hparams.fft_size // 2 + 1, None, hparams, uniforms, seed, norm_mode(hparams) != 1, device)
+
+
+def inv_mel_spectrogram_list(mels, hparams, uniforms=None, seed=None, mel_basis=None, device="cuda:0"):
+    """inv_mel_spectrogram for a list of (T_i, num_mels) mel spectrograms; see inv_linear_spectrogram_list (uniforms are
+    (T_i, fft_size/2 + 1) here too)"""
+    basis = _default_basis(hparams)[1] if mel_basis is None else np.asarray(mel_basis)
+    if basis.ndim != 2 or basis.shape[1] != hparams.fft_size // 2 + 1:
+        raise ValueError("the basis is %s, not (num_mels, %d)" % (basis.shape, hparams.fft_size // 2 + 1))
+    return _griffin_lim_list(mels, basis.shape[0], basis, hparams, uniforms, seed, True, device)
 
 
 def save_wav(wav, path, sr):

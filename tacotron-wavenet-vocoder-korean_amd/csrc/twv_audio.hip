@@ -15,6 +15,7 @@
 #include <math.h>
 #include <stdint.h>
 #include <string>
+#include <vector>
 #include "../../include/twv_amd.h"
 #include "twv_dev.hpp"
 
@@ -30,9 +31,14 @@
     } while (0)
 
 struct twv_griffin_lim {
-    int n_fft, hop, win, frames, batch, nbin, len;        // len = hop * (frames - 1) samples per utterance
+    int n_fft, hop, win, frames, batch, nbin, len;        // len = hop * (frames - 1) samples per utterance (ragged: of the longest)
+    long long tf, ts, tc;                                 // frames, samples and de-emphasis chunks of the whole batch
     hipfftHandle c2r, r2c;
     bool have_plans;
+    // twv_griffin_lim_create_ragged only: the table the ragged kernels read, three arrays of batch + 1 ascending offsets -- frames,
+    // samples, de-emphasis chunks -- so utterance b has f0[b+1] - f0[b] frames, s0[b+1] - s0[b] samples, c0[b+1] - c0[b] chunks
+    bool ragged;
+    std::vector<long long> table;
 };
 
 #define GA_STRIDE(i, n) for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (long long)gridDim.x * blockDim.x)
@@ -174,7 +180,119 @@ __global__ void ga_deemph_kernel(const float* x, const float* ends, float* y, in
         for (int n = n0; n < n1; ++n) { acc = xs[n] + k * acc; ys[n] = acc; }
     }
 }
+// ---- utterances of unequal lengths (twv_griffin_lim_create_ragged): the four kernels above with per-utterance boundaries ----
+// The flat index runs over the packed batch; which utterance an element belongs to comes from the handle's offset table (off:
+// nb + 1 ascending 64-bit entries, off[0] = 0, no empty utterance).  Every workgroup searches the table for its first and its last
+// element -- the same values in every lane, so scalar work -- and only a workgroup that straddles a boundary searches per lane,
+// between those two.  Workgroups of 256, 64-bit indices.
+// largest b in [lo, hi] with off[b] <= x  (off[lo] <= x)
+__device__ __forceinline__ int ga_utt_of(const long long* __restrict__ off, int lo, int hi, long long x)
+{
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (off[mid] <= x) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+// A workgroup takes tiles of `tile` consecutive elements, one table search per tile: the search is a chain of dependent loads, which
+// a tile of 256 elements does not cover (measured: DESIGN.md section 3g).  At most GA_RAGGED_BLOCKS workgroups, grid-stride beyond.
+#define GA_RAGGED_TILE 2048
+#define GA_RAGGED_BLOCKS 2048
+#define GA_RAGGED_STRIDE(base, n, tile) for (long long base = (long long)blockIdx.x * (tile); base < (n); base += (long long)gridDim.x * (tile))
+static inline int ga_ragged_grid(long long n, int tile) { long long g = (n + tile - 1) / tile; return (int)(g < 1 ? 1 : (g > GA_RAGGED_BLOCKS ? GA_RAGGED_BLOCKS : g)); }
+
+// ga_ola_kernel's arithmetic and term order; the contributing frames are clipped to utterance b's own [0, frames_b - 1]
+__global__ void ga_ola_ragged_kernel(const float* ft, float* y, const long long* __restrict__ f0, const long long* __restrict__ s0, int nb,
+                                     long long total, int n_fft, int hop, int win)
+{
+    const float inv_n = 1.0f / (float)n_fft;
+    GA_RAGGED_STRIDE(base, total, GA_RAGGED_TILE) {
+        const long long last = base + GA_RAGGED_TILE - 1 < total ? base + GA_RAGGED_TILE - 1 : total - 1;
+        const int blo = ga_utt_of(s0, 0, nb - 1, base), bhi = ga_utt_of(s0, 0, nb - 1, last);     // two independent chains of loads
+        for (long long idx = base + threadIdx.x; idx <= last; idx += 256) {
+            const int b = blo == bhi ? blo : ga_utt_of(s0, blo, bhi, idx);
+            const long long fb = f0[b];
+            const int frames = (int)(f0[b + 1] - fb), n = (int)(idx - s0[b]);
+            const int np_ = n + n_fft / 2;
+            int i0 = (np_ - n_fft + hop) / hop; if (np_ - n_fft + 1 <= 0) i0 = 0;
+            int i1 = np_ / hop; if (i1 > frames - 1) i1 = frames - 1;
+            float acc = 0.0f, wss = 0.0f;
+            for (int i = i0; i <= i1; ++i) {
+                const int k = np_ - i * hop;
+                if (k < 0 || k >= n_fft) continue;
+                const float w = ga_window(k, n_fft, win);
+                acc += w * (ft[(fb + i) * n_fft + k] * inv_n);
+                wss += w * w;
+            }
+            y[idx] = wss > 1.17549435e-38f ? acc / wss : acc;
+        }
+    }
+}
+// ga_frame_kernel's arithmetic; the reflection is at utterance b's own ends, so no neighbour's sample is read.  The table is
+// searched by frame row (idx / n_fft).
+__global__ void ga_frame_ragged_kernel(const float* y, float* fr, const long long* __restrict__ f0, const long long* __restrict__ s0, int nb,
+                                       long long total, int n_fft, int hop, int win)
+{
+    GA_RAGGED_STRIDE(base, total, GA_RAGGED_TILE) {
+        const long long last = base + GA_RAGGED_TILE - 1 < total ? base + GA_RAGGED_TILE - 1 : total - 1;
+        const int blo = ga_utt_of(f0, 0, nb - 1, base / n_fft), bhi = ga_utt_of(f0, 0, nb - 1, last / n_fft);
+        for (long long idx = base + threadIdx.x; idx <= last; idx += 256) {
+            const int k = (int)(idx % n_fft);
+            const long long row = idx / n_fft;
+            const int b = blo == bhi ? blo : ga_utt_of(f0, blo, bhi, row);
+            const long long sb = s0[b];
+            const int i = (int)(row - f0[b]), len = (int)(s0[b + 1] - sb);
+            const float w = ga_window(k, n_fft, win);
+            float v = 0.0f;
+            if (w != 0.0f) {
+                int j = i * hop + k - n_fft / 2;
+                if (j < 0) j = -j;
+                if (j >= len) j = 2 * (len - 1) - j;
+                v = w * y[sb + j];
+            }
+            fr[idx] = v;
+        }
+    }
+}
+// ga_deemph_ends_kernel / ga_deemph_kernel over the packed chunks: utterance b has c0[b+1] - c0[b] = ceil(len_b / 2048) of them and
+// the chain of chunk ends restarts from a zero state at c0[b]; an utterance of one chunk reads no `ends` entry
+__global__ void ga_deemph_ends_ragged_kernel(const float* x, float* ends, const long long* __restrict__ s0, const long long* __restrict__ c0,
+                                             int nb, long long total, float k)
+{
+    GA_RAGGED_STRIDE(base, total, 256) {                   // one chunk of 2048 samples per lane
+        const long long idx = base + threadIdx.x, last = base + 255 < total ? base + 255 : total - 1;
+        const int blo = ga_utt_of(c0, 0, nb - 1, base), bhi = ga_utt_of(c0, 0, nb - 1, last);
+        if (idx >= total) continue;
+        const int b = blo == bhi ? blo : ga_utt_of(c0, blo, bhi, idx);
+        const int c = (int)(idx - c0[b]), len = (int)(s0[b + 1] - s0[b]);
+        const float* xs = x + s0[b];
+        const int n0 = c * GA_DEEMPH_CHUNK, n1 = n0 + GA_DEEMPH_CHUNK < len ? n0 + GA_DEEMPH_CHUNK : len;
+        float acc = 0.0f;
+        for (int n = n0; n < n1; ++n) acc = xs[n] + k * acc;
+        ends[idx] = acc;
+    }
+}
+__global__ void ga_deemph_ragged_kernel(const float* x, const float* ends, float* y, const long long* __restrict__ s0,
+                                        const long long* __restrict__ c0, int nb, long long total, float k, float k_chunk)
+{
+    GA_RAGGED_STRIDE(base, total, 256) {                   // one chunk of 2048 samples per lane
+        const long long idx = base + threadIdx.x, last = base + 255 < total ? base + 255 : total - 1;
+        const int blo = ga_utt_of(c0, 0, nb - 1, base), bhi = ga_utt_of(c0, 0, nb - 1, last);
+        if (idx >= total) continue;
+        const int b = blo == bhi ? blo : ga_utt_of(c0, blo, bhi, idx);
+        const int c = (int)(idx - c0[b]), len = (int)(s0[b + 1] - s0[b]);
+        const float* xs = x + s0[b];
+        const float* es = ends + c0[b];
+        float* ys = y + s0[b];
+        const int n0 = c * GA_DEEMPH_CHUNK, n1 = n0 + GA_DEEMPH_CHUNK < len ? n0 + GA_DEEMPH_CHUNK : len;
+        float acc = 0.0f;
+        for (int j = 0; j < c; ++j) acc = es[j] + k_chunk * acc;          // = y[n0 - 1] of this utterance
+        for (int n = n0; n < n1; ++n) { acc = xs[n] + k * acc; ys[n] = acc; }
+    }
+}
 static bool ga_preemphasis_ok(double k) { return k >= -1.0 && k <= 1.0; }      // false for NaN
+
+static long long ga_chunks(long long len) { return (len + GA_DEEMPH_CHUNK - 1) / GA_DEEMPH_CHUNK; }
 
 extern "C" int twv_griffin_lim_create(int n_fft, int hop, int win_length, int n_frames, int batch, twv_griffin_lim** out)
 {
@@ -184,7 +302,37 @@ extern "C" int twv_griffin_lim_create(int n_fft, int hop, int win_length, int n_
     twv_griffin_lim* h = new twv_griffin_lim();
     h->n_fft = n_fft; h->hop = hop; h->win = win_length; h->frames = n_frames; h->batch = batch; h->nbin = n_fft / 2 + 1;
     h->len = hop * (n_frames - 1);
+    h->tf = (long long)batch * n_frames; h->ts = (long long)batch * h->len; h->tc = batch * ga_chunks(h->len);
     h->have_plans = false;
+    h->ragged = false;
+    *out = h;
+    return TWV_OK;
+}
+extern "C" int twv_griffin_lim_create_ragged(int n_fft, int hop, int win_length, const int32_t* n_frames_host, int batch, twv_griffin_lim** out)
+{
+    if (!out || n_fft < 8 || (n_fft & 1) || hop < 1 || win_length < 1 || win_length > n_fft || !n_frames_host || batch < 1)
+        return twv_fail(TWV_E_INVALID, "bad argument");
+    std::vector<long long> table(3 * ((size_t)batch + 1), 0);
+    long long* f0 = table.data(); long long* s0 = f0 + batch + 1; long long* c0 = s0 + batch + 1;
+    int longest = 0;
+    for (int b = 0; b < batch; ++b) {
+        const int T = n_frames_host[b];
+        if (T < 2) return twv_fail(TWV_E_INVALID, "utterance " + std::to_string(b) + ": fewer than 2 frames");
+        const long long len = (long long)hop * (T - 1);
+        if (len <= n_fft / 2)
+            return twv_fail(TWV_E_INVALID, "utterance " + std::to_string(b) + ": signal shorter than the reflect padding (n_fft/2)");
+        if (len > 0x7fffffffLL - n_fft) return twv_fail(TWV_E_INVALID, "utterance " + std::to_string(b) + ": too many samples");
+        f0[b + 1] = f0[b] + T; s0[b + 1] = s0[b] + len; c0[b + 1] = c0[b] + ga_chunks(len);
+        if ((int)len > longest) longest = (int)len;
+    }
+    if (f0[batch] > 0x7fffffffLL) return twv_fail(TWV_E_INVALID, "more frames in the batch than one hipFFT plan takes (2^31 - 1)");
+    twv_griffin_lim* h = new twv_griffin_lim();
+    h->n_fft = n_fft; h->hop = hop; h->win = win_length; h->frames = 0; h->batch = batch; h->nbin = n_fft / 2 + 1;
+    h->len = longest;
+    h->tf = f0[batch]; h->ts = s0[batch]; h->tc = c0[batch];
+    h->have_plans = false;
+    h->ragged = true;
+    h->table.swap(table);
     *out = h;
     return TWV_OK;
 }
@@ -194,32 +342,46 @@ extern "C" void twv_griffin_lim_destroy(twv_griffin_lim* h)
     delete h;
 }
 extern "C" int twv_griffin_lim_samples(const twv_griffin_lim* h) { return h->len; }
+extern "C" int64_t twv_griffin_lim_total_frames(const twv_griffin_lim* h) { return h->tf; }
+extern "C" int64_t twv_griffin_lim_total_samples(const twv_griffin_lim* h) { return h->ts; }
+extern "C" int twv_griffin_lim_offsets(const twv_griffin_lim* h, int64_t* frame_offsets_host, int64_t* sample_offsets_host)
+{
+    if (!h) return twv_fail(TWV_E_INVALID, "bad argument");
+    for (int b = 0; b <= h->batch; ++b) {
+        if (frame_offsets_host) frame_offsets_host[b] = h->ragged ? h->table[b] : (long long)b * h->frames;
+        if (sample_offsets_host) sample_offsets_host[b] = h->ragged ? h->table[(size_t)h->batch + 1 + b] : (long long)b * h->len;
+    }
+    return TWV_OK;
+}
+static size_t ga_table_bytes(const twv_griffin_lim* h) { return h->ragged ? h->table.size() * sizeof(long long) + 256 : 0; }
 extern "C" size_t twv_griffin_lim_workspace_bytes(const twv_griffin_lim* h)
 {
-    const long long bf = (long long)h->batch * h->frames;
-    const long long nchunk = (h->len + GA_DEEMPH_CHUNK - 1) / GA_DEEMPH_CHUNK;
-    return (size_t)(bf * h->nbin * 4 + bf * h->nbin * 8 * 2 + bf * h->n_fft * 4 + (long long)h->batch * h->len * 4 + h->batch * nchunk * 4 + 4096);
+    return (size_t)(h->tf * h->nbin * 4 + h->tf * h->nbin * 8 * 2 + h->tf * h->n_fft * 4 + h->ts * 4 + h->tc * 4 + 4096) + ga_table_bytes(h);
 }
 
 // utils/audio.py:127-137 + :27-30 for magnitudes already in the workspace (ga_workspace): random initial phase, iters x {stft -> unit
 // phase -> istft}, inverse pre-emphasis.  Shared by both fronts below.
-struct ga_workspace { float* mag; float2* spec; float2* D; float* ft; float* y; float* ends; };
+struct ga_workspace { float* mag; float2* spec; float2* D; float* ft; float* y; float* ends; long long* table; };
 static ga_workspace ga_carve(const twv_griffin_lim* h, void* workspace)
 {
-    const long long bf = (long long)h->batch * h->frames, nspec = bf * h->nbin;
+    const long long bf = h->tf, nspec = bf * h->nbin;
     ga_workspace p;
     char* w = (char*)workspace;
     p.mag = (float*)w; w += (nspec * 4 + 255) / 256 * 256;
     p.spec = (float2*)w; w += (nspec * 8 + 255) / 256 * 256;
     p.D = (float2*)w; w += (nspec * 8 + 255) / 256 * 256;
     p.ft = (float*)w; w += (bf * h->n_fft * 4 + 255) / 256 * 256;
-    p.y = (float*)w; w += ((long long)h->batch * h->len * 4 + 255) / 256 * 256;
-    p.ends = (float*)w;                                    // batch * ceil(len / 2048) chunk ends of the de-emphasis
+    p.y = (float*)w; w += (h->ts * 4 + 255) / 256 * 256;
+    p.ends = (float*)w; w += (h->tc * 4 + 255) / 256 * 256;   // one chunk end of the de-emphasis per 2048 samples of every utterance
+    p.table = (long long*)w;                               // ragged handles: the offset table (ga_table_bytes)
     return p;
 }
+static int ga_griffin_lim_ragged(twv_griffin_lim* h, const ga_workspace& p, const float* uniforms, int iters, double preemphasis, float* out,
+                                 hipStream_t st);
 static int ga_griffin_lim(twv_griffin_lim* h, const ga_workspace& p, const float* uniforms, int iters, double preemphasis, float* out, hipStream_t st)
 {
-    const long long bf = (long long)h->batch * h->frames, nspec = bf * h->nbin;
+    if (h->ragged) return ga_griffin_lim_ragged(h, p, uniforms, iters, preemphasis, out, st);
+    const long long bf = h->tf, nspec = bf * h->nbin;
     float* mag = p.mag; float2* spec = p.spec; float2* D = p.D; float* ft = p.ft; float* y = p.y;
     if (!h->have_plans) {
         int n[1] = {h->n_fft};
@@ -250,6 +412,42 @@ static int ga_griffin_lim(twv_griffin_lim* h, const ga_workspace& p, const float
     HIPCHK(hipGetLastError());
     return TWV_OK;
 }
+// the same sequence for a ragged handle: the per-bin kernels and the plans are flat over the packed frames; overlap-add, framing and
+// the de-emphasis read the offset table, which goes into the workspace first, in stream order.  As many launches as above.
+static int ga_griffin_lim_ragged(twv_griffin_lim* h, const ga_workspace& p, const float* uniforms, int iters, double preemphasis, float* out,
+                                 hipStream_t st)
+{
+    const long long bf = h->tf, nspec = bf * h->nbin;
+    float* mag = p.mag; float2* spec = p.spec; float2* D = p.D; float* ft = p.ft; float* y = p.y;
+    const int nb = h->batch;
+    const long long* f0 = p.table; const long long* s0 = f0 + nb + 1; const long long* c0 = s0 + nb + 1;
+    if (!h->have_plans) {
+        int n[1] = {h->n_fft};
+        FFTCHK(hipfftPlanMany(&h->c2r, 1, n, nullptr, 1, h->nbin, nullptr, 1, h->n_fft, HIPFFT_C2R, (int)bf));
+        FFTCHK(hipfftPlanMany(&h->r2c, 1, n, nullptr, 1, h->n_fft, nullptr, 1, h->nbin, HIPFFT_R2C, (int)bf));
+        h->have_plans = true;
+    }
+    FFTCHK(hipfftSetStream(h->c2r, st));
+    FFTCHK(hipfftSetStream(h->r2c, st));
+    HIPCHK(hipMemcpyAsync(p.table, h->table.data(), h->table.size() * sizeof(long long), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(ga_phase_init_kernel, dim3(ga_grid(nspec)), dim3(256), 0, st, mag, uniforms, spec, nspec);
+    for (int it = 0; it <= iters; ++it) {
+        FFTCHK(hipfftExecC2R(h->c2r, (hipfftComplex*)spec, ft));
+        hipLaunchKernelGGL(ga_ola_ragged_kernel, dim3(ga_ragged_grid(h->ts, GA_RAGGED_TILE)), dim3(256), 0, st, ft, y, f0, s0, nb, h->ts, h->n_fft, h->hop, h->win);
+        if (it == iters) break;
+        hipLaunchKernelGGL(ga_frame_ragged_kernel, dim3(ga_ragged_grid(bf * h->n_fft, GA_RAGGED_TILE)), dim3(256), 0, st, y, ft, f0, s0, nb, bf * h->n_fft, h->n_fft,
+                           h->hop, h->win);
+        FFTCHK(hipfftExecR2C(h->r2c, ft, (hipfftComplex*)D));
+        hipLaunchKernelGGL(ga_phase_kernel, dim3(ga_grid(nspec)), dim3(256), 0, st, mag, D, spec, nspec);
+    }
+    const dim3 dgrid(ga_ragged_grid(h->tc, 256));
+    if (h->tc > nb)                                        // some utterance has more than one chunk
+        hipLaunchKernelGGL(ga_deemph_ends_ragged_kernel, dgrid, dim3(256), 0, st, y, p.ends, s0, c0, nb, h->tc, (float)preemphasis);
+    hipLaunchKernelGGL(ga_deemph_ragged_kernel, dgrid, dim3(256), 0, st, y, p.ends, out, s0, c0, nb, h->tc, (float)preemphasis,
+                       (float)pow(preemphasis, (double)GA_DEEMPH_CHUNK));
+    HIPCHK(hipGetLastError());
+    return TWV_OK;
+}
 
 extern "C" int twv_inv_linear_spectrogram(twv_griffin_lim* h, const float* lin, const float* uniforms, int iters, double power, double ref_level_db,
                                           double max_abs_value, double min_level_db, double preemphasis, void* workspace, float* out, void* stream)
@@ -257,7 +455,7 @@ extern "C" int twv_inv_linear_spectrogram(twv_griffin_lim* h, const float* lin, 
     if (!ga_preemphasis_ok(preemphasis)) return twv_fail(TWV_E_INVALID, "preemphasis must be in [-1, 1]");
     if (!h || !lin || !uniforms || !workspace || !out || iters < 0) return twv_fail(TWV_E_INVALID, "bad argument");
     hipStream_t st = (hipStream_t)stream;
-    const long long nspec = (long long)h->batch * h->frames * h->nbin;
+    const long long nspec = h->tf * h->nbin;
     const ga_workspace p = ga_carve(h, workspace);
     hipLaunchKernelGGL(ga_mag_kernel, dim3(ga_grid(nspec)), dim3(256), 0, st, lin, p.mag, nspec, 1, (float)max_abs_value, (float)min_level_db,
                        (float)ref_level_db, (float)power);
@@ -274,7 +472,7 @@ extern "C" int twv_inv_spectrogram(twv_griffin_lim* h, const float* spec, int n_
     if (!inv_basis && n_channels != h->nbin) return twv_fail(TWV_E_INVALID, "a linear spectrogram has n_fft/2 + 1 channels; a mel spectrogram needs inv_basis");
     if (inv_basis && n_channels > 12288) return twv_fail(TWV_E_INVALID, "n_channels too large");
     hipStream_t st = (hipStream_t)stream;
-    const long long bf = (long long)h->batch * h->frames, nspec = bf * h->nbin;
+    const long long bf = h->tf, nspec = bf * h->nbin;
     const ga_workspace p = ga_carve(h, workspace);
     if (inv_basis)
         hipLaunchKernelGGL(ga_mel_mag_kernel, dim3((unsigned)bf), dim3(256), (size_t)n_channels * 4, st, spec, inv_basis, p.mag, n_channels, h->nbin,

@@ -108,8 +108,14 @@ class Synthesizer(object):
     def synthesize(self, texts=None, tokens=None, base_path=None, paths=None, speaker_ids=None, start_of_sentence=None,
                    end_of_sentence=True, pre_word_num=0, post_word_num=0, pre_surplus_idx=0, post_surplus_idx=1,
                    use_short_concat=False, manual_attention_mode=0, base_alignment_path=None, librosa_trim=False,
-                   attention_trim=True, isKorean=True, seed=None):
-        """synthesizer.py:72-199.  Returns one result per utterance: True when files were written, else the wav bytes."""
+                   attention_trim=True, isKorean=True, seed=None, griffin_lim="per_utterance"):
+        """synthesizer.py:72-199.  Returns one result per utterance: True when files were written, else the wav bytes.
+        griffin_lim="per_utterance" (the default) runs Griffin-Lim on one trimmed utterance after the other, as synthesizer.py:258
+        does; "batched" trims them all, runs ONE audio.inv_linear_spectrogram_list call over the utterances of unequal lengths and
+        writes the same files / returns the same kind of bytes per utterance (with `seed`, utterance i still draws
+        RandomState(seed).rand(1, T_i, F): the stream restarts per utterance as in the loop)."""
+        if griffin_lim not in ("per_utterance", "batched"):
+            raise ValueError("griffin_lim must be 'per_utterance' or 'batched', got %r" % (griffin_lim,))
         if manual_attention_mode or base_alignment_path is not None:
             raise ValueError("manual attention (synthesizer.py:137-196) is out of scope of this path (SURVEY.md section 8)")
         if use_short_concat or librosa_trim:
@@ -133,6 +139,10 @@ class Synthesizer(object):
         wavs = out["linear"].cpu().numpy()
         alignments = out["alignments"].cpu().numpy()
         mels = out["mel"].cpu().numpy()
+        if griffin_lim == "batched":
+            return save_audio_batched(list(enumerate(zip(wavs, alignments, paths, texts, sequences, mels))), base_path=base_path,
+                                      end_of_sentence=end_of_sentence, attention_trim=attention_trim, time_str=time_str,
+                                      hparams=self.hparams, seed=seed)
         results = []
         for item in enumerate(zip(wavs, alignments, paths, texts, sequences, mels)):
             results.append(plot_graph_and_save_audio(item, base_path=base_path, start_of_sentence=start_of_sentence,
@@ -174,6 +184,41 @@ def plot_graph_and_save_audio(args, base_path=None, start_of_sentence=None, end_
     io_out = io.BytesIO()
     wavfile.write(io_out, hparams.sample_rate, pcm)
     return io_out.getvalue()
+
+
+def save_audio_batched(items, base_path=None, end_of_sentence=None, attention_trim=False, time_str=None, hparams=hparams, seed=None):
+    """plot_graph_and_save_audio for all utterances of a call with ONE Griffin-Lim call: every utterance is trimmed by its attention,
+    audio.inv_linear_spectrogram_list runs them at their own lengths, then each gets its own peak normalisation (wav_to_int16) and
+    the same files (`<path>.wav` + the mel `<path>.npy`) or bytes as the loop gives."""
+    from .audio import inv_linear_spectrogram_list
+    from .e2e import attention_trim_frames
+    from .ops import wav_to_int16
+    from scipy.io import wavfile
+    trimmed = []
+    for idx, (wav, alignment, path, text, sequence, mel) in items:
+        if attention_trim and end_of_sentence:
+            spec_end_idx = attention_trim_frames(alignment, len(sequence), hparams.reduction_factor)     # synthesizer.py:232-256
+            wav, mel = wav[:spec_end_idx], mel[:spec_end_idx]
+        trimmed.append((idx, wav, path, mel))
+    uniforms = None
+    if seed is not None:                                      # the loop's draw per utterance: the stream restarts at every one
+        F = hparams.fft_size // 2 + 1
+        uniforms = [np.random.RandomState(seed).rand(1, len(wav), F)[0] for _, wav, _, _ in trimmed]
+    audio = inv_linear_spectrogram_list([wav for _, wav, _, _ in trimmed], hparams, uniforms=uniforms)
+    results = []
+    for (idx, wav, path, mel), audio_out in zip(trimmed, audio):
+        pcm = wav_to_int16(audio_out[None]).cpu().numpy().reshape(-1)                 # utils/audio.py:14-17 save_wav, per utterance
+        if path or base_path:
+            current_path = add_postfix(path, idx) if path else "{}/{}.{}.wav".format(base_path, time_str or get_time(), idx)
+            os.makedirs(os.path.dirname(os.path.abspath(current_path)), exist_ok=True)
+            wavfile.write(current_path, hparams.sample_rate, pcm)
+            np.save(current_path.replace(".wav", ".npy"), mel)
+            results.append(True)
+        else:
+            io_out = io.BytesIO()
+            wavfile.write(io_out, hparams.sample_rate, pcm)
+            results.append(io_out.getvalue())
+    return results
 
 
 def main(argv=None):
