@@ -234,6 +234,36 @@ int twv_tacotron_infer(const twv_tacotron* h, const void* packed, const int32_t*
                        const int32_t* speaker_ids, int batch, int t_in, void* workspace, float* mel, float* linear,
                        float* alignments, int32_t* status, void* stream);
 
+/* A pass with mel targets: Tacotron.initialize(..., mel_targets, ...) (tacotron/tacotron.py:36-37), whose decoder runs under
+ * TacoTrainingHelper (tacotron/helpers.py:44-87) for exactly steps = t_out / r steps instead of max_iters.
+ *   teacher_forced = 0  the reference's test_model (train_tacotron.py:154-155, rnn_decoder_test_mode=True): free-running, every step is fed
+ *                       the last frame of its own output.  mel_targets gives nothing but the length and may be NULL.
+ *   teacher_forced = 1  step 0 is fed the zero go-frame, step t = 1 .. steps - 1 the ground-truth frame mel_targets[n][t*r - 1][:]
+ *                       (helpers.py:55, :86); no other target row is read (row t_out - 1 would feed a step after the last).  The output mels are the "ground-truth aligned" mels a vocoder is fine-tuned on.
+ * mel_targets: device float[batch][t_out][num_mels].  t_out must be a multiple of reduction_factor and 1 <= t_out / r <= max_iters
+ * (dynamic_decode stops at max_iters and the workspace is sized by it: the workspace of twv_tacotron_workspace_bytes serves any t_out).
+ * Outputs: mel (B, t_out, num_mels), linear (B, t_out, num_freq) or NULL, alignments (B, t_in, t_out / r) or NULL.
+ * The code is twv_tacotron_infer's -- which is this pass with t_out = max_iters * r and no targets -- so every decoder kernel, attention type,
+ * model_type and option that serves infer serves this call, and the free-running pass of max_iters steps gives infer's bits.
+ * Every layer stays in inference mode in BOTH modes: no dropout, moving-average batch normalisation.  The reference reaches teacher forcing only
+ * together with its training-mode layers (is_training = not rnn_decoder_test_mode: prenet dropout, batch statistics); those belong to a
+ * training step and are not built, so the teacher-forced pass is the evaluation-mode graph fed the targets, not the reference's training graph.
+ * Padding frames are not masked (helpers.py:57-59).  Refused with TWV_E_INVALID before anything is launched: a null handle or buffer,
+ * t_out % r != 0, t_out / r outside 1 .. max_iters, teacher_forced without mel_targets. */
+int twv_tacotron_forward_targets(const twv_tacotron* h, const void* packed, const int32_t* tokens, const int32_t* lengths,
+                                 const int32_t* speaker_ids, int batch, int t_in, const float* mel_targets, int t_out,
+                                 int teacher_forced, void* workspace, float* mel, float* linear, float* alignments,
+                                 int32_t* status, void* stream);
+/* Tacotron.add_loss (tacotron.py:258-282) on device buffers: out = device double[4] = loss, mel_loss, linear_loss, loss_without_coeff.
+ * mel / mel_targets (B, t_out, num_mels), linear / linear_targets (B, t_out, num_freq), loss_coeff (B) float (required: pass ones where the
+ * examples carry none, datafeeder_tacotron.py:263).  prioritize_loss != 0: the band [int(165 / (sample_rate * 0.5) * num_freq),
+ * int(5000 / (sample_rate * 0.5) * num_freq)) of the bins enters once more, linear_loss = 0.5 * (mean(l1) + mean(l1_priority)).
+ * Every term is formed in float64 from the float32 inputs and summed in a tree whose order depends on the sizes only (no atomics): two calls
+ * give the same bits.  Each input is read once; the block partials live in stream-ordered scratch (hipMallocAsync) for the call's duration. */
+int twv_tacotron_loss(const float* mel, const float* linear, const float* mel_targets, const float* linear_targets,
+                      const float* loss_coeff, int batch, int t_out, int num_mels, int num_freq, int prioritize_loss,
+                      double sample_rate, double* out, void* stream);
+
 /* launch geometry (performance only, results are bit-identical): "decoder_groups" = 0 auto (the XCD-resident decoder kernel wherever it
  * fits -- batch <= 32, t_in <= 512, 256 CUs, decoder widths divisible by 4, not model_type 'simple', attention_type bah_mon_norm -- else the split kernel with 16 / 8 / 4
  * workgroups per utterance), 1/2/4/8/16 = the split kernel with that many workgroups per utterance, 32 = the XCD-resident kernel or an

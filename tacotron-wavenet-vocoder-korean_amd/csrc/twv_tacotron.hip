@@ -840,7 +840,20 @@ struct DecArgs {
     long long packed_bytes;
     unsigned long long* prof;   // optional [iters][16] s_memtime stamps of workgroup 0 (tuning aid)
     int nbias;                  // total bias floats over the decoder stages
+    const float* tgt;           // teacher forcing (helpers.py:86, the kernels' TF instantiations): [N][iters*R][M] ground-truth frames, step
+                                // it + 1 is fed row (it + 1) * R - 1; not read when the decoder runs free (helpers.py:84, TF = false)
 };
+// the frame fed to step it + 1, element j of M: the target row when teacher-forced (TF), else the step's own last output frame `v`.  Read
+// straight from global memory by every workgroup that keeps the frame (targets are read-only: no exchange); the last step feeds nothing,
+// so it reads no target.  TF is a template parameter of the three decoder kernels: as a run-time test of a.tgt the feed cost the resident
+// kernel (which lives at the scalar-register limit) 0.5 % (B = 8) to 0.9 % (B = 32) of a free-running pass in same-box alternation; the
+// TF = false instantiations are the kernels without the feed.
+template <bool TF>
+__device__ __forceinline__ float dec_next_frame(const DecArgs& a, int n, int it, int M, int R, int j, float v)
+{
+    if constexpr (TF) return it + 1 < a.iters ? a.tgt[(((long long)n * a.iters + it + 1) * R - 1) * M + j] : v;
+    else return v;
+}
 // GEMV chunk partials of the split and the single-workgroup decoder (floats): one area, as large as the stage that needs most of it
 __host__ __device__ __forceinline__ int dec_partials(int M, int R, int D1, int SEc, int ENC, int AS, int DR, int T)
 {
@@ -938,6 +951,7 @@ __device__ __forceinline__ void dec_gru(rsrc_t rs, const float* P, long long oWg
     __syncthreads();
 }
 
+template <bool TF>
 __global__ void __launch_bounds__(512) tc_decoder_kernel(DecArgs a)
 {
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1093,7 +1107,7 @@ __global__ void __launch_bounds__(512) tc_decoder_kernel(DecArgs a)
         if (tid < M * R) {
             const float v = dec_combine(o_part, DR, tid) + P[a.w.ob + tid];
             a.mel[((long long)n * a.iters + it) * M * R + tid] = v;                 // tacotron.py:204 reshape
-            if (tid >= M * (R - 1)) lds[o_frame + tid - M * (R - 1)] = v;
+            if (tid >= M * (R - 1)) lds[o_frame + tid - M * (R - 1)] = dec_next_frame<TF>(a, n, it, M, R, tid - M * (R - 1), v);
         }
         __syncthreads();
         TWV_STAMP(9)
@@ -1386,7 +1400,7 @@ __host__ __device__ __forceinline__ DecgCarve decg_carve(int M, int R, int D1, i
     c.total = o + 3;                                      // (+ 3: the most c.tab's alignment can take; the launch has always asked for it)
     return c;
 }
-template <bool PROF, bool DEF, int AK = AK_MON>
+template <bool PROF, bool DEF, int AK = AK_MON, bool TF = false>
 __global__ void __launch_bounds__(512) tc_decoder_g_kernel(DecGArgs ga)
 {
     const DecArgs& a = ga.d;
@@ -1627,7 +1641,7 @@ __global__ void __launch_bounds__(512) tc_decoder_g_kernel(DecGArgs ga)
                             lds[o_y + j] = v; lds[o_cat + j] = v; lds[o_cat + DR + j] = lds[o_hr0 + j];
                         } else if (post == DP_OUT) {         // tacotron.py:204 reshape; helpers.py:40 last frame fed back
                             if (g == 0) a.mel[((long long)n * a.iters + it) * M * R + j] = v;
-                            if (j >= M * (R - 1)) lds[o_frame + j - M * (R - 1)] = v;
+                            if (j >= M * (R - 1)) lds[o_frame + j - M * (R - 1)] = dec_next_frame<TF>(a, n, it, M, R, j - M * (R - 1), v);
                         } else if (post == DP_QUERY) {       // the processed query goes into its skewed table
                             lds[dst + j + ((j >> 5) << 2)] = v;
                         } else {
@@ -1676,7 +1690,7 @@ __global__ void __launch_bounds__(512) tc_decoder_g_kernel(DecGArgs ga)
                 for (int i = tid; i < M * R; i += 512) {
                     const float v = lds[o_out + i];
                     if (g == 0) a.mel[((long long)n * a.iters + it) * M * R + i] = v;
-                    if (i >= M * (R - 1)) lds[o_frame + i - M * (R - 1)] = v;
+                    if (i >= M * (R - 1)) lds[o_frame + i - M * (R - 1)] = dec_next_frame<TF>(a, n, it, M, R, i - M * (R - 1), v);
                 }
                 __syncthreads();
                 TWV_STAMP(53)
@@ -2051,7 +2065,7 @@ __device__ __forceinline__ float xdec_chunk_sum(const int b, float v)
 // DEF: the hparams-default decoder sizes (hparams.py:126-158) as compile-time constants: the LDS carve and most index arithmetic fold
 // (the kernel lives at the scalar-register limit: every run-time size is a spilled SGPR somewhere in the step loop)
 // MM: the tasks run on the matrix core (three or four utterances per XCD); with one or two the row-broadcast fmas are shorter.
-template <bool PROF, bool DEF, bool MM>
+template <bool PROF, bool DEF, bool MM, bool TF = false>
 __global__ void __launch_bounds__(512) tc_decoder_x_kernel(DecXArgs xa)
 {
 #define XSTAMPT(k) if (PROF && a.prof && xcc == 0 && g == 0 && tid == 0 && it == 3) a.prof[st * 16 + (k)] = __builtin_amdgcn_s_memtime();
@@ -2220,7 +2234,7 @@ __global__ void __launch_bounds__(512) tc_decoder_x_kernel(DecXArgs xa)
         } else if (kind == XG_OUT) {               // tacotron.py:204 reshape; helpers.py:40 last frame fed back
             if (col >= M * (R - 1)) {              // (the mel frame itself is written by its publisher)
 #pragma unroll
-                for (int u = 0; u < kXU; ++u) if (u < nu) lds[u * UST + u_frame + col - M * (R - 1)] = v[u];
+                for (int u = 0; u < kXU; ++u) if (u < nu) lds[u * UST + u_frame + col - M * (R - 1)] = dec_next_frame<TF>(a, n0 + u, it, M, R, col - M * (R - 1), v[u]);
             }
         } else if (kind == XG_PQ) {                // the processed query goes into its skewed table
 #pragma unroll
@@ -3134,28 +3148,39 @@ static TacoRoute taco_route(const twv_tacotron* h, int N, int T, int cus)
     if (r.kind != TK_X && r.lds_floats * 4 > kLdsBudget) return refuse("decoder LDS footprint exceeds 160 KiB (t_in too large)");
     return r;
 }
-// a route's instantiation: <PROF, DEF, MM> / <PROF, DEF, AK> (the other attention kinds have no instrumented build: a profile buffer is ignored there)
-static const void* taco_decoder_fn(const TacoRoute& r, bool prof)
+// a route's instantiation: <PROF, DEF, MM, TF> / <PROF, DEF, AK, TF> (the other attention kinds and the teacher-forced pass have no instrumented
+// build: a profile buffer is ignored there).  TF = the step is fed the target frame (DecArgs::tgt) instead of its own last frame.
+template <bool TF>
+static const void* taco_decoder_fn_tf(const TacoRoute& r)
 {
     const bool def = r.def, mm = r.mm;
-    if (r.kind == TK_ONE) return (const void*)tc_decoder_kernel;
+    if (r.kind == TK_ONE) return (const void*)tc_decoder_kernel<TF>;
     if (r.kind == TK_X)
-        return prof ? (def ? (mm ? (const void*)tc_decoder_x_kernel<true, true, true> : (const void*)tc_decoder_x_kernel<true, true, false>)
-                           : (mm ? (const void*)tc_decoder_x_kernel<true, false, true> : (const void*)tc_decoder_x_kernel<true, false, false>))
-                    : (def ? (mm ? (const void*)tc_decoder_x_kernel<false, true, true> : (const void*)tc_decoder_x_kernel<false, true, false>)
-                           : (mm ? (const void*)tc_decoder_x_kernel<false, false, true> : (const void*)tc_decoder_x_kernel<false, false, false>));
-    return r.ak == AK_SOFT ? (def ? (const void*)tc_decoder_g_kernel<false, true, AK_SOFT> : (const void*)tc_decoder_g_kernel<false, false, AK_SOFT>)
-         : r.ak == AK_LUONG ? (def ? (const void*)tc_decoder_g_kernel<false, true, AK_LUONG> : (const void*)tc_decoder_g_kernel<false, false, AK_LUONG>)
-         : r.ak == AK_LOC ? (def ? (const void*)tc_decoder_g_kernel<false, true, AK_LOC> : (const void*)tc_decoder_g_kernel<false, false, AK_LOC>)
-         : prof ? (def ? (const void*)tc_decoder_g_kernel<true, true> : (const void*)tc_decoder_g_kernel<true, false>)
-                : (def ? (const void*)tc_decoder_g_kernel<false, true> : (const void*)tc_decoder_g_kernel<false, false>);
+        return def ? (mm ? (const void*)tc_decoder_x_kernel<false, true, true, TF> : (const void*)tc_decoder_x_kernel<false, true, false, TF>)
+                   : (mm ? (const void*)tc_decoder_x_kernel<false, false, true, TF> : (const void*)tc_decoder_x_kernel<false, false, false, TF>);
+    return r.ak == AK_SOFT ? (def ? (const void*)tc_decoder_g_kernel<false, true, AK_SOFT, TF> : (const void*)tc_decoder_g_kernel<false, false, AK_SOFT, TF>)
+         : r.ak == AK_LUONG ? (def ? (const void*)tc_decoder_g_kernel<false, true, AK_LUONG, TF> : (const void*)tc_decoder_g_kernel<false, false, AK_LUONG, TF>)
+         : r.ak == AK_LOC ? (def ? (const void*)tc_decoder_g_kernel<false, true, AK_LOC, TF> : (const void*)tc_decoder_g_kernel<false, false, AK_LOC, TF>)
+         : (def ? (const void*)tc_decoder_g_kernel<false, true, AK_MON, TF> : (const void*)tc_decoder_g_kernel<false, false, AK_MON, TF>);
+}
+static const void* taco_decoder_fn(const TacoRoute& r, bool prof, bool tf)
+{
+    const bool def = r.def, mm = r.mm;
+    if (tf) return taco_decoder_fn_tf<true>(r);
+    if (prof && r.kind == TK_X)
+        return def ? (mm ? (const void*)tc_decoder_x_kernel<true, true, true> : (const void*)tc_decoder_x_kernel<true, true, false>)
+                   : (mm ? (const void*)tc_decoder_x_kernel<true, false, true> : (const void*)tc_decoder_x_kernel<true, false, false>);
+    if (prof && r.kind == TK_G && r.ak == AK_MON) return def ? (const void*)tc_decoder_g_kernel<true, true> : (const void*)tc_decoder_g_kernel<true, false>;
+    return taco_decoder_fn_tf<false>(r);
 }
 
-extern "C" int twv_tacotron_infer(const twv_tacotron* h, const void* packed, const int32_t* tokens, const int32_t* lengths,
-                                  const int32_t* speaker_ids, int batch, int t_in, void* workspace, float* mel, float* linear,
-                                  float* alignments, int32_t* status, void* stream)
+// One pass of the graph for `steps` decoder steps (t_out = steps * r output frames): the body of twv_tacotron_infer (steps = max_iters, no
+// targets) and of twv_tacotron_forward_targets (steps = t_out / r; `targets` non-null = teacher forcing).  The workspace is carved for
+// max_iters steps, so any 1 <= steps <= max_iters fits it; the callers have checked their arguments.
+static int taco_forward(const twv_tacotron* h, const void* packed, const int32_t* tokens, const int32_t* lengths,
+                        const int32_t* speaker_ids, int batch, int t_in, int steps, const float* targets, void* workspace, float* mel,
+                        float* linear, float* alignments, int32_t* status, void* stream)
 {
-    if (!h || !packed || !tokens || !lengths || !workspace || !mel || !status) return twv_fail(TWV_E_INVALID, "null argument");
     if (!speaker_ids && h->d.num_speakers > 1) return twv_fail(TWV_E_INVALID, "speaker_ids is required for a multi-speaker model");
     if (batch < 1 || t_in < 1 || t_in > 1024) return twv_fail(TWV_E_INVALID, "batch >= 1 and 1 <= t_in <= 1024 required");
     const twv_tacotron_dims& d = h->d;
@@ -3164,7 +3189,7 @@ extern "C" int twv_tacotron_infer(const twv_tacotron* h, const void* packed, con
     const int N = batch, T = t_in, rows = N * T;
     const int E = d.embedding_size, SE = d.speaker_embedding_size, P0 = d.enc_prenet_sizes[0], P1 = d.enc_prenet_sizes[1],
               A = d.attention_size, AS = d.attention_state_size, DR = d.dec_rnn_size, M = d.num_mels, R = d.reduction_factor, ENC = 2 * d.enc_rnn_size;
-    const int TO = d.max_iters * R, rowsP = N * TO, dstride = AS + d.dec_layer_num * DR;
+    const int TO = steps * R, rowsP = N * TO, dstride = AS + d.dec_layer_num * DR;
     // the decoder kernel of this call, or its refusal -- before anything is launched
     const int cus = taco_cus();
     if (cus < 0) return twv_fail(TWV_E_HIP, "hipDeviceGetAttribute(hipDeviceAttributeMultiprocessorCount) failed");
@@ -3226,7 +3251,7 @@ extern "C" int twv_tacotron_infer(const twv_tacotron* h, const void* packed, con
     for (int i = 0; i < d.dec_layer_num; ++i) { da.w.rWg[i] = h->rWg[i].off; da.w.rbg[i] = h->rbg[i].off; da.w.rWc[i] = h->rWc[i].off; da.w.rbc[i] = h->rbc[i].off; }
     da.w.oW = h->oW.off; da.w.ob = h->ob.off; da.keys = w.keys; da.memo = w.memo; da.init = dinit; da.lengths = lengths;
     da.N = N; da.T = T; da.M = M; da.R = R; da.D0 = d.dec_prenet_sizes[0]; da.D1 = d.dec_prenet_sizes[1]; da.A = A; da.AS = AS; da.ENC = ENC;
-    da.DR = DR; da.layers = d.dec_layer_num; da.iters = d.max_iters; da.mel = mel; da.align = alignments; da.status = status;
+    da.DR = DR; da.layers = d.dec_layer_num; da.iters = steps; da.tgt = targets; da.mel = mel; da.align = alignments; da.status = status;
     da.SEc = simple ? SE : 0; da.semb = simple ? w.semb : nullptr;
     da.packed_bytes = (long long)h->packed_floats * 4; da.prof = h->prof; da.nbias = r.nbias;
     DecXArgs xa; DecGArgs ga; void* kargs[1] = {&da};
@@ -3245,7 +3270,7 @@ extern "C" int twv_tacotron_infer(const twv_tacotron* h, const void* packed, con
     }
     // plain launch (the route keeps the workgroups of the split and the resident kernel co-resident); a cooperative launch was measured and
     // dropped, see twv_wavenet.hip
-    const void* kfn = taco_decoder_fn(r, da.prof != nullptr);
+    const void* kfn = taco_decoder_fn(r, da.prof != nullptr, targets != nullptr);
     HIPCHK(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(r.lds_floats * 4)));
     HIPCHK(hipLaunchKernel(kfn, dim3(r.wgs), dim3(512), kargs, (size_t)r.lds_floats * 4, st));
     // ---- tacotron.py:209 post CBHG (no lengths, zero init), :219 linear projection
@@ -3260,6 +3285,32 @@ extern "C" int twv_tacotron_infer(const twv_tacotron* h, const void* packed, con
     return TWV_OK;
 }
 
+extern "C" int twv_tacotron_infer(const twv_tacotron* h, const void* packed, const int32_t* tokens, const int32_t* lengths,
+                                  const int32_t* speaker_ids, int batch, int t_in, void* workspace, float* mel, float* linear,
+                                  float* alignments, int32_t* status, void* stream)
+{
+    if (!h || !packed || !tokens || !lengths || !workspace || !mel || !status) return twv_fail(TWV_E_INVALID, "null argument");
+    return taco_forward(h, packed, tokens, lengths, speaker_ids, batch, t_in, h->d.max_iters, nullptr, workspace, mel, linear, alignments, status, stream);
+}
+
+// tacotron.py:36-37 initialize(..., mel_targets, ...): the decoder under TacoTrainingHelper (helpers.py:44-87) for t_out / r steps, free-running
+// (rnn_decoder_test_mode, the reference's test_model) or fed the ground-truth frames.  Every refusal comes before the device is looked at.
+extern "C" int twv_tacotron_forward_targets(const twv_tacotron* h, const void* packed, const int32_t* tokens, const int32_t* lengths,
+                                            const int32_t* speaker_ids, int batch, int t_in, const float* mel_targets, int t_out,
+                                            int teacher_forced, void* workspace, float* mel, float* linear, float* alignments,
+                                            int32_t* status, void* stream)
+{
+    if (!h) return twv_fail(TWV_E_INVALID, "null handle");
+    if (!packed || !tokens || !lengths || !workspace || !mel || !status) return twv_fail(TWV_E_INVALID, "null argument");
+    const int R = h->d.reduction_factor;
+    if (t_out % R != 0) return twv_fail(TWV_E_INVALID, "t_out must be a multiple of reduction_factor");
+    if (t_out / R < 1 || t_out / R > h->d.max_iters)
+        return twv_fail(TWV_E_INVALID, "steps = t_out / reduction_factor must satisfy 1 <= steps <= max_iters (dynamic_decode and the workspace stop there)");
+    if (teacher_forced && !mel_targets) return twv_fail(TWV_E_INVALID, "teacher_forced needs mel_targets");
+    return taco_forward(h, packed, tokens, lengths, speaker_ids, batch, t_in, t_out / R, teacher_forced ? mel_targets : nullptr, workspace, mel,
+                        linear, alignments, status, stream);
+}
+
 // taco_route's answer for (handle, batch, t_in, options) on the current device as a measurement label (bench.py's `tacotron.roofline.kernel`,
 // `batch_sweep`; static strings).  Where infer refuses the call: the kernel that would serve it, "" where there is none.
 extern "C" const char* twv_tacotron_decoder_kernel_name(const twv_tacotron* h, int batch, int t_in)
@@ -3270,4 +3321,158 @@ extern "C" const char* twv_tacotron_decoder_kernel_name(const twv_tacotron* h, i
     // (without a device only the choices that do not look at it are answered: the other attention types, the single-workgroup kernel)
     if (cus < 0 && h->d.attention_type == TWV_ATT_BAH_MON_NORM && r.kind != TK_ONE) return "";
     return r.kind == TK_X ? "tc_decoder_x_kernel" : r.kind == TK_G ? "tc_decoder_g_kernel" : r.kind == TK_ONE ? "tc_decoder_kernel" : "";
+}
+
+// =====================================================================================================
+//  tacotron.py:258-282 add_loss: the four evaluation losses of a pass with targets
+// =====================================================================================================
+// Six sums over the elements, every term formed in float64 from the float32 inputs: |mel_t - mel| and |lin_t - lin| (all bins, and the
+// priority band [lo, hi) of the bins), each plain and times the utterance's loss_coeff.  Work is cut into UNITS that one wave takes whole, so
+// that the utterance (its coefficient) and the bin index cost nothing per element: a row (b, t) of the linear spectrogram, or 1024 consecutive
+// mel values of one utterance.  Lanes stride a unit 64 apart (coalesced 256-byte requests), four loads of each input in flight.
+// Summation order is fixed by the sizes alone: per-thread partials in unit order -> the wave's shuffle tree -> the block's waves in order
+// (tc_loss_kernel) -> per-thread partials over the blocks, shuffle tree, waves in order (tc_loss_finish_kernel).  No atomics: two runs give the
+// same bits.  Each input is read once.
+constexpr int kLossWaves = 4, kLossMaxBlocks = 1024, kLossMelUnit = 1024;
+enum { LS_MEL = 0, LS_MELC, LS_L1, LS_L1C, LS_PR, LS_PRC, LS_N };
+struct LossArgs {
+    const float *mel, *lin, *mel_t, *lin_t, *coeff;
+    int B, TO, M, F, lo, hi, prioritize;
+    long long rows;             // B * TO: the linear units
+    int mel_units;              // mel units per utterance: ceil(TO * M / kLossMelUnit)
+    long long units;            // rows + B * mel_units
+    double* part;               // [blocks][LS_N]
+    int blocks;
+    double* out;                // [4] loss, mel_loss, linear_loss, loss_without_coeff
+};
+__device__ __forceinline__ double loss_wave_sum(double v)
+{
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v = v + __shfl_down(v, o);
+    return v;           // (lane 0 holds the wave's sum)
+}
+__global__ void __launch_bounds__(kLossWaves * 64) tc_loss_kernel(LossArgs a)
+{
+    __shared__ double wsum[kLossWaves][LS_N];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    double s[LS_N] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    const long long stride = (long long)gridDim.x * kLossWaves;
+    for (long long unit = (long long)blockIdx.x * kLossWaves + wave; unit < a.units; unit += stride) {
+        if (unit < a.rows) {
+            const int b = (int)(unit / a.TO);
+            const double c = (double)a.coeff[b];
+            const float* x = a.lin + unit * a.F;
+            const float* y = a.lin_t + unit * a.F;
+            auto term = [&](int f, float xv, float yv) {
+                const double d = fabs((double)yv - (double)xv);
+                s[LS_L1] += d; s[LS_L1C] += d * c;
+                if (f >= a.lo && f < a.hi) { s[LS_PR] += d; s[LS_PRC] += d * c; }
+            };
+            int f = lane;
+            for (; f + 192 < a.F; f += 256) {
+                const float x0 = x[f], x1 = x[f + 64], x2 = x[f + 128], x3 = x[f + 192];
+                const float y0 = y[f], y1 = y[f + 64], y2 = y[f + 128], y3 = y[f + 192];
+                term(f, x0, y0); term(f + 64, x1, y1); term(f + 128, x2, y2); term(f + 192, x3, y3);
+            }
+            for (; f < a.F; f += 64) term(f, x[f], y[f]);
+        } else {
+            const long long m = unit - a.rows;
+            const int b = (int)(m / a.mel_units), ck = (int)(m - (long long)b * a.mel_units);
+            const double c = (double)a.coeff[b];
+            const long long per = (long long)a.TO * a.M, e0 = (long long)ck * kLossMelUnit;
+            const int cnt = (int)(per - e0 < kLossMelUnit ? per - e0 : kLossMelUnit);
+            const float* x = a.mel + b * per + e0;
+            const float* y = a.mel_t + b * per + e0;
+            auto term = [&](float xv, float yv) {
+                const double d = fabs((double)yv - (double)xv);
+                s[LS_MEL] += d; s[LS_MELC] += d * c;
+            };
+            int e = lane;
+            for (; e + 192 < cnt; e += 256) {
+                const float x0 = x[e], x1 = x[e + 64], x2 = x[e + 128], x3 = x[e + 192];
+                const float y0 = y[e], y1 = y[e + 64], y2 = y[e + 128], y3 = y[e + 192];
+                term(x0, y0); term(x1, y1); term(x2, y2); term(x3, y3);
+            }
+            for (; e < cnt; e += 64) term(x[e], y[e]);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < LS_N; ++k) {
+        const double w = loss_wave_sum(s[k]);
+        if (lane == 0) wsum[wave][k] = w;
+    }
+    __syncthreads();
+    if (threadIdx.x < LS_N) {
+        double v = wsum[0][threadIdx.x];
+        for (int w = 1; w < kLossWaves; ++w) v = v + wsum[w][threadIdx.x];
+        a.part[(long long)blockIdx.x * LS_N + threadIdx.x] = v;
+    }
+}
+// one workgroup: the block partials in a fixed tree, then tacotron.py:274-282
+__global__ void __launch_bounds__(256) tc_loss_finish_kernel(LossArgs a)
+{
+    __shared__ double wsum[4][LS_N];
+    __shared__ double tot[LS_N];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    double s[LS_N] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int i = tid; i < a.blocks; i += 256)
+        for (int k = 0; k < LS_N; ++k) s[k] += a.part[(long long)i * LS_N + k];
+#pragma unroll
+    for (int k = 0; k < LS_N; ++k) {
+        const double w = loss_wave_sum(s[k]);
+        if (lane == 0) wsum[wave][k] = w;
+    }
+    __syncthreads();
+    if (tid < LS_N) tot[tid] = ((wsum[0][tid] + wsum[1][tid]) + wsum[2][tid]) + wsum[3][tid];
+    __syncthreads();
+    if (tid == 0) {
+        const double nm = (double)a.rows * a.M, nl = (double)a.rows * a.F, np = (double)a.rows * (a.hi - a.lo);     // (an empty band: 0 / 0, as reduce_mean)
+        const double mel = tot[LS_MEL] / nm, melc = tot[LS_MELC] / nm, l1 = tot[LS_L1] / nl, l1c = tot[LS_L1C] / nl;
+        double loss, linear;
+        if (a.prioritize) {
+            const double pr = tot[LS_PR] / np, prc = tot[LS_PRC] / np;
+            loss = melc + 0.5 * l1c + 0.5 * prc;            // tacotron.py:274-275
+            linear = 0.5 * (l1 + pr);                       // :276
+        } else {
+            loss = melc + l1c;                              // :278
+            linear = l1;                                    // :279
+        }
+        a.out[0] = loss; a.out[1] = mel; a.out[2] = linear; a.out[3] = mel + linear;      // :281-282
+    }
+}
+
+extern "C" int twv_tacotron_loss(const float* mel, const float* linear, const float* mel_targets, const float* linear_targets,
+                                 const float* loss_coeff, int batch, int t_out, int num_mels, int num_freq, int prioritize_loss,
+                                 double sample_rate, double* out, void* stream)
+{
+    if (!mel || !linear || !mel_targets || !linear_targets || !out) return twv_fail(TWV_E_INVALID, "null argument");
+    if (!loss_coeff) return twv_fail(TWV_E_INVALID, "loss_coeff is required (ones where the examples carry none, datafeeder_tacotron.py:263)");
+    if (batch < 1 || t_out < 1 || num_mels < 1 || num_freq < 1) return twv_fail(TWV_E_INVALID, "batch, t_out, num_mels and num_freq must be >= 1");
+    if (prioritize_loss && !(sample_rate > 0.0)) return twv_fail(TWV_E_INVALID, "prioritize_loss needs sample_rate > 0");
+    hipStream_t st = (hipStream_t)stream;
+    LossArgs a = {};
+    a.mel = mel; a.lin = linear; a.mel_t = mel_targets; a.lin_t = linear_targets; a.coeff = loss_coeff;
+    a.B = batch; a.TO = t_out; a.M = num_mels; a.F = num_freq; a.prioritize = prioritize_loss ? 1 : 0;
+    if (prioritize_loss) {              // tacotron.py:269-272; a slice's bounds are clipped to the axis
+        const int hi = (int)(5000 / (sample_rate * 0.5) * num_freq), lo = (int)(165 / (sample_rate * 0.5) * num_freq);
+        a.lo = lo < 0 ? 0 : (lo > num_freq ? num_freq : lo);
+        a.hi = hi < a.lo ? a.lo : (hi > num_freq ? num_freq : hi);
+    }
+    a.rows = (long long)batch * t_out;
+    a.mel_units = (int)(((long long)t_out * num_mels + kLossMelUnit - 1) / kLossMelUnit);
+    a.units = a.rows + (long long)batch * a.mel_units;
+    const long long want = (a.units + kLossWaves - 1) / kLossWaves;
+    a.blocks = (int)(want < kLossMaxBlocks ? want : kLossMaxBlocks);
+    a.out = out;
+    // the block partials live in stream-ordered scratch (48 KB at most): allocated, used by the two kernels and freed in stream order
+    void* part = nullptr;
+    HIPCHK(hipMallocAsync(&part, (size_t)a.blocks * LS_N * sizeof(double), st));
+    a.part = (double*)part;
+    hipLaunchKernelGGL(tc_loss_kernel, dim3(a.blocks), dim3(kLossWaves * 64), 0, st, a);
+    hipLaunchKernelGGL(tc_loss_finish_kernel, dim3(1), dim3(256), 0, st, a);
+    const hipError_t le = hipGetLastError();
+    HIPCHK(hipFreeAsync(part, st));
+    HIPCHK(le);
+    return TWV_OK;
 }

@@ -245,7 +245,75 @@ class Tacotron(object):
                                                   _ptr(mel), _ptr(lin), _ptr(al), _ptr(status), _stream()))
         self.inputs, self.input_lengths, self.speaker_id = tok, ln, sp
         self.mel_outputs, self.linear_outputs, self.alignments = mel, lin, al
+        self.mel_targets = None                              # (the outputs no longer belong to a pass with targets: add_loss refuses)
         return mel, lin, al
+
+    def forward_targets(self, inputs, input_lengths, speaker_id, mel_targets, teacher_forced=False, want_linear=True, want_alignments=True):
+        """`.initialize(inputs, input_lengths, num_speakers, speaker_id, mel_targets, ...)` (tacotron.py:36-37): the decoder under
+        TacoTrainingHelper (helpers.py:44-87) for mel_targets.shape[1] / r steps.  teacher_forced=False is the reference's test_model
+        (rnn_decoder_test_mode=True: free-running, the targets give the length only); teacher_forced=True feeds step t >= 1 the target
+        frame t*r - 1.  Every layer stays in inference mode in both (no dropout, moving-average batch norm: the reference's training-mode
+        layers belong to a training step).  mel_targets: (N, T_out, num_mels) array or tensor, T_out a multiple of r, T_out / r <= max_iters."""
+        hp = self._hparams
+        with torch.cuda.device(self.device):
+            tok = torch.as_tensor(np.asarray(inputs, np.int32), device=self.device).contiguous()
+            N, T = tok.shape
+            ln = torch.as_tensor(np.asarray(input_lengths, np.int32), device=self.device).contiguous()
+            sp = None
+            if self.num_speakers > 1:
+                sp = torch.as_tensor(np.asarray(speaker_id, np.int32), device=self.device).contiguous()
+            if not torch.is_tensor(mel_targets):
+                mel_targets = torch.from_numpy(np.ascontiguousarray(mel_targets, np.float32))
+            tgt = mel_targets.to(device=self.device, dtype=torch.float32).contiguous()
+            if tgt.dim() != 3 or tgt.shape[0] != N or tgt.shape[2] != hp.num_mels:
+                raise ValueError("mel_targets must be (%d, T_out, %d), got %s" % (N, hp.num_mels, tuple(tgt.shape)))
+            TO = int(tgt.shape[1])
+            if TO < 1:
+                raise ValueError("mel_targets has no frames: T_out / r decoder steps must satisfy 1 <= steps <= max_iters")
+            steps = TO // hp.reduction_factor                    # (a T_out the library refuses is refused there, before this is used)
+            need = self._L.twv_tacotron_workspace_bytes(self._h, N, T) // 4
+            if self._ws is None or self._ws.numel() < need:
+                self._ws = torch.empty(need, dtype=torch.float32, device=self.device)
+            mel = torch.empty((N, TO, hp.num_mels), dtype=torch.float32, device=self.device)
+            lin = torch.empty((N, TO, hp.num_freq), dtype=torch.float32, device=self.device) if want_linear else None
+            al = torch.empty((N, T, max(steps, 1)), dtype=torch.float32, device=self.device) if want_alignments else None
+            status = torch.zeros(4, dtype=torch.int32, device=self.device)
+            _lib.check(self._L.twv_tacotron_forward_targets(self._h, _ptr(self._packed), _ptr(tok), _ptr(ln), _ptr(sp), N, T, _ptr(tgt), TO,
+                                                            1 if teacher_forced else 0, _ptr(self._ws), _ptr(mel), _ptr(lin), _ptr(al),
+                                                            _ptr(status), _stream()))
+        self.inputs, self.input_lengths, self.speaker_id = tok, ln, sp
+        self.mel_outputs, self.linear_outputs, self.alignments, self.mel_targets = mel, lin, al, tgt
+        return mel, lin, al
+
+    def add_loss(self, linear_targets, loss_coeff=None):
+        """tacotron.py:258-282 on the outputs of the last forward_targets pass: sets `.loss`, `.mel_loss`, `.linear_loss` and
+        `.loss_without_coeff` (Python floats) and returns them as a dict.  loss_coeff: one factor per utterance (ones when None,
+        datafeeder_tacotron.py:263).  Reads hp.prioritize_loss, hp.sample_rate, hp.num_freq."""
+        hp = self._hparams
+        if getattr(self, "mel_targets", None) is None or getattr(self, "linear_outputs", None) is None:
+            raise ValueError("add_loss needs a forward_targets pass with want_linear=True first")
+        mel, lin, tgt = self.mel_outputs, self.linear_outputs, self.mel_targets
+        N, TO = int(mel.shape[0]), int(mel.shape[1])
+        if tuple(tgt.shape) != tuple(mel.shape) or tuple(lin.shape) != (N, TO, hp.num_freq):
+            raise ValueError("outputs %s / %s and mel_targets %s do not belong to one forward_targets pass"
+                             % (tuple(mel.shape), tuple(lin.shape), tuple(tgt.shape)))
+        with torch.cuda.device(self.device):
+            if not torch.is_tensor(linear_targets):
+                linear_targets = torch.from_numpy(np.ascontiguousarray(linear_targets, np.float32))
+            lt = linear_targets.to(device=self.device, dtype=torch.float32).contiguous()
+            if tuple(lt.shape) != (N, TO, hp.num_freq):
+                raise ValueError("linear_targets must be %s, got %s" % ((N, TO, hp.num_freq), tuple(lt.shape)))
+            co = np.ones(N, np.float32) if loss_coeff is None else np.asarray(loss_coeff, np.float32).reshape(-1)
+            if co.shape != (N,):
+                raise ValueError("loss_coeff must hold one factor per utterance (%d), got shape %s" % (N, co.shape))
+            co = torch.from_numpy(co).to(self.device)
+            out = torch.empty(4, dtype=torch.float64, device=self.device)
+            _lib.check(self._L.twv_tacotron_loss(_ptr(mel), _ptr(lin), _ptr(tgt), _ptr(lt), _ptr(co), N, TO, hp.num_mels, hp.num_freq,
+                                                 1 if hp.prioritize_loss else 0, float(hp.sample_rate), _ptr(out), _stream()))
+            v = [float(x) for x in out.cpu().numpy()]
+        self.linear_targets, self.loss_coeff = lt, co
+        self.loss, self.mel_loss, self.linear_loss, self.loss_without_coeff = v
+        return {"loss": v[0], "mel_loss": v[1], "linear_loss": v[2], "loss_without_coeff": v[3]}
 
 
 def __getattr__(name):
