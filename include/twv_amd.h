@@ -412,6 +412,7 @@ int64_t twv_resample_out_samples(const twv_resampler* h, int64_t n_in); /* ceil(
 size_t twv_resample_workspace_bytes(const twv_resampler* h);
 int twv_resample_filter_host(const twv_resampler* h, float* out);       /* HOST float[phases * taps]: the table, row-major */
 const char* twv_resample_kernel_name(const twv_resampler* h);           /* which instantiation twv_resample launches (the handle owns it) */
+int twv_resample_rounds(const twv_resampler* h);                        /* rounds per workgroup: a tile is phases * rounds outputs */
 /* in (batch, max_samples_in[, channels]) device: in_format 0 = float32, 1 = int16 (scaled by 1 / 32768); channels 1, or 2 interleaved
  * and averaged (librosa.load's mono=True) -- both happen while the input is staged, there is no separate pass.  lengths_host[batch]
  * (HOST; NULL = every utterance has max_samples_in), 0 <= len <= max_samples_in.  out (batch, out_samples(max_samples_in)) float32

@@ -1,5 +1,6 @@
 #!/usr/bin/env python
-"""Records the parity measurement of tests/test_resample_gpu.py (seven rate pairs, a ragged batch of five utterances each: device vs
+"""Records the parity measurement of tests/test_resample_gpu.py (thirteen rate pairs, one for every route of the kernel, each named
+with its route -- instantiation, chunks, lanes that are not live, LDS bytes --, a ragged batch of five utterances each: device vs
 float64 checker, beside the float32 run of the checker and the bar derived from it) in profiles/resample_parity.txt.  Needs the GPU."""
 import os
 import sys

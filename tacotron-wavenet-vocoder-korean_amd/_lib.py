@@ -234,6 +234,7 @@ def lib():
     L.twv_resample_workspace_bytes.argtypes = [vp]; L.twv_resample_workspace_bytes.restype = C.c_size_t
     L.twv_resample_filter_host.argtypes = [vp, fp]
     L.twv_resample_kernel_name.argtypes = [vp]; L.twv_resample_kernel_name.restype = C.c_char_p
+    L.twv_resample_rounds.argtypes = [vp]
     L.twv_resample.argtypes = [vp, vp, C.c_int, C.c_int, ip, vp, fp, vp]
     L.twv_wav_to_int16.argtypes = [fp, C.c_int, C.c_int64, vp, fp, vp]
     L.twv_eval_elementwise.argtypes = [C.c_int, fp, C.c_int64, fp, vp]
@@ -284,7 +285,7 @@ EXPORTS = ["twv_last_error", "twv_version", "twv_wavenet_create", "twv_wavenet_d
            "twv_griffin_lim_workspace_bytes", "twv_inv_linear_spectrogram", "twv_inv_spectrogram", "twv_spectrogram_create",
            "twv_spectrogram_destroy", "twv_spectrogram_frames", "twv_spectrogram_workspace_bytes", "twv_spectrogram_analyze", "twv_crc32c",
            "twv_resample_create", "twv_resample_destroy", "twv_resample_phases", "twv_resample_taps", "twv_resample_out_samples",
-           "twv_resample_workspace_bytes", "twv_resample_filter_host", "twv_resample_kernel_name", "twv_resample",
+           "twv_resample_workspace_bytes", "twv_resample_filter_host", "twv_resample_kernel_name", "twv_resample_rounds", "twv_resample",
            "twv_griffin_lim_create_ragged", "twv_griffin_lim_total_frames", "twv_griffin_lim_total_samples", "twv_griffin_lim_offsets"]
 
 

@@ -185,6 +185,7 @@ extern "C" int twv_resample_phases(const twv_resampler* h) { return h->L; }
 extern "C" int twv_resample_taps(const twv_resampler* h) { return h->taps; }
 extern "C" int64_t twv_resample_out_samples(const twv_resampler* h, int64_t n_in) { return n_in < 0 ? -1 : (int64_t)rs_out_samples(h, n_in); }
 extern "C" const char* twv_resample_kernel_name(const twv_resampler* h) { return h->name.c_str(); }
+extern "C" int twv_resample_rounds(const twv_resampler* h) { return h->lr * h->chunks; }
 
 static size_t rs_round(size_t n) { return (n + 255) / 256 * 256; }
 extern "C" size_t twv_resample_workspace_bytes(const twv_resampler* h)

@@ -14,8 +14,39 @@ import numpy as np
 
 ZEROS, ROLLOFF, BETA = 64, 0.9475937167399596, 14.769656459379492
 RATES = (8000, 11025, 16000, 22050, 24000, 32000, 44100, 48000, 96000)
-PAIRS = ((44100, 24000), (48000, 24000), (16000, 24000), (22050, 24000), (8000, 24000), (24000, 16000), (44100, 16000))
+PAIRS = ((44100, 24000), (48000, 24000), (16000, 24000), (22050, 24000), (8000, 24000), (24000, 16000), (44100, 16000),
+         # one pair for every route of the kernel the seven above leave out (ROUTES below)
+         (11025, 32000), (32000, 11025), (96000, 11025), (96000, 44100), (16000, 11025), (96000, 8000))
 RATIO, FLOOR = 8.0, 5e-6            # tests/train_cases.py: float32 sums in another order
+
+# What twv_resample_create decides per pair, held as the expected table (tests/test_resample_cpu.py asserts it on the host):
+# pair -> (L, M, taps, LR, chunks, lanes of a wave that are not live, LDS bytes of a workgroup).  LR is the instantiation
+# rs_resample_kernel<LR>; rounds per workgroup = LR * chunks; a wave holds 64 / LR phases, so L % (64 / LR) phases of the last wave's
+# are live and the rest of its lanes are not.  What each of the added pairs pins:
+#   11025 -> 32000  <4>, upsampling                    32000 -> 11025  <4>, chunks 2, lanes that are not live
+#   96000 -> 11025  <4>, 1120 taps, a wave almost all dead            96000 -> 44100  <16>, chunks 2, lanes that are not live
+#   16000 -> 11025  <16> with more than 64 KiB of LDS                 96000 -> 8000   <64>, 1536 taps, L = 1
+ROUTES = {
+    (44100, 24000): (80, 147, 240, 64, 1, 0, 59716),
+    (48000, 24000): (1, 2, 256, 64, 64, 0, 50692),
+    (16000, 24000): (3, 2, 128, 64, 32, 0, 42244),
+    (22050, 24000): (160, 147, 128, 64, 1, 0, 80388),
+    (8000, 24000): (3, 1, 128, 64, 32, 0, 34052),
+    (24000, 16000): (2, 3, 192, 64, 32, 0, 42244),
+    (44100, 16000): (160, 441, 360, 16, 1, 0, 40228),
+    (11025, 32000): (1280, 441, 128, 4, 1, 0, 28692),
+    (32000, 11025): (441, 1280, 376, 4, 2, 28, 57020),
+    (96000, 11025): (147, 1280, 1120, 4, 2, 52, 50292),
+    (96000, 44100): (147, 320, 280, 16, 2, 16, 61488),
+    (16000, 11025): (441, 640, 192, 16, 1, 48, 70836),
+    (96000, 8000): (1, 12, 1536, 64, 16, 0, 59524),
+}
+
+
+def lds_bytes(L, M, taps, rounds):
+    """twv_resample.hip's carve restated: rounds * M + taps staged inputs, L * rounds gathered outputs spread by o + o / 32, one pad"""
+    o = L * rounds
+    return 4 * (rounds * M + taps + o + o // 32 + 1)
 
 
 def ratio(sr_in, sr_out):

@@ -120,6 +120,62 @@ def test_spectrogram_create_refusals_without_a_device():
     L.twv_spectrogram_destroy(h)
 
 
+def test_n_fft_8192_is_refused_before_any_device_work():
+    """the magnitude tile of sa_output_kernel is 4 x (n_fft/2 + 1) floats: 65 536 bytes at n_fft 8190, the largest accepted, 65 552 at
+    8192.  analyze refuses on the host (TWV_E_UNSUPPORTED): the pointers are never touched and nothing is launched -- this test has no
+    device.  (8190 itself runs in tests/test_audio_analysis_geometry_gpu.py.)"""
+    from twvk_amd import _lib
+    L = _lib.lib()
+    rc, h = _create(L, 8192, 2048, 8192, 0, None, 9000, 1)
+    assert rc == 0
+    ws = C.create_string_buffer(16)                                         # never reached
+    rc = L.twv_spectrogram_analyze(h, C.cast(ws, C.c_void_p), None, 0.97, 20.0, -100.0, 4.0, 1, C.cast(ws, C.c_void_p), None, C.cast(ws, C.c_void_p),
+                                   None, None)
+    assert rc == 2 and b"n_fft above 8190" in L.twv_last_error()
+    L.twv_spectrogram_destroy(h)
+    rc, h = _create(L, 8190, 2048, 8190, 0, None, 9000, 1)
+    assert rc == 0
+    L.twv_spectrogram_destroy(h)
+
+
+def test_geometry_table_conditions_hold_on_the_checker():
+    """tests/audio_analysis_cases.py's table, on the checker alone, so that a change of the inputs cannot empty a case of the GPU tests:
+    the amplitude bar stays tight (e_f32 <= 2.5e-6: twice the worst measured, 1.2e-6), no float64 linear value sits on a clip edge and
+    no mel value on the upper one (there the amplitude measure would be blind), at most half of an utterance's mel values sit on the
+    lower one (worst: 0.40, the row with ten empty filters), and the float64 run's own agreement with oracle.audio_np.stft
+    (audio_analysis_ref.stages) holds at every row.  Also what the rows are there for."""
+    import audio_analysis_cases as K
+    from test_audio_analysis_gpu import _bar
+    assert len(K.TABLE) == len(K.SEEDS) == 10
+    assert sorted(r[0] for r in K.TABLE if r[0] % 4 == 2) == [126, 2058, 8190]
+    assert K.empty_filters(K.TABLE[5]) == 10 and K.empty_filters(K.TABLE[9]) == 1 and K.n_mels_of(K.TABLE[9]) == 300
+    band = np.flatnonzero(K.basis(K.TABLE[9])[100])
+    assert band[0] == 200 and band[-1] == 259 and (K.basis(K.TABLE[9])[[0, 299]] != 0).all()
+    assert 4 * 4 * (8190 // 2 + 1) == 64 * 1024 and 4 * 8190 == 32760 and 2058 // 2 + 1 == 1024 + 6
+    for row in K.TABLE:
+        hp, basis, wavs, refs = K.row_case(row)                             # (the float64 run asserts against oracle.audio_np.stft)
+        assert all(len(w) > row[0] // 2 and w.dtype == np.float32 for w in wavs) and basis.dtype == np.float32
+        for b, (w, ref) in enumerate(zip(wavs, refs)):
+            m64, l64, m32, l32 = ref
+            assert m64.shape == (1 + len(w) // row[2], K.n_mels_of(row)) and l64.shape == (m64.shape[0], row[0] // 2 + 1)
+            assert m32.dtype == l32.dtype == np.float32
+            for name, d, d32, bar, e, e32, abar in K.measures(m32, l32, ref, hp):
+                assert e == e32 and 0 < e32 <= 2.5e-6 and abar <= K.AMP_BAR_CAP, (K.row_id(row), b, name, e32, abar)
+            assert not (np.abs(l64) == hp.max_abs_value).any(), (K.row_id(row), b)
+            assert not (m64 == hp.max_abs_value).any(), (K.row_id(row), b)
+            assert (m64 == -hp.max_abs_value).mean() <= 0.5, (K.row_id(row), b)
+    # the dB bar is test_audio_analysis_gpu._bar's, unchanged
+    hp, basis, wavs, refs = K.row_case(K.TABLE[6])
+    _, _, bar_m, bar_l, dm, dl = _bar(wavs[0], hp, basis)
+    assert (bar_m, dm) == K.db_bar(refs[0][2], refs[0][0]) and (bar_l, dl) == K.db_bar(refs[0][3], refs[0][1])
+    # the inputs of the no-clip settings at (126, 100, 30): accepted, and refused
+    for setting in (dict(allow_clipping_in_normalization=False), dict(allow_clipping_in_normalization=False, symmetric_mels=False)):
+        hp = K.hparams(K.SETTINGS_ROW, **setting)
+        m, l = R.spectrograms(R.noclip_signal(hp.preemphasis), hp, basis)
+        assert m is not None and l is not None
+        assert R.spectrograms(np.zeros(500, np.float32), hp, basis) == (None, None)
+
+
 def test_trim_on_a_built_signal():
     """0.5 s of zeros, 1 s of tone, 0.5 s of zeros at 24 kHz: the kept interval contains the whole tone and at most trim_fft_size samples
     of silence on either side"""

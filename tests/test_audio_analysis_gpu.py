@@ -1,6 +1,7 @@
 """-m gpu: waveform -> mel / linear spectrogram on the device (twv_spectrogram_analyze) against the float64 numpy checker
 (tests/audio_analysis_ref.py), known answers no restatement stands behind, the general inverse (twv_inv_spectrogram), and
-wav files -> npz examples -> feeder -> one training step -> generation.  Default hparams unless said.
+wav files -> npz examples -> feeder -> one training step -> generation.  Default hparams unless said; every other geometry and
+kernel route is tests/test_audio_analysis_geometry_gpu.py's.
 
 Tolerance of the float32 device path: the checker runs the SAME lines in float32; near min_level a float32 FFT's absolute error is a
 large relative error, so the reachable distance depends on the signal and that run measures it.  Bar = max(8 x that distance, 1e-5):

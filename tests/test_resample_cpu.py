@@ -65,6 +65,38 @@ def test_create_is_host_only_for_every_standard_pair():
     assert n == 72
 
 
+def test_every_route_of_the_kernel_has_its_pair():
+    """resample_ref.ROUTES is what twv_resample_create decides for the pairs the GPU tests iterate (LR from the kernel's name, rounds =
+    LR * chunks from twv_resample_rounds, L and taps from their accessors), and over the table every instantiation, chunks > 1 at the
+    two narrow ones, lanes that are not live at both, a tile above 64 KiB at <16> and the long rows keep a pair: a retuning of the
+    carve that moves a pair to another route fails here instead of silently dropping the GPU suite's cover of the route it left."""
+    assert set(R.ROUTES) == set(R.PAIRS) and len(R.PAIRS) == 13
+    seen = {}
+    for pair in R.PAIRS:
+        up, down, taps, lr, chunks, dead, lds = R.ROUTES[pair]
+        assert (up, down) == R.ratio(*pair)
+        L, h, rc = _create(*pair)
+        assert rc == 0, (pair, L.twv_last_error())
+        try:
+            assert L.twv_resample_phases(h) == up and L.twv_resample_taps(h) == taps, pair
+            assert L.twv_resample_kernel_name(h).decode() == "rs_resample_kernel<%d>" % lr, pair
+            assert L.twv_resample_rounds(h) == lr * chunks, pair
+        finally:
+            L.twv_resample_destroy(h)
+        lanes = 64 // lr                                          # phases a wave has in flight
+        assert dead == (lanes - up % lanes) % lanes * lr, pair
+        assert lds == R.lds_bytes(up, down, taps, lr * chunks) <= 80 * 1024, pair
+        seen.setdefault(lr, []).append((chunks, up % lanes != 0, lds, taps, up >= down))
+    assert set(seen) == {64, 16, 4}
+    for lr in (16, 4):
+        assert any(c > 1 for c, _, _, _, _ in seen[lr]), "chunks > 1 at LR %d" % lr
+        assert any(d for _, d, _, _, _ in seen[lr]), "lanes that are not live at LR %d" % lr
+    assert any(c > 1 for c, _, _, _, _ in seen[64])
+    assert any(lds > 64 * 1024 for _, _, lds, _, _ in seen[16]), "a tile above 64 KiB at LR 16"
+    assert any(t == 1120 for _, _, _, t, _ in seen[4]) and any(t == 1536 for _, _, _, t, _ in seen[64]), "the long rows"
+    assert any(u for _, _, _, _, u in seen[4]), "upsampling at LR 4"
+
+
 def test_kernel_is_in_the_library():
     import subprocess
     from twvk_amd import _lib

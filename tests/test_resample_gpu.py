@@ -4,7 +4,11 @@ generate._load_seed.
 
 Bar of every device-against-checker comparison: max|gpu - f64| <= max(8 x max|f32 checker - f64|, 5e-6 x max|f64|) (resample_ref.bar;
 8 and 5e-6 are tests/train_cases.py's RATIO and FLOOR for float32 sums in another order).  The float32 checker is 1.4-2.3e-7 of the
-peak from float64 on these inputs, so the bar is 5e-6 of the peak; one sample of shift or a missing gain s are 0.25-0.46 of it."""
+peak from float64 on the first seven pairs' inputs, so the bar is 5e-6 of the peak; one sample of shift or a missing gain s are
+0.25-0.46 of it.  resample_ref.PAIRS holds a pair for every route of the kernel (resample_ref.ROUTES: the three instantiations,
+chunks 1 and 2, lanes that are not live, a tile above 64 KiB of LDS, rows of 1120 and 1536 taps); on the added pairs the float32
+checker is 3e-11 ... 2.9e-7 absolute from float64.  The impulse test needs no bar: one non-zero product per output."""
+import ctypes as C
 import functools
 import os
 
@@ -39,12 +43,29 @@ def _device_batch(pair):
     return out, lengths
 
 
+def _route(pair):
+    """which kernel the library launches for the pair, from the handle's own accessors"""
+    from twvk_amd import _lib
+    L = _lib.lib()
+    h = C.c_void_p()
+    _lib.check(L.twv_resample_create(pair[0], pair[1], 30000, 5, C.byref(h)))
+    try:
+        name, up, taps, rounds = L.twv_resample_kernel_name(h).decode(), L.twv_resample_phases(h), L.twv_resample_taps(h), L.twv_resample_rounds(h)
+    finally:
+        L.twv_resample_destroy(h)
+    lr = int(name[name.index("<") + 1:-1])
+    return "%s, L %d, M %d, %d taps, chunks %d (tile of %d outputs), %d lanes of the last wave not live, %d bytes of LDS" % (
+        name, up, R.ratio(*pair)[1], taps, rounds // lr, up * rounds, (64 // lr - up % (64 // lr)) % (64 // lr) * lr,
+        R.lds_bytes(up, R.ratio(*pair)[1], taps, rounds))
+
+
 def parity_report(log=print):
     """per pair and utterance: the device's distance to the float64 checker, the float32 checker's, and the bar
     (scripts/resample_parity.py records it)"""
     rows = []
     for pair in R.PAIRS:
         wavs, refs = _case(pair)
+        log("%5d -> %5d route: %s" % (pair[0], pair[1], _route(pair)))
         out, lengths = _device_batch(pair)
         got = out.cpu().numpy()
         for b, (w, (y64, bar, d32)) in enumerate(zip(wavs, refs)):
@@ -78,6 +99,88 @@ def test_alone_equals_batch(pair):
         one, n = resample(w, pair[0], pair[1])
         assert n == [lengths[b]] and one.shape == (1, lengths[b])
         assert torch.equal(one[0], out[b, :lengths[b]]), (pair, b)
+
+
+ONE_PER_LR = ((96000, 8000), (96000, 44100), (32000, 11025))          # <64>, <16>, <4> (resample_ref.ROUTES)
+
+
+@pytest.mark.parametrize("pair", ONE_PER_LR, ids=["%d-%d" % p for p in ONE_PER_LR])
+def test_impulse_returns_the_table(pair):
+    """x = delta[n - n0]: with t M = q L + p every output is ONE product, 1 * c[p][q + W - n0], plus zeros -- exact in any order, so
+    the device must return float32(c[p][k]) of twv_resample_filter_host to the bit (+0 for a tap out of range), no tolerance.  Phase,
+    tap index and tile seams at every tile.  n0 = 5000 in 12 000 samples, and n0 on the first tile boundary (rounds * M input samples,
+    rounds from twv_resample_rounds), where the impulse's outputs lie in two workgroups."""
+    from twvk_amd import _lib
+    from twvk_amd.audio import resample
+    up, down = R.ratio(*pair)
+    L = _lib.lib()
+    h = C.c_void_p()
+    _lib.check(L.twv_resample_create(pair[0], pair[1], 12000, 1, C.byref(h)))
+    try:
+        taps, rounds = L.twv_resample_taps(h), L.twv_resample_rounds(h)
+        tab = np.empty((up, taps), np.float32)
+        _lib.check(L.twv_resample_filter_host(h, tab.ctypes.data_as(C.c_void_p)))
+    finally:
+        L.twv_resample_destroy(h)
+    assert (taps, rounds) == (R.ROUTES[pair][2], R.ROUTES[pair][3] * R.ROUTES[pair][4])
+    W, tile_out, seam = taps // 2, up * rounds, rounds * down
+    for n0, n in ((5000, 12000), (seam, max(12000, seam + 2000))):
+        x = np.zeros(n, np.float32)
+        x[n0] = 1.0
+        out, lengths = resample(x, pair[0], pair[1])
+        got = out[0].cpu().numpy()
+        t = np.arange(R.out_samples(n, *pair), dtype=np.int64)
+        q, p = np.divmod(t * down, up)
+        k = q + W - n0
+        inside = (k >= 0) & (k < taps)
+        want = np.where(inside, tab[p, np.clip(k, 0, taps - 1)], np.float32(0.0))
+        assert lengths == [len(t)] and got.shape == want.shape and inside.sum() >= taps * up // down - 1
+        if n0 == seam:                                             # outputs of the impulse on either side of the seam
+            assert inside[:tile_out].any() and inside[tile_out:].any(), (pair, tile_out)
+        assert np.count_nonzero(want) > 0.9 * inside.sum()
+        bad = np.flatnonzero(got != want)
+        assert not bad.size, (pair, n0, bad[:5], got[bad[:5]], want[bad[:5]])
+
+
+@pytest.mark.parametrize("pair", [(96000, 8000), (16000, 11025), (96000, 11025)], ids=["96000-8000", "16000-11025", "96000-11025"])
+def test_nothing_stale_nothing_behind(pair):
+    """the C-ABI itself, one pair per instantiation (<64>; <16> above 64 KiB of LDS; <4>): the workspace holds NaN before the first call
+    (the table is uploaded by that call), `out` holds NaN with 1024 marked floats behind it, the batch is (30 000, 1, 0) samples --
+    the Python front never passes a length of 0, the host code accepts it (n_out = 0: every tile of the row takes the zero branch) --
+    and the input past each length is 7.  Afterwards every row is finite, inside the bar up to n_out, exactly 0 from n_out to the
+    stride, and the marks are intact."""
+    import torch
+    from twvk_amd import _lib
+    from twvk_amd.audio import _ptr, _stream
+    wavs, refs = _case(pair)
+    L = _lib.lib()
+    B, n, GUARD, MARK = 3, 30000, 1024, -12345.0
+    x = torch.full((B, n), 7.0, device="cuda:0")
+    x[0] = torch.from_numpy(wavs[4]).cuda(); x[1, :1] = torch.from_numpy(wavs[0]).cuda()
+    lengths = np.asarray([n, 1, 0], np.int32)
+    h = C.c_void_p()
+    _lib.check(L.twv_resample_create(pair[0], pair[1], n, B, C.byref(h)))
+    try:
+        stride = int(L.twv_resample_out_samples(h, n))
+        n_out = [int(L.twv_resample_out_samples(h, int(v))) for v in lengths]
+        assert stride == R.out_samples(n, *pair) and n_out == [stride, len(refs[0][0]), 0]
+        ws = torch.full((L.twv_resample_workspace_bytes(h) // 4 + 64,), float("nan"), device="cuda:0")
+        buf = torch.full((B * stride + GUARD,), float("nan"), device="cuda:0")
+        buf[B * stride:] = MARK
+        _lib.check(L.twv_resample(h, _ptr(x), 0, 1, lengths.ctypes.data_as(C.c_void_p), _ptr(ws), _ptr(buf), _stream()))
+        torch.cuda.synchronize()
+    finally:
+        L.twv_resample_destroy(h)
+    got = buf.cpu().numpy()
+    assert (got[B * stride:] == MARK).all(), "written behind the output"
+    got = got[:B * stride].reshape(B, stride)
+    assert np.isfinite(got).all(), "a row element was left unwritten"
+    for b, (y64, bar, d32) in enumerate((refs[4], refs[0])):
+        d = np.abs(got[b, :n_out[b]] - y64).max()
+        print("%s utterance %d: max|gpu - f64| = %.3e, f32 checker %.3e, bar %.3e" % (pair, b, d, d32, bar))
+        assert d <= bar, (pair, b, d, d32, bar)
+        assert not got[b, n_out[b]:].any()
+    assert not got[2].any()
 
 
 def _tone(f, sr, n, amp=0.5):
