@@ -242,6 +242,56 @@ __device__ __forceinline__ float dot16_dpp(const float (&w)[16], float z, float 
     return c0 + c1;
 }
 
+// two independent half chunks (different tiles, different Z operands) interleaved instruction by instruction: four fma chains in
+// flight instead of two, as dot32_dpp_x2 does with eight (conv1 workgroups split by output half: 2 half tiles per wave).  Each
+// result is the lane's (s0+s1) or (s2+s3); the caller joins the row pairs with v_permlane16_swap as layer_back_dpp does.
+__device__ __forceinline__ void dot16_dpp_x2(const float (&wa)[16], float za, const float (&wb)[16], float zb, float& ra, float& rb)
+{
+    float c0 = 0.0f, c1 = 0.0f, d0 = 0.0f, d1 = 0.0f;
+    asm volatile(
+        "s_nop 1\n" TWV_ALIGN8
+        "v_fmac_f32_dpp %0, %4, %6 row_newbcast:0 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %2, %5, %14 row_newbcast:0 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %1, %4, %7 row_newbcast:1 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %3, %5, %15 row_newbcast:1 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %0, %4, %8 row_newbcast:2 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %2, %5, %16 row_newbcast:2 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %1, %4, %9 row_newbcast:3 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %3, %5, %17 row_newbcast:3 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %0, %4, %10 row_newbcast:4 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %2, %5, %18 row_newbcast:4 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %1, %4, %11 row_newbcast:5 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %3, %5, %19 row_newbcast:5 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %0, %4, %12 row_newbcast:6 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %2, %5, %20 row_newbcast:6 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %1, %4, %13 row_newbcast:7 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %3, %5, %21 row_newbcast:7 row_mask:0xf bank_mask:0xf"
+        : "+v"(c0), "+v"(c1), "+v"(d0), "+v"(d1)
+        : "v"(za), "v"(zb), "v"(wa[0]), "v"(wa[1]), "v"(wa[2]), "v"(wa[3]), "v"(wa[4]), "v"(wa[5]), "v"(wa[6]), "v"(wa[7]), "v"(wb[0]), "v"(wb[1]), "v"(wb[2]), "v"(wb[3]), "v"(wb[4]), "v"(wb[5]), "v"(wb[6]), "v"(wb[7]));
+    asm volatile(
+        "s_nop 1\n" TWV_ALIGN8
+        "v_fmac_f32_dpp %0, %4, %6 row_newbcast:8 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %2, %5, %14 row_newbcast:8 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %1, %4, %7 row_newbcast:9 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %3, %5, %15 row_newbcast:9 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %0, %4, %8 row_newbcast:10 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %2, %5, %16 row_newbcast:10 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %1, %4, %9 row_newbcast:11 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %3, %5, %17 row_newbcast:11 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %0, %4, %10 row_newbcast:12 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %2, %5, %18 row_newbcast:12 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %1, %4, %11 row_newbcast:13 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %3, %5, %19 row_newbcast:13 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %0, %4, %12 row_newbcast:14 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %2, %5, %20 row_newbcast:14 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %1, %4, %13 row_newbcast:15 row_mask:0xf bank_mask:0xf\n"
+        "v_fmac_f32_dpp %3, %5, %21 row_newbcast:15 row_mask:0xf bank_mask:0xf"
+        : "+v"(c0), "+v"(c1), "+v"(d0), "+v"(d1)
+        : "v"(za), "v"(zb), "v"(wa[8]), "v"(wa[9]), "v"(wa[10]), "v"(wa[11]), "v"(wa[12]), "v"(wa[13]), "v"(wa[14]), "v"(wa[15]), "v"(wb[8]), "v"(wb[9]), "v"(wb[10]), "v"(wb[11]), "v"(wb[12]), "v"(wb[13]), "v"(wb[14]), "v"(wb[15]));
+    ra = c0 + c1;
+    rb = d0 + d1;
+}
+
 // ---- the two contractions ON the generation chain (AC-1b): chain 0 starts from the addend, the other chains from their FIRST PRODUCT
 // (v_mul_f32_dpp -- no zero-initialised accumulators: four v_mov fewer per layer; fma(w, x, -0) == w * x for every w and x, so the C
 // restatement of the CPU checker starts those chains from -0).  profiles/r05_chain_contract_ubench.txt, contract C7.

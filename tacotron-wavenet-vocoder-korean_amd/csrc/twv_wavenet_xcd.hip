@@ -13,7 +13,9 @@
 //       chain workgroup   (1 per stream): 6 waves x 5 layers (tap-1 conv kernel in VGPRs, 32 per lane and layer; dense kernel in LDS), 1 head wave
 //       service workgroup (1 per stream): tap-0 conv kernels, the delay lines (model.py:49-64 queues; in the stream's state buffer)
 //       skip workgroups   (8 per XCD): slice g of the 30 skip kernels (model.py:94-96)
-//       conv1 workgroups  (8 per XCD): slice g of conv1d_1 and its two chunks of conv1d_2 (model.py:158-165)
+//       conv1 workgroups  (8 per XCD): slice g of conv1d_1 and its two chunks of conv1d_2 (model.py:158-165); at one stream per XCD
+//                              (batch <= 8, MoL, 2..30 layers) SIXTEEN: (slice g, output half) of conv1d_1 and its one chunk of conv1d_2,
+//                              every tile in the dense half-chunk form -- chain + service + 8 skip + 16 conv1 + 4 lc = 30 of the 32 CUs
 //       lc workgroups   (2-4 per XCD): create_upsample + lc_filter/lc_gate projections (model.py:102-111,75-83), running ahead of
 //                              the chain through a ring: neither the upsampled condition nor a projection table exists in HBM
 //     More than 30 layers (hparams.py's default stack has 50): a SECOND chain workgroup takes layers 30.. (one L2 hop away), the
@@ -229,12 +231,14 @@ constexpr int kTraceStep = 2000;
 // where a wave is (instrumented build only): read back from the exchange area after a watchdog abort
 #define XMARK(role_, stage_) do { if ((INSTR & 1) && lane == 0) xb_store(rs, (int)XcdExch::MARK + (role_) * 8 + (int)(threadIdx.x >> 6), 0, (unsigned)t + 1u, (float)(stage_)); } while (0)
 
-enum { ROLE_CHAIN = 0, ROLE_SERVICE = 1, ROLE_SKIP0 = 2, ROLE_CONV0 = 10, ROLE_LC0 = 18 };     // slots of the stage markers (XMARK)
+enum { ROLE_CHAIN = 0, ROLE_SERVICE = 1, ROLE_SKIP0 = 2, ROLE_CONV0 = 10 };     // slots of the stage markers (XMARK); the lc workgroups follow the n_conv1 conv1 slots
 constexpr int kXcdStreamsPerXcd = kXcdStreams / 8;
 
 struct XArgs {
     XcdLaunch p;
     int n_lc_wg, lc_lpw;      // lc workgroups per XCD, layers per lc wave
+    int n_conv1;              // conv1 workgroups per XCD: 8 (conv1_role), or 16 at one stream per XCD (conv1_half_role).  Host (total_roles) and
+                              // kernel (ticket bound, role decoding, marker slots) both read THIS field
     int total_roles;          // role workgroups of the whole launch (all XCDs): what roles_resident counts up to
 };
 
@@ -1113,6 +1117,26 @@ __device__ __forceinline__ void conv1_load_last_skip(const XcdLaunch& a, const i
     load_tile(wl, a.P + lb + LayerOff::SK + (long long)v * kTile, lane);
     if (L.use_bias != 0) bl = a.P[lb + LayerOff::SK + (long long)L.NSJ * kTile + v * 64 + lane];
 }
+// 32 outputs x 32 terms of a standard tile image ([kq][64 outputs][4], outputs obase .. obase+31) in the dense half-chunk form of
+// twv_dpp.hpp: lane (row, n) holds output n + 16 (row / 2) and its terms k = dpp_dense_k(lane, i).  Terms i = 2j, 2j+1 are the
+// neighbours k = 4j + {0,1} (even rows) or 4j + {2,3} (odd rows) of the image: eight 8-byte loads.
+__device__ __forceinline__ void load_half_tile(float (&w)[16], const float* base, const int obase, const int lane)
+{
+    const float2* p = reinterpret_cast<const float2*>(base + (obase + dpp_dense_out(lane)) * 4 + (((lane >> 4) & 1) ? 2 : 0));
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const float2 q = p[j * 128];
+        w[2 * j] = q.x; w[2 * j + 1] = q.y;
+    }
+}
+// the conv1d_2 chunk of a summing wave (model.py:161-165): h in the Z layout, the chunk's four AC-1 chains from +0 split over the row
+// pairs as in layer_back_dpp; every lane ends with the value of output dpp_dense_out(lane)
+__device__ __forceinline__ float conv1d2_chunk_dpp(const float (&t2)[16], const float h)
+{
+    const float s = dot16_dpp(t2, h);
+    const auto ds = __builtin_amdgcn_permlane16_swap(__float_as_uint(s), __float_as_uint(s), false, false);
+    return __uint_as_float(ds[0]) + __uint_as_float(ds[1]);
+}
 
 // KF: see conv1_fetch_h1.  The last layer's z -> skip workgroup -> dot / sum / publish -> conv1 path (0.31 + 0.33 + 0.25 us behind the last
 // layer) becomes z -> conv1 (0.31 us) in parallel with the second-to-last layer's trip through the skip workgroup.
@@ -1133,11 +1157,13 @@ __device__ __forceinline__ void conv1_role(const XArgs& xa, const SX& sx, int g,
     load_tile(ta, a.P + L.off_w1 + ((long long)g * NCH + c0) * kTile, lane);
     load_tile(tb, a.P + L.off_w1 + ((long long)g * NCH + c1) * kTile, lane);
     const bool summer = v < 2;
+    // summer v needs only h[32v .. 32v+31] of the block, and needs it in the Z layout: the lane sums the partials of THAT output
+    const int hz = 32 * v + dpp_z_index(lane);
     float b1v = 0.0f;
-    Tile t2;
+    float t2[16];
     if (summer) {
-        if (use_bias) b1v = a.P[L.off_b1 + g * 64 + lane];
-        load_tile(t2, a.P + L.off_w2 + (long long)(2 * g + v) * kTile, lane);
+        if (use_bias) b1v = a.P[L.off_b1 + g * 64 + hz];
+        load_half_tile(t2, a.P + L.off_w2 + (long long)(2 * g + v) * kTile, 0, lane);
     }
     Tile wl;                                                              // KF: the last layer's skip kernel, output block v
     float bl = 0.0f;
@@ -1199,16 +1225,16 @@ __device__ __forceinline__ void conv1_role(const XArgs& xa, const SX& sx, int g,
                 XSTAMP(g == 0 && v == 0, 24);
                 float cp[16];
 #pragma unroll
-                for (int ch = 0; ch < 16; ++ch) cp[ch] = lds[ob + O_PART + ch * 64 + lane];
+                for (int ch = 0; ch < 16; ++ch) cp[ch] = lds[ob + O_PART + ch * 64 + hz];
                 __builtin_amdgcn_sched_barrier(0);
                 float r = cp[0];                                            // AC-1: chunk values added in chunk order
 #pragma unroll
                 for (int ch = 1; ch < 16; ++ch) r = r + cp[ch];
                 if (use_bias) r = r + b1v;
                 const float h = r > 0.0f ? r : 0.0f;                         // model.py:160
-                // conv1d_2 chunk 2g+v reads h[32v .. 32v+31] of this block
-                const float p = (v == 0) ? dot_readlane_pipe(t2, h) : dot_readlane_pipe32(t2, h);
-                if (lane < 32) xb_store(rs, (int)XcdExch::PT, (g * 32 + lane) * 2 + v, tag, p);     // chunk 2g+v of output `lane`, next to its pair
+                // conv1d_2 chunk 2g+v reads h[32v .. 32v+31] of this block: 16 DPP fmacs per lane (half-chunk form)
+                const float p = conv1d2_chunk_dpp(t2, h);
+                if ((lane & 16) == 0) xb_store(rs, (int)XcdExch::PT, (g * 32 + dpp_dense_out(lane)) * 2 + v, tag, p);     // chunk 2g+v of the lane's output, next to its pair
                 WTRACE(prof_slot >= 0 && k == 0, 480 + g * 2 + v);
                 XSTAMP(g == 0 && v == 0, 25);
             }
@@ -1219,6 +1245,104 @@ __device__ __forceinline__ void conv1_role(const XArgs& xa, const SX& sx, int g,
         for (int k = 0; k < NS; ++k) xb_store(sx.rs[k], (int)XcdExch::CTRL + 1, 0, 1u, 0.0f);       // the waves waiting on the LDS counter see it in poll_tick
     }
     WACC_OUT(a.prof, prof_slot, v);
+}
+
+// =====================================================================================================================
+//  CONV1 workgroup (g, hh) at ONE STREAM PER XCD (batch <= 8: sixteen conv1 workgroups instead of eight, 30 of the XCD's 32 CUs carry
+//  a role): outputs 64 g + 32 hh .. + 31 of conv1d_1 for all 16 chunks, then the ONE chunk 2g + hh of conv1d_2 that reads them.
+//  A tile is 32 outputs x 32 terms, the dense half-chunk form of twv_dpp.hpp: 16 fmacs per tile instead of 32, and the two waves that
+//  share a SIMD issue 2 x 32 of them instead of 2 x 64.
+//  Wave v polls the granules conv1_role's wave v polls (the last layer's z, h1[64 v ..]); lane (row, n) asks for
+//      rows 0, 1: h1[64 v + a(n)], h1[64 v + b(n)]      rows 2, 3: the same + 32
+//  (the last layer's skip tile and bias follow the same lane map), so ONE v_permlane32_swap makes the Z-layout operand of chunk 2v
+//  ([lo, lo]) and of chunk 2v + 1 ([hi, hi]).  Same fmas, same chains, same order of the chunk sum as conv1_role: same bits.
+// =====================================================================================================================
+template <int INSTR, int KF>
+__device__ __forceinline__ void conv1_half_role(const XArgs& xa, const XStreams<1>& sx, const int g, const int hh)
+{
+    static_assert(KF > 0, "the last layer's skip 1x1 runs here");
+    const XcdLaunch& a = xa.p;
+    const Layout& L = a.lay;
+    const int v = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int T = a.T, NCH = L.NCH;
+    const bool use_bias = L.use_bias != 0;
+    const rsrc_t rs = sx.rs[0];
+    const int b = sx.b[0];
+    Poll pl{rs, a.status, 0, false};
+    constexpr int O_PART = 0, O_CNT = 16 * 64;                            // LDS floats: chunk partials [16][32] | arrival counter (as in conv1_role)
+    if (threadIdx.x == 0) LDSI(O_CNT) = 0;
+    __syncthreads();
+    const int c0 = 2 * v, c1 = 2 * v + 1;                                 // this wave's chunks
+    float ta[16], tb[16];
+    load_half_tile(ta, a.P + L.off_w1 + ((long long)g * NCH + c0) * kTile, 32 * hh, lane);
+    load_half_tile(tb, a.P + L.off_w1 + ((long long)g * NCH + c1) * kTile, 32 * hh, lane);
+    const int zi = dpp_z_index(lane), od = dpp_dense_out(lane);
+    const int hl = 32 * (lane >> 5) + zi;                                 // the lane holds h1[64 v + hl]
+    const bool summer = v == 0;
+    float b1v = 0.0f;
+    float t2[16];
+    if (summer) {
+        if (use_bias) b1v = a.P[L.off_b1 + g * 64 + 32 * hh + zi];
+        load_half_tile(t2, a.P + L.off_w2 + (long long)(2 * g + hh) * kTile, 0, lane);
+    }
+    Tile wl;                                                              // the last layer's skip kernel, output block v, lane map hl
+    float bl = 0.0f;
+    conv1_load_last_skip(a, v, hl, wl, bl);
+    const int zc_lane = lane_of_z((lane < 32 ? 0 : 16) + (lane & 15));
+    unsigned long long t_arr = 0, period = 0;
+    for (int t = 0; t < T && !pl.dead; ++t) {
+        asm volatile(".p2align 6");                        // (XALIGN, see chain_many_role)
+        const unsigned tag = (unsigned)t + 1u;
+        if (period) nap_until(t_arr + period - (period >> 3));
+        XMARK(ROLE_CONV0 + 2 * g + hh, 1);
+        bool saw_z = false;
+        const unsigned long long q = conv1_fetch_h1<KF, false>(pl, rs, v, hl, tag, L.NL - 1, zc_lane, wl.w, bl, use_bias, saw_z);
+        (void)saw_z;
+        // (no exit here on a watchdog abort: see the chain role; the loops end at their heads)
+        const unsigned long long now_arr = __builtin_amdgcn_s_memtime();       // read only: the arithmetic follows the dots (as in the chain)
+        XSTAMP(g == 0 && hh == 0 && v == 0, 22);
+        const unsigned hq = (unsigned)q;
+        const auto hs = __builtin_amdgcn_permlane32_swap(hq, hq, false, false);          // [lo, lo] = chunk c0 in the Z layout, [hi, hi] = chunk c1
+        float s0, s1;
+        dot16_dpp_x2(ta, __uint_as_float(hs[0]), tb, __uint_as_float(hs[1]), s0, s1);
+        const auto d0 = __builtin_amdgcn_permlane16_swap(__float_as_uint(s0), __float_as_uint(s0), false, false);
+        const auto d1 = __builtin_amdgcn_permlane16_swap(__float_as_uint(s1), __float_as_uint(s1), false, false);
+        const float r0 = __uint_as_float(d0[0]) + __uint_as_float(d0[1]);               // (s0+s1)+(s2+s3) of output `od`, on both rows of the pair
+        const float r1 = __uint_as_float(d1[0]) + __uint_as_float(d1[1]);
+        if ((lane & 16) == 0) {
+            lds[O_PART + c0 * 32 + od] = r0;
+            lds[O_PART + c1 * 32 + od] = r1;
+        }
+        asm volatile("" ::: "memory");
+        if (lane == 0) __hip_atomic_fetch_add(&LDSI(O_CNT), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        {
+            const unsigned long long d = now_arr - t_arr;
+            period = (t_arr != 0 && d < (1ull << 18)) ? d : 0;
+            t_arr = now_arr;
+        }
+        XSTAMP(g == 0 && hh == 0 && v == 0, 23);
+        XMARK(ROLE_CONV0 + 2 * g + hh, 2);
+        if (summer) {
+            pl.it = 0;
+            while (LDSVI(O_CNT) < 8 * (t + 1)) { if (!poll_tick(pl, 62)) break; }
+            // (no exit here on a watchdog abort: see the chain role; the loops end at their heads)
+            asm volatile("" ::: "memory");
+            XSTAMP(g == 0 && hh == 0, 24);
+            float cp[16];
+#pragma unroll
+            for (int ch = 0; ch < 16; ++ch) cp[ch] = lds[O_PART + ch * 32 + zi];
+            __builtin_amdgcn_sched_barrier(0);
+            float r = cp[0];                                            // AC-1: chunk values added in chunk order
+#pragma unroll
+            for (int ch = 1; ch < 16; ++ch) r = r + cp[ch];
+            if (use_bias) r = r + b1v;
+            const float h = r > 0.0f ? r : 0.0f;                         // model.py:160
+            const float p = conv1d2_chunk_dpp(t2, h);                    // conv1d_2 chunk 2g+hh reads exactly this workgroup's 32 values
+            if ((lane & 16) == 0) xb_store(rs, (int)XcdExch::PT, (g * 32 + od) * 2 + hh, tag, p);
+            XSTAMP(g == 0 && hh == 0, 25);
+        }
+    }
+    if (pl.dead && lane == 0) xb_store(rs, (int)XcdExch::CTRL + 1, 0, 1u, 0.0f);       // the wave waiting on the LDS counter sees it in poll_tick
 }
 
 // =====================================================================================================================
@@ -1426,7 +1550,7 @@ __device__ __forceinline__ void lc_role(const XArgs& xa, const XStreams<NS>& sx,
                 if (k >= ns_rt) break;
                 const rsrc_t rs = sx.rs[k];
                 pl.rs = rs;
-                XMARK(ROLE_LC0 + wg, 1);
+                XMARK(ROLE_CONV0 + xa.n_conv1 + wg, 1);
                 pl.it = 0;
                 while (!pl.dead) {
                     const unsigned long long q = xb_load_t<BAR>(rs, (int)XcdExch::CTRL, 0);
@@ -1599,12 +1723,13 @@ __global__ void __launch_bounds__(512) wn_xcd_generate_kernel(XArgs xa)
     for (int i = threadIdx.x; i < kXcdStreamsPerXcd * kSkipLdsWords * 2 + 64; i += blockDim.x) lds[i] = 0.0f;
     __syncthreads();
     ticket = s_ticket;
-    // roles of an XCD with ns streams: ns chains (of one or two workgroups), ns service workgroups, then ONE set of 8 skip + 8 conv1 +
-    // n_lc workgroups
+    // roles of an XCD with ns streams: ns chains (of one or two workgroups), ns service workgroups, then ONE set of 8 skip + n_conv1
+    // conv1 + n_lc workgroups
     const int ns = xcc < (unsigned)a.B && xcc < 8u ? (a.B - (int)xcc + 7) / 8 : 0;
     constexpr int nseg = BIGK ? 2 : 1;
     const int nchain = ns * nseg;
-    if (ticket >= nchain + ns + 16 + xa.n_lc_wg) return;        // surplus workgroup (or an XCD without a stream)
+    const int nc1 = xa.n_conv1;
+    if (ticket >= nchain + ns + 8 + nc1 + xa.n_lc_wg) return;   // surplus workgroup (or an XCD without a stream)
     if (!roles_resident(xa)) return;                            // the device is busy: nobody starts (status 90)
     const bool forced = a.forced != nullptr;
     auto exch_of = [&](int b) { return __builtin_amdgcn_make_buffer_rsrc(a.exch + (long long)b * XcdExch::WORDS, 0, (int)(XcdExch::WORDS * 8), 0x00020000); };
@@ -1640,7 +1765,7 @@ __global__ void __launch_bounds__(512) wn_xcd_generate_kernel(XArgs xa)
         else service_role<INSTR, BIGK>(xa, b, rs);
         return;
     }
-    const int role = ticket - nchain - ns;                       // 0-7 skip, 8-15 conv1, 16.. lc
+    const int role = ticket - nchain - ns;                       // 0-7 skip, 8 .. 8+nc1-1 conv1, then lc
     auto shared_roles = [&](auto nsc) {
         constexpr int NS = decltype(nsc)::value;
         XStreams<NS> sx;
@@ -1660,8 +1785,13 @@ __global__ void __launch_bounds__(512) wn_xcd_generate_kernel(XArgs xa)
                 else if constexpr (kUnfolded) skip_role<INSTR, NS, BIGK, 0>(xa, sx, role);
             }
         }
-        else if (role < 16) {
+        else if (role < 8 + nc1) {
             if (!forced) {
+                // sixteen workgroups (output block, output half) where xcd_launch says so: one stream per XCD, MoL, the fold applies
+                constexpr bool kHalf = !ONEHOT && !BIGK && NS == 1 && KF > 0 && (ONE || INSTR != 0);
+                if constexpr (kHalf) {
+                    if (nc1 == 16) { conv1_half_role<INSTR, KF>(xa, sx, (role - 8) >> 1, (role - 8) & 1); return; }
+                }
                 if constexpr (ONEHOT) {
                     if (fold) conv1_onehot_role<INSTR, NS, KF>(xa, sx, role - 8);
                     else if constexpr (kUnfolded) conv1_onehot_role<INSTR, NS, 0>(xa, sx, role - 8);
@@ -1670,7 +1800,7 @@ __global__ void __launch_bounds__(512) wn_xcd_generate_kernel(XArgs xa)
                 else if constexpr (kUnfolded) conv1_role<INSTR, NS>(xa, sx, role - 8);
             }
         }
-        else lc_role<INSTR, NS, BIGK>(xa, sx, role - 16);
+        else lc_role<INSTR, NS, BIGK>(xa, sx, role - 8 - nc1);
     };
     if constexpr (BIGK) {                                         // at most two streams per XCD (LDS of the skip workgroups)
         if (ns == 1) shared_roles(std::integral_constant<int, 1>{});
@@ -2652,7 +2782,7 @@ int xcd_lc_workgroups(const Layout& L)
     const int waves = (L.NL + lpw - 1) / lpw;
     return (waves + 7) / 8;
 }
-int xcd_workgroups_per_stream(const Layout& L) { return ROLE_LC0 + xcd_lc_workgroups(L); }
+int xcd_workgroups_per_stream(const Layout& L) { return ROLE_CONV0 + 8 + xcd_lc_workgroups(L); }
 size_t xcd_exchange_bytes(int batch) { return (size_t)batch * XcdExch::WORDS * 8 + 64; }
 void xcd_pack(float* packed, const float* blob, const Layout& L, hipStream_t st)
 {
@@ -2672,11 +2802,13 @@ int xcd_launch(const XcdLaunch& p, hipStream_t st)
     // chain workgroup: hand-off boxes + the dense kernels of its layers + the waves' streamed half tiles (152 KiB); more than 30 layers: the skip / service workgroups
     // keep the tiles of layers 0 .. NL-41 in LDS next to their value slots (159 KiB of the CU's 160)
     const bool many = xcd_uses_many(p.lay, p.B, p.many);
+    // one stream per XCD, MoL, at most 30 layers, a layer in front of the folded ones: the conv1 stage on sixteen workgroups (conv1_half_role)
+    xa.n_conv1 = (!many && p.B <= 8 && p.lay.scalar && p.lay.NL <= kXcdSeg0Layers && p.lay.NL > TWV_XCD_KF && TWV_XCD_KF > 0) ? 16 : 8;
     xa.total_roles = 0;
     for (int x = 0; x < 8 && x < p.B; ++x) {
         const int ns = (p.B - x + 7) / 8;
-        if (many) xa.total_roles += 2 * ((ns + kMS - 1) / kMS) + 16 + xa.n_lc_wg;
-        else xa.total_roles += ns * (p.lay.NL > kXcdSeg0Layers ? 2 : 1) + ns + 16 + xa.n_lc_wg;
+        if (many) xa.total_roles += 2 * ((ns + kMS - 1) / kMS) + 8 + xa.n_conv1 + xa.n_lc_wg;
+        else xa.total_roles += ns * (p.lay.NL > kXcdSeg0Layers ? 2 : 1) + ns + 8 + xa.n_conv1 + xa.n_lc_wg;
     }
     const size_t shm = many ? (size_t)kManyLds * 4 : p.lay.NL > kXcdSeg0Layers ? (size_t)159 * 1024 : (size_t)kXcdChainLdsFloats * 4;
     int dev = 0, cus = 256;
