@@ -324,6 +324,40 @@ int twv_clip_by_global_norm(float* grads, int64_t n, double pre_scale, double cl
 int twv_adam_ema_step(float* params, const float* grads, float* m, float* v, float* ema, int64_t n, double lr, double beta1,
                       double beta2, double eps, int64_t t, double ema_decay, double grad_scale, void* stream);
 
+/* ======================================= WaveNet scoring: per-sample negative log-likelihood =======================================
+ * The add_loss graph with reduce=False (wavenet/model.py:247-312: drop last sample, create_upsample, 'valid' convolutions with the
+ * local condition sliced from the front of every layer, model.py:79-80; targets audio[rf:]; wavenet/mixture.py:27-81
+ * discretized_mix_logistic_loss(reduce=False), or model.py:257-296 softmax cross-entropy for the one-hot model) on a batch of WINDOWS:
+ * forward only, no gradient, no mean.  For a hop-aligned start s the graph on the crop audio[s : s+n], mel[s/hop : (s+n)/hop] gives the
+ * whole utterance's values at positions s+rf .. s+n-1 (the front slice is shift-invariant at hop multiples), so the host scores an
+ * utterance of any length as windows with a halo of ceil(rf / hop) * hop samples (score.py) and memory is bounded by (slots, window). */
+typedef struct twv_wavenet_scorer twv_wavenet_scorer;
+/* accepts what twv_wavenet_train_create accepts (R = D = 32, 80 mel channels, gc with a cardinality, out_channels = 3*nr <= 96 or
+ * quantization_channels in [2, 512]); everything else is TWV_E_UNSUPPORTED, as is slots * window_samples * 256 >= 2^31 where the local
+ * condition is projected at frame rate (three upsampling stages, 32 <= hop <= 512).  TWV_E_INVALID: window_samples not a multiple of
+ * the hop size (datafeeder_wavenet.py:38) or <= the receptive field (model.py:31-39). */
+int twv_wavenet_score_create(const twv_wavenet_dims* dims, int slots, int window_samples, twv_wavenet_scorer** out);
+void twv_wavenet_score_destroy(twv_wavenet_scorer* h);
+size_t twv_wavenet_score_workspace_bytes(const twv_wavenet_scorer* h);      /* a function of (dims, slots, window_samples) only */
+int twv_wavenet_score_output_width(const twv_wavenet_scorer* h);            /* window_samples - receptive_field (model.py:135) */
+/* host-only label for tests and measurements, a string the handle owns:
+ *   "lc=<fused|staged> head=<skinny|gemm> loss=<mol<10>|mol<0>|softmax> carve_floats=<n>" (lc as twv_wavenet_train_route) */
+const char* twv_wavenet_score_route(const twv_wavenet_scorer* h);
+/* nll (slots, window_samples - rf) float32, overwritten: nll[b][p] = the loss term of target audio[b][p + rf] (model.py:286-296) for
+ * p < lengths_host[b] - rf, 0 for the positions slot b does not have.  params: the flat blob of twv_wavenet_train_param_floats floats
+ * in the order of weights.tensor_specs (a trainer's params or EMA shadows as they are).  audio (slots, window_samples) float in [-1,1];
+ * lc (slots, window_samples/hop, 80); gc_ids (slots) int32, a valid id for idle slots too.  lengths_host (HOST, slots): samples in each
+ * slot from its start -- a multiple of the hop size in (rf, window_samples], or 0 for an idle slot; anything else is TWV_E_INVALID
+ * before anything is launched.  Rows past a slot's length are neither read nor written.  workspace: workspace_bytes of device memory in
+ * any state (nothing relies on its contents). */
+int twv_wavenet_score_windows(twv_wavenet_scorer* h, const float* params, const float* audio, const float* lc, const int32_t* gc_ids,
+                              const int32_t* lengths_host, void* workspace, float* nll, void* stream);
+/* out_double2 (device double[2], overwritten) = (sum, count) of nll[b][keep_from_host[b] .. keep_to_host[b] - 1] over the slots
+ * (0 <= from <= to <= width, else TWV_E_INVALID): model.py:290's mean is sum / count over the windows of a list.  Float64, one fixed
+ * order of additions: two runs give the same bits. */
+int twv_wavenet_score_reduce(const float* nll, const int32_t* keep_from_host, const int32_t* keep_to_host, int slots, int width,
+                             double* out_double2, void* stream);
+
 /* ======================================= spectrogram -> waveform (Griffin-Lim) =======================================
  * Replaces synthesizer.py:258 `inv_linear_spectrogram(wav.T, hparams)` (utils/audio.py:77-92, 127-146, 27-30): denormalise,
  * dB -> amplitude, ** power, Griffin-Lim with librosa's stft/istft conventions, inverse pre-emphasis.  FFTs by hipFFT. */

@@ -267,6 +267,13 @@ def lib():
     L.twv_clip_by_global_norm.argtypes = [fp, C.c_int64, C.c_double, C.c_double, vp, vp]
     L.twv_adam_ema_step.argtypes = [fp, fp, fp, fp, fp, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int64,
                                     C.c_double, C.c_double, vp]
+    L.twv_wavenet_score_create.argtypes = [C.POINTER(Dims), C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    L.twv_wavenet_score_destroy.argtypes = [vp]; L.twv_wavenet_score_destroy.restype = None
+    L.twv_wavenet_score_workspace_bytes.argtypes = [vp]; L.twv_wavenet_score_workspace_bytes.restype = C.c_size_t
+    L.twv_wavenet_score_output_width.argtypes = [vp]
+    L.twv_wavenet_score_route.argtypes = [vp]; L.twv_wavenet_score_route.restype = C.c_char_p
+    L.twv_wavenet_score_windows.argtypes = [vp, fp, fp, fp, ip, ip, vp, fp, vp]
+    L.twv_wavenet_score_reduce.argtypes = [fp, ip, ip, C.c_int, C.c_int, dp, vp]
     L.twv_crc32c.argtypes = [vp, C.c_size_t, C.c_uint32]; L.twv_crc32c.restype = C.c_uint32
     _lib = L
     return L
@@ -286,7 +293,9 @@ EXPORTS = ["twv_last_error", "twv_version", "twv_wavenet_create", "twv_wavenet_d
            "twv_spectrogram_destroy", "twv_spectrogram_frames", "twv_spectrogram_workspace_bytes", "twv_spectrogram_analyze", "twv_crc32c",
            "twv_resample_create", "twv_resample_destroy", "twv_resample_phases", "twv_resample_taps", "twv_resample_out_samples",
            "twv_resample_workspace_bytes", "twv_resample_filter_host", "twv_resample_kernel_name", "twv_resample_rounds", "twv_resample",
-           "twv_griffin_lim_create_ragged", "twv_griffin_lim_total_frames", "twv_griffin_lim_total_samples", "twv_griffin_lim_offsets"]
+           "twv_griffin_lim_create_ragged", "twv_griffin_lim_total_frames", "twv_griffin_lim_total_samples", "twv_griffin_lim_offsets",
+           "twv_wavenet_score_create", "twv_wavenet_score_destroy", "twv_wavenet_score_workspace_bytes", "twv_wavenet_score_output_width",
+           "twv_wavenet_score_route", "twv_wavenet_score_windows", "twv_wavenet_score_reduce"]
 
 
 class TacoDims(C.Structure):

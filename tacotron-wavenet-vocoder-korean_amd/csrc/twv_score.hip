@@ -1,0 +1,592 @@
+// twv_score.hip -- MI355X (gfx950) WaveNet scoring: per-sample negative log-likelihood of given audio + its C-ABI (include/twv_amd.h).
+//
+// Scoring is the reference's add_loss graph with reduce=False (citations into hccho2/Tacotron-Wavenet-Vocoder-Korean):
+//   wavenet/model.py:247-312  add_loss: drop the last sample, create_upsample, the 'valid' convolution network (model.py:112-167,
+//                             train_mode=True, local condition sliced from the FRONT of every layer, model.py:79-80), targets audio[rf:]
+//   wavenet/mixture.py:27-81  discretized_mix_logistic_loss(num_class=2**16, reduce=False);  model.py:257-296 the one-hot model's
+//                             softmax cross-entropy
+// -- NOT the incremental (generation) graph.  A call scores one batch of WINDOWS: slot b holds len_b <= window samples (a hop
+// multiple > rf, or 0 = idle) and gets nll[b][p], p < len_b - rf, the loss terms of the training graph on that crop.  Whole utterances
+// are cut into hop-aligned windows with a receptive-field halo by the host (score.py); DESIGN.md 3s' has the argument why that is exact.
+//
+// Layout: a slot's rows start at its first sample (row t of layer l exists for off[l] <= t < len_b - 1), so a shorter slot is the same
+// picture with fewer rows: the skip slice starts at row rf - 1 whatever the length.  The residual stack is ONE forward-only kernel per
+// layer (sc_layer_fwd_kernel: the MFMA scheme of the training step's tr_layer_fwd_kernel, no TH / SG, X ping-pongs between two
+// buffers, rows outside a slot load nothing and store nothing); its skip inputs go to the stacked ZC columns that the head consumes.
+// Front (weight views, unfold / one-hot gather, gc gather, upsampler stages or ctab / Q) and head (stacked skip GEMM, conv1d_1,
+// conv1d_2) are the training step's own forward kernels, launched from here unchanged (declared below, defined in twv_train.hip).
+// The loss kernels write per-row terms only: no gradient, no mean.
+#include <hip/hip_runtime.h>
+#include <rocblas/rocblas.h>
+#include <stdint.h>
+#include <string>
+#include "../../include/twv_amd.h"
+#include "twv_dev.hpp"
+
+#define HIPCHK(expr)                                                                                              \
+    do {                                                                                                          \
+        hipError_t e_ = (expr);                                                                                   \
+        if (e_ != hipSuccess) return twv_fail(TWV_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));     \
+    } while (0)
+#define BLASCHK(expr)                                                                                             \
+    do {                                                                                                          \
+        rocblas_status s_ = (expr);                                                                               \
+        if (s_ != rocblas_status_success) return twv_fail(TWV_E_HIP, std::string(#expr) + ": rocblas status " + std::to_string((int)s_)); \
+    } while (0)
+
+// ---- the training step's forward kernels (twv_train.hip; that file is left as it is: its measured traffic is keyed to its text) ----
+__global__ void tr_up_fwd_kernel(const float* K, const float* in, float* out, long long total, int f, int Lc);
+__global__ void tr_ctab_kernel(const float* K0, const float* K1, const float* K2, int f0, int f1, int f2, float* ctab);
+__global__ void tr_mel_shift_kernel(const float* mel, float* ms, long long frames, int Lc);
+__global__ void tr_unfold_kernel(const float* audio, float* xunf, int B, int T, int Tn, int ifw);
+__global__ void tr_onehot_causal_fwd_kernel(const float* Wc, const int32_t* q, float* x0, int B, int T, int Tn, int Q);
+__global__ void tr_gather_emb_kernel(const float* table, const int32_t* ids, float* out, int B, int G);
+__global__ void tr_views_kernel(float* canon, float* views, float* wsall, int NL, long long c_layer0, long long lstride, long long o_wf, long long o_wg,
+                                long long o_lcf, long long o_lcg, long long o_gcf, long long o_gcg, long long o_ws, int L, int G, int S, int dir);
+__global__ void tr_bias_sum_kernel(const float* biases, int nb, long long strideb, float* out, int C);
+__global__ void tr_bias_relu_kernel(float* x, const float* biases, int nb, long long strideb, const float* bias, int C, long long n);
+__global__ void tr_bias_relu4_kernel(float4* x, const float4* bias, int C4, long long n4);
+__global__ void tr_bias_add_kernel(float* x, const float* bias, int C, long long n);
+template <bool XRELU>
+__global__ void tr_skinny_nn_kernel(const float* X, int ldx, const float* W, int ldw, const float* bias, long long rows, int K, int N,
+                                    float* Y, int ldy, const float* xb);
+
+struct twv_wavenet_scorer {
+    twv_wavenet_dims d;
+    int slots, T, Tn, rf, ow, NL, S, O, L, G, ifw, hop, F;   // T = window samples, Tn = T - 1 rows, ow = T - rf, F = T / hop frames
+    int off[TWV_MAX_LAYERS + 1];                             // receptive offset of layer l's INPUT (off[0] = ifw - 1), off[NL] = rf - 1
+    long long c_causal, c_gcemb, c_layer0, c_lstride, c_w1, c_b1, c_w2, c_b2, c_up[4], nparams;
+    long long o_wf, o_bf, o_wg, o_bg, o_gcf, o_gcg, o_lcf, o_lcg, o_wd, o_bd, o_ws, o_bs;      // inside a layer block
+    rocblas_handle blas;
+    long long carve_floats;
+    std::string route;
+};
+
+// ---------------------------------------------------------------------------------------------------------------
+//  kernels
+// ---------------------------------------------------------------------------------------------------------------
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4t __attribute__((ext_vector_type(4)));
+typedef float f32x2t __attribute__((ext_vector_type(2)));
+#define GRID_STRIDE(i, n) for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (long long)gridDim.x * blockDim.x)
+static inline int sc_tg(long long n) { long long g = (n + 255) / 256; return (int)(g < 1 ? 1 : (g > 32768 ? 32768 : g)); }
+
+// the training step's activations (v_exp_f32 / v_rcp_f32, ~1e-6 relative): scoring is held to the same float32 bar
+__device__ __forceinline__ float sc_sigmoid_fast(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
+__device__ __forceinline__ float sc_tanh_fast(float x) { return 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(-2.0f * x)) - 1.0f; }
+__device__ __forceinline__ f32x4t sc_ld4(const float* p, bool ok) { f32x4t z = {0.f, 0.f, 0.f, 0.f}; return ok ? *reinterpret_cast<const f32x4t*>(p) : z; }
+
+// ===================================================================================================================
+//  Forward-only gated layer (model.py:66-101 train mode) on the f32 matrix cores, the scheme of tr_layer_fwd_kernel:
+//  one wave owns 32-row tiles (rows = consecutive t of one slot); per tile
+//      pre[32 x 64] = X[t-d] W0 + X[t] W1 + lc term          v_mfma_f32_32x32x2_f32, B operands (filter, gate) from LDS
+//      z = tanh(pre_f + bias + gc) * sigmoid(pre_g + bias + gc);   x_next = X[t] + z Wd + bd   (z: C layout -> A layout through LDS)
+//  FUSED: lc term = sum_j ctab[phase(t - o)][j] * Q_j[frame(t - o)] (frame-rate projections, hop >= 32: at most two frames per tile);
+//  else 80 more k-steps over the materialised upsampler rows U[t - o].
+//  A row is touched only if it exists: o <= t < len_b - 1 (o = the layer's output offset).  Every load of a row that does not exist is
+//  predicated off (the operand is 0) and nothing is stored for it, so the workspace needs no clearing and a shorter or idle slot
+//  cannot reach its neighbour's rows.  Writes x_next and, for rows t >= rf - 1, the layer's 32 columns of the stacked skip input ZC.
+// ===================================================================================================================
+struct ScLayerArgs {
+    const float* X; const float* U; const float* gcp;        // (slots*Tn,32) (slots*T,80) (slots,64)
+    const float* W0; const float* W1; const float* Wlc;      // views (32,64) (32,64) (80,64): columns filter | gate
+    const float* Wd;                                         // (32,32)
+    const float* bf; const float* bg; const float* bd;       // nullable
+    float* XN; float* ZC;                                    // ZC already offset to this layer's 32 columns
+    const int32_t* lens;                                     // (slots) samples per slot, 0 = idle
+    int slots, T, Tn, d, o, cut, ow, ldz, tpb, t_lo;         // cut = rf - 1; tiles walked per slot start at row t_lo = (o / 32) * 32
+    const float* Q; const float* ctab; int hop, F;           // FUSED: Q[((b*F + frame)*4 + j)*64 + column], ctab[phase*4 + j]
+};
+constexpr int kScLcSteps = 10;                               // 80 / 8
+constexpr int kScSteps = 32 + 4 * kScLcSteps;                // tap0 16 + tap1 16 + lc 40 MFMA steps per column half
+
+template <bool FUSED>
+__global__ void __launch_bounds__(512) sc_layer_fwd_kernel(ScLayerArgs a)
+{
+    __shared__ float bt[(FUSED ? 32 : kScSteps) * 128];      // [step][lane][filter, gate]
+    __shared__ __attribute__((aligned(16))) float cts[FUSED ? 4 * 512 : 4];   // ctab (hop <= 512)
+    __shared__ float bdt[16 * 64];                           // dense: [step][lane]
+    __shared__ __attribute__((aligned(16))) float zt[8][32 * 36];
+    if (FUSED) for (int e = threadIdx.x; e < a.hop * 4; e += 512) cts[e] = a.ctab[e];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int n = lane & 31, hh = lane >> 5;
+    for (int e = threadIdx.x; e < (FUSED ? 32 : kScSteps) * 64; e += 512) {
+        const int s = e >> 6, l = e & 63, nn = l & 31, h2 = l >> 5;
+        const float* W; int ij;
+        if (s < 16) { W = a.W0; ij = s; } else if (s < 32) { W = a.W1; ij = s - 16; } else { W = a.Wlc; ij = s - 32; }
+        const int k = 8 * (ij >> 2) + 4 * h2 + (ij & 3);
+        bt[e * 2] = W[k * 64 + nn]; bt[e * 2 + 1] = W[k * 64 + 32 + nn];
+    }
+    for (int e = threadIdx.x; e < 16 * 64; e += 512) {
+        const int s = e >> 6, l = e & 63;
+        bdt[e] = a.Wd[(8 * (s >> 2) + 4 * (l >> 5) + (s & 3)) * 32 + (l & 31)];
+    }
+    __syncthreads();
+    const float vbf = a.bf ? a.bf[n] : 0.0f, vbg = a.bg ? a.bg[n] : 0.0f, vbd = a.bd ? a.bd[n] : 0.0f;
+    const f32x16 zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    const int ntiles = a.slots * a.tpb, nwaves = gridDim.x * 8;
+    for (int tile = blockIdx.x * 8 + wave; tile < ntiles; tile += nwaves) {
+        const int b = tile / a.tpb, t0 = (tile - b * a.tpb) * 32 + a.t_lo;
+        const int Tb = a.lens[b] - 1;                        // the slot's rows: its last sample is a target only (idle slot: -1)
+        if (t0 >= Tb) continue;                              // wave-uniform: the whole tile lies behind the slot's end (zt is wave-private)
+        // ---- A operands: lane (row, hh) carries k = 8i + 4hh .. +3 of its row
+        f32x4t x0[4], x1[4], u[FUSED ? 1 : kScLcSteps];
+        {
+            const int t = t0 + n;
+            const bool ok = t < Tb && t >= a.o;
+            const float* xr = a.X + ((long long)b * a.Tn + t) * 32 + 4 * hh;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                x0[i] = sc_ld4(xr - (long long)a.d * 32 + 8 * i, ok);      // t - d >= off[l]: a row of the layer's input
+                x1[i] = sc_ld4(xr + 8 * i, ok);
+            }
+            if (!FUSED) {
+                const float* ur = a.U + ((long long)b * a.T + (t - a.o)) * 80 + 4 * hh;
+#pragma unroll
+                for (int i = 0; i < kScLcSteps; ++i) u[i] = sc_ld4(ur + 8 * i, ok);
+            }
+        }
+        // residual operand and gc projection in the output (C) layout: lane = channel n, register r = row (r&3) + 8(r>>2) + 4hh
+        const float gcf = a.gcp ? a.gcp[b * 64 + n] : 0.0f, gcg = a.gcp ? a.gcp[b * 64 + 32 + n] : 0.0f;
+        float xres[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int t = t0 + (r & 3) + 8 * (r >> 2) + 4 * hh;
+            xres[r] = (t < Tb && t >= a.o) ? a.X[((long long)b * a.Tn + t) * 32 + n] : 0.0f;
+        }
+        f32x16 cf = zero, cg = zero;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const f32x2t w = *reinterpret_cast<const f32x2t*>(&bt[((4 * i + j) * 64 + lane) * 2]);
+                cf = __builtin_amdgcn_mfma_f32_32x32x2f32(x0[i][j], w[0], cf, 0, 0, 0);
+                cg = __builtin_amdgcn_mfma_f32_32x32x2f32(x0[i][j], w[1], cg, 0, 0, 0);
+            }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const f32x2t w = *reinterpret_cast<const f32x2t*>(&bt[((16 + 4 * i + j) * 64 + lane) * 2]);
+                cf = __builtin_amdgcn_mfma_f32_32x32x2f32(x1[i][j], w[0], cf, 0, 0, 0);
+                cg = __builtin_amdgcn_mfma_f32_32x32x2f32(x1[i][j], w[1], cg, 0, 0, 0);
+            }
+        if (!FUSED) {
+#pragma unroll
+            for (int i = 0; i < kScLcSteps; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const f32x2t w = *reinterpret_cast<const f32x2t*>(&bt[((32 + 4 * i + j) * 64 + lane) * 2]);
+                    cf = __builtin_amdgcn_mfma_f32_32x32x2f32(u[i][j], w[0], cf, 0, 0, 0);
+                    cg = __builtin_amdgcn_mfma_f32_32x32x2f32(u[i][j], w[1], cg, 0, 0, 0);
+                }
+        } else {
+            // rows of the tile: U row u = t - o; at most two frames per 32-row tile (hop >= 32).  fA < F: t0 < Tb <= T - 1.
+            int u0 = t0 - a.o; u0 = u0 < 0 ? 0 : u0;
+            const int fA = u0 / a.hop, fB = fA + 1 < a.F ? fA + 1 : fA;
+            const int edge = (fA + 1) * a.hop;                               // first U row of frame fA + 1
+            const float* qa = a.Q + (((long long)b * a.F + fA) * 4) * 64 + n;
+            const float* qb = a.Q + (((long long)b * a.F + fB) * 4) * 64 + n;
+            float qfa[4], qga[4], qfb[4], qgb[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { qfa[j] = qa[j * 64]; qga[j] = qa[j * 64 + 32]; qfb[j] = qb[j * 64]; qgb[j] = qb[j * 64 + 32]; }
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                int uu = t0 - a.o + (r & 3) + 8 * (r >> 2) + 4 * hh;
+                uu = uu < 0 ? 0 : uu;                                         // rows below the layer's offset are discarded by the epilogue
+                const bool hi = uu >= edge;
+                int ph = uu - (hi ? edge : edge - a.hop);
+                ph = ph < a.hop ? ph : a.hop - 1;                             // (only rows past the window's end, discarded as well)
+                const f32x4t c = *reinterpret_cast<const f32x4t*>(&cts[ph * 4]);
+                const float f0 = hi ? qfb[0] : qfa[0], f1 = hi ? qfb[1] : qfa[1], f2 = hi ? qfb[2] : qfa[2], f3 = hi ? qfb[3] : qfa[3];
+                const float g0 = hi ? qgb[0] : qga[0], g1 = hi ? qgb[1] : qga[1], g2 = hi ? qgb[2] : qga[2], g3 = hi ? qgb[3] : qga[3];
+                cf[r] += ((c[0] * f0 + c[1] * f1) + c[2] * f2) + c[3] * f3;
+                cg[r] += ((c[0] * g0 + c[1] * g1) + c[2] * g2) + c[3] * g3;
+            }
+        }
+        // ---- gated unit; rows that do not exist give z = 0 (a select, not a product: whatever their accumulators hold)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int rl = (r & 3) + 8 * (r >> 2) + 4 * hh, t = t0 + rl;
+            const bool valid = t < Tb && t >= a.o;
+            const float th = sc_tanh_fast((cf[r] + vbf) + gcf), sg = sc_sigmoid_fast((cg[r] + vbg) + gcg);
+            const float z = valid ? th * sg : 0.0f;
+            if (valid && t >= a.cut) a.ZC[((long long)b * a.ow + (t - a.cut)) * a.ldz + n] = z;       // model.py:94-96: the last len_b - rf rows
+            zt[wave][rl * 36 + n] = z;
+        }
+        // ---- dense 1x1 + residual: z as A operand (row layout) back from this wave's LDS patch
+        f32x16 cd = zero;
+        {
+            const float* zr = &zt[wave][n * 36 + 4 * hh];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const f32x4t q = *reinterpret_cast<const f32x4t*>(zr + 8 * i);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) cd = __builtin_amdgcn_mfma_f32_32x32x2f32(q[j], bdt[(4 * i + j) * 64 + lane], cd, 0, 0, 0);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int t = t0 + (r & 3) + 8 * (r >> 2) + 4 * hh;
+            if (t < Tb && t >= a.o) a.XN[((long long)b * a.Tn + t) * 32 + n] = (xres[r] + cd[r]) + vbd;
+        }
+    }
+}
+
+// ---- per-row loss terms --------------------------------------------------------------------------------------------
+// mixture.py:27-81 discretized_mix_logistic_loss(num_class=2**16, reduce=False), one row: the branch structure of the training step's
+// tr_mol_row (edge branches at -0.999 / +0.999, cdf_delta > 1e-5, the log-scale clamp at log(1e-14)), forward only.
+// NR > 0: the number of mixtures as a compile-time constant (the per-mixture terms stay in registers)
+__device__ __forceinline__ float sc_softplus(float x) { return x > 20.0f ? x : log1pf(expf(x)); }
+__device__ __forceinline__ float sc_sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
+template <int NR>
+__device__ __forceinline__ float sc_mol_row(const float* yr, float tgt, int nr_)
+{
+    const int nr = NR > 0 ? NR : nr_;
+    constexpr int CAP = NR > 0 ? NR : 32;
+    const float lsmin = -32.23619130191664f, h = 1.0f / 65535.0f, logc = logf(65535.0f / 2.0f);
+    float lm = -3.0e38f;
+#pragma unroll
+    for (int i = 0; i < nr; ++i) lm = fmaxf(lm, yr[i]);
+    float se = 0.0f;
+#pragma unroll
+    for (int i = 0; i < nr; ++i) se += expf(yr[i] - lm);
+    const float lse_logit = lm + logf(se);
+    float a[CAP];
+    float amax = -3.0e38f;
+#pragma unroll
+    for (int i = 0; i < nr; ++i) {
+        const float mu = yr[nr + i], s = fmaxf(yr[2 * nr + i], lsmin);
+        const float cen = tgt - mu, inv = expf(-s);
+        const float plus = inv * (cen + h), mn = inv * (cen - h), mid = inv * cen;
+        const float delta = sc_sigm(plus) - sc_sigm(mn);
+        float lp;
+        if (tgt < -0.999f) lp = plus - sc_softplus(plus);
+        else if (tgt > 0.999f) lp = -sc_softplus(mn);
+        else if (delta > 1e-5f) lp = logf(fmaxf(delta, 1e-12f));
+        else lp = mid - s - 2.0f * sc_softplus(mid) - logc;
+        a[i] = lp + (yr[i] - lse_logit);
+        amax = fmaxf(amax, a[i]);
+    }
+    float sa = 0.0f;
+#pragma unroll
+    for (int i = 0; i < nr; ++i) sa += expf(a[i] - amax);
+    return -(amax + logf(sa));
+}
+// one thread per (slot, p): nll[slot][p] for p < len - rf (target audio[slot][p + rf]), 0 for the positions the slot does not have
+template <int NR>
+__global__ __launch_bounds__(256) void sc_mol_nll_kernel(const float* y, const float* audio, const int32_t* lens, int slots, int T, int ow, int rf, int nr, float* nll)
+{
+    GRID_STRIDE(r, (long long)slots * ow) {
+        const int p = (int)(r % ow), b = (int)(r / ow);
+        float v = 0.0f;
+        if (p < lens[b] - rf) v = sc_mol_row<NR>(y + r * 3 * nr, audio[(long long)b * T + p + rf], nr);
+        nll[r] = v;
+    }
+}
+// model.py:293-296 softmax_cross_entropy_with_logits_v2(one-hot target), unreduced; one wave per row of Q logits (tr_softmax_ce_kernel's passes)
+__global__ __launch_bounds__(256) void sc_softmax_nll_kernel(const float* y, const int32_t* q, const int32_t* lens, int slots, int T, int ow, int rf, int Q, float* nll)
+{
+    const int lane = threadIdx.x & 63;
+    const long long rows = (long long)slots * ow;
+    for (long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); r < rows; r += (long long)gridDim.x * 4) {
+        const int p = (int)(r % ow), b = (int)(r / ow);
+        if (p >= lens[b] - rf) { if (lane == 0) nll[r] = 0.0f; continue; }                  // wave-uniform
+        const int tgt = q[(long long)b * T + p + rf];
+        const float* yr = y + r * Q;
+        float m = -3.0e38f;
+        for (int i = lane; i < Q; i += 64) m = fmaxf(m, yr[i]);
+        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+        float se = 0.0f;
+        for (int i = lane; i < Q; i += 64) se += expf(yr[i] - m);
+        for (int o = 32; o > 0; o >>= 1) se += __shfl_xor(se, o);
+        if (lane == 0) nll[r] = (m + logf(se)) - yr[tgt];
+    }
+}
+
+// ---- (sum, count) of the kept positions: float64, one workgroup, a fixed order (thread i takes columns from + i, from + i + 1024, ...
+// of slot 0, then of slot 1, ...; then a fixed tree) -- two runs give the same bits.  Up to 64 slots per launch; a later launch of the
+// same call adds to what the earlier ones left (the launches of a stream run in order).
+struct ScKeep { int from[64], to[64]; };
+__global__ __launch_bounds__(1024) void sc_reduce_kernel(const float* nll, ScKeep k, int nslot, int width, int first, double* out)
+{
+    double s = 0.0;
+    long long cnt = 0;
+    for (int b = 0; b < nslot; ++b) {
+        const float* row = nll + (long long)b * width;
+        for (int p = k.from[b] + (int)threadIdx.x; p < k.to[b]; p += 1024) s += (double)row[p];
+        cnt += k.to[b] - k.from[b];
+    }
+    __shared__ double sh[1024];
+    sh[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = 512; w >= 1; w >>= 1) {
+        if ((int)threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        out[0] = (first ? 0.0 : out[0]) + sh[0];
+        out[1] = (first ? 0.0 : out[1]) + (double)cnt;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+//  host
+// ---------------------------------------------------------------------------------------------------------------
+// row-major C[M,N] (ldc) = A[M,K] * B[K,N]
+static rocblas_status sc_gemm(rocblas_handle h, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C, int ldc)
+{
+    const float one = 1.0f, zero = 0.0f;
+    return rocblas_sgemm(h, rocblas_operation_none, rocblas_operation_none, N, M, K, &one, B, ldb, A, lda, &zero, C, ldc);
+}
+
+// Which kernel families twv_wavenet_score_windows runs: the ONE place the predicates are written (create, the dispatch and the label).
+enum { SC_LOSS_MOL10 = 0, SC_LOSS_MOLN = 1, SC_LOSS_SOFTMAX = 2 };
+struct ScoreRoute {
+    bool fused_lc;      // sc_layer_fwd_kernel<true> on frame-rate lc projections (tr_ctab / tr_mel_shift + one batched GEMM); else the
+                        // materialised upsampler (tr_up_fwd) and sc_layer_fwd_kernel<false>.  The training step's predicate.
+    bool skinny;        // conv1d_2 as tr_skinny_nn_kernel<true> (conv1d_1's bias + relu applied to what it loads); else rocBLAS + bias kernels
+    int loss;           // SC_LOSS_*
+};
+static ScoreRoute sc_route(const twv_wavenet_dims& d, int slots, int window)
+{
+    ScoreRoute r;
+    int hop = 1;
+    for (int i = 0; i < d.n_upsample; ++i) hop *= d.upsample_factor[i];
+    r.fused_lc = d.n_upsample == 3 && hop >= 32 && hop <= 512 && d.lc_channels == 80;
+    int rf = (d.scalar_input ? d.initial_filter_width : 2);           // model.py:31-39
+    for (int l = 0; l < d.n_layers; ++l) rf += d.dilations[l];
+    const long long RO = (long long)slots * (window - rf);
+    const int S = d.skip_channels, O = d.scalar_input ? d.out_channels : d.quantization_channels;
+    r.skinny = O <= 32 && (S & 63) == 0 && S * 32 * 4 <= 64 * 1024 && RO * S * 4 < (1LL << 31);
+    r.loss = !d.scalar_input ? SC_LOSS_SOFTMAX : (O / 3 == 10 ? SC_LOSS_MOL10 : SC_LOSS_MOLN);
+    return r;
+}
+
+// The workspace carve, each piece rounded up to 64 floats: create runs it on a null base for the SIZE, score_windows for the pointers.
+// Nothing here grows with the utterances: it is (slots, window) activations of TWO layers, the stacked skip input and the head.
+struct ScoreCarve {
+    float* ups[5]; long long upT[5];
+    float *xunf; int32_t* qin; int32_t* lens;
+    float *XA, *XB, *ZC, *SK, *C1, *Y, *emb, *GCP, *WV, *WS, *bsum, *ctab, *melsh, *Qall;
+    long long vstride, q_ls;
+};
+static long long sc_carve(const twv_wavenet_scorer* h, float* base, ScoreCarve& c)
+{
+    const twv_wavenet_dims& d = h->d;
+    const int B = h->slots, T = h->T, Tn = h->Tn, NL = h->NL, S = h->S, O = h->O, L = h->L, G = h->G, ow = h->ow;
+    const long long Rr = (long long)B * Tn, RT = (long long)B * T, RO = (long long)B * ow;
+    const bool fused = sc_route(d, B, T).fused_lc;
+    long long used = 0;
+    auto take = [&](long long n) { float* p = base ? base + used : nullptr; used += (n + 63) / 64 * 64; return p; };
+    c.upT[0] = h->F;
+    for (int i = 0; i < d.n_upsample; ++i) c.upT[i + 1] = c.upT[i] * d.upsample_factor[i];
+    c.ups[0] = nullptr;                                      // (the caller's mel frames)
+    for (int i = 1; i <= d.n_upsample; ++i) c.ups[i] = take(fused ? 0 : (long long)B * c.upT[i] * L);
+    c.xunf = take(d.scalar_input ? Rr * h->ifw : 0);
+    c.qin = reinterpret_cast<int32_t*>(take(d.scalar_input ? 0 : RT));
+    c.lens = reinterpret_cast<int32_t*>(take(B));
+    c.XA = take(Rr * 32); c.XB = take(Rr * 32);              // the layers' activations ping-pong
+    const int ZW = NL * 32;                                  // stacked skip input: ZC[(b,p)][l*32 + j]
+    c.ZC = take(RO * ZW);
+    c.SK = take(RO * S); c.C1 = take(RO * S);
+    c.Y = take(RO * O);
+    c.emb = take((long long)B * G);
+    c.GCP = take((long long)B * 64 * NL);
+    c.vstride = 64LL * (64 + L + G);
+    c.WV = take(c.vstride * NL); c.WS = take((long long)ZW * S);       // weight views (tr_views_kernel)
+    c.bsum = take(S);
+    c.ctab = take(fused ? 4LL * 512 : 0);
+    c.melsh = take(fused ? (long long)B * h->F * 4 * L : 0);
+    c.q_ls = (long long)B * h->F * 4 * 64;
+    c.Qall = take(fused ? (c.q_ls + 64) * NL : 0);
+    return used;
+}
+
+extern "C" int twv_wavenet_score_create(const twv_wavenet_dims* dims, int slots, int window_samples, twv_wavenet_scorer** out)
+{
+    if (dims && dims->gc_channels > 0 && dims->gc_cardinality < 1)
+        return twv_fail(TWV_E_UNSUPPORTED, "scoring needs global_condition_cardinality (the gc_embedding table is a variable of the graph; model.py:191-195)");
+    if (!dims || !out || slots < 1) return twv_fail(TWV_E_INVALID, "bad argument");
+    const twv_wavenet_dims& d = *dims;
+    if (d.n_layers < 1 || d.n_layers > TWV_MAX_LAYERS || d.n_upsample < 0 || d.n_upsample > 4) return twv_fail(TWV_E_INVALID, "bad dims");
+    if (d.residual_channels != 32 || d.dilation_channels != 32) return twv_fail(TWV_E_UNSUPPORTED, "scoring is built for residual_channels = dilation_channels = 32 only");
+    if (d.scalar_input && (d.out_channels < 3 || d.out_channels % 3 || d.out_channels > 96)) return twv_fail(TWV_E_UNSUPPORTED, "out_channels must be 3*nr_mix <= 96");
+    if (!d.scalar_input && (d.quantization_channels < 2 || d.quantization_channels > 512)) return twv_fail(TWV_E_UNSUPPORTED, "quantization_channels must be in [2, 512] for scoring");
+    if (d.lc_channels != 80 || !d.gc_channels) return twv_fail(TWV_E_UNSUPPORTED, "scoring expects num_mels = 80 local and global conditioning (train_vocoder.py, hparams.py:30)");
+    // the limit of the training step's fused route (twv_wavenet_train_create), kept: memory is bounded by the window batch, a longer
+    // utterance is more windows, never a larger batch
+    if (sc_route(d, slots, window_samples).fused_lc && (long long)slots * window_samples * 256 >= (1LL << 31))
+        return twv_fail(TWV_E_UNSUPPORTED, "slots x window too large on the fused lc route (slots * window_samples < 8.3 M): score with fewer slots or a shorter window");
+    twv_wavenet_scorer* h = new twv_wavenet_scorer();
+    h->d = d; h->slots = slots; h->T = window_samples; h->Tn = window_samples - 1; h->NL = d.n_layers; h->S = d.skip_channels;
+    h->O = d.scalar_input ? d.out_channels : d.quantization_channels;
+    h->L = d.lc_channels; h->G = d.gc_channels; h->ifw = d.scalar_input ? d.initial_filter_width : 2;   // model.py:36-39
+    h->hop = 1;
+    for (int i = 0; i < d.n_upsample; ++i) h->hop *= d.upsample_factor[i];
+    if (window_samples < 1 || window_samples % h->hop) { delete h; return twv_fail(TWV_E_INVALID, "window_samples must be a multiple of the hop size (datafeeder_wavenet.py:38)"); }
+    h->F = window_samples / h->hop;
+    h->off[0] = h->ifw - 1;
+    for (int l = 0; l < h->NL; ++l) h->off[l + 1] = h->off[l] + d.dilations[l];
+    h->rf = h->off[h->NL] + 1;
+    h->ow = window_samples - h->rf;                                   // model.py:135 output_width
+    if (h->ow < 1) { delete h; return twv_fail(TWV_E_INVALID, "window_samples must exceed the receptive field"); }
+    // canonical blob offsets: the order of weights.tensor_specs, as in twv_wavenet_train_create
+    long long c = 0;
+    const int R = 32, D = 32, ub = d.use_biases ? 1 : 0;
+    h->c_causal = c; c += d.scalar_input ? (long long)h->ifw * R : 2LL * d.quantization_channels * R;
+    h->c_gcemb = c; c += (long long)d.gc_cardinality * h->G;
+    h->c_layer0 = c;
+    long long q = 0;
+    h->o_wf = q; q += 2 * R * D; h->o_bf = q; q += ub * D;
+    h->o_wg = q; q += 2 * R * D; h->o_bg = q; q += ub * D;
+    h->o_gcf = q; q += (long long)h->G * D; h->o_gcg = q; q += (long long)h->G * D;
+    h->o_lcf = q; q += (long long)h->L * D; h->o_lcg = q; q += (long long)h->L * D;
+    h->o_wd = q; q += D * R; h->o_bd = q; q += ub * R;
+    h->o_ws = q; q += (long long)D * h->S; h->o_bs = q; q += (long long)ub * h->S;
+    h->c_lstride = q; c += q * h->NL;
+    h->c_w1 = c; c += (long long)h->S * h->S; h->c_b1 = c; c += (long long)ub * h->S;
+    h->c_w2 = c; c += (long long)h->S * h->O; h->c_b2 = c; c += (long long)ub * h->O;
+    for (int i = 0; i < d.n_upsample; ++i) { h->c_up[i] = c; c += (long long)d.upsample_factor[i] * 2; }
+    h->nparams = c;
+    h->blas = nullptr;
+    ScoreCarve sizes;
+    h->carve_floats = sc_carve(h, nullptr, sizes);
+    const ScoreRoute r = sc_route(d, slots, window_samples);
+    h->route = std::string("lc=") + (r.fused_lc ? "fused" : "staged") + " head=" + (r.skinny ? "skinny" : "gemm") +
+               " loss=" + (r.loss == SC_LOSS_MOL10 ? "mol<10>" : r.loss == SC_LOSS_MOLN ? "mol<0>" : "softmax") +
+               " carve_floats=" + std::to_string(h->carve_floats);
+    *out = h;
+    return TWV_OK;
+}
+extern "C" void twv_wavenet_score_destroy(twv_wavenet_scorer* h)
+{
+    if (h && h->blas) rocblas_destroy_handle(h->blas);
+    delete h;
+}
+extern "C" size_t twv_wavenet_score_workspace_bytes(const twv_wavenet_scorer* h) { return h ? (size_t)h->carve_floats * 4 : 0; }
+extern "C" int twv_wavenet_score_output_width(const twv_wavenet_scorer* h) { return h ? h->ow : 0; }
+extern "C" const char* twv_wavenet_score_route(const twv_wavenet_scorer* h) { return h ? h->route.c_str() : ""; }
+
+extern "C" int twv_wavenet_score_windows(twv_wavenet_scorer* h, const float* params, const float* audio, const float* lc, const int32_t* gc_ids,
+                                         const int32_t* lengths_host, void* workspace, float* nll, void* stream)
+{
+    if (!h || !params || !audio || !lc || !gc_ids || !lengths_host || !workspace || !nll) return twv_fail(TWV_E_INVALID, "null argument");
+    const twv_wavenet_dims& d = h->d;
+    const int B = h->slots, T = h->T, Tn = h->Tn, NL = h->NL, S = h->S, O = h->O, L = h->L, G = h->G, ow = h->ow, rf = h->rf, F = h->F;
+    for (int b = 0; b < B; ++b) {
+        const int n = lengths_host[b];
+        if (n != 0 && (n < 0 || n > T || n % h->hop || n <= rf))
+            return twv_fail(TWV_E_INVALID, "slot " + std::to_string(b) + ": length " + std::to_string(n) + " must be 0 (idle) or a multiple of the hop size " +
+                                           std::to_string(h->hop) + " in (" + std::to_string(rf) + ", " + std::to_string(T) + "]");
+    }
+    ScoreCarve cv;
+    if (sc_carve(h, (float*)workspace, cv) != h->carve_floats)
+        return twv_fail(TWV_E_INVALID, "internal: the workspace carve does not match the size twv_wavenet_score_create computed");
+    hipStream_t st = (hipStream_t)stream;
+    if (!h->blas) BLASCHK(rocblas_create_handle(&h->blas));
+    BLASCHK(rocblas_set_stream(h->blas, st));
+    BLASCHK(rocblas_set_pointer_mode(h->blas, rocblas_pointer_mode_host));
+    rocblas_handle bl = h->blas;
+    const ScoreRoute route = sc_route(d, B, T);
+    const long long Rr = (long long)B * Tn, RT = (long long)B * T, RO = (long long)B * ow;
+    const bool ub = d.use_biases != 0;
+    const float* P = params;
+    const int ZW = NL * 32;
+    const long long vstride = cv.vstride, q_ls = cv.q_ls;
+    if (route.skinny) HIPCHK(hipFuncSetAttribute((const void*)tr_skinny_nn_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
+    HIPCHK(hipMemcpyAsync(cv.lens, lengths_host, (size_t)B * 4, hipMemcpyHostToDevice, st));   // (pageable source: staged before the call returns)
+#define K1(kern, n, ...) hipLaunchKernelGGL(kern, dim3(sc_tg(n)), dim3(256), 0, st, __VA_ARGS__)
+#define LP(l) (P + h->c_layer0 + (long long)(l) * h->c_lstride)
+    // ================= front: the training step's forward kernels on all slots x window rows =================
+    K1(tr_views_kernel, (vstride + 32LL * S) * NL, const_cast<float*>(P), cv.WV, cv.WS, NL, h->c_layer0, h->c_lstride, h->o_wf, h->o_wg, h->o_lcf, h->o_lcg,
+       h->o_gcf, h->o_gcg, h->o_ws, L, G, S, 0);
+    float* ups[5] = {const_cast<float*>(lc), cv.ups[1], cv.ups[2], cv.ups[3], cv.ups[4]};
+    for (int i = 0; i < d.n_upsample && !route.fused_lc; ++i)         // model.py:276 create_upsample
+        K1(tr_up_fwd_kernel, (long long)B * cv.upT[i + 1] * L, P + h->c_up[i], ups[i], ups[i + 1], (long long)B * cv.upT[i + 1] * L, d.upsample_factor[i], L);
+    const float* U = ups[d.n_upsample];
+    K1(tr_gather_emb_kernel, (long long)B * G, P + h->c_gcemb, gc_ids, cv.emb, B, G);            // model.py:197-198
+    float* X[2] = {cv.XA, cv.XB};
+    if (d.scalar_input) {
+        K1(tr_unfold_kernel, Rr * h->ifw, audio, cv.xunf, B, T, Tn, h->ifw);
+        BLASCHK(sc_gemm(bl, (int)Rr, 32, h->ifw, cv.xunf, h->ifw, P + h->c_causal, 32, X[0], 32));                       // model.py:131
+    } else {
+        const int rc = twv_mu_law_encode(audio, RT, d.quantization_channels, cv.qin, st);                                 // model.py:257
+        if (rc) return rc;
+        K1(tr_onehot_causal_fwd_kernel, Rr * 32, P + h->c_causal, cv.qin, X[0], B, T, Tn, d.quantization_channels);
+    }
+    const float one = 1.0f, zero = 0.0f;
+    if (route.fused_lc) {
+        K1(tr_ctab_kernel, h->hop, P + h->c_up[0], P + h->c_up[1], P + h->c_up[2], d.upsample_factor[0], d.upsample_factor[1], d.upsample_factor[2], cv.ctab);
+        K1(tr_mel_shift_kernel, (long long)B * F * 4 * L, lc, cv.melsh, (long long)B * F, L);
+        BLASCHK(rocblas_sgemm_strided_batched(bl, rocblas_operation_none, rocblas_operation_none, 64, B * F * 4, L, &one, cv.WV + 64 * 64, 64, vstride,
+                                              cv.melsh, L, 0, &zero, cv.Qall, 64, q_ls + 64, NL));
+    }
+    // model.py:71-73 gc projections of every layer: GCP[l] (B x 64) = emb (B x G) . Wgc_l (G x 64)
+    BLASCHK(rocblas_sgemm_strided_batched(bl, rocblas_operation_none, rocblas_operation_none, 64, B, G, &one, cv.WV + (64 + L) * 64, 64, vstride,
+                                          cv.emb, G, 0, &zero, cv.GCP, 64, (long long)B * 64, NL));
+    // ================= the residual stack: one forward-only kernel per layer =================
+    for (int l = 0; l < NL; ++l) {
+        const float* Lp = LP(l);
+        const float* Wv = cv.WV + l * vstride;
+        ScLayerArgs fa;
+        fa.X = X[l & 1]; fa.XN = X[(l + 1) & 1]; fa.U = U; fa.gcp = cv.GCP + (long long)l * B * 64;
+        fa.W0 = Wv; fa.W1 = Wv + 32 * 64; fa.Wlc = Wv + 64 * 64; fa.Wd = Lp + h->o_wd;
+        fa.bf = ub ? Lp + h->o_bf : nullptr; fa.bg = ub ? Lp + h->o_bg : nullptr; fa.bd = ub ? Lp + h->o_bd : nullptr;
+        fa.ZC = cv.ZC + l * 32; fa.lens = cv.lens;
+        fa.slots = B; fa.T = T; fa.Tn = Tn; fa.d = d.dilations[l]; fa.o = h->off[l + 1]; fa.cut = rf - 1; fa.ow = ow; fa.ldz = ZW;
+        fa.t_lo = (fa.o / 32) * 32;                          // whole tiles in front of the layer's offset hold no row: not walked
+        fa.tpb = (Tn + 31) / 32 - fa.t_lo / 32;
+        fa.Q = cv.Qall + l * (q_ls + 64); fa.ctab = cv.ctab; fa.hop = h->hop; fa.F = F;
+        const int ntiles = B * fa.tpb;
+        int nwg = (ntiles + 7) / 8; nwg = nwg > 256 ? 256 : nwg;     // one workgroup (8 waves, 2 per SIMD) per CU, each wave walks its tiles
+        if (route.fused_lc) hipLaunchKernelGGL(sc_layer_fwd_kernel<true>, dim3(nwg), dim3(512), 0, st, fa);
+        else hipLaunchKernelGGL(sc_layer_fwd_kernel<false>, dim3(nwg), dim3(512), 0, st, fa);
+    }
+    // ================= head: model.py:150-165 (sum of the skip 1x1 convs == ONE GEMM against the stacked skip kernels) =================
+    // over all slots x ow rows: the rows a slot does not have hold whatever the workspace held; every row is a function of itself only,
+    // and the loss kernels below write those positions as 0
+    BLASCHK(sc_gemm(bl, (int)RO, S, ZW, cv.ZC, ZW, cv.WS, S, cv.SK, S));
+    if ((S & 3) == 0) {
+        if (ub) K1(tr_bias_sum_kernel, S, LP(0) + h->o_bs, NL, h->c_lstride, cv.bsum, S);
+        K1(tr_bias_relu4_kernel, RO * S / 4, (float4*)cv.SK, ub ? (const float4*)cv.bsum : nullptr, S / 4, RO * S / 4);
+    } else {
+        K1(tr_bias_relu_kernel, RO * S, cv.SK, ub ? LP(0) + h->o_bs : nullptr, ub ? NL : 0, h->c_lstride, (const float*)nullptr, S, RO * S);
+    }
+    BLASCHK(sc_gemm(bl, (int)RO, S, S, cv.SK, S, P + h->c_w1, S, cv.C1, S));
+    if (route.skinny) {
+        hipLaunchKernelGGL(tr_skinny_nn_kernel<true>, dim3(1024), dim3(256), (size_t)S * 33 * 4, st, cv.C1, S, P + h->c_w2, O, ub ? P + h->c_b2 : nullptr, RO, S, O,
+                           cv.Y, O, ub ? P + h->c_b1 : nullptr);
+    } else {
+        if ((S & 3) == 0 && (h->c_b1 & 3) == 0) K1(tr_bias_relu4_kernel, RO * S / 4, (float4*)cv.C1, ub ? (const float4*)(P + h->c_b1) : nullptr, S / 4, RO * S / 4);
+        else K1(tr_bias_relu_kernel, RO * S, cv.C1, (const float*)nullptr, 0, 0LL, ub ? P + h->c_b1 : nullptr, S, RO * S);
+        BLASCHK(sc_gemm(bl, (int)RO, O, S, cv.C1, S, P + h->c_w2, O, cv.Y, O));
+        if (ub) K1(tr_bias_add_kernel, RO * O, cv.Y, P + h->c_b2, O, RO * O);
+    }
+    // ================= per-row loss terms =================
+    if (route.loss == SC_LOSS_MOL10) K1(sc_mol_nll_kernel<10>, RO, cv.Y, audio, cv.lens, B, T, ow, rf, O / 3, nll);
+    else if (route.loss == SC_LOSS_MOLN) K1(sc_mol_nll_kernel<0>, RO, cv.Y, audio, cv.lens, B, T, ow, rf, O / 3, nll);
+    else hipLaunchKernelGGL(sc_softmax_nll_kernel, dim3(sc_tg(RO * 64)), dim3(256), 0, st, cv.Y, cv.qin, cv.lens, B, T, ow, rf, O, nll);
+#undef K1
+#undef LP
+    HIPCHK(hipGetLastError());
+    return TWV_OK;
+}
+
+extern "C" int twv_wavenet_score_reduce(const float* nll, const int32_t* keep_from_host, const int32_t* keep_to_host, int slots, int width,
+                                        double* out_double2, void* stream)
+{
+    if (!nll || !keep_from_host || !keep_to_host || !out_double2 || slots < 1 || width < 1) return twv_fail(TWV_E_INVALID, "bad argument");
+    for (int b = 0; b < slots; ++b)
+        if (keep_from_host[b] < 0 || keep_from_host[b] > keep_to_host[b] || keep_to_host[b] > width)
+            return twv_fail(TWV_E_INVALID, "slot " + std::to_string(b) + ": kept columns must satisfy 0 <= from <= to <= width");
+    hipStream_t st = (hipStream_t)stream;
+    for (int b0 = 0; b0 < slots; b0 += 64) {
+        ScKeep k;
+        const int n = slots - b0 < 64 ? slots - b0 : 64;
+        for (int i = 0; i < 64; ++i) { k.from[i] = i < n ? keep_from_host[b0 + i] : 0; k.to[i] = i < n ? keep_to_host[b0 + i] : 0; }
+        hipLaunchKernelGGL(sc_reduce_kernel, dim3(1), dim3(1024), 0, st, nll + (long long)b0 * width, k, n, width, b0 == 0 ? 1 : 0, out_double2);
+    }
+    HIPCHK(hipGetLastError());
+    return TWV_OK;
+}
