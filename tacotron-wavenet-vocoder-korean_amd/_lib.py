@@ -69,7 +69,7 @@ def tacotron_hash():
     return _hash_files([os.path.join(CSRC, f) for f in TACOTRON_SOURCES], code_only=True)
 
 
-TRAIN_SOURCES = ("twv_train.hip", "twv_dev.hpp", "twv_math.hpp", "twv_layout.hpp")      # twv_dev.hpp includes the other two headers
+TRAIN_SOURCES = ("twv_train.hip", "twv_wavenet_graph.hpp", "twv_dev.hpp", "twv_math.hpp", "twv_layout.hpp")      # twv_dev.hpp includes the last two headers
 
 
 def train_hash():

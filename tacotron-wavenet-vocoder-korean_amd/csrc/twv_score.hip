@@ -14,7 +14,8 @@
 // layer (sc_layer_fwd_kernel: the MFMA scheme of the training step's tr_layer_fwd_kernel, no TH / SG, X ping-pongs between two
 // buffers, rows outside a slot load nothing and store nothing); its skip inputs go to the stacked ZC columns that the head consumes.
 // Front (weight views, unfold / one-hot gather, gc gather, upsampler stages or ctab / Q) and head (stacked skip GEMM, conv1d_1,
-// conv1d_2) are the training step's own forward kernels, launched from here unchanged (declared below, defined in twv_train.hip).
+// conv1d_2) are the training step's own: wavenet_forward_front / wavenet_forward_head (twv_wavenet_graph.hpp, defined in twv_train.hip
+// beside their kernels).  The same header holds the model description both handles embed: geometry, canonical offsets, refusals, route.
 // The loss kernels write per-row terms only: no gradient, no mean.
 #include <hip/hip_runtime.h>
 #include <rocblas/rocblas.h>
@@ -22,41 +23,10 @@
 #include <string>
 #include "../../include/twv_amd.h"
 #include "twv_dev.hpp"
-
-#define HIPCHK(expr)                                                                                              \
-    do {                                                                                                          \
-        hipError_t e_ = (expr);                                                                                   \
-        if (e_ != hipSuccess) return twv_fail(TWV_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));     \
-    } while (0)
-#define BLASCHK(expr)                                                                                             \
-    do {                                                                                                          \
-        rocblas_status s_ = (expr);                                                                               \
-        if (s_ != rocblas_status_success) return twv_fail(TWV_E_HIP, std::string(#expr) + ": rocblas status " + std::to_string((int)s_)); \
-    } while (0)
-
-// ---- the training step's forward kernels (twv_train.hip; that file is left as it is: its measured traffic is keyed to its text) ----
-__global__ void tr_up_fwd_kernel(const float* K, const float* in, float* out, long long total, int f, int Lc);
-__global__ void tr_ctab_kernel(const float* K0, const float* K1, const float* K2, int f0, int f1, int f2, float* ctab);
-__global__ void tr_mel_shift_kernel(const float* mel, float* ms, long long frames, int Lc);
-__global__ void tr_unfold_kernel(const float* audio, float* xunf, int B, int T, int Tn, int ifw);
-__global__ void tr_onehot_causal_fwd_kernel(const float* Wc, const int32_t* q, float* x0, int B, int T, int Tn, int Q);
-__global__ void tr_gather_emb_kernel(const float* table, const int32_t* ids, float* out, int B, int G);
-__global__ void tr_views_kernel(float* canon, float* views, float* wsall, int NL, long long c_layer0, long long lstride, long long o_wf, long long o_wg,
-                                long long o_lcf, long long o_lcg, long long o_gcf, long long o_gcg, long long o_ws, int L, int G, int S, int dir);
-__global__ void tr_bias_sum_kernel(const float* biases, int nb, long long strideb, float* out, int C);
-__global__ void tr_bias_relu_kernel(float* x, const float* biases, int nb, long long strideb, const float* bias, int C, long long n);
-__global__ void tr_bias_relu4_kernel(float4* x, const float4* bias, int C4, long long n4);
-__global__ void tr_bias_add_kernel(float* x, const float* bias, int C, long long n);
-template <bool XRELU>
-__global__ void tr_skinny_nn_kernel(const float* X, int ldx, const float* W, int ldw, const float* bias, long long rows, int K, int N,
-                                    float* Y, int ldy, const float* xb);
+#include "twv_wavenet_graph.hpp"
 
 struct twv_wavenet_scorer {
-    twv_wavenet_dims d;
-    int slots, T, Tn, rf, ow, NL, S, O, L, G, ifw, hop, F;   // T = window samples, Tn = T - 1 rows, ow = T - rf, F = T / hop frames
-    int off[TWV_MAX_LAYERS + 1];                             // receptive offset of layer l's INPUT (off[0] = ifw - 1), off[NL] = rf - 1
-    long long c_causal, c_gcemb, c_layer0, c_lstride, c_w1, c_b1, c_w2, c_b2, c_up[4], nparams;
-    long long o_wf, o_bf, o_wg, o_bg, o_gcf, o_gcg, o_lcf, o_lcg, o_wd, o_bd, o_ws, o_bs;      // inside a layer block
+    WavenetGraph g;                                          // rows = slots, T = window samples
     rocblas_handle blas;
     long long carve_floats;
     std::string route;
@@ -69,7 +39,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4t __attribute__((ext_vector_type(4)));
 typedef float f32x2t __attribute__((ext_vector_type(2)));
 #define GRID_STRIDE(i, n) for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (long long)gridDim.x * blockDim.x)
-static inline int sc_tg(long long n) { long long g = (n + 255) / 256; return (int)(g < 1 ? 1 : (g > 32768 ? 32768 : g)); }
 
 // the training step's activations (v_exp_f32 / v_rcp_f32, ~1e-6 relative): scoring is held to the same float32 bar
 __device__ __forceinline__ float sc_sigmoid_fast(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
@@ -333,36 +302,6 @@ __global__ __launch_bounds__(1024) void sc_reduce_kernel(const float* nll, ScKee
 // ---------------------------------------------------------------------------------------------------------------
 //  host
 // ---------------------------------------------------------------------------------------------------------------
-// row-major C[M,N] (ldc) = A[M,K] * B[K,N]
-static rocblas_status sc_gemm(rocblas_handle h, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C, int ldc)
-{
-    const float one = 1.0f, zero = 0.0f;
-    return rocblas_sgemm(h, rocblas_operation_none, rocblas_operation_none, N, M, K, &one, B, ldb, A, lda, &zero, C, ldc);
-}
-
-// Which kernel families twv_wavenet_score_windows runs: the ONE place the predicates are written (create, the dispatch and the label).
-enum { SC_LOSS_MOL10 = 0, SC_LOSS_MOLN = 1, SC_LOSS_SOFTMAX = 2 };
-struct ScoreRoute {
-    bool fused_lc;      // sc_layer_fwd_kernel<true> on frame-rate lc projections (tr_ctab / tr_mel_shift + one batched GEMM); else the
-                        // materialised upsampler (tr_up_fwd) and sc_layer_fwd_kernel<false>.  The training step's predicate.
-    bool skinny;        // conv1d_2 as tr_skinny_nn_kernel<true> (conv1d_1's bias + relu applied to what it loads); else rocBLAS + bias kernels
-    int loss;           // SC_LOSS_*
-};
-static ScoreRoute sc_route(const twv_wavenet_dims& d, int slots, int window)
-{
-    ScoreRoute r;
-    int hop = 1;
-    for (int i = 0; i < d.n_upsample; ++i) hop *= d.upsample_factor[i];
-    r.fused_lc = d.n_upsample == 3 && hop >= 32 && hop <= 512 && d.lc_channels == 80;
-    int rf = (d.scalar_input ? d.initial_filter_width : 2);           // model.py:31-39
-    for (int l = 0; l < d.n_layers; ++l) rf += d.dilations[l];
-    const long long RO = (long long)slots * (window - rf);
-    const int S = d.skip_channels, O = d.scalar_input ? d.out_channels : d.quantization_channels;
-    r.skinny = O <= 32 && (S & 63) == 0 && S * 32 * 4 <= 64 * 1024 && RO * S * 4 < (1LL << 31);
-    r.loss = !d.scalar_input ? SC_LOSS_SOFTMAX : (O / 3 == 10 ? SC_LOSS_MOL10 : SC_LOSS_MOLN);
-    return r;
-}
-
 // The workspace carve, each piece rounded up to 64 floats: create runs it on a null base for the SIZE, score_windows for the pointers.
 // Nothing here grows with the utterances: it is (slots, window) activations of TWO layers, the stacked skip input and the head.
 struct ScoreCarve {
@@ -371,12 +310,12 @@ struct ScoreCarve {
     float *XA, *XB, *ZC, *SK, *C1, *Y, *emb, *GCP, *WV, *WS, *bsum, *ctab, *melsh, *Qall;
     long long vstride, q_ls;
 };
-static long long sc_carve(const twv_wavenet_scorer* h, float* base, ScoreCarve& c)
+static long long sc_carve(const WavenetGraph* h, float* base, ScoreCarve& c)
 {
     const twv_wavenet_dims& d = h->d;
-    const int B = h->slots, T = h->T, Tn = h->Tn, NL = h->NL, S = h->S, O = h->O, L = h->L, G = h->G, ow = h->ow;
+    const int B = h->rows, T = h->T, Tn = h->Tn, NL = h->NL, S = h->S, O = h->O, L = h->L, G = h->G, ow = h->ow;
     const long long Rr = (long long)B * Tn, RT = (long long)B * T, RO = (long long)B * ow;
-    const bool fused = sc_route(d, B, T).fused_lc;
+    const bool fused = wavenet_route(*h).fused_lc;
     long long used = 0;
     auto take = [&](long long n) { float* p = base ? base + used : nullptr; used += (n + 63) / 64 * 64; return p; };
     c.upT[0] = h->F;
@@ -405,57 +344,15 @@ static long long sc_carve(const twv_wavenet_scorer* h, float* base, ScoreCarve& 
 
 extern "C" int twv_wavenet_score_create(const twv_wavenet_dims* dims, int slots, int window_samples, twv_wavenet_scorer** out)
 {
-    if (dims && dims->gc_channels > 0 && dims->gc_cardinality < 1)
-        return twv_fail(TWV_E_UNSUPPORTED, "scoring needs global_condition_cardinality (the gc_embedding table is a variable of the graph; model.py:191-195)");
-    if (!dims || !out || slots < 1) return twv_fail(TWV_E_INVALID, "bad argument");
-    const twv_wavenet_dims& d = *dims;
-    if (d.n_layers < 1 || d.n_layers > TWV_MAX_LAYERS || d.n_upsample < 0 || d.n_upsample > 4) return twv_fail(TWV_E_INVALID, "bad dims");
-    if (d.residual_channels != 32 || d.dilation_channels != 32) return twv_fail(TWV_E_UNSUPPORTED, "scoring is built for residual_channels = dilation_channels = 32 only");
-    if (d.scalar_input && (d.out_channels < 3 || d.out_channels % 3 || d.out_channels > 96)) return twv_fail(TWV_E_UNSUPPORTED, "out_channels must be 3*nr_mix <= 96");
-    if (!d.scalar_input && (d.quantization_channels < 2 || d.quantization_channels > 512)) return twv_fail(TWV_E_UNSUPPORTED, "quantization_channels must be in [2, 512] for scoring");
-    if (d.lc_channels != 80 || !d.gc_channels) return twv_fail(TWV_E_UNSUPPORTED, "scoring expects num_mels = 80 local and global conditioning (train_vocoder.py, hparams.py:30)");
-    // the limit of the training step's fused route (twv_wavenet_train_create), kept: memory is bounded by the window batch, a longer
-    // utterance is more windows, never a larger batch
-    if (sc_route(d, slots, window_samples).fused_lc && (long long)slots * window_samples * 256 >= (1LL << 31))
-        return twv_fail(TWV_E_UNSUPPORTED, "slots x window too large on the fused lc route (slots * window_samples < 8.3 M): score with fewer slots or a shorter window");
+    if (!out) return twv_fail(TWV_E_INVALID, "bad argument");
     twv_wavenet_scorer* h = new twv_wavenet_scorer();
-    h->d = d; h->slots = slots; h->T = window_samples; h->Tn = window_samples - 1; h->NL = d.n_layers; h->S = d.skip_channels;
-    h->O = d.scalar_input ? d.out_channels : d.quantization_channels;
-    h->L = d.lc_channels; h->G = d.gc_channels; h->ifw = d.scalar_input ? d.initial_filter_width : 2;   // model.py:36-39
-    h->hop = 1;
-    for (int i = 0; i < d.n_upsample; ++i) h->hop *= d.upsample_factor[i];
-    if (window_samples < 1 || window_samples % h->hop) { delete h; return twv_fail(TWV_E_INVALID, "window_samples must be a multiple of the hop size (datafeeder_wavenet.py:38)"); }
-    h->F = window_samples / h->hop;
-    h->off[0] = h->ifw - 1;
-    for (int l = 0; l < h->NL; ++l) h->off[l + 1] = h->off[l] + d.dilations[l];
-    h->rf = h->off[h->NL] + 1;
-    h->ow = window_samples - h->rf;                                   // model.py:135 output_width
-    if (h->ow < 1) { delete h; return twv_fail(TWV_E_INVALID, "window_samples must exceed the receptive field"); }
-    // canonical blob offsets: the order of weights.tensor_specs, as in twv_wavenet_train_create
-    long long c = 0;
-    const int R = 32, D = 32, ub = d.use_biases ? 1 : 0;
-    h->c_causal = c; c += d.scalar_input ? (long long)h->ifw * R : 2LL * d.quantization_channels * R;
-    h->c_gcemb = c; c += (long long)d.gc_cardinality * h->G;
-    h->c_layer0 = c;
-    long long q = 0;
-    h->o_wf = q; q += 2 * R * D; h->o_bf = q; q += ub * D;
-    h->o_wg = q; q += 2 * R * D; h->o_bg = q; q += ub * D;
-    h->o_gcf = q; q += (long long)h->G * D; h->o_gcg = q; q += (long long)h->G * D;
-    h->o_lcf = q; q += (long long)h->L * D; h->o_lcg = q; q += (long long)h->L * D;
-    h->o_wd = q; q += D * R; h->o_bd = q; q += ub * R;
-    h->o_ws = q; q += (long long)D * h->S; h->o_bs = q; q += (long long)ub * h->S;
-    h->c_lstride = q; c += q * h->NL;
-    h->c_w1 = c; c += (long long)h->S * h->S; h->c_b1 = c; c += (long long)ub * h->S;
-    h->c_w2 = c; c += (long long)h->S * h->O; h->c_b2 = c; c += (long long)ub * h->O;
-    for (int i = 0; i < d.n_upsample; ++i) { h->c_up[i] = c; c += (long long)d.upsample_factor[i] * 2; }
-    h->nparams = c;
+    const int rc = wavenet_graph_init(h->g, dims, slots, window_samples, "scoring");
+    if (rc) { delete h; return rc; }
     h->blas = nullptr;
     ScoreCarve sizes;
-    h->carve_floats = sc_carve(h, nullptr, sizes);
-    const ScoreRoute r = sc_route(d, slots, window_samples);
-    h->route = std::string("lc=") + (r.fused_lc ? "fused" : "staged") + " head=" + (r.skinny ? "skinny" : "gemm") +
-               " loss=" + (r.loss == SC_LOSS_MOL10 ? "mol<10>" : r.loss == SC_LOSS_MOLN ? "mol<0>" : "softmax") +
-               " carve_floats=" + std::to_string(h->carve_floats);
+    h->carve_floats = sc_carve(&h->g, nullptr, sizes);
+    const WavenetRoute r = wavenet_route(h->g);
+    h->route = wavenet_route_label(r, r.skinny ? "skinny" : "gemm") + " carve_floats=" + std::to_string(h->carve_floats);
     *out = h;
     return TWV_OK;
 }
@@ -465,110 +362,75 @@ extern "C" void twv_wavenet_score_destroy(twv_wavenet_scorer* h)
     delete h;
 }
 extern "C" size_t twv_wavenet_score_workspace_bytes(const twv_wavenet_scorer* h) { return h ? (size_t)h->carve_floats * 4 : 0; }
-extern "C" int twv_wavenet_score_output_width(const twv_wavenet_scorer* h) { return h ? h->ow : 0; }
+extern "C" int twv_wavenet_score_output_width(const twv_wavenet_scorer* h) { return h ? h->g.ow : 0; }
 extern "C" const char* twv_wavenet_score_route(const twv_wavenet_scorer* h) { return h ? h->route.c_str() : ""; }
 
 extern "C" int twv_wavenet_score_windows(twv_wavenet_scorer* h, const float* params, const float* audio, const float* lc, const int32_t* gc_ids,
                                          const int32_t* lengths_host, void* workspace, float* nll, void* stream)
 {
     if (!h || !params || !audio || !lc || !gc_ids || !lengths_host || !workspace || !nll) return twv_fail(TWV_E_INVALID, "null argument");
-    const twv_wavenet_dims& d = h->d;
-    const int B = h->slots, T = h->T, Tn = h->Tn, NL = h->NL, S = h->S, O = h->O, L = h->L, G = h->G, ow = h->ow, rf = h->rf, F = h->F;
+    const WavenetGraph& g = h->g;
+    const twv_wavenet_dims& d = g.d;
+    const int B = g.rows, T = g.T, Tn = g.Tn, NL = g.NL, O = g.O, ow = g.ow, rf = g.rf, F = g.F;
     for (int b = 0; b < B; ++b) {
         const int n = lengths_host[b];
-        if (n != 0 && (n < 0 || n > T || n % h->hop || n <= rf))
+        if (n != 0 && (n < 0 || n > T || n % g.hop || n <= rf))
             return twv_fail(TWV_E_INVALID, "slot " + std::to_string(b) + ": length " + std::to_string(n) + " must be 0 (idle) or a multiple of the hop size " +
-                                           std::to_string(h->hop) + " in (" + std::to_string(rf) + ", " + std::to_string(T) + "]");
+                                           std::to_string(g.hop) + " in (" + std::to_string(rf) + ", " + std::to_string(T) + "]");
     }
     ScoreCarve cv;
-    if (sc_carve(h, (float*)workspace, cv) != h->carve_floats)
+    if (sc_carve(&g, (float*)workspace, cv) != h->carve_floats)
         return twv_fail(TWV_E_INVALID, "internal: the workspace carve does not match the size twv_wavenet_score_create computed");
     hipStream_t st = (hipStream_t)stream;
     if (!h->blas) BLASCHK(rocblas_create_handle(&h->blas));
     BLASCHK(rocblas_set_stream(h->blas, st));
     BLASCHK(rocblas_set_pointer_mode(h->blas, rocblas_pointer_mode_host));
-    rocblas_handle bl = h->blas;
-    const ScoreRoute route = sc_route(d, B, T);
-    const long long Rr = (long long)B * Tn, RT = (long long)B * T, RO = (long long)B * ow;
+    const WavenetRoute route = wavenet_route(g);
+    const long long RO = (long long)B * ow;
     const bool ub = d.use_biases != 0;
     const float* P = params;
     const int ZW = NL * 32;
     const long long vstride = cv.vstride, q_ls = cv.q_ls;
-    if (route.skinny) HIPCHK(hipFuncSetAttribute((const void*)tr_skinny_nn_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
     HIPCHK(hipMemcpyAsync(cv.lens, lengths_host, (size_t)B * 4, hipMemcpyHostToDevice, st));   // (pageable source: staged before the call returns)
-#define K1(kern, n, ...) hipLaunchKernelGGL(kern, dim3(sc_tg(n)), dim3(256), 0, st, __VA_ARGS__)
-#define LP(l) (P + h->c_layer0 + (long long)(l) * h->c_lstride)
-    // ================= front: the training step's forward kernels on all slots x window rows =================
-    K1(tr_views_kernel, (vstride + 32LL * S) * NL, const_cast<float*>(P), cv.WV, cv.WS, NL, h->c_layer0, h->c_lstride, h->o_wf, h->o_wg, h->o_lcf, h->o_lcg,
-       h->o_gcf, h->o_gcg, h->o_ws, L, G, S, 0);
-    float* ups[5] = {const_cast<float*>(lc), cv.ups[1], cv.ups[2], cv.ups[3], cv.ups[4]};
-    for (int i = 0; i < d.n_upsample && !route.fused_lc; ++i)         // model.py:276 create_upsample
-        K1(tr_up_fwd_kernel, (long long)B * cv.upT[i + 1] * L, P + h->c_up[i], ups[i], ups[i + 1], (long long)B * cv.upT[i + 1] * L, d.upsample_factor[i], L);
-    const float* U = ups[d.n_upsample];
-    K1(tr_gather_emb_kernel, (long long)B * G, P + h->c_gcemb, gc_ids, cv.emb, B, G);            // model.py:197-198
+    // ================= front: the training step's, on all slots x window rows =================
+    WavenetFwdBufs fb;
+    fb.ups[0] = const_cast<float*>(lc);
+    for (int i = 1; i < 5; ++i) fb.ups[i] = cv.ups[i];
+    fb.upT = cv.upT; fb.xunf = cv.xunf; fb.qin = cv.qin;
+    fb.X0 = cv.XA; fb.emb = cv.emb; fb.GCP = cv.GCP; fb.WV = cv.WV; fb.WS = cv.WS; fb.ctab = cv.ctab; fb.melsh = cv.melsh; fb.Qall = cv.Qall;
+    fb.vstride = vstride; fb.q_ls = q_ls;
+    fb.ZC = cv.ZC; fb.SK = cv.SK; fb.C1 = cv.C1; fb.Y = cv.Y; fb.bsum = cv.bsum;
+    if (int rc = wavenet_forward_front(g, P, audio, gc_ids, fb, h->blas, st)) return rc;
+    const float* U = fb.ups[d.n_upsample];
     float* X[2] = {cv.XA, cv.XB};
-    if (d.scalar_input) {
-        K1(tr_unfold_kernel, Rr * h->ifw, audio, cv.xunf, B, T, Tn, h->ifw);
-        BLASCHK(sc_gemm(bl, (int)Rr, 32, h->ifw, cv.xunf, h->ifw, P + h->c_causal, 32, X[0], 32));                       // model.py:131
-    } else {
-        const int rc = twv_mu_law_encode(audio, RT, d.quantization_channels, cv.qin, st);                                 // model.py:257
-        if (rc) return rc;
-        K1(tr_onehot_causal_fwd_kernel, Rr * 32, P + h->c_causal, cv.qin, X[0], B, T, Tn, d.quantization_channels);
-    }
-    const float one = 1.0f, zero = 0.0f;
-    if (route.fused_lc) {
-        K1(tr_ctab_kernel, h->hop, P + h->c_up[0], P + h->c_up[1], P + h->c_up[2], d.upsample_factor[0], d.upsample_factor[1], d.upsample_factor[2], cv.ctab);
-        K1(tr_mel_shift_kernel, (long long)B * F * 4 * L, lc, cv.melsh, (long long)B * F, L);
-        BLASCHK(rocblas_sgemm_strided_batched(bl, rocblas_operation_none, rocblas_operation_none, 64, B * F * 4, L, &one, cv.WV + 64 * 64, 64, vstride,
-                                              cv.melsh, L, 0, &zero, cv.Qall, 64, q_ls + 64, NL));
-    }
-    // model.py:71-73 gc projections of every layer: GCP[l] (B x 64) = emb (B x G) . Wgc_l (G x 64)
-    BLASCHK(rocblas_sgemm_strided_batched(bl, rocblas_operation_none, rocblas_operation_none, 64, B, G, &one, cv.WV + (64 + L) * 64, 64, vstride,
-                                          cv.emb, G, 0, &zero, cv.GCP, 64, (long long)B * 64, NL));
     // ================= the residual stack: one forward-only kernel per layer =================
     for (int l = 0; l < NL; ++l) {
-        const float* Lp = LP(l);
+        const float* Lp = P + g.c_layer0 + (long long)l * g.c_lstride;
         const float* Wv = cv.WV + l * vstride;
         ScLayerArgs fa;
         fa.X = X[l & 1]; fa.XN = X[(l + 1) & 1]; fa.U = U; fa.gcp = cv.GCP + (long long)l * B * 64;
-        fa.W0 = Wv; fa.W1 = Wv + 32 * 64; fa.Wlc = Wv + 64 * 64; fa.Wd = Lp + h->o_wd;
-        fa.bf = ub ? Lp + h->o_bf : nullptr; fa.bg = ub ? Lp + h->o_bg : nullptr; fa.bd = ub ? Lp + h->o_bd : nullptr;
+        fa.W0 = Wv; fa.W1 = Wv + 32 * 64; fa.Wlc = Wv + 64 * 64; fa.Wd = Lp + g.lo.wd;
+        fa.bf = ub ? Lp + g.lo.bf : nullptr; fa.bg = ub ? Lp + g.lo.bg : nullptr; fa.bd = ub ? Lp + g.lo.bd : nullptr;
         fa.ZC = cv.ZC + l * 32; fa.lens = cv.lens;
-        fa.slots = B; fa.T = T; fa.Tn = Tn; fa.d = d.dilations[l]; fa.o = h->off[l + 1]; fa.cut = rf - 1; fa.ow = ow; fa.ldz = ZW;
+        fa.slots = B; fa.T = T; fa.Tn = Tn; fa.d = d.dilations[l]; fa.o = g.off[l + 1]; fa.cut = rf - 1; fa.ow = ow; fa.ldz = ZW;
         fa.t_lo = (fa.o / 32) * 32;                          // whole tiles in front of the layer's offset hold no row: not walked
         fa.tpb = (Tn + 31) / 32 - fa.t_lo / 32;
-        fa.Q = cv.Qall + l * (q_ls + 64); fa.ctab = cv.ctab; fa.hop = h->hop; fa.F = F;
+        fa.Q = cv.Qall + l * (q_ls + 64); fa.ctab = cv.ctab; fa.hop = g.hop; fa.F = F;
         const int ntiles = B * fa.tpb;
         int nwg = (ntiles + 7) / 8; nwg = nwg > 256 ? 256 : nwg;     // one workgroup (8 waves, 2 per SIMD) per CU, each wave walks its tiles
         if (route.fused_lc) hipLaunchKernelGGL(sc_layer_fwd_kernel<true>, dim3(nwg), dim3(512), 0, st, fa);
         else hipLaunchKernelGGL(sc_layer_fwd_kernel<false>, dim3(nwg), dim3(512), 0, st, fa);
     }
-    // ================= head: model.py:150-165 (sum of the skip 1x1 convs == ONE GEMM against the stacked skip kernels) =================
-    // over all slots x ow rows: the rows a slot does not have hold whatever the workspace held; every row is a function of itself only,
-    // and the loss kernels below write those positions as 0
-    BLASCHK(sc_gemm(bl, (int)RO, S, ZW, cv.ZC, ZW, cv.WS, S, cv.SK, S));
-    if ((S & 3) == 0) {
-        if (ub) K1(tr_bias_sum_kernel, S, LP(0) + h->o_bs, NL, h->c_lstride, cv.bsum, S);
-        K1(tr_bias_relu4_kernel, RO * S / 4, (float4*)cv.SK, ub ? (const float4*)cv.bsum : nullptr, S / 4, RO * S / 4);
-    } else {
-        K1(tr_bias_relu_kernel, RO * S, cv.SK, ub ? LP(0) + h->o_bs : nullptr, ub ? NL : 0, h->c_lstride, (const float*)nullptr, S, RO * S);
-    }
-    BLASCHK(sc_gemm(bl, (int)RO, S, S, cv.SK, S, P + h->c_w1, S, cv.C1, S));
-    if (route.skinny) {
-        hipLaunchKernelGGL(tr_skinny_nn_kernel<true>, dim3(1024), dim3(256), (size_t)S * 33 * 4, st, cv.C1, S, P + h->c_w2, O, ub ? P + h->c_b2 : nullptr, RO, S, O,
-                           cv.Y, O, ub ? P + h->c_b1 : nullptr);
-    } else {
-        if ((S & 3) == 0 && (h->c_b1 & 3) == 0) K1(tr_bias_relu4_kernel, RO * S / 4, (float4*)cv.C1, ub ? (const float4*)(P + h->c_b1) : nullptr, S / 4, RO * S / 4);
-        else K1(tr_bias_relu_kernel, RO * S, cv.C1, (const float*)nullptr, 0, 0LL, ub ? P + h->c_b1 : nullptr, S, RO * S);
-        BLASCHK(sc_gemm(bl, (int)RO, O, S, cv.C1, S, P + h->c_w2, O, cv.Y, O));
-        if (ub) K1(tr_bias_add_kernel, RO * O, cv.Y, P + h->c_b2, O, RO * O);
-    }
+    // ================= head: the training step's (model.py:150-165), over all slots x ow rows =================
+    // the rows a slot does not have hold whatever the workspace held; every row is a function of itself only, and the loss kernels
+    // below write those positions as 0.  conv1d_1's bias + relu pass is skipped whenever conv1d_2 is the skinny kernel.
+    if (int rc = wavenet_forward_head(g, P, fb, route.skinny, route.skinny, h->blas, st)) return rc;
     // ================= per-row loss terms =================
-    if (route.loss == SC_LOSS_MOL10) K1(sc_mol_nll_kernel<10>, RO, cv.Y, audio, cv.lens, B, T, ow, rf, O / 3, nll);
-    else if (route.loss == SC_LOSS_MOLN) K1(sc_mol_nll_kernel<0>, RO, cv.Y, audio, cv.lens, B, T, ow, rf, O / 3, nll);
-    else hipLaunchKernelGGL(sc_softmax_nll_kernel, dim3(sc_tg(RO * 64)), dim3(256), 0, st, cv.Y, cv.qin, cv.lens, B, T, ow, rf, O, nll);
+#define K1(kern, n, ...) hipLaunchKernelGGL(kern, dim3(tg(n)), dim3(256), 0, st, __VA_ARGS__)
+    if (route.loss == WG_LOSS_MOL10) K1(sc_mol_nll_kernel<10>, RO, cv.Y, audio, cv.lens, B, T, ow, rf, O / 3, nll);
+    else if (route.loss == WG_LOSS_MOLN) K1(sc_mol_nll_kernel<0>, RO, cv.Y, audio, cv.lens, B, T, ow, rf, O / 3, nll);
+    else hipLaunchKernelGGL(sc_softmax_nll_kernel, dim3(tg(RO * 64)), dim3(256), 0, st, cv.Y, cv.qin, cv.lens, B, T, ow, rf, O, nll);
 #undef K1
-#undef LP
     HIPCHK(hipGetLastError());
     return TWV_OK;
 }

@@ -18,6 +18,8 @@
 // gradients are plain library GEMMs (rocBLAS).  MoL / softmax-CE loss (forward + analytic backward), deterministic
 // reductions, the transposed-conv upsampler and the Adam/EMA update are hand-written HIP kernels.  Parameters and gradients
 // stay in the canonical checkpoint layout (TF variable order, kernels (K, N) row-major).
+// The model description (geometry, canonical offsets, refusals, route predicates) is twv_wavenet_graph.hpp's, shared with scoring
+// (twv_score.hip); the forward front and head that header declares are defined here, beside their kernels, and launched by both.
 // This is a floating-point training step: parity is by tolerance against an independent PyTorch-CPU fp32 autograd model.
 #include <hip/hip_runtime.h>
 #include <rocblas/rocblas.h>
@@ -26,25 +28,10 @@
 #include <string>
 #include "../../include/twv_amd.h"
 #include "twv_dev.hpp"
+#include "twv_wavenet_graph.hpp"
 
-#define HIPCHK(expr)                                                                                              \
-    do {                                                                                                          \
-        hipError_t e_ = (expr);                                                                                   \
-        if (e_ != hipSuccess) return twv_fail(TWV_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));     \
-    } while (0)
-#define BLASCHK(expr)                                                                                             \
-    do {                                                                                                          \
-        rocblas_status s_ = (expr);                                                                               \
-        if (s_ != rocblas_status_success) return twv_fail(TWV_E_HIP, std::string(#expr) + ": rocblas status " + std::to_string((int)s_)); \
-    } while (0)
-
-struct TrainLayerOff { long long wf, bf, wg, bg, gcf, gcg, lcf, lcg, wd, bd, ws, bs; };
 struct twv_wavenet_trainer {
-    twv_wavenet_dims d;
-    int B, T, Tn, rf, ow, NL, S, O, L, G, ifw, hop;
-    int off[TWV_MAX_LAYERS + 1];          // receptive offset of layer l's INPUT (off[0] = ifw-1), off[NL] = rf-1
-    long long c_causal, c_gcemb, c_layer0, c_lstride, c_w1, c_b1, c_w2, c_b2, c_up[4], nparams;
-    TrainLayerOff lo;                     // offsets inside a layer block
+    WavenetGraph g;                       // rows = batch entries, T = samples each
     rocblas_handle blas;
     long long ws_floats;
     long long l2_off;                     // twv_wavenet_train_l2's scratch inside the workspace (floats)
@@ -69,7 +56,6 @@ __device__ __forceinline__ void tr_bst4(rsrc_t r, unsigned off, f32x4t v)
     __builtin_amdgcn_raw_buffer_store_b128(u32x4{__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])}, r, (int)off, 0, 0);
 }
 #define GRID_STRIDE(i, n) for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (long long)gridDim.x * blockDim.x)
-static inline int tg(long long n) { long long g = (n + 255) / 256; return (int)(g < 1 ? 1 : (g > 32768 ? 32768 : g)); }
 
 // model.py:102-111 one transposed-conv stage: out[b, t*f+a, m] = K[a,0]*in[b,t,m] + K[a,1]*in[b,t,m-1]
 __global__ void tr_up_fwd_kernel(const float* K, const float* in, float* out, long long total, int f, int Lc)
@@ -612,7 +598,7 @@ struct LayerFwdArgs {
     int B, T, Tn, d, o, ow, ldz, tpb;                        // tpb = tiles per batch entry the launch walks (ceil(Tn / 32) - t_lo / 32)
     int t_lo;                                                // first row the launch walks in every batch entry (a multiple of 32): the rows
                                                              // below it lie in front of the layer's receptive offset (see the host code)
-    // FUSED lc projection (see tr_layer_fwd_kernel): Q[((b*F + frame)*4 + j)*64 + column] = (mel shifted by j bins) . Wlc of this layer,
+    // FUSED lc projection (see tr_layer_fwdc_kernel): Q[((b*F + frame)*4 + j)*64 + column] = (mel shifted by j bins) . Wlc of this layer,
     // ctab[phase*4 + j] = the 4-tap composition of the three upsampling kernels at that phase of the hop
     const float* Q; const float* ctab; int hop, F;
 };
@@ -712,7 +698,6 @@ __global__ __launch_bounds__(256, 2) void tr_conv2_bwd_kernel(const float* dY, i
 }
 
 struct LayerA { f32x4t x0[4], x1[4], u[kLcSteps]; };
-template <bool FUSED>
 __device__ __forceinline__ void tr_layer_load(LayerA& A, const LayerFwdArgs& a, int tile, int lane)
 {
     const int b = tile / a.tpb, t = (tile - b * a.tpb) * 32 + a.t_lo + (lane & 31), hh = (lane >> 5) * 4;
@@ -724,32 +709,24 @@ __device__ __forceinline__ void tr_layer_load(LayerA& A, const LayerFwdArgs& a, 
         A.x0[i] = tr_ld4(xr - (long long)a.d * 32 + 8 * i, in && t >= a.d);
         A.x1[i] = tr_ld4(xr + 8 * i, in);
     }
-    if (!FUSED) {
 #pragma unroll
-        for (int i = 0; i < kLcSteps; ++i) A.u[i] = tr_ld4(ur + 8 * i, in && t >= a.o);
-    }
+    for (int i = 0; i < kLcSteps; ++i) A.u[i] = tr_ld4(ur + 8 * i, in && t >= a.o);
 }
 
 // Two waves per SIMD (8 per workgroup, <= 256 registers each): while one wave runs its gated-unit epilogue on the VALU the other
 // wave's MFMAs keep the matrix pipe busy -- a lone wave issues in order and never overlaps the two (SQ_VALU_MFMA_COEXEC_CYCLES = 0
 // with one wave per SIMD).  The B operands therefore live in LDS, one conflict-free ds_read_b64 (filter, gate) per MFMA pair.
 constexpr int kFwdSteps = 32 + 4 * kLcSteps;                 // tap0 16 + tap1 16 + lc 40 = 72 MFMA steps per column half
-// FUSED: the upsampled local condition is never read.  model.py:102-111's three transposed convolutions (kernel (f, 2): two
-// adjacent mel bins) compose to a 4-tap filter over mel bins whose taps depend only on the phase inside the hop, so
-//   lc projection(t) = sum_j ctab[phase(t)][j] * Q_j[frame(t)],   Q_j = (mel shifted by j bins) . Wlc      (26 frames per entry)
-// -- 8 VALU fmas per output row instead of 80 MFMA k-steps per tile, and 320 bytes per row less HBM traffic (a third of the
-// kernel's).  Same function, different float association: the training parity is tolerance-based (tests/test_train_gpu.py).
-template <bool FUSED>
+// The local condition term is 80 more k-steps over the materialised upsampler rows U[t - o] (the staged route: any upsampler the
+// fused route below does not take).
 __global__ void __launch_bounds__(512) tr_layer_fwd_kernel(LayerFwdArgs a)
 {
-    __shared__ float bt[(FUSED ? 32 : kFwdSteps) * 128];     // [step][lane][filter, gate]
-    __shared__ __attribute__((aligned(16))) float cts[FUSED ? 4 * 512 : 4];   // ctab (hop <= 512)
-    if (FUSED) for (int e = threadIdx.x; e < a.hop * 4; e += 512) cts[e] = a.ctab[e];
+    __shared__ float bt[kFwdSteps * 128];                    // [step][lane][filter, gate]
     __shared__ float bdt[16 * 64];                           // dense: [step][lane]
     __shared__ float zt[8][32 * 36];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int n = lane & 31, hh = lane >> 5;
-    for (int e = threadIdx.x; e < (FUSED ? 32 : kFwdSteps) * 64; e += 512) {
+    for (int e = threadIdx.x; e < kFwdSteps * 64; e += 512) {
         const int s = e >> 6, l = e & 63, nn = l & 31, h2 = l >> 5;
         const float* W; int ij;
         if (s < 16) { W = a.W0; ij = s; } else if (s < 32) { W = a.W1; ij = s - 16; } else { W = a.Wlc; ij = s - 32; }
@@ -767,7 +744,7 @@ __global__ void __launch_bounds__(512) tr_layer_fwd_kernel(LayerFwdArgs a)
     const int ntiles = a.B * a.tpb, nwaves = gridDim.x * 8;
     for (int tile = blockIdx.x * 8 + wave; tile < ntiles; tile += nwaves) {
         LayerA A;
-        tr_layer_load<FUSED>(A, a, tile, lane);
+        tr_layer_load(A, a, tile, lane);
         // residual operand and gc projection in the output (C) layout: requested now, consumed after the MFMAs
         const int b = tile / a.tpb, t0 = (tile - b * a.tpb) * 32 + a.t_lo;
         const float gcf = a.gcp ? a.gcp[b * 64 + n] : 0.0f, gcg = a.gcp ? a.gcp[b * 64 + 32 + n] : 0.0f;
@@ -806,39 +783,14 @@ __global__ void __launch_bounds__(512) tr_layer_fwd_kernel(LayerFwdArgs a)
                 cf = __builtin_amdgcn_mfma_f32_32x32x2f32(A.x1[i][j], w[0], cf, 0, 0, 0);
                 cg = __builtin_amdgcn_mfma_f32_32x32x2f32(A.x1[i][j], w[1], cg, 0, 0, 0);
             }
-        if (!FUSED) {
 #pragma unroll
-            for (int i = 0; i < kLcSteps; ++i)
+        for (int i = 0; i < kLcSteps; ++i)
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const f32x2t w = *reinterpret_cast<const f32x2t*>(&bt[((32 + 4 * i + j) * 64 + lane) * 2]);
-                    cf = __builtin_amdgcn_mfma_f32_32x32x2f32(A.u[i][j], w[0], cf, 0, 0, 0);
-                    cg = __builtin_amdgcn_mfma_f32_32x32x2f32(A.u[i][j], w[1], cg, 0, 0, 0);
-                }
-        } else {
-            // rows of the tile: U row u = t - o; at most two frames per 32-row tile (hop >= 32)
-            int u0 = t0 - a.o; u0 = u0 < 0 ? 0 : u0;
-            const int fA = u0 / a.hop, fB = fA + 1 < a.F ? fA + 1 : fA;
-            const int edge = (fA + 1) * a.hop;                               // first U row of frame fA + 1
-            const float* qa = a.Q + (((long long)b * a.F + fA) * 4) * 64 + n;
-            const float* qb = a.Q + (((long long)b * a.F + fB) * 4) * 64 + n;
-            float qfa[4], qga[4], qfb[4], qgb[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { qfa[j] = qa[j * 64]; qga[j] = qa[j * 64 + 32]; qfb[j] = qb[j * 64]; qgb[j] = qb[j * 64 + 32]; }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                int u = t0 - a.o + (r & 3) + 8 * (r >> 2) + 4 * hh;
-                u = u < 0 ? 0 : u;                                            // rows below the layer's offset are discarded by the epilogue
-                const bool hi = u >= edge;
-                int ph = u - (hi ? edge : edge - a.hop);
-                ph = ph < a.hop ? ph : a.hop - 1;                             // (only rows past the utterance end, discarded as well)
-                const f32x4t c = *reinterpret_cast<const f32x4t*>(&cts[ph * 4]);
-                const float f0 = hi ? qfb[0] : qfa[0], f1 = hi ? qfb[1] : qfa[1], f2 = hi ? qfb[2] : qfa[2], f3 = hi ? qfb[3] : qfa[3];
-                const float g0 = hi ? qgb[0] : qga[0], g1 = hi ? qgb[1] : qga[1], g2 = hi ? qgb[2] : qga[2], g3 = hi ? qgb[3] : qga[3];
-                cf[r] += ((c[0] * f0 + c[1] * f1) + c[2] * f2) + c[3] * f3;
-                cg[r] += ((c[0] * g0 + c[1] * g1) + c[2] * g2) + c[3] * g3;
+            for (int j = 0; j < 4; ++j) {
+                const f32x2t w = *reinterpret_cast<const f32x2t*>(&bt[((32 + 4 * i + j) * 64 + lane) * 2]);
+                cf = __builtin_amdgcn_mfma_f32_32x32x2f32(A.u[i][j], w[0], cf, 0, 0, 0);
+                cg = __builtin_amdgcn_mfma_f32_32x32x2f32(A.u[i][j], w[1], cg, 0, 0, 0);
             }
-        }
         // ---- gated unit (C layout: lane = channel n, register r = row (r&3) + 8(r>>2) + 4hh)
         if (interior) {
             float* thp = a.TH + lrow; float* sgp = a.SG + lrow;
@@ -897,14 +849,20 @@ __global__ void __launch_bounds__(512) tr_layer_fwd_kernel(LayerFwdArgs a)
 
 // -------------------------------------------------------------------------------------------------------------------
 //  The FUSED forward layer with every HBM access a fully coalesced 16-byte-per-lane instruction (round 3).
-//  Anatomy of tr_layer_fwd_kernel<true> (ablation builds, profiles/r03_train_layer_anatomy.txt): its time is the SUM of its phases --
+//  FUSED: the upsampled local condition is never read.  model.py:102-111's three transposed convolutions (kernel (f, 2): two
+//  adjacent mel bins) compose to a 4-tap filter over mel bins whose taps depend only on the phase inside the hop, so
+//    lc projection(t) = sum_j ctab[phase(t)][j] * Q_j[frame(t)],   Q_j = (mel shifted by j bins) . Wlc      (26 frames per entry)
+//  -- 8 VALU fmas per output row instead of 80 MFMA k-steps per tile, and 320 bytes per row less HBM traffic (a third of the
+//  kernel's).  Same function, different float association: the training parity is tolerance-based (tests/test_train_gpu.py).
+//  Anatomy of this kernel's plain form, one float4 row load per lane (the training step ran it before this one; scoring still does,
+//  as sc_layer_fwd_kernel<true>) (ablation builds, profiles/r03_train_layer_anatomy.txt): its time is the SUM of its phases --
 //  the CU's waves run them in step -- and the memory phases are priced per INSTRUCTION, not per byte: ~22 cycles of the CU's
 //  address path for a dword store of two 128-byte rows, ~13 for such a load, ~88 for a float4 row load that touches 32 lines; 120 of
 //  them per 32-row tile = 2.5 k of the 4.25 k cycles a tile costs a CU (MFMA 1.3 k).  Here a tile enters and leaves as 1 KB
 //  instructions (lane l: the l-th float4 of eight consecutive 128-byte rows): 8 loads and 12 (16 with the skip slice) stores per
 //  tile; the MFMA operand layouts (A: lane = row, C: lane = channel) are reached through three wave-private 32 x 36 LDS patches
 //  (144-byte row stride: the b128 row reads and the b32 column accesses are both conflict-free).  The next tile's rows are
-//  requested before this tile's MFMAs.  Same arithmetic as tr_layer_fwd_kernel<true>.
+//  requested before this tile's MFMAs.  Same arithmetic as sc_layer_fwd_kernel<true> (twv_score.hip), the remaining plain form.
 // -------------------------------------------------------------------------------------------------------------------
 constexpr int kPatch = 32 * 36;
 #ifdef TWV_TRPROF
@@ -1136,7 +1094,7 @@ struct LayerBwdArgs {
     const float* zeros;                                      // >= 1 KB of zeros (masked LDS-DMA lanes read here)
     int B, T, Tn, d, o, ow, ldz, tpb;
     int t_lo, tpbf;                                          // first row walked per batch entry (see LayerFwdArgs); ceil(Tn / 32) = the tile count tsum / PT are indexed by
-    // FUSED lc path (see tr_layer_fwd_kernel): frame-rate projections Q of this layer; D[(b*T + u)*4 + j] accumulates, over the layers,
+    // FUSED lc path (see tr_layer_fwdc_kernel): frame-rate projections Q of this layer; D[(b*T + u)*4 + j] accumulates, over the layers,
     // sum_columns dPRE[row of U-row u] * Q_j[frame(u)] -- all the upsampling kernels' gradients need (tr_dctab / tr_up_grad kernels)
     const float* Q; float* D; int hop, F;
     // bwd1: the hop's tap table and this layer's per-tile partial sums PT[tile][2 frame slots][4 taps][64 columns] of ctab[phase][j] * dPRE
@@ -1469,7 +1427,6 @@ __global__ __launch_bounds__(256) void tr_demb_kernel(const float* dgcp, const f
 
 // Two waves per SIMD as in the forward kernel: the transposed weights (B operands) live in LDS, [step][lane][8] with
 // (W1^T, W0^T, Wlc^T block 0, 1, 2) per lane, fetched as one ds_read_b128 + one ds_read_b32 per MFMA group.
-template <bool FUSED>
 __global__ void __launch_bounds__(512) tr_layer_bwd2_kernel(LayerBwdArgs a)
 {
     __shared__ __attribute__((aligned(16))) float bt2[32 * 64 * 8];
@@ -1486,22 +1443,11 @@ __global__ void __launch_bounds__(512) tr_layer_bwd2_kernel(LayerBwdArgs a)
     __syncthreads();
     const f32x16 zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     const int ntiles = a.B * a.tpb, nwaves = gridDim.x * 8;
-    // (descriptors are the FUSED path's: twv_wavenet_train_create bounds the sizes to 31 bits only for that path; the pointer path takes any size)
-    const rsrc_t rpre = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.dPRE), 0, FUSED ? (int)((long long)a.B * a.Tn * 64 * 4) : 0, 0x00020000);
-    const rsrc_t rdxn = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.dXn), 0, FUSED ? (int)((long long)a.B * a.Tn * 32 * 4) : 0, 0x00020000);
-    const rsrc_t rdx = __builtin_amdgcn_make_buffer_rsrc(a.dX, 0, FUSED ? (int)((long long)a.B * a.Tn * 32 * 4) : 0, 0x00020000);
-    const rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(FUSED ? a.D : a.dX, 0, FUSED ? (int)((long long)a.B * a.T * 4 * 4) : 0, 0x00020000);
     for (int tile = blockIdx.x * 8 + wave; tile < ntiles; tile += nwaves) {
         const int b = tile / a.tpb, t0 = (tile - b * a.tpb) * 32 + a.t_lo;
         const int t = t0 + (lane & 31);
         f32x4t qa[8], qb[8];
-        if (FUSED) {
-            // no branch around a memory instruction (see tr_layer_fwdc_kernel): out-of-range rows read 0 through the descriptor
-            const unsigned p = (unsigned)((((long long)b * a.Tn + t) * 64 + 4 * hh) * 4);
-            const unsigned pa_ = t < a.Tn ? p : 0x80000000u, pb_ = t + a.d < a.Tn ? p + (unsigned)a.d * 256u : 0x80000000u;   // (+ 32 i stays out of range)
-#pragma unroll
-            for (int i = 0; i < 8; ++i) { qa[i] = tr_bld4(rpre, pa_ + 32 * i); qb[i] = tr_bld4(rpre, pb_ + 32 * i); }
-        } else {
+        {
             const float* p = a.dPRE + ((long long)b * a.Tn + t) * 64 + 4 * hh;
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
@@ -1511,23 +1457,17 @@ __global__ void __launch_bounds__(512) tr_layer_bwd2_kernel(LayerBwdArgs a)
         }
         // operands of the read-modify-writes in the output (C) layout: requested before the MFMAs.  Interior tiles (all rows inside
         // the utterance and above the layer's receptive offset) use per-lane pointers + compile-time row offsets, no predicates.
-        const bool interior = !FUSED && t0 >= a.o && t0 + 32 <= a.Tn;
+        const bool interior = t0 >= a.o && t0 + 32 <= a.Tn;
         const long long lrow = ((long long)b * a.Tn + t0 + 4 * hh) * 32 + n;
         float* up = a.dU + ((long long)b * a.T + (t0 - a.o) + 4 * hh) * 80 + n;
         float rx[16], r0[16], r1[16], r2[16];
-        if (FUSED) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int ro = (r & 3) + 8 * (r >> 2);
-                rx[r] = load_f32_b(rdxn, t0 + ro + 4 * hh < a.Tn ? (int)((lrow + ro * 32) * 4) : -1, 0);
-            }
-        } else if (interior) {
+        if (interior) {
             const float* xp = a.dXn + lrow;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int ro = (r & 3) + 8 * (r >> 2);
                 rx[r] = xp[ro * 32];
-                if (!FUSED) { r0[r] = up[ro * 80]; r1[r] = up[ro * 80 + 32]; r2[r] = n < 16 ? up[ro * 80 + 64] : 0.0f; }
+                r0[r] = up[ro * 80]; r1[r] = up[ro * 80 + 32]; r2[r] = n < 16 ? up[ro * 80 + 64] : 0.0f;
             }
         } else {
 #pragma unroll
@@ -1535,33 +1475,8 @@ __global__ void __launch_bounds__(512) tr_layer_bwd2_kernel(LayerBwdArgs a)
                 const int tt = t0 + (r & 3) + 8 * (r >> 2) + 4 * hh;
                 const bool in = tt < a.Tn, v = in && tt >= a.o;
                 rx[r] = in ? a.dXn[((long long)b * a.Tn + tt) * 32 + n] : 0.0f;
-                if (!FUSED) {
-                    const float* ur = a.dU + ((long long)b * a.T + (tt - a.o)) * 80;
-                    r0[r] = v ? ur[n] : 0.0f; r1[r] = v ? ur[32 + n] : 0.0f; r2[r] = (v && n < 16) ? ur[64 + n] : 0.0f;
-                }
-            }
-        }
-        if (FUSED) {
-            // D[u][j] += dPRE[row] . Q_j[frame(u)] over the 64 columns: this lane holds 32 of them (row = lane & 31, columns 8i + 4hh + 0..3)
-            const int u = t - a.o;
-            const bool v = t < a.Tn && u >= 0;
-            const int f = v ? u / a.hop : 0;
-            const float* qr = a.Q + (((long long)b * a.F + f) * 4) * 64 + 4 * hh;
-            float dj[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const f32x4t q4 = *reinterpret_cast<const f32x4t*>(qr + j * 64 + 8 * i);
-                    dj[j] += (qa[i][0] * q4[0] + qa[i][1] * q4[1]) + (qa[i][2] * q4[2] + qa[i][3] * q4[3]);
-                }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) dj[j] += __shfl_xor(dj[j], 32);
-            {
-                const unsigned od = hh == 0 && v ? (unsigned)((((long long)b * a.T + u) * 4) * 4) : 0xFFFFFFFFu;
-                f32x4t cur = tr_bld4(rd, od);
-                cur[0] += dj[0]; cur[1] += dj[1]; cur[2] += dj[2]; cur[3] += dj[3];
-                tr_bst4(rd, od, cur);
+                const float* ur = a.dU + ((long long)b * a.T + (tt - a.o)) * 80;
+                r0[r] = v ? ur[n] : 0.0f; r1[r] = v ? ur[32 + n] : 0.0f; r2[r] = (v && n < 16) ? ur[64 + n] : 0.0f;
             }
         }
         f32x16 cx = zero, c0 = zero, c1 = zero, c2 = zero;
@@ -1573,29 +1488,19 @@ __global__ void __launch_bounds__(512) tr_layer_bwd2_kernel(LayerBwdArgs a)
                 const f32x4t w4 = *reinterpret_cast<const f32x4t*>(wq);
                 const float w5 = wq[4];
                 cx = __builtin_amdgcn_mfma_f32_32x32x2f32(qa[i][j], w4[0], cx, 0, 0, 0);
-                if (!FUSED) {
-                    c0 = __builtin_amdgcn_mfma_f32_32x32x2f32(qa[i][j], w4[2], c0, 0, 0, 0);
-                    c1 = __builtin_amdgcn_mfma_f32_32x32x2f32(qa[i][j], w4[3], c1, 0, 0, 0);
-                    c2 = __builtin_amdgcn_mfma_f32_32x32x2f32(qa[i][j], w5, c2, 0, 0, 0);
-                }
+                c0 = __builtin_amdgcn_mfma_f32_32x32x2f32(qa[i][j], w4[2], c0, 0, 0, 0);
+                c1 = __builtin_amdgcn_mfma_f32_32x32x2f32(qa[i][j], w4[3], c1, 0, 0, 0);
+                c2 = __builtin_amdgcn_mfma_f32_32x32x2f32(qa[i][j], w5, c2, 0, 0, 0);
                 cx = __builtin_amdgcn_mfma_f32_32x32x2f32(qb[i][j], w4[1], cx, 0, 0, 0);
             }
-        if (FUSED) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int ro = (r & 3) + 8 * (r >> 2);
-                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(rx[r] + cx[r]), rdx, t0 + ro + 4 * hh < a.Tn ? (int)((lrow + ro * 32) * 4) : -1, 0, 0);
-            }
-        } else if (interior) {
+        if (interior) {
             float* dxp = a.dX + lrow;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int ro = (r & 3) + 8 * (r >> 2);
                 dxp[ro * 32] = rx[r] + cx[r];
-                if (!FUSED) {
-                    up[ro * 80] = r0[r] + c0[r]; up[ro * 80 + 32] = r1[r] + c1[r];
-                    if (n < 16) up[ro * 80 + 64] = r2[r] + c2[r];
-                }
+                up[ro * 80] = r0[r] + c0[r]; up[ro * 80 + 32] = r1[r] + c1[r];
+                if (n < 16) up[ro * 80 + 64] = r2[r] + c2[r];
             }
         } else {
 #pragma unroll
@@ -1603,7 +1508,7 @@ __global__ void __launch_bounds__(512) tr_layer_bwd2_kernel(LayerBwdArgs a)
                 const int tt = t0 + (r & 3) + 8 * (r >> 2) + 4 * hh;
                 if (tt < a.Tn) {
                     a.dX[((long long)b * a.Tn + tt) * 32 + n] = rx[r] + cx[r];
-                    if (!FUSED && tt >= a.o) {
+                    if (tt >= a.o) {
                         float* ur = a.dU + ((long long)b * a.T + (tt - a.o)) * 80;
                         ur[n] = r0[r] + c0[r]; ur[32 + n] = r1[r] + c1[r];
                         if (n < 16) ur[64 + n] = r2[r] + c2[r];
@@ -1617,7 +1522,7 @@ __global__ void __launch_bounds__(512) tr_layer_bwd2_kernel(LayerBwdArgs a)
 // The FUSED backward-2 layer with the dPRE tiles fetched as 1 KB instructions (lane l: the l-th float4 of four consecutive 256-byte rows)
 // and turned into MFMA A operands (lane = row) through two wave-private 32 x 68 LDS patches -- the row loads of tr_layer_bwd2_kernel
 // touch 32 lines per instruction (16 + 16 of them per tile, ~88 cycles of the CU's address path each; profiles/r03_train_layer_anatomy.txt).
-// Same arithmetic as tr_layer_bwd2_kernel<true>.
+// Same arithmetic as tr_layer_bwd2_kernel with, in place of its dU term, D[u][j] += dPRE[row] . Q_j[frame(u)] (see LayerBwdArgs).
 __global__ void __launch_bounds__(512) tr_layer_bwd2c_kernel(LayerBwdArgs a)
 {
     __shared__ __attribute__((aligned(16))) float btc[32 * 64 * 2];          // [step][lane][W1^T, W0^T]
@@ -1854,32 +1759,19 @@ static rocblas_status gemm_tn_splitk(rocblas_handle h, hipStream_t st, int M, in
     return rocblas_status_success;
 }
 
-// Which kernel families twv_wavenet_train_loss_grad runs for (dims, batch, n_samples).  The ONE place these predicates are written:
-// create (the 32-bit addressing limit of the fused route), loss_grad (the dispatch) and twv_wavenet_train_route (the label a test
-// reads) all call it.
-enum { TR_LOSS_MOL10 = 0, TR_LOSS_MOLN = 1, TR_LOSS_SOFTMAX = 2 };
-struct TrainRoute {
-    bool fused_lc;      // tr_layer_fwdc / bwd1<true> / bwd2c on frame-rate lc projections; else the materialised upsampler + the <false> kernels
-    bool skinny;        // tr_skinny_nn_kernel for conv1d_2; else rocBLAS + tr_bias_add_kernel
+// What the training step adds to the shared route (wavenet_route, twv_wavenet_graph.hpp): create, loss_grad (the dispatch) and
+// twv_wavenet_train_route (the label a test reads) all call tr_route.
+struct TrainRoute : WavenetRoute {
     bool fuse_c2;       // tr_conv2_bwd_kernel (dC1, db1, dW2 in one pass; conv1d_1's relu applied by its readers)
-    int loss;           // TR_LOSS_*
     int nsplit;         // K slabs (whole batch entries) of the wide weight gradients
 };
-static TrainRoute tr_route(const twv_wavenet_dims& d, int batch, int n_samples)
+static TrainRoute tr_route(const WavenetGraph& g)
 {
     TrainRoute r;
-    int hop = 1;
-    for (int i = 0; i < d.n_upsample; ++i) hop *= d.upsample_factor[i];
-    r.fused_lc = d.n_upsample == 3 && hop >= 32 && hop <= 512 && d.lc_channels == 80;
-    int rf = (d.scalar_input ? d.initial_filter_width : 2);           // model.py:31-39
-    for (int l = 0; l < d.n_layers; ++l) rf += d.dilations[l];
-    const long long RO = (long long)batch * (n_samples - rf);
-    const int S = d.skip_channels, O = d.scalar_input ? d.out_channels : d.quantization_channels;
-    r.skinny = O <= 32 && (S & 63) == 0 && S * 32 * 4 <= 64 * 1024 && RO * S * 4 < (1LL << 31);
-    r.fuse_c2 = r.skinny && (S & 63) == 0 && 2048 % (S >> 6) == 0;      // (`part`: 2048 x 64 floats)
-    r.loss = !d.scalar_input ? TR_LOSS_SOFTMAX : (O / 3 == 10 ? TR_LOSS_MOL10 : TR_LOSS_MOLN);
+    static_cast<WavenetRoute&>(r) = wavenet_route(g);
+    r.fuse_c2 = r.skinny && (g.S & 63) == 0 && 2048 % (g.S >> 6) == 0;      // (`part`: 2048 x 64 floats)
     r.nsplit = 1;
-    for (int c = 2; c <= 16 && c <= batch; ++c) if (batch % c == 0) r.nsplit = c;   // slabs of whole batch entries: RO = B * ow rows
+    for (int c = 2; c <= 16 && c <= g.rows; ++c) if (g.rows % c == 0) r.nsplit = c;   // slabs of whole batch entries: RO = B * ow rows
     return r;
 }
 
@@ -1893,10 +1785,10 @@ struct TrainCarve {
     float *ctab, *melsh, *Qall, *Dbuf, *dctab, *PTall, *Rall, *tsum, *dGCPall, *bsum64;
     long long vstride, slab_ls, q_ls, pt_ls, tsum_ls;
 };
-static long long tr_carve(const twv_wavenet_trainer* h, float* base, TrainCarve& c)
+static long long tr_carve(const WavenetGraph* h, float* base, TrainCarve& c)
 {
     const twv_wavenet_dims& d = h->d;
-    const int B = h->B, T = h->T, Tn = h->Tn, NL = h->NL, S = h->S, O = h->O, L = h->L, G = h->G, ow = h->ow;
+    const int B = h->rows, T = h->T, Tn = h->Tn, NL = h->NL, S = h->S, O = h->O, L = h->L, G = h->G, ow = h->ow;
     const long long Rr = (long long)B * Tn, RT = (long long)B * T, RO = (long long)B * ow;
     long long used = 0;
     auto take = [&](long long n) { float* p = base ? base + used : nullptr; used += (n + 63) / 64 * 64; return p; };
@@ -1946,66 +1838,24 @@ static long long tr_carve(const twv_wavenet_trainer* h, float* base, TrainCarve&
 
 extern "C" int twv_wavenet_train_create(const twv_wavenet_dims* dims, int batch, int n_samples, twv_wavenet_trainer** out)
 {
-    if (dims && dims->gc_channels > 0 && dims->gc_cardinality < 1)
-        return twv_fail(TWV_E_UNSUPPORTED, "training needs global_condition_cardinality (the gc_embedding table is a trained variable; model.py:191-195)");
-    if (!dims || !out || batch < 1) return twv_fail(TWV_E_INVALID, "bad argument");
-    const twv_wavenet_dims& d = *dims;
-    if (d.n_layers < 1 || d.n_layers > TWV_MAX_LAYERS || d.n_upsample < 0 || d.n_upsample > 4) return twv_fail(TWV_E_INVALID, "bad dims");
-    // only the FUSED layer kernels (tr_layer_fwdc_kernel / tr_layer_bwd2c_kernel: three upsampling stages, 32 <= hop <= 512, 80 mel
-    // channels: tr_route) address a layer's activations with 32-bit byte offsets; the pointer kernels of every other model keep 64-bit
-    // addresses and take any size
-    if (tr_route(d, batch, n_samples).fused_lc && (long long)batch * n_samples * 64 * 4 >= (1LL << 31))
-        return twv_fail(TWV_E_UNSUPPORTED, "batch x samples too large: the fused layer kernels address a layer's activations with 32-bit byte offsets (batch * samples < 8.3 M)");
-    if (d.residual_channels != 32 || d.dilation_channels != 32) return twv_fail(TWV_E_UNSUPPORTED, "training is built for residual_channels = dilation_channels = 32 only: training at other widths is not built");
-    if (d.scalar_input && (d.out_channels % 3 || d.out_channels > 96)) return twv_fail(TWV_E_UNSUPPORTED, "out_channels must be 3*nr_mix <= 96");
-    if (!d.scalar_input && (d.quantization_channels < 2 || d.quantization_channels > 512)) return twv_fail(TWV_E_UNSUPPORTED, "quantization_channels must be in [2, 512] for training");
-    if (d.lc_channels != 80 || !d.gc_channels) return twv_fail(TWV_E_UNSUPPORTED, "the training step expects num_mels = 80 local and global conditioning (train_vocoder.py, hparams.py:30)");
+    if (!out) return twv_fail(TWV_E_INVALID, "bad argument");
     twv_wavenet_trainer* h = new twv_wavenet_trainer();
-    h->d = d; h->B = batch; h->T = n_samples; h->Tn = n_samples - 1; h->NL = d.n_layers; h->S = d.skip_channels; h->O = d.scalar_input ? d.out_channels : d.quantization_channels;
-    h->L = d.lc_channels; h->G = d.gc_channels; h->ifw = d.scalar_input ? d.initial_filter_width : 2;   // model.py:36-39
-    h->hop = 1;
-    for (int i = 0; i < d.n_upsample; ++i) h->hop *= d.upsample_factor[i];
-    if (n_samples % h->hop) { delete h; return twv_fail(TWV_E_INVALID, "n_samples must be a multiple of the hop size (datafeeder_wavenet.py:41-47)"); }
-    h->off[0] = h->ifw - 1;
-    for (int l = 0; l < h->NL; ++l) h->off[l + 1] = h->off[l] + d.dilations[l];
-    h->rf = h->off[h->NL] + 1;
-    h->ow = n_samples - h->rf;                                        // model.py:135 output_width
-    if (h->ow < 1) { delete h; return twv_fail(TWV_E_INVALID, "n_samples must exceed the receptive field"); }
-    // canonical blob offsets (same order as weights.tensor_specs / the generation path)
-    long long c = 0;
-    const int R = 32, D = 32, ub = d.use_biases ? 1 : 0;
-    h->c_causal = c; c += d.scalar_input ? (long long)h->ifw * R : 2LL * d.quantization_channels * R;
-    h->c_gcemb = c; c += (long long)d.gc_cardinality * h->G;
-    h->c_layer0 = c;
-    long long q = 0;
-    h->lo.wf = q; q += 2 * R * D; h->lo.bf = q; q += ub * D;
-    h->lo.wg = q; q += 2 * R * D; h->lo.bg = q; q += ub * D;
-    h->lo.gcf = q; q += (long long)h->G * D; h->lo.gcg = q; q += (long long)h->G * D;
-    h->lo.lcf = q; q += (long long)h->L * D; h->lo.lcg = q; q += (long long)h->L * D;
-    h->lo.wd = q; q += D * R; h->lo.bd = q; q += ub * R;
-    h->lo.ws = q; q += (long long)D * h->S; h->lo.bs = q; q += (long long)ub * h->S;
-    h->c_lstride = q; c += q * h->NL;
-    h->c_w1 = c; c += (long long)h->S * h->S; h->c_b1 = c; c += (long long)ub * h->S;
-    h->c_w2 = c; c += (long long)h->S * h->O; h->c_b2 = c; c += (long long)ub * h->O;
-    for (int i = 0; i < d.n_upsample; ++i) { h->c_up[i] = c; c += (long long)d.upsample_factor[i] * 2; }
-    h->nparams = c;
+    const int rc = wavenet_graph_init(h->g, dims, batch, n_samples, "training");
+    if (rc) { delete h; return rc; }
     h->blas = nullptr;
     h->ws_clean = nullptr;
     // workspace: exactly what loss_grad carves (tr_carve on a null base), then twv_wavenet_train_l2's scratch
     TrainCarve sizes;
-    long long f = h->carve_floats = tr_carve(h, nullptr, sizes);
+    long long f = h->carve_floats = tr_carve(&h->g, nullptr, sizes);
     // twv_wavenet_train_l2's scratch (nparams squares + the partial sums) has a region of its OWN behind everything loss_grad carves: at
     // the start of the workspace it overwrote rows that the fused layer kernels rely on staying zero (the rows in front of a layer's
     // receptive offset are cleared once and never written again) -- harmless only while every gradient is finite
     h->l2_off = f;
-    f += (h->nparams + 63) / 64 * 64 + 1024;
+    f += (h->g.nparams + 63) / 64 * 64 + 1024;
     h->ws_floats = f;
-    {
-        const TrainRoute r = tr_route(d, batch, n_samples);
-        h->route = std::string("lc=") + (r.fused_lc ? "fused" : "staged") + " head=" + (r.fuse_c2 ? "skinny+c2bwd" : r.skinny ? "skinny" : "gemm") +
-                   " loss=" + (r.loss == TR_LOSS_MOL10 ? "mol<10>" : r.loss == TR_LOSS_MOLN ? "mol<0>" : "softmax") + " nsplit=" + std::to_string(r.nsplit) +
-                   " carve_floats=" + std::to_string(h->carve_floats);
-    }
+    const TrainRoute r = tr_route(h->g);
+    h->route = wavenet_route_label(r, r.fuse_c2 ? "skinny+c2bwd" : r.skinny ? "skinny" : "gemm") + " nsplit=" + std::to_string(r.nsplit) +
+               " carve_floats=" + std::to_string(h->carve_floats);
     *out = h;
     return TWV_OK;
 }
@@ -2020,10 +1870,78 @@ extern "C" int twv_wavenet_train_reset_workspace(twv_wavenet_trainer* h)
     h->ws_clean = nullptr;                                // the next twv_wavenet_train_loss_grad clears whatever workspace it is given
     return TWV_OK;
 }
-extern "C" size_t twv_wavenet_train_param_floats(const twv_wavenet_trainer* h) { return (size_t)h->nparams; }
+extern "C" size_t twv_wavenet_train_param_floats(const twv_wavenet_trainer* h) { return (size_t)h->g.nparams; }
 extern "C" size_t twv_wavenet_train_workspace_bytes(const twv_wavenet_trainer* h) { return (size_t)h->ws_floats * 4; }
-extern "C" int twv_wavenet_train_output_width(const twv_wavenet_trainer* h) { return h->ow; }
+extern "C" int twv_wavenet_train_output_width(const twv_wavenet_trainer* h) { return h->g.ow; }
 extern "C" const char* twv_wavenet_train_route(const twv_wavenet_trainer* h) { return h ? h->route.c_str() : ""; }
+
+#define K1(kern, n, ...) hipLaunchKernelGGL(kern, dim3(tg(n)), dim3(256), 0, st, __VA_ARGS__)
+// The forward front and head (twv_wavenet_graph.hpp): the training step and scoring (twv_score.hip) both launch exactly these
+int wavenet_forward_front(const WavenetGraph& g, const float* P, const float* audio, const int32_t* gc_ids, const WavenetFwdBufs& b,
+                          rocblas_handle bl, hipStream_t st)
+{
+    const twv_wavenet_dims& d = g.d;
+    const int B = g.rows, T = g.T, Tn = g.Tn, NL = g.NL, S = g.S, L = g.L, G = g.G, F = g.F;
+    const long long Rr = (long long)B * Tn, RT = (long long)B * T;
+    const bool fused_lc = wavenet_route(g).fused_lc;
+    const float one = 1.0f, zero = 0.0f;
+    K1(tr_views_kernel, (b.vstride + 32LL * S) * NL, const_cast<float*>(P), b.WV, b.WS, NL, g.c_layer0, g.c_lstride, g.lo.wf, g.lo.wg, g.lo.lcf, g.lo.lcg,
+       g.lo.gcf, g.lo.gcg, g.lo.ws, L, G, S, 0);
+    for (int i = 0; i < d.n_upsample && !fused_lc; ++i)     // model.py:276 create_upsample (the fused lc path never materialises it)
+        K1(tr_up_fwd_kernel, (long long)B * b.upT[i + 1] * L, P + g.c_up[i], b.ups[i], b.ups[i + 1], (long long)B * b.upT[i + 1] * L, d.upsample_factor[i], L);
+    K1(tr_gather_emb_kernel, (long long)B * G, P + g.c_gcemb, gc_ids, b.emb, B, G);   // model.py:197-198
+    if (d.scalar_input) {
+        K1(tr_unfold_kernel, Rr * g.ifw, audio, b.xunf, B, T, Tn, g.ifw);
+        BLASCHK(gemm_rm(bl, false, false, (int)Rr, 32, g.ifw, 1.f, b.xunf, g.ifw, P + g.c_causal, 32, 0.f, b.X0, 32));   // model.py:131
+    } else {
+        if (int rc = twv_mu_law_encode(audio, RT, d.quantization_channels, b.qin, st)) return rc;                        // model.py:257
+        K1(tr_onehot_causal_fwd_kernel, Rr * 32, P + g.c_causal, b.qin, b.X0, B, T, Tn, d.quantization_channels);
+    }
+    if (fused_lc) {
+        // per step: the hop's tap table from the three upsampling kernels, the bin-shifted mel frames, and every layer's frame-rate
+        // lc projections Q_l = melsh (B*F*4 x 80) . Wlc_l (80 x 64) as one strided-batched GEMM
+        K1(tr_ctab_kernel, g.hop, P + g.c_up[0], P + g.c_up[1], P + g.c_up[2], d.upsample_factor[0], d.upsample_factor[1], d.upsample_factor[2], b.ctab);
+        K1(tr_mel_shift_kernel, (long long)B * F * 4 * L, b.ups[0], b.melsh, (long long)B * F, L);
+        BLASCHK(rocblas_sgemm_strided_batched(bl, rocblas_operation_none, rocblas_operation_none, 64, B * F * 4, L, &one, b.WV + 64 * 64, 64, b.vstride,
+                                              b.melsh, L, 0, &zero, b.Qall, 64, b.q_ls + 64, NL));
+    }
+    // model.py:71-73 gc projections of every layer: GCP[l] (B x 64) = emb (B x G) . Wgc_l (G x 64)
+    BLASCHK(rocblas_sgemm_strided_batched(bl, rocblas_operation_none, rocblas_operation_none, 64, B, G, &one, b.WV + (64 + L) * 64, 64, b.vstride,
+                                          b.emb, G, 0, &zero, b.GCP, 64, (long long)B * 64, NL));
+    return TWV_OK;
+}
+// model.py:94-96,150-165: sum over layers of the skip 1x1 convs == ONE GEMM against the stacked skip kernels, then
+// (+ all skip biases) relu -> 1x1 -> relu -> 1x1
+int wavenet_forward_head(const WavenetGraph& g, const float* P, const WavenetFwdBufs& b, bool skinny, bool c1_raw, rocblas_handle bl, hipStream_t st)
+{
+    const int NL = g.NL, S = g.S, O = g.O, ZW = NL * 32;
+    const long long RO = (long long)g.rows * g.ow;
+    const bool ub = g.d.use_biases != 0;
+    const float* bs0 = P + g.c_layer0 + g.lo.bs;            // layer 0's skip bias; layer l's lies l * c_lstride behind it
+    if (c1_raw) HIPCHK(hipFuncSetAttribute((const void*)tr_skinny_nn_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
+    BLASCHK(gemm_rm(bl, false, false, (int)RO, S, ZW, 1.f, b.ZC, ZW, b.WS, S, 0.f, b.SK, S));
+    if ((S & 3) == 0) {
+        if (ub) K1(tr_bias_sum_kernel, S, bs0, NL, g.c_lstride, b.bsum, S);
+        K1(tr_bias_relu4_kernel, RO * S / 4, (float4*)b.SK, ub ? (const float4*)b.bsum : nullptr, S / 4, RO * S / 4);
+    } else {
+        K1(tr_bias_relu_kernel, RO * S, b.SK, ub ? bs0 : nullptr, ub ? NL : 0, g.c_lstride, nullptr, S, RO * S);
+    }
+    BLASCHK(gemm_rm(bl, false, false, (int)RO, S, S, 1.f, b.SK, S, P + g.c_w1, S, 0.f, b.C1, S));
+    // conv1d_1's activation: with c1_raw the relu(. + b1) pass over the (RO, S) array is never run -- its readers (the skinny projection
+    // here; in the training step conv1d_2's fused backward: mask of dC1 and operand of dW2) apply it to what they load
+    if (!c1_raw) {
+        if ((S & 3) == 0 && (g.c_b1 & 3) == 0) K1(tr_bias_relu4_kernel, RO * S / 4, (float4*)b.C1, ub ? (const float4*)(P + g.c_b1) : nullptr, S / 4, RO * S / 4);
+        else K1(tr_bias_relu_kernel, RO * S, b.C1, nullptr, 0, 0, ub ? P + g.c_b1 : nullptr, S, RO * S);
+    }
+    if (skinny) {
+        if (c1_raw) hipLaunchKernelGGL(tr_skinny_nn_kernel<true>, dim3(1024), dim3(256), (size_t)S * 33 * 4, st, b.C1, S, P + g.c_w2, O, ub ? P + g.c_b2 : nullptr, RO, S, O, b.Y, O, ub ? P + g.c_b1 : nullptr);
+        else hipLaunchKernelGGL(tr_skinny_nn_kernel<false>, dim3(1024), dim3(256), (size_t)S * 32 * 4, st, b.C1, S, P + g.c_w2, O, ub ? P + g.c_b2 : nullptr, RO, S, O, b.Y, O, (const float*)nullptr);
+    } else {
+        BLASCHK(gemm_rm(bl, false, false, (int)RO, O, S, 1.f, b.C1, S, P + g.c_w2, O, 0.f, b.Y, O));
+        if (ub) K1(tr_bias_add_kernel, RO * O, b.Y, P + g.c_b2, O, RO * O);
+    }
+    return TWV_OK;
+}
 
 extern "C" int twv_wavenet_train_loss_grad(twv_wavenet_trainer* h, const float* params, const float* audio, const float* lc,
                                            const int32_t* gc_ids, void* workspace, float* loss, float* grads, void* stream)
@@ -2034,20 +1952,21 @@ extern "C" int twv_wavenet_train_loss_grad(twv_wavenet_trainer* h, const float* 
     BLASCHK(rocblas_set_stream(h->blas, st));
     BLASCHK(rocblas_set_pointer_mode(h->blas, rocblas_pointer_mode_host));
     rocblas_handle bl = h->blas;
-    const twv_wavenet_dims& d = h->d;
-    const int B = h->B, T = h->T, Tn = h->Tn, NL = h->NL, S = h->S, O = h->O, L = h->L, G = h->G, ow = h->ow, rf = h->rf, nr = O / 3;
+    const WavenetGraph& g = h->g;
+    const twv_wavenet_dims& d = g.d;
+    const int B = g.rows, T = g.T, Tn = g.Tn, NL = g.NL, S = g.S, O = g.O, L = g.L, G = g.G, ow = g.ow, rf = g.rf, nr = O / 3;
     const long long Rr = (long long)B * Tn, RT = (long long)B * T, RO = (long long)B * ow;
     const bool ub = d.use_biases != 0;
     const float* P = params;
     float* Gd = grads;
     // ---- workspace carve (tr_carve: the function create sized the workspace with), checked BEFORE the first device operation
     TrainCarve cv;
-    if (tr_carve(h, (float*)workspace, cv) != h->carve_floats || h->carve_floats > h->l2_off || h->l2_off > h->ws_floats)
+    if (tr_carve(&g, (float*)workspace, cv) != h->carve_floats || h->carve_floats > h->l2_off || h->l2_off > h->ws_floats)
         return twv_fail(TWV_E_INVALID, "internal: the workspace carve does not match the size twv_wavenet_train_create computed");
-    const TrainRoute route = tr_route(d, B, T);
+    const TrainRoute route = tr_route(g);
     const bool fused_lc = route.fused_lc;
     const int nsplit = route.nsplit;
-    HIPCHK(hipMemsetAsync(grads, 0, (size_t)h->nparams * 4, st));
+    HIPCHK(hipMemsetAsync(grads, 0, (size_t)g.nparams * 4, st));
     HIPCHK(hipMemsetAsync(loss, 0, 4, st));
     // A workspace seen for the first time is cleared once: the layer kernels do not walk the tiles in front of a layer's receptive offset,
     // and masked rows of the tiles they do walk may read those rows as operands of products with zero (0 x NaN would not be zero).
@@ -2069,15 +1988,13 @@ extern "C" int twv_wavenet_train_loss_grad(twv_wavenet_trainer* h, const float* 
     float *zpage = cv.zpage, *kpart = cv.kpart, *wpart = cv.wpart, *ctab = cv.ctab, *melsh = cv.melsh, *Qall = cv.Qall, *Dbuf = cv.Dbuf, *dctab = cv.dctab;
     float *PTall = cv.PTall, *Rall = cv.Rall, *tsum = cv.tsum, *dGCPall = cv.dGCPall, *bsum64 = cv.bsum64;
     const long long vstride = cv.vstride, slab_ls = cv.slab_ls, q_ls = cv.q_ls, pt_ls = cv.pt_ls, tsum_ls = cv.tsum_ls;
-    const int F = T / h->hop;                                // mel frames per entry
+    const int F = T / g.hop;                                // mel frames per entry
     HIPCHK(hipMemsetAsync(zpage, 0, 4096, st));
     HIPCHK(hipFuncSetAttribute((const void*)tr_layer_bwd1_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * BS_FLOATS * 4));
     HIPCHK(hipFuncSetAttribute((const void*)tr_layer_bwd1_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (4 * BS_FLOATS + 2048) * 4));
-    HIPCHK(hipFuncSetAttribute((const void*)tr_skinny_nn_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
     int rc = TWV_OK;
-#define K1(kern, n, ...) hipLaunchKernelGGL(kern, dim3(tg(n)), dim3(256), 0, st, __VA_ARGS__)
-#define LP(l) (P + h->c_layer0 + (long long)(l) * h->c_lstride)
-#define LG(l) (Gd + h->c_layer0 + (long long)(l) * h->c_lstride)
+#define LP(l) (P + g.c_layer0 + (long long)(l) * g.c_lstride)
+#define LG(l) (Gd + g.c_layer0 + (long long)(l) * g.c_lstride)
     // out[seg][c] = column sums of x (nseg slabs of `rows` rows); deterministic two-stage reduction
     auto colsum = [&](const float* x, long long rows, int C, int ldx, int nseg, float* out, int ldo) {
         int nchunk = (int)(rows / 256); const int cap = nseg > 8 ? 32 : 256; nchunk = nchunk < 1 ? 1 : (nchunk > cap ? cap : nchunk);
@@ -2106,44 +2023,24 @@ extern "C" int twv_wavenet_train_loss_grad(twv_wavenet_trainer* h, const float* 
     };
     do {
         // ================= forward =================
-        K1(tr_views_kernel, (vstride + 32LL * S) * NL, const_cast<float*>(P), WV, WS, NL, h->c_layer0, h->c_lstride, h->lo.wf, h->lo.wg, h->lo.lcf, h->lo.lcg,
-           h->lo.gcf, h->lo.gcg, h->lo.ws, L, G, S, 0);
-        for (int i = 0; i < d.n_upsample && !fused_lc; ++i)     // model.py:276 create_upsample (the fused lc path never materialises it)
-            K1(tr_up_fwd_kernel, (long long)B * upT[i + 1] * L, P + h->c_up[i], ups[i], ups[i + 1], (long long)B * upT[i + 1] * L, d.upsample_factor[i], L);
-        K1(tr_gather_emb_kernel, (long long)B * G, P + h->c_gcemb, gc_ids, emb, B, G);   // model.py:197-198
-        if (d.scalar_input) {
-            K1(tr_unfold_kernel, Rr * h->ifw, audio, xunf, B, T, Tn, h->ifw);
-            if ((rc = gemm_rm(bl, false, false, (int)Rr, 32, h->ifw, 1.f, xunf, h->ifw, P + h->c_causal, 32, 0.f, X[0], 32))) break;   // model.py:131
-        } else {
-            if ((rc = twv_mu_law_encode(audio, RT, d.quantization_channels, qin, st))) break;                                         // model.py:257
-            K1(tr_onehot_causal_fwd_kernel, Rr * 32, P + h->c_causal, qin, X[0], B, T, Tn, d.quantization_channels);
-        }
-        if (fused_lc) {
-            // per step: the hop's tap table from the three upsampling kernels, the bin-shifted mel frames, and every layer's frame-rate
-            // lc projections Q_l = melsh (B*F*4 x 80) . Wlc_l (80 x 64) as one strided-batched GEMM
-            K1(tr_ctab_kernel, h->hop, P + h->c_up[0], P + h->c_up[1], P + h->c_up[2], d.upsample_factor[0], d.upsample_factor[1], d.upsample_factor[2], ctab);
-            K1(tr_mel_shift_kernel, (long long)B * F * 4 * L, lc, melsh, (long long)B * F, L);
-            const float one = 1.0f, zero = 0.0f;
-            rc |= rocblas_sgemm_strided_batched(bl, rocblas_operation_none, rocblas_operation_none, 64, B * F * 4, L, &one, WV + 64 * 64, 64, vstride,
-                                                melsh, L, 0, &zero, Qall, 64, q_ls + 64, NL);
-            if (rc) break;
-        }
-        {   // model.py:71-73 gc projections of every layer: GCP[l] (B x 64) = emb (B x G) . Wgc_l (G x 64)
-            const float one = 1.0f, zero = 0.0f;
-            rc |= rocblas_sgemm_strided_batched(bl, rocblas_operation_none, rocblas_operation_none, 64, B, G, &one, WV + (64 + L) * 64, 64, vstride,
-                                                emb, G, 0, &zero, GCP, 64, (long long)B * 64, NL);
-            if (rc) break;
-        }
+        WavenetFwdBufs fb;
+        for (int i = 0; i < 5; ++i) fb.ups[i] = ups[i];
+        fb.upT = cv.upT; fb.xunf = cv.xunf; fb.qin = qin;
+        fb.X0 = X[0]; fb.emb = emb; fb.GCP = GCP; fb.WV = WV; fb.WS = WS; fb.ctab = ctab; fb.melsh = melsh; fb.Qall = Qall;
+        fb.vstride = vstride; fb.q_ls = q_ls;
+        fb.ZC = ZC; fb.SK = SK; fb.C1 = C1; fb.Y = Y;
+        fb.bsum = part;                                       // S floats; `part` is free between the column sums
+        if (int frc = wavenet_forward_front(g, P, audio, gc_ids, fb, bl, st)) return frc;
         for (int l = 0; l < NL && !rc; ++l) {
-            const int dl = d.dilations[l], o = h->off[l + 1];
+            const int dl = d.dilations[l], o = g.off[l + 1];
             const float* Lp = LP(l);
             const float* Wv = WV + l * vstride;                 // tap0 | tap1 | lc | gc views, 64 columns = filter|gate
             // model.py:71-73 gc projection (tiny), then the fused layer: conv_filter | conv_gate taps, lc projection, gated unit,
             // dense + residual, skip input slice
             float* gcp = GCP + (long long)l * B * 64;                // all layers' projections: one strided-batched GEMM before the loop
             LayerFwdArgs fa;
-            fa.X = X[l]; fa.U = U; fa.gcp = gcp; fa.W0 = Wv; fa.W1 = Wv + 32 * 64; fa.Wlc = Wv + 64 * 64; fa.Wd = Lp + h->lo.wd;
-            fa.bf = ub ? Lp + h->lo.bf : nullptr; fa.bg = ub ? Lp + h->lo.bg : nullptr; fa.bd = ub ? Lp + h->lo.bd : nullptr;
+            fa.X = X[l]; fa.U = U; fa.gcp = gcp; fa.W0 = Wv; fa.W1 = Wv + 32 * 64; fa.Wlc = Wv + 64 * 64; fa.Wd = Lp + g.lo.wd;
+            fa.bf = ub ? Lp + g.lo.bf : nullptr; fa.bg = ub ? Lp + g.lo.bg : nullptr; fa.bd = ub ? Lp + g.lo.bd : nullptr;
             fa.TH = TH[l]; fa.SG = SG[l]; fa.XN = X[l + 1]; fa.ZC = ZC + l * 32;
             fa.B = B; fa.T = T; fa.Tn = Tn; fa.d = dl; fa.o = o; fa.ow = ow; fa.ldz = ZW; fa.tpb = (Tn + 31) / 32;
             // Rows t < o of this layer's output do not exist in the reference ('valid' convolutions, model.py:71-96: every layer is d
@@ -2156,70 +2053,48 @@ extern "C" int twv_wavenet_train_loss_grad(twv_wavenet_trainer* h, const float* 
                 const int ntiles = B * fa.tpb;
                 int nwg = (ntiles + 7) / 8; nwg = nwg > 256 ? 256 : nwg;      // one workgroup (8 waves, 2 per SIMD) per CU, each wave walks its tiles
                 int nwgc = (ntiles + kFwdcWaves - 1) / kFwdcWaves; nwgc = nwgc > 256 ? 256 : nwgc;
-                fa.Q = Qall + l * (q_ls + 64); fa.ctab = ctab; fa.hop = h->hop; fa.F = F;
+                fa.Q = Qall + l * (q_ls + 64); fa.ctab = ctab; fa.hop = g.hop; fa.F = F;
                 if (fused_lc) hipLaunchKernelGGL(tr_layer_fwdc_kernel, dim3(nwgc), dim3(kFwdcWaves * 64), 0, st, fa);
-                else hipLaunchKernelGGL(tr_layer_fwd_kernel<false>, dim3(nwg), dim3(512), 0, st, fa);
+                else hipLaunchKernelGGL(tr_layer_fwd_kernel, dim3(nwg), dim3(512), 0, st, fa);
             }
         }
         if (rc) break;
-        // model.py:94-96,150-165: sum over layers of the skip 1x1 convs == ONE GEMM against the stacked skip kernels, then
-        // (+ all skip biases) relu -> 1x1 -> relu -> 1x1
-        if ((rc = gemm_rm(bl, false, false, (int)RO, S, ZW, 1.f, ZC, ZW, WS, S, 0.f, SK, S))) break;
-        if ((S & 3) == 0) {
-            float* bsum = part;                                   // S floats; `part` is free between the column sums
-            if (ub) K1(tr_bias_sum_kernel, S, LP(0) + h->lo.bs, NL, h->c_lstride, bsum, S);
-            K1(tr_bias_relu4_kernel, RO * S / 4, (float4*)SK, ub ? (const float4*)bsum : nullptr, S / 4, RO * S / 4);
-        } else {
-            K1(tr_bias_relu_kernel, RO * S, SK, ub ? LP(0) + h->lo.bs : nullptr, ub ? NL : 0, h->c_lstride, nullptr, S, RO * S);
-        }
-        if ((rc = gemm_rm(bl, false, false, (int)RO, S, S, 1.f, SK, S, P + h->c_w1, S, 0.f, C1, S))) break;
-        // conv1d_1's activation: with the skinny output projection (MoL head) the relu(. + b1) pass over the (RO, S) array is never run --
-        // its readers (the projection forward; conv1d_2's fused backward: mask of dC1 and operand of dW2) apply it to what they load
-        const bool skinny = route.skinny, fuse_c2 = route.fuse_c2;           // (tr_route)
-        const bool c1_raw = fuse_c2;
-        const float* b1p = ub ? P + h->c_b1 : nullptr;
-        if (!c1_raw) {
-            if ((S & 3) == 0 && (h->c_b1 & 3) == 0) K1(tr_bias_relu4_kernel, RO * S / 4, (float4*)C1, ub ? (const float4*)(P + h->c_b1) : nullptr, S / 4, RO * S / 4);
-            else K1(tr_bias_relu_kernel, RO * S, C1, nullptr, 0, 0, ub ? P + h->c_b1 : nullptr, S, RO * S);
-        }
-        if (skinny) {
-            if (c1_raw) hipLaunchKernelGGL(tr_skinny_nn_kernel<true>, dim3(1024), dim3(256), (size_t)S * 33 * 4, st, C1, S, P + h->c_w2, O, ub ? P + h->c_b2 : nullptr, RO, S, O, Y, O, b1p);
-            else hipLaunchKernelGGL(tr_skinny_nn_kernel<false>, dim3(1024), dim3(256), (size_t)S * 32 * 4, st, C1, S, P + h->c_w2, O, ub ? P + h->c_b2 : nullptr, RO, S, O, Y, O, (const float*)nullptr);
-        } else {
-            if ((rc = gemm_rm(bl, false, false, (int)RO, O, S, 1.f, C1, S, P + h->c_w2, O, 0.f, Y, O))) break;
-            if (ub) K1(tr_bias_add_kernel, RO * O, Y, P + h->c_b2, O, RO * O);
-        }
+        // head: conv1d_1's relu pass is skipped only when conv1d_2's fused backward reads the pre-activations (tr_route); at S = 192 the
+        // skinny projection runs on activated C1
+        const bool fuse_c2 = route.fuse_c2;
+        const float* b1p = ub ? P + g.c_b1 : nullptr;
+        if (int hrc = wavenet_forward_head(g, P, fb, route.skinny, fuse_c2, bl, st)) return hrc;
         // model.py:286-290 loss
         // per-row terms, then the same two-stage column sum as the bias gradients: the loss is bit-reproducible run to run
         float* row_loss = dS;                                       // (RO) scratch: dS is not written before the backward pass
-        if (route.loss == TR_LOSS_MOL10) K1(tr_mol_loss_kernel<10>, RO, Y, audio, B, T, ow, rf, nr, 1.0f / (float)RO, row_loss, dY);
-        else if (route.loss == TR_LOSS_MOLN) K1(tr_mol_loss_kernel<0>, RO, Y, audio, B, T, ow, rf, nr, 1.0f / (float)RO, row_loss, dY);
+        if (route.loss == WG_LOSS_MOL10) K1(tr_mol_loss_kernel<10>, RO, Y, audio, B, T, ow, rf, nr, 1.0f / (float)RO, row_loss, dY);
+        else if (route.loss == WG_LOSS_MOLN) K1(tr_mol_loss_kernel<0>, RO, Y, audio, B, T, ow, rf, nr, 1.0f / (float)RO, row_loss, dY);
         else hipLaunchKernelGGL(tr_softmax_ce_kernel, dim3(tg(RO * 64)), dim3(256), 0, st, Y, qin, B, T, ow, rf, O, 1.0f / (float)RO, row_loss, dY);
         colsum(row_loss, RO, 1, 1, 1, loss, 1);
         // ================= backward =================
-        if (!fuse_c2) wgrad(C1, S, dY, O, RO, S, O, Gd + h->c_w2, O);                                              // dW2 = H2^T dY (the tall-skinny MFMA kernel)
-        if (ub) colsum(dY, RO, O, O, 1, Gd + h->c_b2, O);
+        if (!fuse_c2) wgrad(C1, S, dY, O, RO, S, O, Gd + g.c_w2, O);                                              // dW2 = H2^T dY (the tall-skinny MFMA kernel)
+        if (ub) colsum(dY, RO, O, O, 1, Gd + g.c_b2, O);
         if (fuse_c2) {                                                                                           // dC1, db1 and dW2: one pass
             const int nwg = 512, nchunk = nwg * 4 / (S >> 6);             // two workgroups per CU (171 registers; at three, 168 + spills: 276 vs 263 us)
-            hipLaunchKernelGGL(tr_conv2_bwd_kernel, dim3(nwg), dim3(256), 0, st, dY, O, P + h->c_w2, C1, b1p, RO, S, dS, part, wpart);
-            if (ub) hipLaunchKernelGGL(tr_colsum_final_kernel, dim3((S + 63) / 64), dim3(256), 0, st, part, nchunk, S, 1, Gd + h->c_b1, S);
-            hipLaunchKernelGGL(tr_tn_reduce_kernel, dim3((S * O + 63) / 64), dim3(1024), 0, st, wpart, nchunk, S, 32, S, O, Gd + h->c_w2, O);
+            hipLaunchKernelGGL(tr_conv2_bwd_kernel, dim3(nwg), dim3(256), 0, st, dY, O, P + g.c_w2, C1, b1p, RO, S, dS, part, wpart);
+            if (ub) hipLaunchKernelGGL(tr_colsum_final_kernel, dim3((S + 63) / 64), dim3(256), 0, st, part, nchunk, S, 1, Gd + g.c_b1, S);
+            hipLaunchKernelGGL(tr_tn_reduce_kernel, dim3((S * O + 63) / 64), dim3(1024), 0, st, wpart, nchunk, S, 32, S, O, Gd + g.c_w2, O);
         } else {
-            rc |= gemm_rm(bl, false, true, (int)RO, S, O, 1.f, dY, O, P + h->c_w2, O, 0.f, dS, S);               // dH2
-            if (ub) relu_bwd_colsum(dS, C1, RO, S, Gd + h->c_b1);                                                // dC1, db1
+            rc |= gemm_rm(bl, false, true, (int)RO, S, O, 1.f, dY, O, P + g.c_w2, O, 0.f, dS, S);               // dH2
+            if (ub) relu_bwd_colsum(dS, C1, RO, S, Gd + g.c_b1);                                                // dC1, db1
             else if ((S & 3) == 0) K1(tr_relu_bwd4_kernel, RO * S / 4, (float4*)dS, (const float4*)C1, RO * S / 4);
             else K1(tr_relu_bwd_kernel, RO * S, dS, C1, RO * S);
         }
-        rc |= gemm_tn_splitk(bl, st, S, S, RO, SK, S, dS, S, Gd + h->c_w1, S, nsplit, kpart);                     // dW1 = H1^T dC1
-        rc |= gemm_rm(bl, false, true, (int)RO, S, S, 1.f, dS, S, P + h->c_w1, S, 0.f, C1, S);                   // dH1 -> C1 buffer
-        if (ub) relu_bwd_colsum(C1, SK, RO, S, LG(0) + h->lo.bs);                                                 // dSK, dbs (layer 0's slot)
+        rc |= gemm_tn_splitk(bl, st, S, S, RO, SK, S, dS, S, Gd + g.c_w1, S, nsplit, kpart);                     // dW1 = H1^T dC1
+        rc |= gemm_rm(bl, false, true, (int)RO, S, S, 1.f, dS, S, P + g.c_w1, S, 0.f, C1, S);                   // dH1 -> C1 buffer
+        if (ub) relu_bwd_colsum(C1, SK, RO, S, LG(0) + g.lo.bs);                                                 // dSK, dbs (layer 0's slot)
         else if ((S & 3) == 0) K1(tr_relu_bwd4_kernel, RO * S / 4, (float4*)C1, (const float4*)SK, RO * S / 4);
         else K1(tr_relu_bwd_kernel, RO * S, C1, SK, RO * S);
         float* dSK = C1;
         // all skip convs at once: dWs (stacked) = ZC^T dSK ; dZC = dSK WS^T ; dbs (identical for every layer) = colsum(dSK)
         rc |= gemm_tn_splitk(bl, st, ZW, S, RO, ZC, ZW, dSK, S, GS, S, nsplit, kpart);
         if (ub) {
-            if (NL > 1) K1(tr_bcast_rows_kernel, (long long)(NL - 1) * S, LG(0) + h->lo.bs, h->c_lstride, NL, S);
+            if (NL > 1) K1(tr_bcast_rows_kernel, (long long)(NL - 1) * S, LG(0) + g.lo.bs, g.c_lstride, NL, S);
         }
         rc |= gemm_rm(bl, false, true, (int)RO, ZW, S, 1.f, dSK, S, WS, S, 0.f, dZC, ZW);
         if (rc) break;
@@ -2230,14 +2105,14 @@ extern "C" int twv_wavenet_train_loss_grad(twv_wavenet_trainer* h, const float* 
         else K1(tr_fill_kernel, RT * L, dUa, 0.0f, RT * L);
         K1(tr_fill_kernel, (long long)B * G, demb, 0.0f, (long long)B * G);
         for (int l = NL - 1; l >= 0 && !rc; --l) {
-            const int dl = d.dilations[l], o = h->off[l + 1];
+            const int dl = d.dilations[l], o = g.off[l + 1];
             const float* Lp = LP(l);
             float* Lg = LG(l);
             const float* Wv = WV + l * vstride;
             float* Gv = GV + l * vstride;
             LayerBwdArgs ba;
             ba.dXn = dXn; ba.dZC = dZC + l * 32; ba.TH = TH[l]; ba.SG = SG[l]; ba.X = X[l]; ba.U = U;
-            ba.W0 = Wv; ba.W1 = Wv + 32 * 64; ba.Wlc = Wv + 64 * 64; ba.Wd = Lp + h->lo.wd;
+            ba.W0 = Wv; ba.W1 = Wv + 32 * 64; ba.Wlc = Wv + 64 * 64; ba.Wd = Lp + g.lo.wd;
             ba.dPRE = PRE; ba.slabs = slabs + l * slab_ls; ba.tsum = tsum + l * tsum_ls; ba.dX = dXc; ba.dU = dUa;
             ba.B = B; ba.T = T; ba.Tn = Tn; ba.d = dl; ba.o = o; ba.ow = ow; ba.ldz = ZW; ba.tpb = (Tn + 31) / 32;
             // backward: dPRE is zero in front of o, dX in front of o - d (the layer input's offset).  Both kernels walk the tiles from
@@ -2250,11 +2125,11 @@ extern "C" int twv_wavenet_train_loss_grad(twv_wavenet_trainer* h, const float* 
             int nwg = (ntiles + 3) / 4; nwg = nwg > 256 ? 256 : nwg;
             int nwg2 = (ntiles_w + 7) / 8; nwg2 = nwg2 > 256 ? 256 : nwg2;
             ba.zeros = zpage;
-            ba.Q = Qall + l * (q_ls + 64); ba.D = Dbuf; ba.hop = h->hop; ba.F = F; ba.ctab = ctab; ba.PT = PTall + l * (pt_ls + 64);
+            ba.Q = Qall + l * (q_ls + 64); ba.D = Dbuf; ba.hop = g.hop; ba.F = F; ba.ctab = ctab; ba.PT = PTall + l * (pt_ls + 64);
             if (fused_lc) hipLaunchKernelGGL(tr_layer_bwd1_kernel<true>, dim3(nwg), dim3(256), (4 * BS_FLOATS + 2048) * 4, st, ba);
             else hipLaunchKernelGGL(tr_layer_bwd1_kernel<false>, dim3(nwg), dim3(256), 4 * BS_FLOATS * 4, st, ba);
             if (fused_lc) hipLaunchKernelGGL(tr_layer_bwd2c_kernel, dim3(nwg2), dim3(512), 0, st, ba);
-            else hipLaunchKernelGGL(tr_layer_bwd2_kernel<false>, dim3(nwg2), dim3(512), 0, st, ba);
+            else hipLaunchKernelGGL(tr_layer_bwd2_kernel, dim3(nwg2), dim3(512), 0, st, ba);
             float* tsw = dXn; dXn = dXc; dXc = tsw;
         }
         if (rc) break;
@@ -2270,13 +2145,13 @@ extern "C" int twv_wavenet_train_loss_grad(twv_wavenet_trainer* h, const float* 
             put(GQ_LCF0, 32, Gv + 64 * 64, 64, vstride); put(GQ_LCG0, 32, Gv + 64 * 64 + 32, 64, vstride);
             put(GQ_LCF1, 32, Gv + 96 * 64, 64, vstride); put(GQ_LCG1, 32, Gv + 96 * 64 + 32, 64, vstride);
             put(GQ_LCF2, L - 64, Gv + 128 * 64, 64, vstride); put(GQ_LCG2, L - 64, Gv + 128 * 64 + 32, 64, vstride);
-            put(GQ_WD, 32, LG(0) + h->lo.wd, 32, h->c_lstride);
+            put(GQ_WD, 32, LG(0) + g.lo.wd, 32, g.c_lstride);
             if (fused_lc) {
                 for (int q = GQ_LCF0; q <= GQ_LCG2; ++q) sd.mrows[q] = 0;       // W_lc's gradient: per-frame sums -> one strided-batched GEMM
                 LayerOffs lo_;
-                for (int l = 0; l < NL; ++l) lo_.o[l] = h->off[l + 1];
+                for (int l = 0; l < NL; ++l) lo_.o[l] = g.off[l + 1];
                 const long long nthr = (long long)B * F * 256;
-                hipLaunchKernelGGL(tr_frame_reduce_kernel, dim3((unsigned)((nthr + 255) / 256), 1, NL), dim3(256), 0, st, PTall, pt_ls + 64, lo_, B, F, h->hop, tpb, Tn,
+                hipLaunchKernelGGL(tr_frame_reduce_kernel, dim3((unsigned)((nthr + 255) / 256), 1, NL), dim3(256), 0, st, PTall, pt_ls + 64, lo_, B, F, g.hop, tpb, Tn,
                                    Rall, q_ls + 64);
                 const float one = 1.0f, zero = 0.0f;
                 rc |= rocblas_sgemm_strided_batched(bl, rocblas_operation_none, rocblas_operation_transpose, 64, L, B * F * 4, &one, Rall, 64, q_ls + 64,
@@ -2286,9 +2161,9 @@ extern "C" int twv_wavenet_train_loss_grad(twv_wavenet_trainer* h, const float* 
             // gc: dGCP[l][b] = sum_t dPRE[b,t] (from the per-tile sums); conv biases = sum_b dGCP[l][b]; dense bias = column sums of the tiles
             colsum(tsum, tpb, 64, 96, NL * B, dGCPall, 64);                                   // segment = (layer, batch entry)
             if (ub) {
-                colsum(tsum + 64, ntiles, 32, 96, NL, LG(0) + h->lo.bd, (int)h->c_lstride);   // segment = layer, outputs c_lstride apart
+                colsum(tsum + 64, ntiles, 32, 96, NL, LG(0) + g.lo.bd, (int)g.c_lstride);   // segment = layer, outputs c_lstride apart
                 colsum(dGCPall, B, 64, 64, NL, bsum64, 64);
-                K1(tr_split_bias_kernel, 64LL * NL, bsum64, LG(0), h->c_lstride, h->lo.bf, h->lo.bg, NL);
+                K1(tr_split_bias_kernel, 64LL * NL, bsum64, LG(0), g.c_lstride, g.lo.bf, g.lo.bg, NL);
             }
             // dWgc_l = emb^T dGCP_l (one strided-batched GEMM over the layers) ; demb += sum_l dGCP_l Wgc_l^T
             {
@@ -2300,22 +2175,22 @@ extern "C" int twv_wavenet_train_loss_grad(twv_wavenet_trainer* h, const float* 
         }
         if (rc) break;
         // causal layer, gc embedding table, upsampler, and the gradient views back into the canonical order
-        if (d.scalar_input) wgrad(xunf, h->ifw, dXn, 32, Rr, h->ifw, 32, Gd + h->c_causal, 32);
+        if (d.scalar_input) wgrad(xunf, g.ifw, dXn, 32, Rr, g.ifw, 32, Gd + g.c_causal, 32);
         else {
             const int Q = d.quantization_channels, nblk = 256;
             const long long rpb = (Rr + nblk - 1) / nblk;
             HIPCHK(hipFuncSetAttribute((const void*)tr_onehot_causal_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * Q * 32 * 4));
             hipLaunchKernelGGL(tr_onehot_causal_bwd_kernel, dim3(nblk), dim3(256), 2 * Q * 32 * 4, st, dXn, qin, ohpart, B, T, Tn, Q, rpb);
-            hipLaunchKernelGGL(tr_colsum_final_kernel, dim3((2 * Q * 32 + 63) / 64), dim3(256), 0, st, ohpart, nblk, 2 * Q * 32, 1, Gd + h->c_causal, 2 * Q * 32);
+            hipLaunchKernelGGL(tr_colsum_final_kernel, dim3((2 * Q * 32 + 63) / 64), dim3(256), 0, st, ohpart, nblk, 2 * Q * 32, 1, Gd + g.c_causal, 2 * Q * 32);
         }
-        K1(tr_scatter_emb_kernel, (long long)d.gc_cardinality * G, demb, gc_ids, Gd + h->c_gcemb, B, G, d.gc_cardinality);
-        K1(tr_views_kernel, (vstride + 32LL * S) * NL, Gd, GV, GS, NL, h->c_layer0, h->c_lstride, h->lo.wf, h->lo.wg, h->lo.lcf, h->lo.lcg,
-           h->lo.gcf, h->lo.gcg, h->lo.ws, L, G, S, 1);
+        K1(tr_scatter_emb_kernel, (long long)d.gc_cardinality * G, demb, gc_ids, Gd + g.c_gcemb, B, G, d.gc_cardinality);
+        K1(tr_views_kernel, (vstride + 32LL * S) * NL, Gd, GV, GS, NL, g.c_layer0, g.c_lstride, g.lo.wf, g.lo.wg, g.lo.lcf, g.lo.lcg,
+           g.lo.gcf, g.lo.gcg, g.lo.ws, L, G, S, 1);
         if (fused_lc) {
             // upsampling kernels: D (per U row) -> dctab (per phase) -> the three (f, 2) kernels
-            hipLaunchKernelGGL(tr_dctab_kernel, dim3(h->hop), dim3(256), 0, st, Dbuf, B, T, h->hop, dctab);
-            K1(tr_up_grad_kernel, 2LL * (d.upsample_factor[0] + d.upsample_factor[1] + d.upsample_factor[2]), P + h->c_up[0], P + h->c_up[1], P + h->c_up[2],
-               d.upsample_factor[0], d.upsample_factor[1], d.upsample_factor[2], dctab, Gd + h->c_up[0], Gd + h->c_up[1], Gd + h->c_up[2]);
+            hipLaunchKernelGGL(tr_dctab_kernel, dim3(g.hop), dim3(256), 0, st, Dbuf, B, T, g.hop, dctab);
+            K1(tr_up_grad_kernel, 2LL * (d.upsample_factor[0] + d.upsample_factor[1] + d.upsample_factor[2]), P + g.c_up[0], P + g.c_up[1], P + g.c_up[2],
+               d.upsample_factor[0], d.upsample_factor[1], d.upsample_factor[2], dctab, Gd + g.c_up[0], Gd + g.c_up[1], Gd + g.c_up[2]);
         } else {
             float* dcur = dUa; float* dnxt = dUb;
             for (int i = d.n_upsample - 1; i >= 0; --i) {
@@ -2323,9 +2198,9 @@ extern "C" int twv_wavenet_train_loss_grad(twv_wavenet_trainer* h, const float* 
                 int nch = (int)(rin / 64); nch = nch < 1 ? 1 : (nch > 256 ? 256 : nch);
                 hipLaunchKernelGGL(tr_up_bwd_k_kernel, dim3(nch, d.upsample_factor[i]), dim3(256), 0, st, ups[i], dcur, part, rin, d.upsample_factor[i], L, nch);
                 hipLaunchKernelGGL(tr_colsum_final_kernel, dim3((2 * d.upsample_factor[i] + 63) / 64), dim3(256), 0, st, part, nch, 2 * d.upsample_factor[i], 1,
-                                   Gd + h->c_up[i], 2 * d.upsample_factor[i]);
+                                   Gd + g.c_up[i], 2 * d.upsample_factor[i]);
                 if (i > 0) {
-                    K1(tr_up_bwd_in_kernel, (long long)B * upT[i] * L, P + h->c_up[i], dcur, dnxt, (long long)B * upT[i] * L, d.upsample_factor[i], L);
+                    K1(tr_up_bwd_in_kernel, (long long)B * upT[i] * L, P + g.c_up[i], dcur, dnxt, (long long)B * upT[i] * L, d.upsample_factor[i], L);
                     float* tsw = dcur; dcur = dnxt; dnxt = tsw;
                 }
             }
@@ -2348,11 +2223,12 @@ extern "C" int twv_wavenet_train_l2(twv_wavenet_trainer* h, const float* params,
 {
     if (!h || !params || !workspace || !loss || !grads) return twv_fail(TWV_E_INVALID, "null argument");
     hipStream_t st = (hipStream_t)stream;
+    const WavenetGraph& g = h->g;
     float* sq = (float*)workspace + h->l2_off;           // nparams floats, then 256 partials + the sum: a region of its own (see create)
-    float* part = sq + (h->nparams + 63) / 64 * 64;
-    L2Layout L{h->c_layer0, h->c_lstride, h->NL, h->lo.bf, h->lo.bg, h->lo.bd, h->lo.bs, 32, 32, h->S, h->c_b1, h->c_b2, h->O, h->d.use_biases};
-    hipLaunchKernelGGL(tr_l2_kernel, dim3(tg(h->nparams)), dim3(256), 0, st, params, grads, sq, h->nparams, (float)strength, L);
-    tr_sum(sq, h->nparams, part, part + 512, st);
+    float* part = sq + (g.nparams + 63) / 64 * 64;
+    L2Layout L{g.c_layer0, g.c_lstride, g.NL, g.lo.bf, g.lo.bg, g.lo.bd, g.lo.bs, 32, 32, g.S, g.c_b1, g.c_b2, g.O, g.d.use_biases};
+    hipLaunchKernelGGL(tr_l2_kernel, dim3(tg(g.nparams)), dim3(256), 0, st, params, grads, sq, g.nparams, (float)strength, L);
+    tr_sum(sq, g.nparams, part, part + 512, st);
     hipLaunchKernelGGL(tr_axpy1_kernel, dim3(1), dim3(64), 0, st, loss, part + 512, (float)strength);
     HIPCHK(hipGetLastError());
     return TWV_OK;

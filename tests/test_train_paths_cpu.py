@@ -1,6 +1,7 @@
 """Host-only side of tests/test_train_paths_gpu.py: every case of the shared table is on the route it is meant to cover (and the
 geometries of tests/test_train_gpu.py are all on the fused one), the float64 checker reaches the branches the cases are there for and
 agrees with its own matmul form away from the default upsampler, and the workspace is as large as what loss_grad carves from it."""
+import ctypes as C
 import itertools
 
 import numpy as np
@@ -120,3 +121,27 @@ def test_default_workspace_did_not_grow():
     """BASELINE configs[3] (64 x 7800, 30 layers, S 512): the estimate this replaced asked for 3 696 327 424 floats (it now takes 3 133 278 976)"""
     route, ws, _ = TC.host_route(**dict(TC.BIG_CASES)["configs[3] 64 x 7800"])
     assert ws <= 3696327424, ws
+
+
+# ---- refusals ---------------------------------------------------------------------------------------------------------------------
+def test_create_refuses_out_channels_that_are_not_three_to_ninety_six_in_threes():
+    """twv_wavenet_train_create and twv_wavenet_score_create share one set of refusals (csrc/twv_wavenet_graph.hpp): out_channels = 0
+    (no mixture at all: nr_mix 0, O 0) used to pass the trainer's own check.  The dims are edited behind the Python model, which has
+    refusals of its own."""
+    from twvk_amd import _lib
+    net = TC._model(device="cpu", **TC._model_kw(TC.PATH_BY_ID["nr5"][1]))
+    L = _lib.lib()
+    UNSUPPORTED = 2
+
+    def create(**over):
+        dims = _lib.Dims.from_buffer_copy(net._dims)
+        for k, v in over.items():
+            setattr(dims, k, v)
+        h = C.c_void_p()
+        return L.twv_wavenet_train_create(C.byref(dims), 2, 900, C.byref(h)), h
+    for oc in (0, 31, 99):
+        rc, h = create(out_channels=oc)
+        assert rc == UNSUPPORTED and not h.value, oc
+    rc, h = create(out_channels=96)
+    assert rc == 0
+    L.twv_wavenet_train_destroy(h)
