@@ -332,17 +332,24 @@ int twv_adam_ema_step(float* params, const float* grads, float* m, float* v, flo
  * whole utterance's values at positions s+rf .. s+n-1 (the front slice is shift-invariant at hop multiples), so the host scores an
  * utterance of any length as windows with a halo of ceil(rf / hop) * hop samples (score.py) and memory is bounded by (slots, window). */
 typedef struct twv_wavenet_scorer twv_wavenet_scorer;
-/* accepts what twv_wavenet_train_create accepts (R = D = 32, 80 mel channels, gc with a cardinality, out_channels = 3*nr <= 96 or
- * quantization_channels in [2, 512]); everything else is TWV_E_UNSUPPORTED, as is slots * window_samples * 256 >= 2^31 where the local
- * condition is projected at frame rate (three upsampling stages, 32 <= hop <= 512).  TWV_E_INVALID: window_samples not a multiple of
+/* accepts what twv_wavenet_train_create accepts (80 mel channels, gc with a cardinality, out_channels = 3*nr <= 96 or
+ * quantization_channels in [2, 512]) at residual_channels = dilation_channels = 32, and the same at 64 and 128 (the training step is
+ * built for 32 only); unequal or other widths and everything else are TWV_E_UNSUPPORTED, as is slots * window_samples * 256 >= 2^31
+ * where the local condition is projected at frame rate (three upsampling stages, 32 <= hop <= 512), at every width.  TWV_E_INVALID: window_samples not a multiple of
  * the hop size (datafeeder_wavenet.py:38) or <= the receptive field (model.py:31-39). */
 int twv_wavenet_score_create(const twv_wavenet_dims* dims, int slots, int window_samples, twv_wavenet_scorer** out);
 void twv_wavenet_score_destroy(twv_wavenet_scorer* h);
 size_t twv_wavenet_score_workspace_bytes(const twv_wavenet_scorer* h);      /* a function of (dims, slots, window_samples) only */
 int twv_wavenet_score_output_width(const twv_wavenet_scorer* h);            /* window_samples - receptive_field (model.py:135) */
 /* host-only label for tests and measurements, a string the handle owns:
- *   "lc=<fused|staged> head=<skinny|gemm> loss=<mol<10>|mol<0>|softmax> carve_floats=<n>" (lc as twv_wavenet_train_route) */
+ *   "lc=<fused|staged> head=<skinny|gemm> loss=<mol<10>|mol<0>|softmax> width=<32|64|128> carve_floats=<n>" (lc as twv_wavenet_train_route) */
 const char* twv_wavenet_score_route(const twv_wavenet_scorer* h);
+/* host only: where a workspace holds two intermediate arrays after twv_wavenet_score_windows, for tests that look at more than the
+ * loss.  name "zc": the stacked skip input ZC[(b, p)][l * dilation_channels + j] (model.py:94-96: layer l's z of the last
+ * window_samples - rf rows), rows = slots * (window_samples - rf), cols = n_layers * dilation_channels; "y": the raw network output
+ * (model.py:150-165), cols = out_channels or quantization_channels.  Row-major at offset_floats floats from the workspace's start;
+ * rows p >= lengths[b] - rf of a slot are not written.  Any other name is TWV_E_INVALID. */
+int twv_wavenet_score_view(const twv_wavenet_scorer* h, const char* name, long long* offset_floats, long long* rows, long long* cols);
 /* nll (slots, window_samples - rf) float32, overwritten: nll[b][p] = the loss term of target audio[b][p + rf] (model.py:286-296) for
  * p < lengths_host[b] - rf, 0 for the positions slot b does not have.  params: the flat blob of twv_wavenet_train_param_floats floats
  * in the order of weights.tensor_specs (a trainer's params or EMA shadows as they are).  audio (slots, window_samples) float in [-1,1];

@@ -272,6 +272,7 @@ def lib():
     L.twv_wavenet_score_workspace_bytes.argtypes = [vp]; L.twv_wavenet_score_workspace_bytes.restype = C.c_size_t
     L.twv_wavenet_score_output_width.argtypes = [vp]
     L.twv_wavenet_score_route.argtypes = [vp]; L.twv_wavenet_score_route.restype = C.c_char_p
+    L.twv_wavenet_score_view.argtypes = [vp, C.c_char_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
     L.twv_wavenet_score_windows.argtypes = [vp, fp, fp, fp, ip, ip, vp, fp, vp]
     L.twv_wavenet_score_reduce.argtypes = [fp, ip, ip, C.c_int, C.c_int, dp, vp]
     L.twv_crc32c.argtypes = [vp, C.c_size_t, C.c_uint32]; L.twv_crc32c.restype = C.c_uint32
@@ -295,7 +296,7 @@ EXPORTS = ["twv_last_error", "twv_version", "twv_wavenet_create", "twv_wavenet_d
            "twv_resample_workspace_bytes", "twv_resample_filter_host", "twv_resample_kernel_name", "twv_resample_rounds", "twv_resample",
            "twv_griffin_lim_create_ragged", "twv_griffin_lim_total_frames", "twv_griffin_lim_total_samples", "twv_griffin_lim_offsets",
            "twv_wavenet_score_create", "twv_wavenet_score_destroy", "twv_wavenet_score_workspace_bytes", "twv_wavenet_score_output_width",
-           "twv_wavenet_score_route", "twv_wavenet_score_windows", "twv_wavenet_score_reduce"]
+           "twv_wavenet_score_route", "twv_wavenet_score_windows", "twv_wavenet_score_reduce", "twv_wavenet_score_view"]
 
 
 class TacoDims(C.Structure):

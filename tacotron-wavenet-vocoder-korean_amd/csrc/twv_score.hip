@@ -17,6 +17,8 @@
 // conv1d_2) are the training step's own: wavenet_forward_front / wavenet_forward_head (twv_wavenet_graph.hpp, defined in twv_train.hip
 // beside their kernels).  The same header holds the model description both handles embed: geometry, canonical offsets, refusals, route.
 // The loss kernels write per-row terms only: no gradient, no mean.
+// residual_channels = dilation_channels = 64 and 128 take the same front, head and loss kernels and sc_layer_wide_fwd_kernel<W, FUSED>
+// per layer; width 32 runs sc_layer_fwd_kernel as before.
 #include <hip/hip_runtime.h>
 #include <rocblas/rocblas.h>
 #include <stdint.h>
@@ -202,6 +204,181 @@ __global__ void __launch_bounds__(512) sc_layer_fwd_kernel(ScLayerArgs a)
     }
 }
 
+// ===================================================================================================================
+//  The same layer at residual = dilation width W = 64 or 128 (ScLayerArgs with W for every 32 and 2W for every 64: X, XN (slots*Tn, W);
+//  views W0, W1 (W, 2W), Wlc (80, 2W), columns filter | gate; Wd (W, W); gcp (slots, 2W); Q[((b*F + frame)*4 + j)*2W + column]; ZC
+//  already offset to the layer's W columns).  The contract is sc_layer_fwd_kernel's: 32-row tiles of one slot, one wave per tile, both
+//  lc routes, rows that do not exist load nothing and store nothing.
+//  The two taps' filter | gate weights are 2W x 2W floats (256 KiB at 128), so the output channels are walked in W / 32 blocks of 32:
+//  for block c
+//      pre_f, pre_g [32 x 32] = X[t-d] W0[:, c] + X[t] W1[:, c] + lc term       B operands: the block's slice [step][lane][filter, gate] in LDS
+//      z_c = tanh(pre_f + bias + gc) * sigmoid(pre_g + bias + gc)               -> ZC, and through the wave's 32 x 36 LDS patch as A operand
+//      acc[o] += z_c Wd[32c .. 32c+31, 32o .. 32o+31]   for all W / 32 output blocks o (W / 2 accumulator registers)
+//  and x_next = X[t] + acc + bd at the end.  A operands (W / 2 registers per tap) are not held: every block reads the tile's rows
+//  again (L1 / L2 hits).  At 64 all slices (64 KiB, staged 104 KiB) stay in LDS and the waves run free of each other; at 128 one slice
+//  (64 KiB, staged 84 KiB) is resident at a time, so the eight waves of a workgroup take eight tiles in step: two barriers per block,
+//  ~1e3 cycles of slice load against ~3e4 cycles of MFMA.  All addresses are 64-bit.
+// ===================================================================================================================
+template <int W, bool FUSED>
+__global__ void __launch_bounds__(512) sc_layer_wide_fwd_kernel(ScLayerArgs a)
+{
+    constexpr int NB = W / 32;                               // channel blocks
+    constexpr int W2 = 2 * W;
+    constexpr int TAP = W / 2;                               // MFMA steps per tap (k = W)
+    constexpr int STEPS = 2 * TAP + (FUSED ? 0 : 4 * kScLcSteps);
+    constexpr bool RES = W == 64;                            // every slice resident
+    constexpr int NSL = RES ? NB : 1;
+    __shared__ __attribute__((aligned(16))) float bt[NSL * STEPS * 128];       // [slice][step][lane][filter, gate]
+    __shared__ float bdt[NSL * NB * 16 * 64];                                   // dense: [slice][out block][step][lane]
+    __shared__ __attribute__((aligned(16))) float cts[FUSED ? 4 * 512 : 4];    // ctab (hop <= 512)
+    __shared__ __attribute__((aligned(16))) float zt[8][32 * 36];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int n = lane & 31, hh = lane >> 5;
+    if (FUSED) for (int e = threadIdx.x; e < a.hop * 4; e += 512) cts[e] = a.ctab[e];
+    // slice c of the weights -> LDS slot `slot` (step s, lane half h2 carries k = 8 (s >> 2) + 4 h2 + (s & 3) of its operand)
+    auto load_slice = [&](int c, int slot) {
+        float* bs = bt + slot * STEPS * 128;
+        for (int e = threadIdx.x; e < STEPS * 64; e += 512) {
+            const int s = e >> 6, l = e & 63, nn = l & 31, h2 = l >> 5;
+            const float* Wp; int ij;
+            if (s < TAP) { Wp = a.W0; ij = s; } else if (s < 2 * TAP) { Wp = a.W1; ij = s - TAP; } else { Wp = a.Wlc; ij = s - 2 * TAP; }
+            const int k = 8 * (ij >> 2) + 4 * h2 + (ij & 3);
+            bs[e * 2] = Wp[k * W2 + c * 32 + nn]; bs[e * 2 + 1] = Wp[k * W2 + W + c * 32 + nn];
+        }
+        float* ds = bdt + slot * NB * 16 * 64;
+        for (int e = threadIdx.x; e < NB * 16 * 64; e += 512) {
+            const int ob = e >> 10, s = (e >> 6) & 15, l = e & 63;
+            ds[e] = a.Wd[(c * 32 + 8 * (s >> 2) + 4 * (l >> 5) + (s & 3)) * W + ob * 32 + (l & 31)];
+        }
+    };
+    if (RES) {
+        for (int c = 0; c < NB; ++c) load_slice(c, c);
+        __syncthreads();
+    }
+    const f32x16 zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    const int ntiles = a.slots * a.tpb, ngroups = (ntiles + 7) / 8;
+    for (int grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {                // block-uniform: every wave meets every barrier
+        const int tile = grp * 8 + wave;
+        const int b = tile < ntiles ? tile / a.tpb : 0, t0 = (tile - b * a.tpb) * 32 + a.t_lo;
+        const int Tb = tile < ntiles ? a.lens[b] - 1 : 0;     // the slot's rows: its last sample is a target only (idle slot: -1)
+        const bool active = tile < ntiles && t0 < Tb;         // wave-uniform: else the whole tile lies behind the slot's end
+        const int t = t0 + n;
+        const bool ok = active && t < Tb && t >= a.o;
+        const float* xr = a.X + ((long long)b * a.Tn + t) * W + 4 * hh;          // lane (row, hh) carries k = 8i + 4hh .. +3 of its row
+        const float* ur = a.U + ((long long)b * a.T + (t - a.o)) * 80 + 4 * hh;
+        f32x16 cd[NB];
+#pragma unroll
+        for (int ob = 0; ob < NB; ++ob) cd[ob] = zero;
+        for (int c = 0; c < NB; ++c) {
+            if (!RES) {
+                __syncthreads();                              // the waves have finished with the slice before
+                load_slice(c, 0);
+                __syncthreads();
+            }
+            if (!active) continue;
+            const float* bs = bt + (RES ? c : 0) * STEPS * 128 + lane * 2;
+            const float* ds = bdt + (RES ? c : 0) * NB * 16 * 64 + lane;
+            f32x16 cf = zero, cg = zero;
+            if (FUSED) {                                      // the lc term first: the accumulators start from it
+                // rows of the tile: U row u = t - o; at most two frames per 32-row tile (hop >= 32).  fA < F: t0 < Tb <= T - 1.
+                int u0 = t0 - a.o; u0 = u0 < 0 ? 0 : u0;
+                const int fA = u0 / a.hop, fB = fA + 1 < a.F ? fA + 1 : fA;
+                const int edge = (fA + 1) * a.hop;                               // first U row of frame fA + 1
+                const float* qa = a.Q + (((long long)b * a.F + fA) * 4) * W2 + c * 32 + n;
+                const float* qb = a.Q + (((long long)b * a.F + fB) * 4) * W2 + c * 32 + n;
+                float qfa[4], qga[4], qfb[4], qgb[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { qfa[j] = qa[j * W2]; qga[j] = qa[j * W2 + W]; qfb[j] = qb[j * W2]; qgb[j] = qb[j * W2 + W]; }
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    int uu = t0 - a.o + (r & 3) + 8 * (r >> 2) + 4 * hh;
+                    uu = uu < 0 ? 0 : uu;                                         // rows below the layer's offset are discarded by the epilogue
+                    const bool hi = uu >= edge;
+                    int ph = uu - (hi ? edge : edge - a.hop);
+                    ph = ph < a.hop ? ph : a.hop - 1;                             // (only rows past the window's end, discarded as well)
+                    const f32x4t ct = *reinterpret_cast<const f32x4t*>(&cts[ph * 4]);
+                    const float f0 = hi ? qfb[0] : qfa[0], f1 = hi ? qfb[1] : qfa[1], f2 = hi ? qfb[2] : qfa[2], f3 = hi ? qfb[3] : qfa[3];
+                    const float g0 = hi ? qgb[0] : qga[0], g1 = hi ? qgb[1] : qga[1], g2 = hi ? qgb[2] : qga[2], g3 = hi ? qgb[3] : qga[3];
+                    cf[r] = ((ct[0] * f0 + ct[1] * f1) + ct[2] * f2) + ct[3] * f3;
+                    cg[r] = ((ct[0] * g0 + ct[1] * g1) + ct[2] * g2) + ct[3] * g3;
+                }
+            }
+#pragma unroll 2
+            for (int i = 0; i < W / 8; ++i) {
+                const f32x4t x0 = sc_ld4(xr - (long long)a.d * W + 8 * i, ok);   // t - d >= off[l]: a row of the layer's input
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const f32x2t w = *reinterpret_cast<const f32x2t*>(&bs[(4 * i + j) * 128]);
+                    cf = __builtin_amdgcn_mfma_f32_32x32x2f32(x0[j], w[0], cf, 0, 0, 0);
+                    cg = __builtin_amdgcn_mfma_f32_32x32x2f32(x0[j], w[1], cg, 0, 0, 0);
+                }
+            }
+#pragma unroll 2
+            for (int i = 0; i < W / 8; ++i) {
+                const f32x4t x1 = sc_ld4(xr + 8 * i, ok);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const f32x2t w = *reinterpret_cast<const f32x2t*>(&bs[(TAP + 4 * i + j) * 128]);
+                    cf = __builtin_amdgcn_mfma_f32_32x32x2f32(x1[j], w[0], cf, 0, 0, 0);
+                    cg = __builtin_amdgcn_mfma_f32_32x32x2f32(x1[j], w[1], cg, 0, 0, 0);
+                }
+            }
+            if (!FUSED) {
+#pragma unroll 2
+                for (int i = 0; i < kScLcSteps; ++i) {
+                    const f32x4t u = sc_ld4(ur + 8 * i, ok);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const f32x2t w = *reinterpret_cast<const f32x2t*>(&bs[(2 * TAP + 4 * i + j) * 128]);
+                        cf = __builtin_amdgcn_mfma_f32_32x32x2f32(u[j], w[0], cf, 0, 0, 0);
+                        cg = __builtin_amdgcn_mfma_f32_32x32x2f32(u[j], w[1], cg, 0, 0, 0);
+                    }
+                }
+            }
+            // ---- gated unit; rows that do not exist give z = 0 (a select, not a product: whatever their accumulators hold)
+            const int ch = c * 32 + n;
+            const float vbf = a.bf ? a.bf[ch] : 0.0f, vbg = a.bg ? a.bg[ch] : 0.0f;
+            const float gcf = a.gcp ? a.gcp[b * W2 + ch] : 0.0f, gcg = a.gcp ? a.gcp[b * W2 + W + ch] : 0.0f;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int rl = (r & 3) + 8 * (r >> 2) + 4 * hh, tr = t0 + rl;
+                const bool valid = tr < Tb && tr >= a.o;
+                const float th = sc_tanh_fast((cf[r] + vbf) + gcf), sg = sc_sigmoid_fast((cg[r] + vbg) + gcg);
+                const float z = valid ? th * sg : 0.0f;
+                if (valid && tr >= a.cut) a.ZC[((long long)b * a.ow + (tr - a.cut)) * a.ldz + ch] = z;     // model.py:94-96: the last len_b - rf rows
+                zt[wave][rl * 36 + n] = z;
+            }
+            // ---- dense 1x1: this block of z as A operand (row layout) back from the wave's LDS patch, into every output block
+            {
+                const float* zr = &zt[wave][n * 36 + 4 * hh];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const f32x4t q = *reinterpret_cast<const f32x4t*>(zr + 8 * i);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+#pragma unroll
+                        for (int ob = 0; ob < NB; ++ob)
+                            cd[ob] = __builtin_amdgcn_mfma_f32_32x32x2f32(q[j], ds[(ob * 16 + 4 * i + j) * 64], cd[ob], 0, 0, 0);
+                }
+            }
+        }
+        if (!active) continue;
+        // ---- residual: x_next = X[t] + z Wd + bd in the output (C) layout: lane = channel, register r = row (r&3) + 8(r>>2) + 4hh
+#pragma unroll
+        for (int ob = 0; ob < NB; ++ob) {
+            const float vbd = a.bd ? a.bd[ob * 32 + n] : 0.0f;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int tr = t0 + (r & 3) + 8 * (r >> 2) + 4 * hh;
+                if (tr < Tb && tr >= a.o) {
+                    const long long at = ((long long)b * a.Tn + tr) * W + ob * 32 + n;
+                    a.XN[at] = (a.X[at] + cd[ob][r]) + vbd;
+                }
+            }
+        }
+    }
+}
+
 // ---- per-row loss terms --------------------------------------------------------------------------------------------
 // mixture.py:27-81 discretized_mix_logistic_loss(num_class=2**16, reduce=False), one row: the branch structure of the training step's
 // tr_mol_row (edge branches at -0.999 / +0.999, cdf_delta > 1e-5, the log-scale clamp at log(1e-14)), forward only.
@@ -309,6 +486,7 @@ struct ScoreCarve {
     float *xunf; int32_t* qin; int32_t* lens;
     float *XA, *XB, *ZC, *SK, *C1, *Y, *emb, *GCP, *WV, *WS, *bsum, *ctab, *melsh, *Qall;
     long long vstride, q_ls;
+    long long o_ZC, o_Y;                                     // where ZC and Y start, in floats from the base (twv_wavenet_score_view)
 };
 static long long sc_carve(const WavenetGraph* h, float* base, ScoreCarve& c)
 {
@@ -325,19 +503,20 @@ static long long sc_carve(const WavenetGraph* h, float* base, ScoreCarve& c)
     c.xunf = take(d.scalar_input ? Rr * h->ifw : 0);
     c.qin = reinterpret_cast<int32_t*>(take(d.scalar_input ? 0 : RT));
     c.lens = reinterpret_cast<int32_t*>(take(B));
-    c.XA = take(Rr * 32); c.XB = take(Rr * 32);              // the layers' activations ping-pong
-    const int ZW = NL * 32;                                  // stacked skip input: ZC[(b,p)][l*32 + j]
-    c.ZC = take(RO * ZW);
+    const int R = h->R, D = h->D;                            // the width (R == D)
+    c.XA = take(Rr * R); c.XB = take(Rr * R);                // the layers' activations ping-pong
+    const int ZW = NL * D;                                   // stacked skip input: ZC[(b,p)][l*D + j]
+    c.o_ZC = used; c.ZC = take(RO * ZW);
     c.SK = take(RO * S); c.C1 = take(RO * S);
-    c.Y = take(RO * O);
+    c.o_Y = used; c.Y = take(RO * O);
     c.emb = take((long long)B * G);
-    c.GCP = take((long long)B * 64 * NL);
-    c.vstride = 64LL * (64 + L + G);
+    c.GCP = take((long long)B * 2 * D * NL);
+    c.vstride = 2LL * D * (2 * R + L + G);
     c.WV = take(c.vstride * NL); c.WS = take((long long)ZW * S);       // weight views (tr_views_kernel)
     c.bsum = take(S);
     c.ctab = take(fused ? 4LL * 512 : 0);
     c.melsh = take(fused ? (long long)B * h->F * 4 * L : 0);
-    c.q_ls = (long long)B * h->F * 4 * 64;
+    c.q_ls = (long long)B * h->F * 4 * 2 * D;
     c.Qall = take(fused ? (c.q_ls + 64) * NL : 0);
     return used;
 }
@@ -346,13 +525,13 @@ extern "C" int twv_wavenet_score_create(const twv_wavenet_dims* dims, int slots,
 {
     if (!out) return twv_fail(TWV_E_INVALID, "bad argument");
     twv_wavenet_scorer* h = new twv_wavenet_scorer();
-    const int rc = wavenet_graph_init(h->g, dims, slots, window_samples, "scoring");
+    const int rc = wavenet_graph_init(h->g, dims, slots, window_samples, "scoring", 128);
     if (rc) { delete h; return rc; }
     h->blas = nullptr;
     ScoreCarve sizes;
     h->carve_floats = sc_carve(&h->g, nullptr, sizes);
     const WavenetRoute r = wavenet_route(h->g);
-    h->route = wavenet_route_label(r, r.skinny ? "skinny" : "gemm") + " carve_floats=" + std::to_string(h->carve_floats);
+    h->route = wavenet_route_label(r, r.skinny ? "skinny" : "gemm") + " width=" + std::to_string(h->g.R) + " carve_floats=" + std::to_string(h->carve_floats);
     *out = h;
     return TWV_OK;
 }
@@ -364,6 +543,18 @@ extern "C" void twv_wavenet_score_destroy(twv_wavenet_scorer* h)
 extern "C" size_t twv_wavenet_score_workspace_bytes(const twv_wavenet_scorer* h) { return h ? (size_t)h->carve_floats * 4 : 0; }
 extern "C" int twv_wavenet_score_output_width(const twv_wavenet_scorer* h) { return h ? h->g.ow : 0; }
 extern "C" const char* twv_wavenet_score_route(const twv_wavenet_scorer* h) { return h ? h->route.c_str() : ""; }
+extern "C" int twv_wavenet_score_view(const twv_wavenet_scorer* h, const char* name, long long* offset_floats, long long* rows, long long* cols)
+{
+    if (!h || !name || !offset_floats || !rows || !cols) return twv_fail(TWV_E_INVALID, "null argument");
+    ScoreCarve cv;
+    sc_carve(&h->g, nullptr, cv);
+    const std::string nm(name);
+    *rows = (long long)h->g.rows * h->g.ow;
+    if (nm == "zc") { *offset_floats = cv.o_ZC; *cols = (long long)h->g.NL * h->g.D; }
+    else if (nm == "y") { *offset_floats = cv.o_Y; *cols = h->g.O; }
+    else return twv_fail(TWV_E_INVALID, "twv_wavenet_score_view: unknown array '" + nm + "' (zc, y)");
+    return TWV_OK;
+}
 
 extern "C" int twv_wavenet_score_windows(twv_wavenet_scorer* h, const float* params, const float* audio, const float* lc, const int32_t* gc_ids,
                                          const int32_t* lengths_host, void* workspace, float* nll, void* stream)
@@ -389,7 +580,7 @@ extern "C" int twv_wavenet_score_windows(twv_wavenet_scorer* h, const float* par
     const long long RO = (long long)B * ow;
     const bool ub = d.use_biases != 0;
     const float* P = params;
-    const int ZW = NL * 32;
+    const int R = g.R, ZW = NL * g.D;
     const long long vstride = cv.vstride, q_ls = cv.q_ls;
     HIPCHK(hipMemcpyAsync(cv.lens, lengths_host, (size_t)B * 4, hipMemcpyHostToDevice, st));   // (pageable source: staged before the call returns)
     // ================= front: the training step's, on all slots x window rows =================
@@ -408,18 +599,26 @@ extern "C" int twv_wavenet_score_windows(twv_wavenet_scorer* h, const float* par
         const float* Lp = P + g.c_layer0 + (long long)l * g.c_lstride;
         const float* Wv = cv.WV + l * vstride;
         ScLayerArgs fa;
-        fa.X = X[l & 1]; fa.XN = X[(l + 1) & 1]; fa.U = U; fa.gcp = cv.GCP + (long long)l * B * 64;
-        fa.W0 = Wv; fa.W1 = Wv + 32 * 64; fa.Wlc = Wv + 64 * 64; fa.Wd = Lp + g.lo.wd;
+        fa.X = X[l & 1]; fa.XN = X[(l + 1) & 1]; fa.U = U; fa.gcp = cv.GCP + (long long)l * B * 2 * R;
+        fa.W0 = Wv; fa.W1 = Wv + R * 2 * R; fa.Wlc = Wv + 2 * R * 2 * R; fa.Wd = Lp + g.lo.wd;
         fa.bf = ub ? Lp + g.lo.bf : nullptr; fa.bg = ub ? Lp + g.lo.bg : nullptr; fa.bd = ub ? Lp + g.lo.bd : nullptr;
-        fa.ZC = cv.ZC + l * 32; fa.lens = cv.lens;
+        fa.ZC = cv.ZC + l * R; fa.lens = cv.lens;
         fa.slots = B; fa.T = T; fa.Tn = Tn; fa.d = d.dilations[l]; fa.o = g.off[l + 1]; fa.cut = rf - 1; fa.ow = ow; fa.ldz = ZW;
         fa.t_lo = (fa.o / 32) * 32;                          // whole tiles in front of the layer's offset hold no row: not walked
         fa.tpb = (Tn + 31) / 32 - fa.t_lo / 32;
         fa.Q = cv.Qall + l * (q_ls + 64); fa.ctab = cv.ctab; fa.hop = g.hop; fa.F = F;
         const int ntiles = B * fa.tpb;
         int nwg = (ntiles + 7) / 8; nwg = nwg > 256 ? 256 : nwg;     // one workgroup (8 waves, 2 per SIMD) per CU, each wave walks its tiles
-        if (route.fused_lc) hipLaunchKernelGGL(sc_layer_fwd_kernel<true>, dim3(nwg), dim3(512), 0, st, fa);
-        else hipLaunchKernelGGL(sc_layer_fwd_kernel<false>, dim3(nwg), dim3(512), 0, st, fa);
+        if (R == 32) {
+            if (route.fused_lc) hipLaunchKernelGGL(sc_layer_fwd_kernel<true>, dim3(nwg), dim3(512), 0, st, fa);
+            else hipLaunchKernelGGL(sc_layer_fwd_kernel<false>, dim3(nwg), dim3(512), 0, st, fa);
+        } else if (R == 64) {                                 // (nwg: one workgroup per group of eight tiles, as above)
+            if (route.fused_lc) hipLaunchKernelGGL((sc_layer_wide_fwd_kernel<64, true>), dim3(nwg), dim3(512), 0, st, fa);
+            else hipLaunchKernelGGL((sc_layer_wide_fwd_kernel<64, false>), dim3(nwg), dim3(512), 0, st, fa);
+        } else {
+            if (route.fused_lc) hipLaunchKernelGGL((sc_layer_wide_fwd_kernel<128, true>), dim3(nwg), dim3(512), 0, st, fa);
+            else hipLaunchKernelGGL((sc_layer_wide_fwd_kernel<128, false>), dim3(nwg), dim3(512), 0, st, fa);
+        }
     }
     // ================= head: the training step's (model.py:150-165), over all slots x ow rows =================
     // the rows a slot does not have hold whatever the workspace held; every row is a function of itself only, and the loss kernels

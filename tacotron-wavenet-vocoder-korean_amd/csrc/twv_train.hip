@@ -465,6 +465,33 @@ __global__ void tr_views_kernel(float* canon, float* views, float* wsall, int NL
         if (dir == 0) *vp = *cp; else *cp = *vp;
     }
 }
+// the same views at residual = dilation width W (scoring at 64 and 128; forward only): per layer [tap0 (W x 2W) = wf[0]|wg[0]]
+// [tap1 (W x 2W)] [lc (L x 2W)] [gc (G x 2W)], vstride = 2W (2W + L + G), and the stacked skip kernel (NL*W x S)
+__global__ void tr_views_wide_kernel(const float* canon, float* views, float* wsall, int NL, long long c_layer0, long long lstride, long long o_wf,
+                                     long long o_wg, long long o_lcf, long long o_lcg, long long o_gcf, long long o_gcg, long long o_ws, int L, int G,
+                                     int S, int W)
+{
+    const int W2 = 2 * W;
+    const long long vstride = (long long)W2 * (W2 + L + G);
+    const long long per = vstride + (long long)W * S;
+    GRID_STRIDE(i, per * NL) {
+        const int l = (int)(i / per);
+        long long q = i % per;
+        const float* cl = canon + c_layer0 + l * lstride;
+        if (q < vstride) {
+            const int col = (int)(q % W2), half = col >= W ? 1 : 0, j = col - half * W;
+            const long long row = q / W2;
+            const float* cp;
+            if (row < W2) cp = cl + (half ? o_wg : o_wf) + row * W + j;                        // (2,W,W): tap*W*W + in*W + out
+            else if (row < W2 + L) cp = cl + (half ? o_lcg : o_lcf) + (row - W2) * W + j;
+            else cp = cl + (half ? o_gcg : o_gcf) + (row - W2 - L) * W + j;
+            views[l * vstride + q] = *cp;
+        } else {
+            q -= vstride;
+            wsall[(long long)l * W * S + q] = cl[o_ws + q];
+        }
+    }
+}
 __global__ void tr_gather_emb_kernel(const float* table, const int32_t* ids, float* out, int B, int G)
 {
     GRID_STRIDE(i, (long long)B * G) out[i] = table[(long long)ids[i / G] * G + (i % G)];
@@ -1631,6 +1658,22 @@ __global__ void tr_onehot_causal_fwd_kernel(const float* Wc, const int32_t* q, f
         x0[i] = v;
     }
 }
+// the same gather at residual width W (scoring at 64 and 128)
+__global__ void tr_onehot_causal_wide_fwd_kernel(const float* Wc, const int32_t* q, float* x0, int B, int T, int Tn, int Q, int W)
+{
+    const long long total = (long long)B * Tn * W;
+    GRID_STRIDE(i, total) {
+        const int j = (int)(i % W);
+        const long long r = i / W;
+        const int t = (int)(r % Tn), b = (int)(r / Tn);
+        float v = 0.0f;
+        if (t >= 1) {
+            const int qa = q[(long long)b * T + t - 1], qb = q[(long long)b * T + t];
+            v = Wc[(long long)qa * W + j] + Wc[((long long)Q + qb) * W + j];
+        }
+        x0[i] = v;
+    }
+}
 // dWc partial tables: block-local LDS accumulation (ds_add_f32), one (2, Q, 32) table per block, reduced afterwards in a fixed order
 __global__ __launch_bounds__(256) void tr_onehot_causal_bwd_kernel(const float* dx0, const int32_t* q, float* part, int B, int T, int Tn, int Q, long long rows_per_block)
 {
@@ -1840,7 +1883,7 @@ extern "C" int twv_wavenet_train_create(const twv_wavenet_dims* dims, int batch,
 {
     if (!out) return twv_fail(TWV_E_INVALID, "bad argument");
     twv_wavenet_trainer* h = new twv_wavenet_trainer();
-    const int rc = wavenet_graph_init(h->g, dims, batch, n_samples, "training");
+    const int rc = wavenet_graph_init(h->g, dims, batch, n_samples, "training", 32);
     if (rc) { delete h; return rc; }
     h->blas = nullptr;
     h->ws_clean = nullptr;
@@ -1882,39 +1925,45 @@ int wavenet_forward_front(const WavenetGraph& g, const float* P, const float* au
 {
     const twv_wavenet_dims& d = g.d;
     const int B = g.rows, T = g.T, Tn = g.Tn, NL = g.NL, S = g.S, L = g.L, G = g.G, F = g.F;
+    const int R = g.R, D2 = 2 * g.D;                         // the width: 32 and 64 columns (filter | gate) in the training step
     const long long Rr = (long long)B * Tn, RT = (long long)B * T;
     const bool fused_lc = wavenet_route(g).fused_lc;
     const float one = 1.0f, zero = 0.0f;
-    K1(tr_views_kernel, (b.vstride + 32LL * S) * NL, const_cast<float*>(P), b.WV, b.WS, NL, g.c_layer0, g.c_lstride, g.lo.wf, g.lo.wg, g.lo.lcf, g.lo.lcg,
-       g.lo.gcf, g.lo.gcg, g.lo.ws, L, G, S, 0);
+    if (R == 32)
+        K1(tr_views_kernel, (b.vstride + 32LL * S) * NL, const_cast<float*>(P), b.WV, b.WS, NL, g.c_layer0, g.c_lstride, g.lo.wf, g.lo.wg, g.lo.lcf, g.lo.lcg,
+           g.lo.gcf, g.lo.gcg, g.lo.ws, L, G, S, 0);
+    else
+        K1(tr_views_wide_kernel, (b.vstride + (long long)g.D * S) * NL, P, b.WV, b.WS, NL, g.c_layer0, g.c_lstride, g.lo.wf, g.lo.wg, g.lo.lcf, g.lo.lcg,
+           g.lo.gcf, g.lo.gcg, g.lo.ws, L, G, S, R);
     for (int i = 0; i < d.n_upsample && !fused_lc; ++i)     // model.py:276 create_upsample (the fused lc path never materialises it)
         K1(tr_up_fwd_kernel, (long long)B * b.upT[i + 1] * L, P + g.c_up[i], b.ups[i], b.ups[i + 1], (long long)B * b.upT[i + 1] * L, d.upsample_factor[i], L);
     K1(tr_gather_emb_kernel, (long long)B * G, P + g.c_gcemb, gc_ids, b.emb, B, G);   // model.py:197-198
     if (d.scalar_input) {
         K1(tr_unfold_kernel, Rr * g.ifw, audio, b.xunf, B, T, Tn, g.ifw);
-        BLASCHK(gemm_rm(bl, false, false, (int)Rr, 32, g.ifw, 1.f, b.xunf, g.ifw, P + g.c_causal, 32, 0.f, b.X0, 32));   // model.py:131
+        BLASCHK(gemm_rm(bl, false, false, (int)Rr, R, g.ifw, 1.f, b.xunf, g.ifw, P + g.c_causal, R, 0.f, b.X0, R));   // model.py:131
     } else {
         if (int rc = twv_mu_law_encode(audio, RT, d.quantization_channels, b.qin, st)) return rc;                        // model.py:257
-        K1(tr_onehot_causal_fwd_kernel, Rr * 32, P + g.c_causal, b.qin, b.X0, B, T, Tn, d.quantization_channels);
+        if (R == 32) K1(tr_onehot_causal_fwd_kernel, Rr * 32, P + g.c_causal, b.qin, b.X0, B, T, Tn, d.quantization_channels);
+        else K1(tr_onehot_causal_wide_fwd_kernel, Rr * R, P + g.c_causal, b.qin, b.X0, B, T, Tn, d.quantization_channels, R);
     }
     if (fused_lc) {
         // per step: the hop's tap table from the three upsampling kernels, the bin-shifted mel frames, and every layer's frame-rate
-        // lc projections Q_l = melsh (B*F*4 x 80) . Wlc_l (80 x 64) as one strided-batched GEMM
+        // lc projections Q_l = melsh (B*F*4 x 80) . Wlc_l (80 x 2D) as one strided-batched GEMM
         K1(tr_ctab_kernel, g.hop, P + g.c_up[0], P + g.c_up[1], P + g.c_up[2], d.upsample_factor[0], d.upsample_factor[1], d.upsample_factor[2], b.ctab);
         K1(tr_mel_shift_kernel, (long long)B * F * 4 * L, b.ups[0], b.melsh, (long long)B * F, L);
-        BLASCHK(rocblas_sgemm_strided_batched(bl, rocblas_operation_none, rocblas_operation_none, 64, B * F * 4, L, &one, b.WV + 64 * 64, 64, b.vstride,
-                                              b.melsh, L, 0, &zero, b.Qall, 64, b.q_ls + 64, NL));
+        BLASCHK(rocblas_sgemm_strided_batched(bl, rocblas_operation_none, rocblas_operation_none, D2, B * F * 4, L, &one, b.WV + 2LL * R * D2, D2, b.vstride,
+                                              b.melsh, L, 0, &zero, b.Qall, D2, b.q_ls + 64, NL));
     }
-    // model.py:71-73 gc projections of every layer: GCP[l] (B x 64) = emb (B x G) . Wgc_l (G x 64)
-    BLASCHK(rocblas_sgemm_strided_batched(bl, rocblas_operation_none, rocblas_operation_none, 64, B, G, &one, b.WV + (64 + L) * 64, 64, b.vstride,
-                                          b.emb, G, 0, &zero, b.GCP, 64, (long long)B * 64, NL));
+    // model.py:71-73 gc projections of every layer: GCP[l] (B x 2D) = emb (B x G) . Wgc_l (G x 2D)
+    BLASCHK(rocblas_sgemm_strided_batched(bl, rocblas_operation_none, rocblas_operation_none, D2, B, G, &one, b.WV + (2LL * R + L) * D2, D2, b.vstride,
+                                          b.emb, G, 0, &zero, b.GCP, D2, (long long)B * D2, NL));
     return TWV_OK;
 }
 // model.py:94-96,150-165: sum over layers of the skip 1x1 convs == ONE GEMM against the stacked skip kernels, then
 // (+ all skip biases) relu -> 1x1 -> relu -> 1x1
 int wavenet_forward_head(const WavenetGraph& g, const float* P, const WavenetFwdBufs& b, bool skinny, bool c1_raw, rocblas_handle bl, hipStream_t st)
 {
-    const int NL = g.NL, S = g.S, O = g.O, ZW = NL * 32;
+    const int NL = g.NL, S = g.S, O = g.O, ZW = NL * g.D;
     const long long RO = (long long)g.rows * g.ow;
     const bool ub = g.d.use_biases != 0;
     const float* bs0 = P + g.c_layer0 + g.lo.bs;            // layer 0's skip bias; layer l's lies l * c_lstride behind it

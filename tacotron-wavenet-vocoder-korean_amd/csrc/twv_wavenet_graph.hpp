@@ -31,6 +31,7 @@ struct WavenetLayerOff { long long wf, bf, wg, bg, gcf, gcg, lcf, lcg, wd, bd, w
 struct WavenetGraph {
     twv_wavenet_dims d;
     int rows, T, Tn, rf, ow, NL, S, O, L, G, ifw, hop, F;    // rows = batch entries / slots, T samples each, Tn = T - 1, ow = T - rf, F = T / hop frames
+    int R, D;                                                // residual / dilation channels: the width (equal; 32, 64 or 128)
     int off[TWV_MAX_LAYERS + 1];                             // receptive offset of layer l's INPUT (off[0] = ifw - 1), off[NL] = rf - 1
     long long c_causal, c_gcemb, c_layer0, c_lstride, c_w1, c_b1, c_w2, c_b2, c_up[4], nparams;
     WavenetLayerOff lo;                                      // offsets inside a layer block
@@ -62,8 +63,9 @@ inline std::string wavenet_route_label(const WavenetRoute& r, const char* head)
 }
 
 // Fills g from (dims, rows, samples) and makes every refusal of twv_wavenet_train_create / twv_wavenet_score_create (`what`: "training" /
-// "scoring", for the texts).  TWV_OK, or the code twv_fail was given.
-inline int wavenet_graph_init(WavenetGraph& g, const twv_wavenet_dims* dims, int rows, int samples, const char* what)
+// "scoring", for the texts).  The width is the caller's to allow: residual_channels = dilation_channels in {32, 64, 128} and at most
+// `max_width` (training: 32, its backward kernels are built for that width; scoring: 128).  TWV_OK, or the code twv_fail was given.
+inline int wavenet_graph_init(WavenetGraph& g, const twv_wavenet_dims* dims, int rows, int samples, const char* what, int max_width)
 {
     const std::string w(what);
     if (dims && dims->gc_channels > 0 && dims->gc_cardinality < 1)
@@ -80,20 +82,26 @@ inline int wavenet_graph_init(WavenetGraph& g, const twv_wavenet_dims* dims, int
     for (int l = 0; l < g.NL; ++l) g.off[l + 1] = g.off[l] + d.dilations[l];
     g.rf = g.off[g.NL] + 1;
     g.ow = samples - g.rf;                                            // model.py:135 output_width
-    if (d.residual_channels != 32 || d.dilation_channels != 32) return twv_fail(TWV_E_UNSUPPORTED, w + " is built for residual_channels = dilation_channels = 32 only: " + w + " at other widths is not built");
+    g.R = d.residual_channels; g.D = d.dilation_channels;
+    if (max_width <= 32) {
+        if (g.R != 32 || g.D != 32) return twv_fail(TWV_E_UNSUPPORTED, w + " is built for residual_channels = dilation_channels = 32 only: " + w + " at other widths is not built");
+    } else if (g.R != g.D || (g.R != 32 && g.R != 64 && g.R != 128) || g.R > max_width) {
+        return twv_fail(TWV_E_UNSUPPORTED, w + " is built for residual_channels = dilation_channels = 32, 64 or 128 only (got " + std::to_string(g.R) + ", " + std::to_string(g.D) + ")");
+    }
     if (d.scalar_input && (d.out_channels < 3 || d.out_channels % 3 || d.out_channels > 96)) return twv_fail(TWV_E_UNSUPPORTED, "out_channels must be 3*nr_mix, 3 <= out_channels <= 96");
     if (!d.scalar_input && (d.quantization_channels < 2 || d.quantization_channels > 512)) return twv_fail(TWV_E_UNSUPPORTED, "quantization_channels must be in [2, 512] for " + w);
     if (d.lc_channels != 80 || !d.gc_channels) return twv_fail(TWV_E_UNSUPPORTED, w + " expects num_mels = 80 local and global conditioning (train_vocoder.py, hparams.py:30)");
     // only the FUSED layer kernels (three upsampling stages, 32 <= hop <= 512, 80 mel channels) address a layer's activations with 32-bit
     // byte offsets; the pointer kernels of every other model keep 64-bit addresses and take any size.  Scoring keeps the limit: its
-    // memory is bounded by the window batch, a longer utterance is more windows, never a larger batch
+    // memory is bounded by the window batch, a longer utterance is more windows, never a larger batch.  The bound is the same at every
+    // width: the wide scoring kernel (sc_layer_wide_fwd_kernel) addresses with 64 bits, so no row it offsets is wider than this one
     if (wavenet_route(g).fused_lc && (long long)rows * samples * 64 * 4 >= (1LL << 31))
         return twv_fail(TWV_E_UNSUPPORTED, w + ": rows x samples too large on the fused lc route: its layer kernels address a layer's activations with 32-bit byte offsets (rows * samples < 8.3 M)");
     if (samples < 1 || samples % g.hop) return twv_fail(TWV_E_INVALID, w + ": the samples per row must be a multiple of the hop size (datafeeder_wavenet.py:38-47)");
     if (g.ow < 1) return twv_fail(TWV_E_INVALID, w + ": the samples per row must exceed the receptive field");
     g.F = samples / g.hop;
     long long c = 0, q = 0;
-    const int R = 32, D = 32, ub = d.use_biases ? 1 : 0;
+    const int R = g.R, D = g.D, ub = d.use_biases ? 1 : 0;
     g.c_causal = c; c += d.scalar_input ? (long long)g.ifw * R : 2LL * d.quantization_channels * R;
     g.c_gcemb = c; c += (long long)d.gc_cardinality * g.G;
     g.c_layer0 = c;
@@ -116,7 +124,7 @@ struct WavenetFwdBufs {
     float* ups[5]; const long long* upT;                     // ups[0] = the caller's mel frames, ups[i] = stage i's output (staged route), upT[i] rows each
     float* xunf; int32_t* qin;                               // unfolded audio (scalar input) / mu-law classes (one-hot input)
     float *X0, *emb, *GCP, *WV, *WS, *ctab, *melsh, *Qall;   // layer 0's input, gc embedding rows and projections, weight views, fused-lc tables
-    long long vstride, q_ls;
+    long long vstride, q_ls;                                 // vstride = 2D * (2R + L + G) floats per layer of WV, q_ls = rows * F * 4 * 2D per layer of Qall
     float *ZC, *SK, *C1, *Y;                                 // head: stacked skip input, skip sum, conv1d_1, conv1d_2 outputs
     float* bsum;                                             // S floats of scratch for the summed skip biases
 };

@@ -118,8 +118,19 @@ class WaveNetScorer(object):
 
     def route(self):
         """which kernel families score() runs (twv_wavenet_score_route) as a dict of strings: lc (fused | staged), head (skinny | gemm),
-        loss (mol<10> | mol<0> | softmax), carve_floats"""
+        loss (mol<10> | mol<0> | softmax), width (32 | 64 | 128), carve_floats"""
         return dict(kv.split("=", 1) for kv in self._L.twv_wavenet_score_route(self._h).decode().split())
+
+    def view(self, name):
+        """what the last run() left in the workspace (twv_wavenet_score_view), a 2-D slice of the workspace tensor: "zc" the stacked skip
+        input (slots * width, n_layers * dilation_channels), "y" the raw network output (slots * width, out channels).  Rows a slot
+        does not have hold whatever the workspace held."""
+        from . import _lib
+        if self._ws is None:
+            raise RuntimeError("no workspace yet: run() first")
+        off, rows, cols = C.c_longlong(), C.c_longlong(), C.c_longlong()
+        _lib.check(self._L.twv_wavenet_score_view(self._h, name.encode(), C.byref(off), C.byref(rows), C.byref(cols)))
+        return self._ws[off.value:off.value + rows.value * cols.value].view(rows.value, cols.value)
 
     def load_weights(self, tensors):
         """a dict of the variables by name (weights.tensor_specs), or a flat float32 blob in that order (WaveNetTrainer.params / .ema)"""
