@@ -294,6 +294,12 @@ const char* twv_tacotron_decoder_kernel_name(const twv_tacotron* h, int batch, i
 typedef struct twv_wavenet_trainer twv_wavenet_trainer;
 /* batch = hparams.wavenet_batch_size, n_samples = crop length fed by DataFeederWavenet (a multiple of the hop size) */
 int twv_wavenet_train_create(const twv_wavenet_dims* dims, int batch, int n_samples, twv_wavenet_trainer** out);
+/* the same with the widest residual_channels = dilation_channels the caller is prepared to run: max_width 32, 64 or 128 (anything else
+ * is TWV_E_INVALID).  With 32 it is twv_wavenet_train_create (which calls it) and refuses with that function's text; above 32 it accepts
+ * equal widths of 32, 64 and 128 up to max_width and refuses the rest with "... 32, 64 or 128 only (got R, D)".  A width-32 handle is
+ * the same handle from either function; every other twv_wavenet_train_* call takes a handle of any width.  At 64 and 128 the step keeps
+ * three width-sized arrays per layer: twv_wavenet_train_workspace_bytes says how much (tens of GB at 30 layers, 64 x 7800, width 128). */
+int twv_wavenet_train_create_w(const twv_wavenet_dims* dims, int batch, int n_samples, int max_width, twv_wavenet_trainer** out);
 void twv_wavenet_train_destroy(twv_wavenet_trainer* h);
 size_t twv_wavenet_train_param_floats(const twv_wavenet_trainer* h);
 size_t twv_wavenet_train_workspace_bytes(const twv_wavenet_trainer* h);
@@ -302,7 +308,7 @@ size_t twv_wavenet_train_workspace_bytes(const twv_wavenet_trainer* h);
 int twv_wavenet_train_reset_workspace(twv_wavenet_trainer* h);
 int twv_wavenet_train_output_width(const twv_wavenet_trainer* h);          /* n_samples - receptive_field (model.py:135) */
 /* host-only: which kernel families twv_wavenet_train_loss_grad runs for this trainer, as a string the handle owns:
- *   "lc=<fused|staged> head=<skinny+c2bwd|skinny|gemm> loss=<mol<10>|mol<0>|softmax> nsplit=<n> carve_floats=<n>"
+ *   "lc=<fused|staged> head=<skinny+c2bwd|skinny|gemm> loss=<mol<10>|mol<0>|softmax> nsplit=<n> width=<32|64|128> carve_floats=<n>"
  * lc: frame-rate lc projections inside the layer kernels, or the materialised upsampler; head: conv1d_2 as the skinny kernel (with or
  * without its fused backward) or library GEMMs; nsplit: K slabs of the wide weight gradients; carve_floats: the floats loss_grad takes
  * from the start of the workspace (workspace_bytes / 4 is at least that).  A label for tests and measurements. */

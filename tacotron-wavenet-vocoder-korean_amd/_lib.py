@@ -256,6 +256,7 @@ def lib():
     L.twv_tacotron_gemm_stats.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]
     L.twv_tacotron_decoder_kernel_name.argtypes = [vp, C.c_int, C.c_int]; L.twv_tacotron_decoder_kernel_name.restype = C.c_char_p
     L.twv_wavenet_train_create.argtypes = [C.POINTER(Dims), C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    L.twv_wavenet_train_create_w.argtypes = [C.POINTER(Dims), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     L.twv_wavenet_train_destroy.argtypes = [vp]; L.twv_wavenet_train_destroy.restype = None
     for n in ("twv_wavenet_train_param_floats", "twv_wavenet_train_workspace_bytes"):
         getattr(L, n).argtypes = [vp]; getattr(L, n).restype = C.c_size_t
@@ -296,7 +297,7 @@ EXPORTS = ["twv_last_error", "twv_version", "twv_wavenet_create", "twv_wavenet_d
            "twv_resample_workspace_bytes", "twv_resample_filter_host", "twv_resample_kernel_name", "twv_resample_rounds", "twv_resample",
            "twv_griffin_lim_create_ragged", "twv_griffin_lim_total_frames", "twv_griffin_lim_total_samples", "twv_griffin_lim_offsets",
            "twv_wavenet_score_create", "twv_wavenet_score_destroy", "twv_wavenet_score_workspace_bytes", "twv_wavenet_score_output_width",
-           "twv_wavenet_score_route", "twv_wavenet_score_windows", "twv_wavenet_score_reduce", "twv_wavenet_score_view"]
+           "twv_wavenet_score_route", "twv_wavenet_score_windows", "twv_wavenet_score_reduce", "twv_wavenet_score_view", "twv_wavenet_train_create_w"]
 
 
 class TacoDims(C.Structure):

@@ -45,6 +45,7 @@ struct twv_wavenet_trainer {
 // ---------------------------------------------------------------------------------------------------------------
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4t __attribute__((ext_vector_type(4)));
+typedef float f32x2t __attribute__((ext_vector_type(2)));
 // 16-byte accesses through a buffer descriptor (out-of-range offset: the load returns zeros, the store is dropped)
 __device__ __forceinline__ f32x4t tr_bld4(rsrc_t r, unsigned off)
 {
@@ -1719,6 +1720,477 @@ __global__ __launch_bounds__(256) void tr_softmax_ce_kernel(const float* y, cons
 // MoL variant writes per-row losses too; the scalar loss is their deterministic two-stage sum
 
 
+// ===================================================================================================================
+//  The step at residual = dilation width W = 64 or 128.  Arrays as in the width-32 step with W for every 32 and 2W for
+//  every 64: X, TH, SG, dX (B*Tn, W); dPRE (B*Tn, 2W), columns filter | gate; views W0, W1 (W, 2W), Wlc (80, 2W), Wgc (G, 2W); Wd (W, W).
+//  Forward: the block scheme of sc_layer_wide_fwd_kernel (twv_score.hip) on right-aligned rows, which also keeps tanh and sigmoid.
+//  Backward: two kernels per layer on v_mfma_f32_32x32x2_f32, 32-row tiles x 32-channel blocks, 64-bit addresses:
+//      tr_layer_wide_bwd1_kernel   dZ = dXn Wd^T + dZC,  gated-unit backward -> dPRE, z (operand of dWd), per-tile column sums
+//      tr_layer_wide_bwd2_kernel   dX = dXn + dPRE[t] W1^T + dPRE[t+d] W0^T, per-tile column sums (the dense bias of the layer below)
+//  Their B operands are the TRANSPOSED weights, written once per step by tr_views_wide_t_kernel (slice loads are then coalesced).
+//  Both walk every tile and write zeros for the rows in front of the layer's offset: dPRE = 0 there is what the row-shifted weight
+//  gradient (X[s]^T dPRE[s+d] over all rows, batch boundaries included) and the frame sums rest on.
+//  The weight gradients are K = rows products on the split-K library path (gemm_tn_splitk); the lc input gradient and the small
+//  reductions are the kernels below.  No atomics, fixed orders.
+// ===================================================================================================================
+// per layer [W1^T (2W x W)] [W0^T (2W x W)] [Wd^T (W x W)]: 5 W^2 floats.  W1^T[k][m] = view W1[m][k] (m = input channel, k = filter | gate column)
+__global__ void tr_views_wide_t_kernel(const float* views, long long vstride, const float* canon, long long c_layer0, long long lstride, long long o_wd,
+                                       float* wt, int NL, int W)
+{
+    const int W2 = 2 * W;
+    const long long per = 5LL * W * W;
+    GRID_STRIDE(i, per * NL) {
+        const int l = (int)(i / per);
+        const long long q = i % per;
+        const float* v = views + l * vstride;
+        float x;
+        if (q < 2LL * W2 * W) {
+            const int tap = q < (long long)W2 * W ? 1 : 0;                      // W1^T first
+            const long long r = q - (tap ? 0 : (long long)W2 * W);
+            const int k = (int)(r / W), m = (int)(r % W);
+            x = v[(long long)tap * W * W2 + (long long)m * W2 + k];
+        } else {
+            const long long r = q - 2LL * W2 * W;
+            const int k = (int)(r / W), zc = (int)(r % W);
+            x = canon[c_layer0 + l * lstride + o_wd + (long long)zc * W + k];
+        }
+        wt[i] = x;
+    }
+}
+// gradient views -> canonical order: the scatter twin of tr_views_wide_kernel
+__global__ void tr_views_wide_bwd_kernel(float* canon, const float* views, const float* wsall, int NL, long long c_layer0, long long lstride, long long o_wf,
+                                         long long o_wg, long long o_lcf, long long o_lcg, long long o_gcf, long long o_gcg, long long o_ws, int L, int G,
+                                         int S, int W)
+{
+    const int W2 = 2 * W;
+    const long long vstride = (long long)W2 * (W2 + L + G);
+    const long long per = vstride + (long long)W * S;
+    GRID_STRIDE(i, per * NL) {
+        const int l = (int)(i / per);
+        long long q = i % per;
+        float* cl = canon + c_layer0 + l * lstride;
+        if (q < vstride) {
+            const int col = (int)(q % W2), half = col >= W ? 1 : 0, j = col - half * W;
+            const long long row = q / W2;
+            float* cp;
+            if (row < W2) cp = cl + (half ? o_wg : o_wf) + row * W + j;
+            else if (row < W2 + L) cp = cl + (half ? o_lcg : o_lcf) + (row - W2) * W + j;
+            else cp = cl + (half ? o_gcg : o_gcf) + (row - W2 - L) * W + j;
+            *cp = views[l * vstride + q];
+        } else {
+            q -= vstride;
+            cl[o_ws + q] = wsall[(long long)l * W * S + q];
+        }
+    }
+}
+
+// forward layer: LayerFwdArgs at width W (gcp (B, 2W), Q[((b*F + frame)*4 + j)*2W + column], ZC offset to the layer's W columns).
+// One wave per 32-row tile of one batch entry, output channels in W / 32 blocks; at 64 every weight slice stays in LDS, at 128 one
+// slice at a time and the eight waves of a workgroup take eight tiles in step (two barriers per block).  Rows t < o are neither
+// computed nor stored (they are zeros of the workspace's one clear); tiles in front of t_lo are not walked.
+template <int W, bool FUSED>
+__global__ void __launch_bounds__(512) tr_layer_wide_fwd_kernel(LayerFwdArgs a)
+{
+    constexpr int NB = W / 32;
+    constexpr int W2 = 2 * W;
+    constexpr int TAP = W / 2;                               // MFMA steps per tap (k = W)
+    constexpr int STEPS = 2 * TAP + (FUSED ? 0 : 4 * kLcSteps);
+    constexpr bool RES = W == 64;                            // every slice resident
+    constexpr int NSL = RES ? NB : 1;
+    __shared__ __attribute__((aligned(16))) float bt[NSL * STEPS * 128];       // [slice][step][lane][filter, gate]
+    __shared__ float bdt[NSL * NB * 16 * 64];                                   // dense: [slice][out block][step][lane]
+    __shared__ __attribute__((aligned(16))) float cts[FUSED ? 4 * 512 : 4];    // ctab (hop <= 512)
+    __shared__ __attribute__((aligned(16))) float zt[8][32 * 36];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int n = lane & 31, hh = lane >> 5;
+    const int cut = a.Tn - a.ow;                             // rf - 1: first row of the skip slice
+    if (FUSED) for (int e = threadIdx.x; e < a.hop * 4; e += 512) cts[e] = a.ctab[e];
+    auto load_slice = [&](int c, int slot) {
+        float* bs = bt + slot * STEPS * 128;
+        for (int e = threadIdx.x; e < STEPS * 64; e += 512) {
+            const int s = e >> 6, l = e & 63, nn = l & 31, h2 = l >> 5;
+            const float* Wp; int ij;
+            if (s < TAP) { Wp = a.W0; ij = s; } else if (s < 2 * TAP) { Wp = a.W1; ij = s - TAP; } else { Wp = a.Wlc; ij = s - 2 * TAP; }
+            const int k = 8 * (ij >> 2) + 4 * h2 + (ij & 3);
+            bs[e * 2] = Wp[k * W2 + c * 32 + nn]; bs[e * 2 + 1] = Wp[k * W2 + W + c * 32 + nn];
+        }
+        float* ds = bdt + slot * NB * 16 * 64;
+        for (int e = threadIdx.x; e < NB * 16 * 64; e += 512) {
+            const int ob = e >> 10, s = (e >> 6) & 15, l = e & 63;
+            ds[e] = a.Wd[(c * 32 + 8 * (s >> 2) + 4 * (l >> 5) + (s & 3)) * W + ob * 32 + (l & 31)];
+        }
+    };
+    if (RES) {
+        for (int c = 0; c < NB; ++c) load_slice(c, c);
+        __syncthreads();
+    }
+    const f32x16 zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    const int ntiles = a.B * a.tpb, ngroups = (ntiles + 7) / 8;
+    for (int grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {                // block-uniform: every wave meets every barrier
+        const int tile = grp * 8 + wave;
+        const bool active = tile < ntiles;
+        const int b = active ? tile / a.tpb : 0, t0 = active ? (tile - b * a.tpb) * 32 + a.t_lo : 0;
+        const int t = t0 + n;
+        const bool ok = active && t < a.Tn && t >= a.o;
+        const float* xr = a.X + ((long long)b * a.Tn + t) * W + 4 * hh;          // lane (row, hh) carries k = 8i + 4hh .. +3 of its row
+        const float* ur = a.U + ((long long)b * a.T + (t - a.o)) * 80 + 4 * hh;
+        f32x16 cd[NB];
+#pragma unroll
+        for (int ob = 0; ob < NB; ++ob) cd[ob] = zero;
+        for (int c = 0; c < NB; ++c) {
+            if (!RES) {
+                __syncthreads();                              // the waves have finished with the slice before
+                load_slice(c, 0);
+                __syncthreads();
+            }
+            if (!active) continue;
+            const float* bs = bt + (RES ? c : 0) * STEPS * 128 + lane * 2;
+            const float* ds = bdt + (RES ? c : 0) * NB * 16 * 64 + lane;
+            f32x16 cf = zero, cg = zero;
+            if (FUSED) {                                      // the lc term first: the accumulators start from it
+                int u0 = t0 - a.o; u0 = u0 < 0 ? 0 : u0;     // U row u = t - o; at most two frames per 32-row tile (hop >= 32)
+                const int fA = u0 / a.hop, fB = fA + 1 < a.F ? fA + 1 : fA;
+                const int edge = (fA + 1) * a.hop;                               // first U row of frame fA + 1
+                const float* qa = a.Q + (((long long)b * a.F + fA) * 4) * W2 + c * 32 + n;
+                const float* qb = a.Q + (((long long)b * a.F + fB) * 4) * W2 + c * 32 + n;
+                float qfa[4], qga[4], qfb[4], qgb[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { qfa[j] = qa[j * W2]; qga[j] = qa[j * W2 + W]; qfb[j] = qb[j * W2]; qgb[j] = qb[j * W2 + W]; }
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    int uu = t0 - a.o + (r & 3) + 8 * (r >> 2) + 4 * hh;
+                    uu = uu < 0 ? 0 : uu;                                         // rows below the layer's offset are discarded by the epilogue
+                    const bool hi = uu >= edge;
+                    int ph = uu - (hi ? edge : edge - a.hop);
+                    ph = ph < a.hop ? ph : a.hop - 1;                             // (only rows past the end, discarded as well)
+                    const f32x4t ct = *reinterpret_cast<const f32x4t*>(&cts[ph * 4]);
+                    const float f0 = hi ? qfb[0] : qfa[0], f1 = hi ? qfb[1] : qfa[1], f2 = hi ? qfb[2] : qfa[2], f3 = hi ? qfb[3] : qfa[3];
+                    const float g0 = hi ? qgb[0] : qga[0], g1 = hi ? qgb[1] : qga[1], g2 = hi ? qgb[2] : qga[2], g3 = hi ? qgb[3] : qga[3];
+                    cf[r] = ((ct[0] * f0 + ct[1] * f1) + ct[2] * f2) + ct[3] * f3;
+                    cg[r] = ((ct[0] * g0 + ct[1] * g1) + ct[2] * g2) + ct[3] * g3;
+                }
+            }
+#pragma unroll 2
+            for (int i = 0; i < W / 8; ++i) {
+                const f32x4t x0 = tr_ld4(xr - (long long)a.d * W + 8 * i, ok);   // t - d >= off[l]: a row of the layer's input
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const f32x2t w = *reinterpret_cast<const f32x2t*>(&bs[(4 * i + j) * 128]);
+                    cf = __builtin_amdgcn_mfma_f32_32x32x2f32(x0[j], w[0], cf, 0, 0, 0);
+                    cg = __builtin_amdgcn_mfma_f32_32x32x2f32(x0[j], w[1], cg, 0, 0, 0);
+                }
+            }
+#pragma unroll 2
+            for (int i = 0; i < W / 8; ++i) {
+                const f32x4t x1 = tr_ld4(xr + 8 * i, ok);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const f32x2t w = *reinterpret_cast<const f32x2t*>(&bs[(TAP + 4 * i + j) * 128]);
+                    cf = __builtin_amdgcn_mfma_f32_32x32x2f32(x1[j], w[0], cf, 0, 0, 0);
+                    cg = __builtin_amdgcn_mfma_f32_32x32x2f32(x1[j], w[1], cg, 0, 0, 0);
+                }
+            }
+            if (!FUSED) {
+#pragma unroll 2
+                for (int i = 0; i < kLcSteps; ++i) {
+                    const f32x4t u = tr_ld4(ur + 8 * i, ok);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const f32x2t w = *reinterpret_cast<const f32x2t*>(&bs[(2 * TAP + 4 * i + j) * 128]);
+                        cf = __builtin_amdgcn_mfma_f32_32x32x2f32(u[j], w[0], cf, 0, 0, 0);
+                        cg = __builtin_amdgcn_mfma_f32_32x32x2f32(u[j], w[1], cg, 0, 0, 0);
+                    }
+                }
+            }
+            // ---- gated unit; rows that do not exist give z = 0 (a select, not a product: whatever their accumulators hold)
+            const int ch = c * 32 + n;
+            const float vbf = a.bf ? a.bf[ch] : 0.0f, vbg = a.bg ? a.bg[ch] : 0.0f;
+            const float gcf = a.gcp[b * W2 + ch], gcg = a.gcp[b * W2 + W + ch];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int rl = (r & 3) + 8 * (r >> 2) + 4 * hh, tr = t0 + rl;
+                const bool valid = tr < a.Tn && tr >= a.o;
+                const float th = tr_tanh_fast((cf[r] + vbf) + gcf), sg = tr_sigmoid_fast((cg[r] + vbg) + gcg);
+                const float z = valid ? th * sg : 0.0f;
+                if (valid) {
+                    const long long at = ((long long)b * a.Tn + tr) * W + ch;
+                    a.TH[at] = th; a.SG[at] = sg;             // what the backward pass needs of this layer
+                    if (tr >= cut) a.ZC[((long long)b * a.ow + (tr - cut)) * a.ldz + ch] = z;     // model.py:94-96: the last ow rows
+                }
+                zt[wave][rl * 36 + n] = z;
+            }
+            // ---- dense 1x1: this block of z as A operand (row layout) back from the wave's LDS patch, into every output block
+            {
+                const float* zr = &zt[wave][n * 36 + 4 * hh];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const f32x4t q = *reinterpret_cast<const f32x4t*>(zr + 8 * i);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+#pragma unroll
+                        for (int ob = 0; ob < NB; ++ob)
+                            cd[ob] = __builtin_amdgcn_mfma_f32_32x32x2f32(q[j], ds[(ob * 16 + 4 * i + j) * 64], cd[ob], 0, 0, 0);
+                }
+            }
+        }
+        if (!active) continue;
+        // ---- residual: x_next = X[t] + z Wd + bd in the output (C) layout: lane = channel, register r = row (r&3) + 8(r>>2) + 4hh
+#pragma unroll
+        for (int ob = 0; ob < NB; ++ob) {
+            const float vbd = a.bd ? a.bd[ob * 32 + n] : 0.0f;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int tr = t0 + (r & 3) + 8 * (r >> 2) + 4 * hh;
+                if (tr < a.Tn && tr >= a.o) {
+                    const long long at = ((long long)b * a.Tn + tr) * W + ob * 32 + n;
+                    a.XN[at] = (a.X[at] + cd[ob][r]) + vbd;
+                }
+            }
+        }
+    }
+}
+
+struct WideBwdArgs {
+    const float* dXn; const float* dZC;                      // (B*Tn, W) gradient of the layer's output; dZC offset to the layer's W columns
+    const float* TH; const float* SG;                        // (B*Tn, W) saved by the forward kernel
+    const float* WdT; const float* W1T; const float* W0T;    // transposed weights (tr_views_wide_t_kernel): (W, W), (2W, W), (2W, W)
+    float* dPRE; float* Zb;                                  // (B*Tn, 2W) filter | gate; (B*Tn, W) z = tanh * sigmoid
+    float* tsum;                                             // this layer's per-tile column sums [tile][3W]: dPRE (2W) | dX of the layer ABOVE (W)
+    float* tsum_below;                                       // the slot of the layer below (bwd2 writes its W columns of dX sums), or nullptr
+    float* dX;                                               // (B*Tn, W)
+    int B, Tn, d, o, ow, ldz, tpb;                           // tpb = ceil(Tn / 32): every tile is walked
+};
+
+// dZ = dXn Wd^T + dZC, then the gated unit's backward from the saved tanh / sigmoid -> dPRE (zero in front of o), z, and the tile's
+// column sums of dPRE.  All W / 32 slices of Wd^T stay in LDS (16 / 64 KiB): the waves run free of each other.  The tile's rows of dXn
+// are read again per block (L1 / L2 hits), as the forward kernel reads X.
+template <int W>
+__global__ void __launch_bounds__(512) tr_layer_wide_bwd1_kernel(WideBwdArgs a)
+{
+    constexpr int NB = W / 32, TAP = W / 2, W2 = 2 * W;
+    __shared__ float bt[NB * TAP * 64];                      // [block c][step][lane]: Wd^T[k][32c + n]
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int n = lane & 31, hh = lane >> 5;
+    const int cut = a.Tn - a.ow;
+    for (int e = threadIdx.x; e < NB * TAP * 64; e += 512) {
+        const int l = e & 63, s = (e >> 6) % TAP, c = (e >> 6) / TAP;
+        const int k = 8 * (s >> 2) + 4 * (l >> 5) + (s & 3);
+        bt[e] = a.WdT[k * W + c * 32 + (l & 31)];
+    }
+    __syncthreads();
+    const int ntiles = a.B * a.tpb, nwaves = gridDim.x * 8;
+    for (int tile = blockIdx.x * 8 + wave; tile < ntiles; tile += nwaves) {
+        const int b = tile / a.tpb, t0 = (tile - b * a.tpb) * 32;
+        const int tl = t0 + n;
+        const float* xr = a.dXn + ((long long)b * a.Tn + tl) * W + 4 * hh;       // lane (row, hh) carries k = 8i + 4hh .. +3 of its row
+        float* ts = a.tsum + (long long)tile * (3 * W);
+#pragma unroll 1
+        for (int c = 0; c < NB; ++c) {
+            const float* bs = bt + c * TAP * 64 + lane;
+            f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll 4
+            for (int i = 0; i < W / 8; ++i) {
+                const f32x4t x = tr_ld4(xr + 8 * i, tl < a.Tn);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(x[j], bs[(4 * i + j) * 64], acc, 0, 0, 0);
+            }
+            const int ch = c * 32 + n;
+            float sf = 0.0f, sgs = 0.0f;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int t = t0 + (r & 3) + 8 * (r >> 2) + 4 * hh;
+                const bool valid = t < a.Tn && t >= a.o;
+                const long long at = ((long long)b * a.Tn + t) * W + ch;
+                float dz = acc[r], th = 0.0f, sg = 0.0f;
+                if (valid) {
+                    th = a.TH[at]; sg = a.SG[at];
+                    if (t >= cut) dz += a.dZC[((long long)b * a.ow + (t - cut)) * a.ldz + ch];
+                }
+                const float dpf = valid ? (dz * sg) * (1.0f - th * th) : 0.0f;
+                const float dpg = valid ? (dz * th) * (sg * (1.0f - sg)) : 0.0f;
+                if (t < a.Tn) {
+                    float* pr = a.dPRE + ((long long)b * a.Tn + t) * W2 + ch;
+                    pr[0] = dpf; pr[W] = dpg;
+                    a.Zb[at] = valid ? th * sg : 0.0f;
+                }
+                sf += dpf; sgs += dpg;
+            }
+            sf += tr_xor32(sf); sgs += tr_xor32(sgs);         // rows 4hh + ... of the two half-waves: both halves hold the tile's sum
+            if (hh == 0) { ts[ch] = sf; ts[W + ch] = sgs; }
+        }
+    }
+}
+
+// dX = dXn + dPRE[t] W1^T + dPRE[t+d] W0^T (rows t + d past the entry's end: no second term), and the tile's column sums of dX.
+// Per output block of 32 channels the B operands are 4W k-values x 32 = 2W steps x 64 lanes (32 / 64 KiB): at 64 both blocks stay in
+// LDS, at 128 one at a time and the workgroup's eight waves take eight tiles in step.  The rows of dPRE are read again per block.
+template <int W>
+__global__ void __launch_bounds__(512) tr_layer_wide_bwd2_kernel(WideBwdArgs a)
+{
+    constexpr int NB = W / 32, W2 = 2 * W;
+    constexpr bool RES = W == 64;
+    constexpr int NSL = RES ? NB : 1;
+    __shared__ float bt[NSL * W2 * 64];                      // [slice][step][lane]: steps 0 .. W-1 from W1^T, W .. 2W-1 from W0^T
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int n = lane & 31, hh = lane >> 5;
+    auto load_slice = [&](int ob, int slot) {
+        float* bs = bt + slot * W2 * 64;
+        for (int e = threadIdx.x; e < W2 * 64; e += 512) {
+            const int l = e & 63, s = e >> 6, ss = s < W ? s : s - W;
+            const int k = 8 * (ss >> 2) + 4 * (l >> 5) + (ss & 3);
+            bs[e] = (s < W ? a.W1T : a.W0T)[k * W + ob * 32 + (l & 31)];
+        }
+    };
+    if (RES) {
+        for (int ob = 0; ob < NB; ++ob) load_slice(ob, ob);
+        __syncthreads();
+    }
+    const int ntiles = a.B * a.tpb, ngroups = (ntiles + 7) / 8;
+    for (int grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {                // block-uniform: every wave meets every barrier
+        const int tile = grp * 8 + wave;
+        const bool active = tile < ntiles;
+        const int b = active ? tile / a.tpb : 0, t0 = active ? (tile - b * a.tpb) * 32 : 0;
+        const int t = t0 + n;
+        const bool ok1 = active && t < a.Tn, ok2 = active && t + a.d < a.Tn;
+        const float* pr = a.dPRE + ((long long)b * a.Tn + t) * W2 + 4 * hh;
+        for (int ob = 0; ob < NB; ++ob) {
+            if (!RES) {
+                __syncthreads();
+                load_slice(ob, 0);
+                __syncthreads();
+            }
+            if (!active) continue;
+            const float* bs = bt + (RES ? ob : 0) * W2 * 64 + lane;
+            f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll 4
+            for (int i = 0; i < W2 / 8; ++i) {
+                const f32x4t p = tr_ld4(pr + 8 * i, ok1);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(p[j], bs[(4 * i + j) * 64], acc, 0, 0, 0);
+            }
+#pragma unroll 4
+            for (int i = 0; i < W2 / 8; ++i) {
+                const f32x4t p = tr_ld4(pr + (long long)a.d * W2 + 8 * i, ok2);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(p[j], bs[(W + 4 * i + j) * 64], acc, 0, 0, 0);
+            }
+            const int ch = ob * 32 + n;
+            float sx = 0.0f;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int tr = t0 + (r & 3) + 8 * (r >> 2) + 4 * hh;
+                if (tr < a.Tn) {
+                    const long long at = ((long long)b * a.Tn + tr) * W + ch;
+                    const float v = a.dXn[at] + acc[r];
+                    a.dX[at] = v;
+                    sx += v;
+                }
+            }
+            sx += tr_xor32(sx);
+            if (hh == 0 && a.tsum_below) a.tsum_below[(long long)tile * (3 * W) + W2 + ch] = sx;
+        }
+    }
+}
+
+// fused lc route, per layer: R[((b*F + f)*4 + j)*2W + c] = sum over the frame's rows (phase ascending) of ctab[phase][j] * dPRE[row][c]
+// (row t = f*hop + phase + o): the operand of the strided-batched dW_lc product.  One thread per (b, f, c).
+__global__ __launch_bounds__(256) void tr_wide_frame_sum_kernel(const float* dPRE, const float* ctab, float* R, int B, int F, int hop, int Tn, int o, int W2)
+{
+    GRID_STRIDE(i, (long long)B * F * W2) {
+        const int c = (int)(i % W2);
+        const long long bf = i / W2;
+        const int b = (int)(bf / F), f = (int)(bf - (long long)b * F);
+        float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
+        for (int ph = 0; ph < hop; ++ph) {
+            const int t = f * hop + ph + o;
+            if (t >= Tn) break;
+            const float v = dPRE[((long long)b * Tn + t) * W2 + c];
+            const float4 ct = *reinterpret_cast<const float4*>(ctab + ph * 4);
+            s0 += ct.x * v; s1 += ct.y * v; s2 += ct.z * v; s3 += ct.w * v;
+        }
+        float* r = R + (bf * 4) * W2 + c;
+        r[0] = s0; r[W2] = s1; r[2 * W2] = s2; r[3 * W2] = s3;
+    }
+}
+// fused lc route, per layer: D[(b*T + u)*4 + j] += sum_c dPRE[(b, u + o)][c] * Q_j[b, frame(u)][c] (the gradient of the hop's tap table,
+// summed over the layers in launch order).  One wave per row: lane l carries columns l, l + 64, ..., then a butterfly (fixed order).
+__global__ __launch_bounds__(256) void tr_wide_dq_kernel(const float* dPRE, const float* Q, float* D, int B, int T, int Tn, int F, int hop, int o, int W2)
+{
+    const int lane = threadIdx.x & 63;
+    const int per = Tn - o;                                  // rows of an entry that exist in this layer
+    const long long rows = (long long)B * per;
+    for (long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); r < rows; r += (long long)gridDim.x * 4) {
+        const int b = (int)(r / per), u = (int)(r - (long long)b * per);
+        const float* p = dPRE + ((long long)b * Tn + u + o) * W2;
+        const float* q = Q + (((long long)b * F + u / hop) * 4) * W2;
+        float s[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        for (int c = lane; c < W2; c += 64) {
+            const float v = p[c];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) s[j] += v * q[j * W2 + c];
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int m = 32; m >= 1; m >>= 1) s[j] += __shfl_xor(s[j], m, 64);
+        if (lane == 0) {
+            float4* d = reinterpret_cast<float4*>(D + ((long long)b * T + u) * 4);
+            float4 v = *d;
+            v.x += s[0]; v.y += s[1]; v.z += s[2]; v.w += s[3];
+            *d = v;
+        }
+    }
+}
+// conv biases of every layer from its 2W summed pre-activation gradients: bf[l] = s[l][0:W], bg[l] = s[l][W:2W]
+__global__ void tr_split_bias_wide_kernel(const float* s2w, float* base, long long lstride, long long o_bf, long long o_bg, int NL, int W)
+{
+    GRID_STRIDE(i, (long long)NL * 2 * W) {
+        const int l = (int)(i / (2 * W)), c = (int)(i % (2 * W));
+        base[(long long)l * lstride + (c < W ? o_bf + c : o_bg + c - W)] = s2w[i];
+    }
+}
+// tr_demb_kernel at 2W columns: demb[b][g] += sum over layers (ascending) and columns of dGCP[l][b][c] * Wgc_l[g][c]; lane l carries
+// columns l, l + 64, ... through the layers, then a butterfly over the lanes (fixed order)
+__global__ __launch_bounds__(256) void tr_demb_wide_kernel(const float* dgcp, const float* wgc0, long long vstride, float* demb, int NL, int B, int G, int W2)
+{
+    const int lane = threadIdx.x & 63;
+    const long long i = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= (long long)B * G) return;
+    const int b = (int)(i / G), g = (int)(i % G);
+    float s = 0.0f;
+    for (int l = 0; l < NL; ++l)
+        for (int c = lane; c < W2; c += 64) s += dgcp[((long long)l * B + b) * W2 + c] * wgc0[(long long)l * vstride + (long long)g * W2 + c];
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
+    if (lane == 0) demb[i] += s;
+}
+// one-hot causal layer's gradient at width W, one 32-column block per launch (2 Q x 32 floats of LDS: 128 KiB at Q = 512, where 2 Q W
+// does not fit).  Block = a slab of rows x the column block; thread = (class group g of 8, column).  Group g owns the table rows of the
+// classes k % 8 == g and walks ALL rows of the slab in order, adding the rows whose class is its own: no two threads touch one entry,
+// so there is no atomic and the order is the row order.  part[(tap*Q + k)][slab][32] -> tr_colsum_final_kernel (segments = table rows).
+__global__ __launch_bounds__(256) void tr_onehot_causal_wide_bwd_kernel(const float* dx0, const int32_t* q, float* part, int B, int T, int Tn, int Q, int W, int cb,
+                                                                         long long rows_per_block)
+{
+    extern __shared__ float tab[];
+    const int nt = 2 * Q * 32;
+    for (int i = threadIdx.x; i < nt; i += 256) tab[i] = 0.0f;
+    __syncthreads();
+    const long long R = (long long)B * Tn;
+    const long long r0 = (long long)blockIdx.x * rows_per_block, r1 = r0 + rows_per_block < R ? r0 + rows_per_block : R;
+    const int c = threadIdx.x & 31, grp = threadIdx.x >> 5;
+    for (long long r = r0; r < r1; ++r) {
+        const int t = (int)(r % Tn), b = (int)(r / Tn);
+        if (t < 1) continue;
+        const int qa = q[(long long)b * T + t - 1], qb = q[(long long)b * T + t];
+        if ((qa & 7) != grp && (qb & 7) != grp) continue;
+        const float gv = dx0[r * W + cb * 32 + c];
+        if ((qa & 7) == grp) tab[qa * 32 + c] += gv;
+        if ((qb & 7) == grp) tab[(Q + qb) * 32 + c] += gv;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < nt; i += 256) part[((long long)(i >> 5) * gridDim.x + blockIdx.x) * 32 + (i & 31)] = tab[i];
+}
+
 // model.py:300-312 optional L2 on every non-bias variable: loss += strength * sum(w^2)/2, grad += strength * w
 struct L2Layout { long long c_layer0, lstride, nl, bf, bg, bd, bs, D, R, S, c_b1, c_b2, O, ub; };
 __device__ __forceinline__ bool tr_is_bias(long long i, const L2Layout& L)
@@ -1826,6 +2298,7 @@ struct TrainCarve {
     float *X[TWV_MAX_LAYERS + 1], *TH[TWV_MAX_LAYERS], *SG[TWV_MAX_LAYERS];
     float *ZC, *dZC, *PRE, *dXa, *dXb, *SK, *C1, *dS, *Y, *dY, *emb, *demb, *GCP, *dGCP, *WV, *WS, *GV, *GS, *part, *slabs, *zpage, *kpart, *wpart;
     float *ctab, *melsh, *Qall, *Dbuf, *dctab, *PTall, *Rall, *tsum, *dGCPall, *bsum64;
+    float *Zb, *WT;                                          // the wide step's (tr_carve_wide): z rows, transposed weights
     long long vstride, slab_ls, q_ls, pt_ls, tsum_ls;
 };
 static long long tr_carve(const WavenetGraph* h, float* base, TrainCarve& c)
@@ -1879,17 +2352,79 @@ static long long tr_carve(const WavenetGraph* h, float* base, TrainCarve& c)
     return used;
 }
 
-extern "C" int twv_wavenet_train_create(const twv_wavenet_dims* dims, int batch, int n_samples, twv_wavenet_trainer** out)
+// The wide step's carve (width W = g.R = g.D of 64 or 128), in TrainCarve's fields: what twv_wavenet_train_loss_grad takes at those widths.
+// Per layer it keeps X, TH and SG (3 W floats per row); dPRE carries max(dilation) rows of zeros behind its last row, so that the
+// row-shifted operand of the tap-0 weight gradient never reads past the buffer.  Buffers of the other lc route are not carved.
+static long long tr_carve_wide(const WavenetGraph* h, float* base, TrainCarve& c)
+{
+    const twv_wavenet_dims& d = h->d;
+    const int B = h->rows, T = h->T, Tn = h->Tn, NL = h->NL, S = h->S, O = h->O, L = h->L, G = h->G, ow = h->ow, W = h->R, W2 = 2 * W;
+    const long long Rr = (long long)B * Tn, RT = (long long)B * T, RO = (long long)B * ow;
+    const bool fused = wavenet_route(*h).fused_lc;
+    long long used = 0;
+    auto take = [&](long long n) { float* p = base ? base + used : nullptr; used += (n + 63) / 64 * 64; return p; };
+    c.upT[0] = h->F;
+    for (int i = 0; i < d.n_upsample; ++i) c.upT[i + 1] = c.upT[i] * d.upsample_factor[i];
+    c.ups[0] = nullptr;                                      // (the caller's mel frames)
+    for (int i = 1; i <= d.n_upsample; ++i) c.ups[i] = take(fused ? 0 : (long long)B * c.upT[i] * L);
+    c.dUa = take(fused ? 0 : RT * L); c.dUb = take(fused ? 0 : RT * L);
+    c.xunf = take(d.scalar_input ? Rr * h->ifw : 0);
+    c.qin = reinterpret_cast<int32_t*>(take(d.scalar_input ? 0 : RT));
+    c.ohpart = take(d.scalar_input ? 0 : 256LL * 2 * d.quantization_channels * 32);
+    for (int l = 0; l <= NL; ++l) c.X[l] = take(Rr * W);
+    for (int l = 0; l < NL; ++l) { c.TH[l] = take(Rr * W); c.SG[l] = take(Rr * W); }
+    const int ZW = NL * W;
+    c.ZC = take(RO * ZW); c.dZC = take(RO * ZW);
+    int dmax = 1;
+    for (int l = 0; l < NL; ++l) dmax = d.dilations[l] > dmax ? d.dilations[l] : dmax;
+    c.PRE = take((Rr + dmax) * W2);
+    c.Zb = take(Rr * W);
+    c.dXa = take(Rr * W); c.dXb = take(Rr * W);
+    c.SK = take(RO * S); c.C1 = take(RO * S); c.dS = take(RO * S);
+    c.Y = take(RO * O); c.dY = take(RO * O);
+    c.emb = take((long long)B * G); c.demb = take((long long)B * G);
+    c.GCP = take((long long)B * W2 * NL);
+    c.vstride = (long long)W2 * (W2 + L + G);
+    c.WV = take(c.vstride * NL); c.WS = take((long long)ZW * S);       // weight views
+    c.GV = take(c.vstride * NL); c.GS = take((long long)ZW * S);       // gradient views
+    c.WT = take(5LL * W * W * NL);                           // transposed tap and dense kernels (tr_views_wide_t_kernel)
+    const int tpb = (Tn + 31) / 32;
+    const long long seg = (long long)NL * B * (tpb / 256 < 1 ? 1 : (tpb / 256 > 32 ? 32 : tpb / 256)) * W2;   // TrRed::colsum over (layer, entry) segments
+    const long long part0 = 512LL * 96 * 64 + 1024LL * 512;  // what TrRed::wgrad divides up
+    c.part = take(seg > part0 ? seg : part0);
+    long long kp = 16LL * (ZW > S ? ZW : S) * S;             // split-K partials: dW1, stacked dWs, the layers' tap and dense gradients,
+    if (kp < 16LL * W * W2) kp = 16LL * W * W2;              // and on the staged route dW_lc as one slab per batch entry
+    if (!fused && kp < (long long)B * L * W2) kp = (long long)B * L * W2;
+    c.kpart = take(kp);
+    c.wpart = take(2048LL * 64 * 32);                        // tr_conv2_bwd_kernel
+    c.ctab = take(fused ? 4LL * 512 : 0);
+    c.melsh = take(fused ? (long long)B * h->F * 4 * L : 0);
+    c.q_ls = (long long)B * h->F * 4 * W2;
+    c.Qall = take(fused ? (c.q_ls + 64) * NL : 0);
+    c.Dbuf = take(fused ? RT * 4 : 0);
+    c.dctab = take(fused ? 4LL * 512 : 0);
+    c.Rall = take(fused ? (c.q_ls + 64) * NL : 0);
+    c.tsum_ls = (long long)B * tpb * 3 * W;                  // layers back to back: the column sums treat (layer, batch entry) as segments
+    c.tsum = take(c.tsum_ls * NL);
+    c.dGCPall = take((long long)B * W2 * NL);
+    c.bsum64 = take((long long)W2 * NL);
+    c.slabs = c.zpage = c.PTall = c.dGCP = nullptr; c.slab_ls = c.pt_ls = 0;      // the width-32 kernels' own
+    return used;
+}
+static long long tr_carve_any(const WavenetGraph* h, float* base, TrainCarve& c) { return h->R == 32 ? tr_carve(h, base, c) : tr_carve_wide(h, base, c); }
+
+extern "C" int twv_wavenet_train_create_w(const twv_wavenet_dims* dims, int batch, int n_samples, int max_width, twv_wavenet_trainer** out)
 {
     if (!out) return twv_fail(TWV_E_INVALID, "bad argument");
+    if (max_width != 32 && max_width != 64 && max_width != 128) return twv_fail(TWV_E_INVALID, "max_width must be 32, 64 or 128 (got " + std::to_string(max_width) + ")");
     twv_wavenet_trainer* h = new twv_wavenet_trainer();
-    const int rc = wavenet_graph_init(h->g, dims, batch, n_samples, "training", 32);
+    const int rc = wavenet_graph_init(h->g, dims, batch, n_samples, "training", max_width);
     if (rc) { delete h; return rc; }
     h->blas = nullptr;
     h->ws_clean = nullptr;
-    // workspace: exactly what loss_grad carves (tr_carve on a null base), then twv_wavenet_train_l2's scratch
+    // workspace: exactly what loss_grad carves (tr_carve / tr_carve_wide on a null base), then twv_wavenet_train_l2's scratch
     TrainCarve sizes;
-    long long f = h->carve_floats = tr_carve(&h->g, nullptr, sizes);
+    long long f = h->carve_floats = tr_carve_any(&h->g, nullptr, sizes);
     // twv_wavenet_train_l2's scratch (nparams squares + the partial sums) has a region of its OWN behind everything loss_grad carves: at
     // the start of the workspace it overwrote rows that the fused layer kernels rely on staying zero (the rows in front of a layer's
     // receptive offset are cleared once and never written again) -- harmless only while every gradient is finite
@@ -1898,9 +2433,13 @@ extern "C" int twv_wavenet_train_create(const twv_wavenet_dims* dims, int batch,
     h->ws_floats = f;
     const TrainRoute r = tr_route(h->g);
     h->route = wavenet_route_label(r, r.fuse_c2 ? "skinny+c2bwd" : r.skinny ? "skinny" : "gemm") + " nsplit=" + std::to_string(r.nsplit) +
-               " carve_floats=" + std::to_string(h->carve_floats);
+               " width=" + std::to_string(h->g.R) + " carve_floats=" + std::to_string(h->carve_floats);
     *out = h;
     return TWV_OK;
+}
+extern "C" int twv_wavenet_train_create(const twv_wavenet_dims* dims, int batch, int n_samples, twv_wavenet_trainer** out)
+{
+    return twv_wavenet_train_create_w(dims, batch, n_samples, 32, out);
 }
 extern "C" void twv_wavenet_train_destroy(twv_wavenet_trainer* h)
 {
@@ -1992,6 +2531,227 @@ int wavenet_forward_head(const WavenetGraph& g, const float* P, const WavenetFwd
     return TWV_OK;
 }
 
+// The step's deterministic reductions over `part` (the carve's scratch for partial sums), shared by the width-32 step and the wide one
+struct TrRed {
+    hipStream_t st; float* part;
+    // out[seg][c] = column sums of x (nseg slabs of `rows` rows); deterministic two-stage reduction
+    void colsum(const float* x, long long rows, int C, int ldx, int nseg, float* out, int ldo) const {
+        int nchunk = (int)(rows / 256); const int cap = nseg > 8 ? 32 : 256; nchunk = nchunk < 1 ? 1 : (nchunk > cap ? cap : nchunk);
+        hipLaunchKernelGGL(tr_colsum_partial_kernel, dim3(nchunk, (C + 63) / 64, nseg), dim3(256), 0, st, x, rows, C, ldx, nchunk, part);
+        hipLaunchKernelGGL(tr_colsum_final_kernel, dim3((nseg * C + 63) / 64), dim3(256), 0, st, part, nchunk, C, nseg, out, ldo);
+    }
+    // dx <- relu'(y) * dx over (rows, C) and, with biases, out[c] = column sums of the result
+    void relu_bwd_colsum(float* dx, const float* y, long long rows, int C, float* out) const {
+        int nchunk = (int)(rows / 256); nchunk = nchunk < 1 ? 1 : (nchunk > 256 ? 256 : nchunk);
+        hipLaunchKernelGGL(tr_relu_bwd_colsum_kernel, dim3(nchunk, (C + 63) / 64, 1), dim3(256), 0, st, dx, y, rows, C, nchunk, part);
+        hipLaunchKernelGGL(tr_colsum_final_kernel, dim3((C + 63) / 64), dim3(256), 0, st, part, nchunk, C, 1, out, C);
+    }
+    // C[M x N](ldc) = A^T B over K rows (tall-skinny weight gradient)
+    void wgrad(const float* A, int lda, const float* Bm, int ldb, long long K, int M, int N, float* C, int ldc) const {
+        const int mb = (M + 31) / 32, nb = (N + 31) / 32;
+        const long long cap = (512LL * 96 * 64 + 1024LL * 512) / ((long long)mb * nb * 1024);     // `part` holds chunks x (mb*32) x (nb*32)
+        // enough workgroups to fill the chip whatever the tile count: a single-tile product (the causal kernel's gradient: M = N = 32) ran on
+        // 256 workgroups of dependent two-row steps: 124 us for 128 MB
+        int chunks = (int)(K / 512); chunks = chunks < 1 ? 1 : (chunks > 1024 ? 1024 : chunks);
+        if (chunks * mb * nb > 4096) chunks = 4096 / (mb * nb) > 0 ? 4096 / (mb * nb) : 1;
+        if (chunks > cap) chunks = (int)cap;
+        long long rpc = (K + chunks - 1) / chunks; rpc = (rpc + 7) / 8 * 8;
+        chunks = (int)((K + rpc - 1) / rpc);
+        hipLaunchKernelGGL(tr_tn_partial_kernel, dim3(chunks, mb, nb), dim3(256), 0, st, A, lda, Bm, ldb, K, M, N, rpc, part);
+        hipLaunchKernelGGL(tr_tn_reduce_kernel, dim3((M * N + 63) / 64), dim3(chunks > 64 ? 1024 : 256), 0, st, part, chunks, mb * 32, nb * 32, M, N, C, ldc);
+    }
+};
+
+// The head's backward pass (model.py:150-165 backward), the same at every width (ZW = NL * width columns of stacked skip input):
+// dW2, db2, dC1, db1, dW1, dSK, the skip biases, the stacked skip kernels' gradient (-> cv.GS) and dZC.  Returns the rocBLAS statuses or-ed.
+static int tr_head_backward(const WavenetGraph& g, const TrainRoute& route, const float* P, float* Gd, const TrainCarve& cv, int ZW,
+                            rocblas_handle bl, hipStream_t st)
+{
+    const int NL = g.NL, S = g.S, O = g.O, nsplit = route.nsplit;
+    const long long RO = (long long)g.rows * g.ow;
+    const bool ub = g.d.use_biases != 0, fuse_c2 = route.fuse_c2;
+    float *ZC = cv.ZC, *dZC = cv.dZC, *SK = cv.SK, *C1 = cv.C1, *dS = cv.dS, *dY = cv.dY, *WS = cv.WS, *GS = cv.GS, *part = cv.part, *kpart = cv.kpart, *wpart = cv.wpart;
+    const float* b1p = ub ? P + g.c_b1 : nullptr;
+    float* bs0 = Gd + g.c_layer0 + g.lo.bs;                 // layer 0's skip-bias gradient
+    const TrRed red{st, part};
+    int rc = 0;
+    if (!fuse_c2) red.wgrad(C1, S, dY, O, RO, S, O, Gd + g.c_w2, O);                                              // dW2 = H2^T dY (the tall-skinny MFMA kernel)
+    if (ub) red.colsum(dY, RO, O, O, 1, Gd + g.c_b2, O);
+    if (fuse_c2) {                                                                                           // dC1, db1 and dW2: one pass
+        const int nwg = 512, nchunk = nwg * 4 / (S >> 6);             // two workgroups per CU (171 registers; at three, 168 + spills: 276 vs 263 us)
+        hipLaunchKernelGGL(tr_conv2_bwd_kernel, dim3(nwg), dim3(256), 0, st, dY, O, P + g.c_w2, C1, b1p, RO, S, dS, part, wpart);
+        if (ub) hipLaunchKernelGGL(tr_colsum_final_kernel, dim3((S + 63) / 64), dim3(256), 0, st, part, nchunk, S, 1, Gd + g.c_b1, S);
+        hipLaunchKernelGGL(tr_tn_reduce_kernel, dim3((S * O + 63) / 64), dim3(1024), 0, st, wpart, nchunk, S, 32, S, O, Gd + g.c_w2, O);
+    } else {
+        rc |= gemm_rm(bl, false, true, (int)RO, S, O, 1.f, dY, O, P + g.c_w2, O, 0.f, dS, S);               // dH2
+        if (ub) red.relu_bwd_colsum(dS, C1, RO, S, Gd + g.c_b1);                                                // dC1, db1
+        else if ((S & 3) == 0) K1(tr_relu_bwd4_kernel, RO * S / 4, (float4*)dS, (const float4*)C1, RO * S / 4);
+        else K1(tr_relu_bwd_kernel, RO * S, dS, C1, RO * S);
+    }
+    rc |= gemm_tn_splitk(bl, st, S, S, RO, SK, S, dS, S, Gd + g.c_w1, S, nsplit, kpart);                     // dW1 = H1^T dC1
+    rc |= gemm_rm(bl, false, true, (int)RO, S, S, 1.f, dS, S, P + g.c_w1, S, 0.f, C1, S);                   // dH1 -> C1 buffer
+    if (ub) red.relu_bwd_colsum(C1, SK, RO, S, bs0);                                                 // dSK, dbs (layer 0's slot)
+    else if ((S & 3) == 0) K1(tr_relu_bwd4_kernel, RO * S / 4, (float4*)C1, (const float4*)SK, RO * S / 4);
+    else K1(tr_relu_bwd_kernel, RO * S, C1, SK, RO * S);
+    float* dSK = C1;
+    // all skip convs at once: dWs (stacked) = ZC^T dSK ; dZC = dSK WS^T ; dbs (identical for every layer) = colsum(dSK)
+    rc |= gemm_tn_splitk(bl, st, ZW, S, RO, ZC, ZW, dSK, S, GS, S, nsplit, kpart);
+    if (ub) {
+        if (NL > 1) K1(tr_bcast_rows_kernel, (long long)(NL - 1) * S, bs0, g.c_lstride, NL, S);
+    }
+    rc |= gemm_rm(bl, false, true, (int)RO, ZW, S, 1.f, dSK, S, WS, S, 0.f, dZC, ZW);
+    return rc;
+}
+
+// twv_wavenet_train_loss_grad at width 64 and 128 (grads, loss and the workspace are cleared by the caller).  Front, head, loss and the
+// head's backward are the width-32 step's own calls; the residual stack runs the tr_layer_wide_* kernels.
+template <int W>
+static int tr_loss_grad_wide(twv_wavenet_trainer* h, const TrainCarve& cv, const float* P, const float* audio, const float* lc, const int32_t* gc_ids,
+                             float* loss, float* Gd, hipStream_t st)
+{
+    rocblas_handle bl = h->blas;
+    const WavenetGraph& g = h->g;
+    const twv_wavenet_dims& d = g.d;
+    constexpr int W2 = 2 * W;
+    const int B = g.rows, T = g.T, Tn = g.Tn, NL = g.NL, S = g.S, O = g.O, L = g.L, G = g.G, ow = g.ow, rf = g.rf, nr = O / 3, F = g.F;
+    const long long Rr = (long long)B * Tn, RT = (long long)B * T, RO = (long long)B * ow;
+    const bool ub = d.use_biases != 0;
+    const TrainRoute route = tr_route(g);
+    const bool fused_lc = route.fused_lc;
+    const int nsplit = route.nsplit, ZW = NL * W, tpb = (Tn + 31) / 32, ntiles = B * tpb;
+    const long long vstride = cv.vstride, q_ls = cv.q_ls;
+    float* ups[5] = {const_cast<float*>(lc), cv.ups[1], cv.ups[2], cv.ups[3], cv.ups[4]};
+    const float* U = ups[d.n_upsample];
+    const TrRed red{st, cv.part};
+    const float one = 1.0f, zero = 0.0f;
+    int rc = 0;
+    // ================= forward =================
+    WavenetFwdBufs fb;
+    for (int i = 0; i < 5; ++i) fb.ups[i] = ups[i];
+    fb.upT = cv.upT; fb.xunf = cv.xunf; fb.qin = cv.qin;
+    fb.X0 = cv.X[0]; fb.emb = cv.emb; fb.GCP = cv.GCP; fb.WV = cv.WV; fb.WS = cv.WS; fb.ctab = cv.ctab; fb.melsh = cv.melsh; fb.Qall = cv.Qall;
+    fb.vstride = vstride; fb.q_ls = q_ls;
+    fb.ZC = cv.ZC; fb.SK = cv.SK; fb.C1 = cv.C1; fb.Y = cv.Y;
+    fb.bsum = cv.part;                                       // S floats; `part` is free between the column sums
+    if (int frc = wavenet_forward_front(g, P, audio, gc_ids, fb, bl, st)) return frc;
+    K1(tr_views_wide_t_kernel, 5LL * W * W * NL, cv.WV, vstride, P, g.c_layer0, g.c_lstride, g.lo.wd, cv.WT, NL, W);
+    for (int l = 0; l < NL; ++l) {
+        const float* Lp = P + g.c_layer0 + (long long)l * g.c_lstride;
+        const float* Wv = cv.WV + l * vstride;               // tap0 | tap1 | lc | gc views, 2W columns = filter | gate
+        LayerFwdArgs fa;
+        fa.X = cv.X[l]; fa.U = U; fa.gcp = cv.GCP + (long long)l * B * W2; fa.W0 = Wv; fa.W1 = Wv + W * W2; fa.Wlc = Wv + W2 * W2; fa.Wd = Lp + g.lo.wd;
+        fa.bf = ub ? Lp + g.lo.bf : nullptr; fa.bg = ub ? Lp + g.lo.bg : nullptr; fa.bd = ub ? Lp + g.lo.bd : nullptr;
+        fa.TH = cv.TH[l]; fa.SG = cv.SG[l]; fa.XN = cv.X[l + 1]; fa.ZC = cv.ZC + l * W;
+        fa.B = B; fa.T = T; fa.Tn = Tn; fa.d = d.dilations[l]; fa.o = g.off[l + 1]; fa.ow = ow; fa.ldz = ZW;
+        fa.t_lo = (fa.o / 32) * 32;                          // whole tiles in front of the layer's offset hold no row: not walked
+        fa.tpb = tpb - fa.t_lo / 32;
+        fa.Q = cv.Qall + l * (q_ls + 64); fa.ctab = cv.ctab; fa.hop = g.hop; fa.F = F;
+        int nwg = (B * fa.tpb + 7) / 8; nwg = nwg > 256 ? 256 : nwg;            // one workgroup of eight waves per group of eight tiles
+        if (fused_lc) hipLaunchKernelGGL((tr_layer_wide_fwd_kernel<W, true>), dim3(nwg), dim3(512), 0, st, fa);
+        else hipLaunchKernelGGL((tr_layer_wide_fwd_kernel<W, false>), dim3(nwg), dim3(512), 0, st, fa);
+    }
+    if (int hrc = wavenet_forward_head(g, P, fb, route.skinny, route.fuse_c2, bl, st)) return hrc;
+    float* row_loss = cv.dS;                                 // (RO) scratch: dS is not written before the backward pass
+    if (route.loss == WG_LOSS_MOL10) K1(tr_mol_loss_kernel<10>, RO, cv.Y, audio, B, T, ow, rf, nr, 1.0f / (float)RO, row_loss, cv.dY);
+    else if (route.loss == WG_LOSS_MOLN) K1(tr_mol_loss_kernel<0>, RO, cv.Y, audio, B, T, ow, rf, nr, 1.0f / (float)RO, row_loss, cv.dY);
+    else hipLaunchKernelGGL(tr_softmax_ce_kernel, dim3(tg(RO * 64)), dim3(256), 0, st, cv.Y, cv.qin, B, T, ow, rf, O, 1.0f / (float)RO, row_loss, cv.dY);
+    red.colsum(row_loss, RO, 1, 1, 1, loss, 1);
+    // ================= backward =================
+    rc |= tr_head_backward(g, route, P, Gd, cv, ZW, bl, st);
+    if (rc) return twv_fail(TWV_E_HIP, "rocBLAS call failed with status " + std::to_string(rc));
+    float* dXn = cv.dXa; float* dXc = cv.dXb;
+    int dmax = 1;
+    for (int l = 0; l < NL; ++l) dmax = d.dilations[l] > dmax ? d.dilations[l] : dmax;
+    K1(tr_fill_kernel, Rr * W, dXn, 0.0f, Rr * W);
+    K1(tr_fill_kernel, (long long)dmax * W2, cv.PRE + Rr * W2, 0.0f, (long long)dmax * W2);      // the rows behind dPRE's last
+    if (fused_lc) K1(tr_fill_kernel, RT * 4, cv.Dbuf, 0.0f, RT * 4);
+    else K1(tr_fill_kernel, RT * L, cv.dUa, 0.0f, RT * L);
+    K1(tr_fill_kernel, (long long)B * G, cv.demb, 0.0f, (long long)B * G);
+    int nwg = (ntiles + 7) / 8; nwg = nwg > 256 ? 256 : nwg;
+    for (int l = NL - 1; l >= 0 && !rc; --l) {
+        const int dl = d.dilations[l], o = g.off[l + 1];
+        const float* Wv = cv.WV + l * vstride;
+        float* Gv = cv.GV + l * vstride;
+        const float* Wt = cv.WT + (long long)l * 5 * W * W;
+        WideBwdArgs ba;
+        ba.dXn = dXn; ba.dZC = cv.dZC + l * W; ba.TH = cv.TH[l]; ba.SG = cv.SG[l];
+        ba.W1T = Wt; ba.W0T = Wt + W2 * W; ba.WdT = Wt + 2 * W2 * W;
+        ba.dPRE = cv.PRE; ba.Zb = cv.Zb; ba.tsum = cv.tsum + l * cv.tsum_ls; ba.tsum_below = l > 0 ? cv.tsum + (l - 1) * cv.tsum_ls : nullptr; ba.dX = dXc;
+        ba.B = B; ba.Tn = Tn; ba.d = dl; ba.o = o; ba.ow = ow; ba.ldz = ZW; ba.tpb = tpb;
+        hipLaunchKernelGGL(tr_layer_wide_bwd1_kernel<W>, dim3(nwg), dim3(512), 0, st, ba);
+        hipLaunchKernelGGL(tr_layer_wide_bwd2_kernel<W>, dim3(nwg), dim3(512), 0, st, ba);
+        // weight gradients, K = all rows: tap 1 = X[t]^T dPRE[t]; tap 0 = X[s]^T dPRE[s + d] (a row s + d of the next entry lies in front
+        // of its offset: dPRE = 0; behind the last entry: the zero rows); dense = z^T dXn
+        rc |= gemm_tn_splitk(bl, st, W, W2, Rr, cv.X[l], W, cv.PRE, W2, Gv + W * W2, W2, nsplit, cv.kpart);
+        rc |= gemm_tn_splitk(bl, st, W, W2, Rr, cv.X[l], W, cv.PRE + (long long)dl * W2, W2, Gv, W2, nsplit, cv.kpart);
+        rc |= gemm_tn_splitk(bl, st, W, W, Rr, cv.Zb, W, dXn, W, Gd + g.c_layer0 + (long long)l * g.c_lstride + g.lo.wd, W, nsplit, cv.kpart);
+        if (fused_lc) {
+            K1(tr_wide_frame_sum_kernel, (long long)B * F * W2, cv.PRE, cv.ctab, cv.Rall + l * (q_ls + 64), B, F, g.hop, Tn, o, W2);
+            hipLaunchKernelGGL(tr_wide_dq_kernel, dim3(tg((long long)B * (Tn - o) * 64)), dim3(256), 0, st, cv.PRE, cv.Qall + l * (q_ls + 64), cv.Dbuf, B, T, Tn, F,
+                               g.hop, o, W2);
+        } else {
+            // dU[b][t - o] += dPRE[b][t] Wlc^T, and dW_lc = sum over entries (in order) of U_b^T dPRE_b: one slab per batch entry
+            rc |= rocblas_sgemm_strided_batched(bl, rocblas_operation_transpose, rocblas_operation_none, L, Tn - o, W2, &one, Wv + W2 * W2, W2, 0,
+                                                cv.PRE + (long long)o * W2, W2, (long long)Tn * W2, &one, cv.dUa, L, (long long)T * L, B);
+            rc |= rocblas_sgemm_strided_batched(bl, rocblas_operation_none, rocblas_operation_transpose, W2, L, Tn - o, &one, cv.PRE + (long long)o * W2, W2,
+                                                (long long)Tn * W2, U, L, (long long)T * L, &zero, cv.kpart, W2, (long long)L * W2, B);
+            K1(tr_splitk_reduce_kernel, (long long)L * W2, cv.kpart, B, (long long)L * W2, W2, Gv + W2 * W2, W2);
+        }
+        float* tsw = dXn; dXn = dXc; dXc = tsw;
+    }
+    if (rc) return twv_fail(TWV_E_HIP, "rocBLAS call failed with status " + std::to_string(rc));
+    // ---- all layers at once: gc and bias column sums from the per-tile sums, dW_lc (fused route), dW_gc, demb
+    if (fused_lc)
+        rc |= rocblas_sgemm_strided_batched(bl, rocblas_operation_none, rocblas_operation_transpose, W2, L, B * F * 4, &one, cv.Rall, W2, q_ls + 64,
+                                            cv.melsh, L, 0, &zero, cv.GV + W2 * W2, W2, vstride, NL);
+    red.colsum(cv.tsum, tpb, W2, 3 * W, NL * B, cv.dGCPall, W2);                                 // segment = (layer, batch entry)
+    if (ub) {
+        // dense bias of layer l = column sums of the dX tiles the layer above left in l's slot (the last layer's: never written, zero)
+        red.colsum(cv.tsum + W2, ntiles, W, 3 * W, NL, Gd + g.c_layer0 + g.lo.bd, (int)g.c_lstride);
+        red.colsum(cv.dGCPall, B, W2, W2, NL, cv.bsum64, W2);
+        K1(tr_split_bias_wide_kernel, (long long)W2 * NL, cv.bsum64, Gd + g.c_layer0, g.c_lstride, g.lo.bf, g.lo.bg, NL, W);
+    }
+    rc |= rocblas_sgemm_strided_batched(bl, rocblas_operation_none, rocblas_operation_transpose, W2, G, B, &one, cv.dGCPall, W2, (long long)B * W2,
+                                        cv.emb, G, 0, &zero, cv.GV + (long long)(W2 + L) * W2, W2, vstride, NL);
+    hipLaunchKernelGGL(tr_demb_wide_kernel, dim3((unsigned)(((long long)B * G + 3) / 4)), dim3(256), 0, st, cv.dGCPall, cv.WV + (long long)(W2 + L) * W2, vstride,
+                       cv.demb, NL, B, G, W2);
+    if (rc) return twv_fail(TWV_E_HIP, "rocBLAS call failed with status " + std::to_string(rc));
+    // causal layer, gc embedding table, upsampler, and the gradient views back into the canonical order
+    if (d.scalar_input) red.wgrad(cv.xunf, g.ifw, dXn, W, Rr, g.ifw, W, Gd + g.c_causal, W);
+    else {
+        const int Q = d.quantization_channels, nblk = 256;
+        const long long rpb = (Rr + nblk - 1) / nblk;
+        HIPCHK(hipFuncSetAttribute((const void*)tr_onehot_causal_wide_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * Q * 32 * 4));
+        for (int cb = 0; cb < W / 32; ++cb) {               // one 32-column block at a time through the same partial tables
+            hipLaunchKernelGGL(tr_onehot_causal_wide_bwd_kernel, dim3(nblk), dim3(256), 2 * Q * 32 * 4, st, dXn, cv.qin, cv.ohpart, B, T, Tn, Q, W, cb, rpb);
+            hipLaunchKernelGGL(tr_colsum_final_kernel, dim3((2 * Q * 32 + 63) / 64), dim3(256), 0, st, cv.ohpart, nblk, 32, 2 * Q, Gd + g.c_causal + cb * 32, W);
+        }
+    }
+    K1(tr_scatter_emb_kernel, (long long)d.gc_cardinality * G, cv.demb, gc_ids, Gd + g.c_gcemb, B, G, d.gc_cardinality);
+    K1(tr_views_wide_bwd_kernel, (vstride + (long long)W * S) * NL, Gd, cv.GV, cv.GS, NL, g.c_layer0, g.c_lstride, g.lo.wf, g.lo.wg, g.lo.lcf, g.lo.lcg,
+       g.lo.gcf, g.lo.gcg, g.lo.ws, L, G, S, W);
+    if (fused_lc) {
+        hipLaunchKernelGGL(tr_dctab_kernel, dim3(g.hop), dim3(256), 0, st, cv.Dbuf, B, T, g.hop, cv.dctab);
+        K1(tr_up_grad_kernel, 2LL * (d.upsample_factor[0] + d.upsample_factor[1] + d.upsample_factor[2]), P + g.c_up[0], P + g.c_up[1], P + g.c_up[2],
+           d.upsample_factor[0], d.upsample_factor[1], d.upsample_factor[2], cv.dctab, Gd + g.c_up[0], Gd + g.c_up[1], Gd + g.c_up[2]);
+    } else {
+        float* dcur = cv.dUa; float* dnxt = cv.dUb;
+        for (int i = d.n_upsample - 1; i >= 0; --i) {
+            const long long rin = (long long)B * cv.upT[i];
+            int nch = (int)(rin / 64); nch = nch < 1 ? 1 : (nch > 256 ? 256 : nch);
+            hipLaunchKernelGGL(tr_up_bwd_k_kernel, dim3(nch, d.upsample_factor[i]), dim3(256), 0, st, ups[i], dcur, cv.part, rin, d.upsample_factor[i], L, nch);
+            hipLaunchKernelGGL(tr_colsum_final_kernel, dim3((2 * d.upsample_factor[i] + 63) / 64), dim3(256), 0, st, cv.part, nch, 2 * d.upsample_factor[i], 1,
+                               Gd + g.c_up[i], 2 * d.upsample_factor[i]);
+            if (i > 0) {
+                K1(tr_up_bwd_in_kernel, (long long)B * cv.upT[i] * L, P + g.c_up[i], dcur, dnxt, (long long)B * cv.upT[i] * L, d.upsample_factor[i], L);
+                float* tsw = dcur; dcur = dnxt; dnxt = tsw;
+            }
+        }
+    }
+    HIPCHK(hipGetLastError());
+    return TWV_OK;
+}
+
 extern "C" int twv_wavenet_train_loss_grad(twv_wavenet_trainer* h, const float* params, const float* audio, const float* lc,
                                            const int32_t* gc_ids, void* workspace, float* loss, float* grads, void* stream)
 {
@@ -2010,11 +2770,10 @@ extern "C" int twv_wavenet_train_loss_grad(twv_wavenet_trainer* h, const float* 
     float* Gd = grads;
     // ---- workspace carve (tr_carve: the function create sized the workspace with), checked BEFORE the first device operation
     TrainCarve cv;
-    if (tr_carve(&g, (float*)workspace, cv) != h->carve_floats || h->carve_floats > h->l2_off || h->l2_off > h->ws_floats)
+    if (tr_carve_any(&g, (float*)workspace, cv) != h->carve_floats || h->carve_floats > h->l2_off || h->l2_off > h->ws_floats)
         return twv_fail(TWV_E_INVALID, "internal: the workspace carve does not match the size twv_wavenet_train_create computed");
     const TrainRoute route = tr_route(g);
     const bool fused_lc = route.fused_lc;
-    const int nsplit = route.nsplit;
     HIPCHK(hipMemsetAsync(grads, 0, (size_t)g.nparams * 4, st));
     HIPCHK(hipMemsetAsync(loss, 0, 4, st));
     // A workspace seen for the first time is cleared once: the layer kernels do not walk the tiles in front of a layer's receptive offset,
@@ -2025,6 +2784,8 @@ extern "C" int twv_wavenet_train_loss_grad(twv_wavenet_trainer* h, const float* 
         HIPCHK(hipMemsetAsync(workspace, 0, (size_t)h->ws_floats * 4, st));
         h->ws_clean = workspace;
     }
+    if (g.R == 64) return tr_loss_grad_wide<64>(h, cv, P, audio, lc, gc_ids, loss, Gd, st);
+    if (g.R == 128) return tr_loss_grad_wide<128>(h, cv, P, audio, lc, gc_ids, loss, Gd, st);
     const long long* upT = cv.upT;
     float* ups[5] = {const_cast<float*>(lc), cv.ups[1], cv.ups[2], cv.ups[3], cv.ups[4]};
     float* U = ups[d.n_upsample];
@@ -2034,7 +2795,7 @@ extern "C" int twv_wavenet_train_loss_grad(twv_wavenet_trainer* h, const float* 
     const int ZW = NL * 32;                                  // stacked skip input: ZC[(b,p)][l*32 + j]
     float *ZC = cv.ZC, *dZC = cv.dZC, *PRE = cv.PRE, *dXa = cv.dXa, *dXb = cv.dXb, *SK = cv.SK, *C1 = cv.C1, *dS = cv.dS, *Y = cv.Y, *dY = cv.dY;
     float *emb = cv.emb, *demb = cv.demb, *GCP = cv.GCP, *WV = cv.WV, *WS = cv.WS, *GV = cv.GV, *GS = cv.GS, *part = cv.part, *slabs = cv.slabs;
-    float *zpage = cv.zpage, *kpart = cv.kpart, *wpart = cv.wpart, *ctab = cv.ctab, *melsh = cv.melsh, *Qall = cv.Qall, *Dbuf = cv.Dbuf, *dctab = cv.dctab;
+    float *zpage = cv.zpage, *ctab = cv.ctab, *melsh = cv.melsh, *Qall = cv.Qall, *Dbuf = cv.Dbuf, *dctab = cv.dctab;
     float *PTall = cv.PTall, *Rall = cv.Rall, *tsum = cv.tsum, *dGCPall = cv.dGCPall, *bsum64 = cv.bsum64;
     const long long vstride = cv.vstride, slab_ls = cv.slab_ls, q_ls = cv.q_ls, pt_ls = cv.pt_ls, tsum_ls = cv.tsum_ls;
     const int F = T / g.hop;                                // mel frames per entry
@@ -2044,32 +2805,9 @@ extern "C" int twv_wavenet_train_loss_grad(twv_wavenet_trainer* h, const float* 
     int rc = TWV_OK;
 #define LP(l) (P + g.c_layer0 + (long long)(l) * g.c_lstride)
 #define LG(l) (Gd + g.c_layer0 + (long long)(l) * g.c_lstride)
-    // out[seg][c] = column sums of x (nseg slabs of `rows` rows); deterministic two-stage reduction
-    auto colsum = [&](const float* x, long long rows, int C, int ldx, int nseg, float* out, int ldo) {
-        int nchunk = (int)(rows / 256); const int cap = nseg > 8 ? 32 : 256; nchunk = nchunk < 1 ? 1 : (nchunk > cap ? cap : nchunk);
-        hipLaunchKernelGGL(tr_colsum_partial_kernel, dim3(nchunk, (C + 63) / 64, nseg), dim3(256), 0, st, x, rows, C, ldx, nchunk, part);
-        hipLaunchKernelGGL(tr_colsum_final_kernel, dim3((nseg * C + 63) / 64), dim3(256), 0, st, part, nchunk, C, nseg, out, ldo);
-    };
-    // dx <- relu'(y) * dx over (rows, C) and, with biases, out[c] = column sums of the result
-    auto relu_bwd_colsum = [&](float* dx, const float* y, long long rows, int C, float* out) {
-        int nchunk = (int)(rows / 256); nchunk = nchunk < 1 ? 1 : (nchunk > 256 ? 256 : nchunk);
-        hipLaunchKernelGGL(tr_relu_bwd_colsum_kernel, dim3(nchunk, (C + 63) / 64, 1), dim3(256), 0, st, dx, y, rows, C, nchunk, part);
-        hipLaunchKernelGGL(tr_colsum_final_kernel, dim3((C + 63) / 64), dim3(256), 0, st, part, nchunk, C, 1, out, C);
-    };
-    // C[M x N](ldc) = A^T B over K rows (tall-skinny weight gradient); optional second output for columns [N, 2N) (filter|gate split)
-    auto wgrad = [&](const float* A, int lda, const float* Bm, int ldb, long long K, int M, int N, float* C, int ldc) {
-        const int mb = (M + 31) / 32, nb = (N + 31) / 32;
-        const long long cap = (512LL * 96 * 64 + 1024LL * 512) / ((long long)mb * nb * 1024);     // `part` holds chunks x (mb*32) x (nb*32)
-        // enough workgroups to fill the chip whatever the tile count: a single-tile product (the causal kernel's gradient: M = N = 32) ran on
-        // 256 workgroups of dependent two-row steps: 124 us for 128 MB
-        int chunks = (int)(K / 512); chunks = chunks < 1 ? 1 : (chunks > 1024 ? 1024 : chunks);
-        if (chunks * mb * nb > 4096) chunks = 4096 / (mb * nb) > 0 ? 4096 / (mb * nb) : 1;
-        if (chunks > cap) chunks = (int)cap;
-        long long rpc = (K + chunks - 1) / chunks; rpc = (rpc + 7) / 8 * 8;
-        chunks = (int)((K + rpc - 1) / rpc);
-        hipLaunchKernelGGL(tr_tn_partial_kernel, dim3(chunks, mb, nb), dim3(256), 0, st, A, lda, Bm, ldb, K, M, N, rpc, part);
-        hipLaunchKernelGGL(tr_tn_reduce_kernel, dim3((M * N + 63) / 64), dim3(chunks > 64 ? 1024 : 256), 0, st, part, chunks, mb * 32, nb * 32, M, N, C, ldc);
-    };
+    const TrRed red{st, part};
+    auto colsum = [&](const float* x, long long rows, int C, int ldx, int nseg, float* out, int ldo) { red.colsum(x, rows, C, ldx, nseg, out, ldo); };
+    auto wgrad = [&](const float* A, int lda, const float* Bm, int ldb, long long K, int M, int N, float* C, int ldc) { red.wgrad(A, lda, Bm, ldb, K, M, N, C, ldc); };
     do {
         // ================= forward =================
         WavenetFwdBufs fb;
@@ -2110,9 +2848,7 @@ extern "C" int twv_wavenet_train_loss_grad(twv_wavenet_trainer* h, const float* 
         if (rc) break;
         // head: conv1d_1's relu pass is skipped only when conv1d_2's fused backward reads the pre-activations (tr_route); at S = 192 the
         // skinny projection runs on activated C1
-        const bool fuse_c2 = route.fuse_c2;
-        const float* b1p = ub ? P + g.c_b1 : nullptr;
-        if (int hrc = wavenet_forward_head(g, P, fb, route.skinny, fuse_c2, bl, st)) return hrc;
+        if (int hrc = wavenet_forward_head(g, P, fb, route.skinny, route.fuse_c2, bl, st)) return hrc;
         // model.py:286-290 loss
         // per-row terms, then the same two-stage column sum as the bias gradients: the loss is bit-reproducible run to run
         float* row_loss = dS;                                       // (RO) scratch: dS is not written before the backward pass
@@ -2121,31 +2857,7 @@ extern "C" int twv_wavenet_train_loss_grad(twv_wavenet_trainer* h, const float* 
         else hipLaunchKernelGGL(tr_softmax_ce_kernel, dim3(tg(RO * 64)), dim3(256), 0, st, Y, qin, B, T, ow, rf, O, 1.0f / (float)RO, row_loss, dY);
         colsum(row_loss, RO, 1, 1, 1, loss, 1);
         // ================= backward =================
-        if (!fuse_c2) wgrad(C1, S, dY, O, RO, S, O, Gd + g.c_w2, O);                                              // dW2 = H2^T dY (the tall-skinny MFMA kernel)
-        if (ub) colsum(dY, RO, O, O, 1, Gd + g.c_b2, O);
-        if (fuse_c2) {                                                                                           // dC1, db1 and dW2: one pass
-            const int nwg = 512, nchunk = nwg * 4 / (S >> 6);             // two workgroups per CU (171 registers; at three, 168 + spills: 276 vs 263 us)
-            hipLaunchKernelGGL(tr_conv2_bwd_kernel, dim3(nwg), dim3(256), 0, st, dY, O, P + g.c_w2, C1, b1p, RO, S, dS, part, wpart);
-            if (ub) hipLaunchKernelGGL(tr_colsum_final_kernel, dim3((S + 63) / 64), dim3(256), 0, st, part, nchunk, S, 1, Gd + g.c_b1, S);
-            hipLaunchKernelGGL(tr_tn_reduce_kernel, dim3((S * O + 63) / 64), dim3(1024), 0, st, wpart, nchunk, S, 32, S, O, Gd + g.c_w2, O);
-        } else {
-            rc |= gemm_rm(bl, false, true, (int)RO, S, O, 1.f, dY, O, P + g.c_w2, O, 0.f, dS, S);               // dH2
-            if (ub) relu_bwd_colsum(dS, C1, RO, S, Gd + g.c_b1);                                                // dC1, db1
-            else if ((S & 3) == 0) K1(tr_relu_bwd4_kernel, RO * S / 4, (float4*)dS, (const float4*)C1, RO * S / 4);
-            else K1(tr_relu_bwd_kernel, RO * S, dS, C1, RO * S);
-        }
-        rc |= gemm_tn_splitk(bl, st, S, S, RO, SK, S, dS, S, Gd + g.c_w1, S, nsplit, kpart);                     // dW1 = H1^T dC1
-        rc |= gemm_rm(bl, false, true, (int)RO, S, S, 1.f, dS, S, P + g.c_w1, S, 0.f, C1, S);                   // dH1 -> C1 buffer
-        if (ub) relu_bwd_colsum(C1, SK, RO, S, LG(0) + g.lo.bs);                                                 // dSK, dbs (layer 0's slot)
-        else if ((S & 3) == 0) K1(tr_relu_bwd4_kernel, RO * S / 4, (float4*)C1, (const float4*)SK, RO * S / 4);
-        else K1(tr_relu_bwd_kernel, RO * S, C1, SK, RO * S);
-        float* dSK = C1;
-        // all skip convs at once: dWs (stacked) = ZC^T dSK ; dZC = dSK WS^T ; dbs (identical for every layer) = colsum(dSK)
-        rc |= gemm_tn_splitk(bl, st, ZW, S, RO, ZC, ZW, dSK, S, GS, S, nsplit, kpart);
-        if (ub) {
-            if (NL > 1) K1(tr_bcast_rows_kernel, (long long)(NL - 1) * S, LG(0) + g.lo.bs, g.c_lstride, NL, S);
-        }
-        rc |= gemm_rm(bl, false, true, (int)RO, ZW, S, 1.f, dSK, S, WS, S, 0.f, dZC, ZW);
+        rc |= tr_head_backward(g, route, P, Gd, cv, ZW, bl, st);
         if (rc) break;
         float* dXn = dXa; float* dXc = dXb;
         K1(tr_fill_kernel, Rr * 32, dXn, 0.0f, Rr * 32);
@@ -2275,7 +2987,7 @@ extern "C" int twv_wavenet_train_l2(twv_wavenet_trainer* h, const float* params,
     const WavenetGraph& g = h->g;
     float* sq = (float*)workspace + h->l2_off;           // nparams floats, then 256 partials + the sum: a region of its own (see create)
     float* part = sq + (g.nparams + 63) / 64 * 64;
-    L2Layout L{g.c_layer0, g.c_lstride, g.NL, g.lo.bf, g.lo.bg, g.lo.bd, g.lo.bs, 32, 32, g.S, g.c_b1, g.c_b2, g.O, g.d.use_biases};
+    L2Layout L{g.c_layer0, g.c_lstride, g.NL, g.lo.bf, g.lo.bg, g.lo.bd, g.lo.bs, g.D, g.R, g.S, g.c_b1, g.c_b2, g.O, g.d.use_biases};
     hipLaunchKernelGGL(tr_l2_kernel, dim3(tg(g.nparams)), dim3(256), 0, st, params, grads, sq, g.nparams, (float)strength, L);
     tr_sum(sq, g.nparams, part, part + 512, st);
     hipLaunchKernelGGL(tr_axpy1_kernel, dim3(1), dim3(64), 0, st, loss, part + 512, (float)strength);

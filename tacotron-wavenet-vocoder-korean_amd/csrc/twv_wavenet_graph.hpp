@@ -64,7 +64,7 @@ inline std::string wavenet_route_label(const WavenetRoute& r, const char* head)
 
 // Fills g from (dims, rows, samples) and makes every refusal of twv_wavenet_train_create / twv_wavenet_score_create (`what`: "training" /
 // "scoring", for the texts).  The width is the caller's to allow: residual_channels = dilation_channels in {32, 64, 128} and at most
-// `max_width` (training: 32, its backward kernels are built for that width; scoring: 128).  TWV_OK, or the code twv_fail was given.
+// `max_width` (training: twv_wavenet_train_create_w's argument, 32 through twv_wavenet_train_create; scoring: 128).  TWV_OK, or the code twv_fail was given.
 inline int wavenet_graph_init(WavenetGraph& g, const twv_wavenet_dims* dims, int rows, int samples, const char* what, int max_width)
 {
     const std::string w(what);

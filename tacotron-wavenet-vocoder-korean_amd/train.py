@@ -62,7 +62,7 @@ class WaveNetTrainer(object):
         self.device = net.device
         self._L = _lib.lib()
         h = C.c_void_p()
-        _lib.check(self._L.twv_wavenet_train_create(C.byref(net._dims), self.batch_size, self.sample_size, C.byref(h)))
+        _lib.check(self._L.twv_wavenet_train_create_w(C.byref(net._dims), self.batch_size, self.sample_size, 128, C.byref(h)))   # widths 32, 64, 128
         self._h = h
         self.n_params = self._L.twv_wavenet_train_param_floats(h)
         self.output_width = self._L.twv_wavenet_train_output_width(h)
@@ -176,7 +176,7 @@ class WaveNetTrainer(object):
 
     def route(self):
         """which kernel families `loss_and_gradients` runs for this trainer (twv_wavenet_train_route), as a dict of strings:
-        lc (fused | staged), head (skinny+c2bwd | skinny | gemm), loss (mol<10> | mol<0> | softmax), nsplit, carve_floats"""
+        lc (fused | staged), head (skinny+c2bwd | skinny | gemm), loss (mol<10> | mol<0> | softmax), nsplit, width (32 | 64 | 128), carve_floats"""
         return dict(kv.split("=", 1) for kv in self._L.twv_wavenet_train_route(self._h).decode().split())
 
     def reset_workspace(self):
