@@ -264,6 +264,50 @@ int twv_tacotron_loss(const float* mel, const float* linear, const float* mel_ta
                       const float* loss_coeff, int batch, int t_out, int num_mels, int num_freq, int prioritize_loss,
                       double sample_rate, double* out, void* stream);
 
+/* ---- Tacotron decoder gradients: the vector-Jacobian product of the teacher-forced decoder ----
+ * Host only: where a twv_tacotron_infer / twv_tacotron_forward_targets call of (batch, t_in) left the pieces the decoder reads from the
+ * encoder side, as (offset, count) in floats from the start of its workspace.  which = "memory" (batch, t_in, 2 * enc_rnn_size; zero past
+ * each length), "keys" (batch, t_in, attention_size) or "decoder_init" (batch, attention_state_size + dec_layer_num * dec_rnn_size: the
+ * attention cell's state, then each residual GRU's).  Any other name, a null argument or a (batch, t_in) the passes refuse: TWV_E_INVALID. */
+int twv_tacotron_workspace_view(const twv_tacotron* h, int batch, int t_in, const char* which, long long* offset_floats, long long* floats);
+
+/* A gradient handle for (batch, t_in, steps) on the model of `h` (which is not kept).  Host only; every refusal comes before the device is
+ * touched.  TWV_E_INVALID: null arguments, steps outside 1 .. max_iters, batch < 1, t_in outside 1 .. 1024.  TWV_E_UNSUPPORTED: what is not
+ * built -- attention types other than bah_mon_norm and bah_mon, model_type 'simple', dec_prenet_sizes or num_mels above 512.
+ * twv_tacotron_decoder_grad_route: a label of the kernels and sizes in use ("kernel=tg_bptt attention=... workgroups_per_utterance=1 ..."). */
+typedef struct twv_tacotron_decoder_grad twv_tacotron_decoder_grad;
+int twv_tacotron_decoder_grad_create(const twv_tacotron* h, int batch, int t_in, int steps, twv_tacotron_decoder_grad** out);
+void twv_tacotron_decoder_grad_destroy(twv_tacotron_decoder_grad* g);
+size_t twv_tacotron_decoder_grad_workspace_bytes(const twv_tacotron_decoder_grad* g);
+const char* twv_tacotron_decoder_grad_route(const twv_tacotron_decoder_grad* g);
+/* The teacher-forced decoder forward (recorded) and its backward through time.
+ * In:  blob          the canonical weights on the device (twv_tacotron_blob_floats floats, the order of tacotron_specs)
+ *      memory        (batch, t_in, 2 * enc_rnn_size), decoder_init (batch, AS + layers * DR), lengths (batch) int32
+ *      mel_targets   (batch, steps * r, num_mels): step 0 is fed zeros, step t the row t * r - 1 (helpers.py:80-87)
+ *      d_mel         (batch, steps * r, num_mels): the cotangent on the mel output
+ *      mask1, mask2  NULL, or (batch, steps, dec_prenet_sizes[i]) multipliers applied after each decoder-prenet relu (TF dropout: 0 or
+ *                    1 / keep_prob; the caller draws them).  NULL masks give the evaluation graph.
+ * Scratch: workspace (twv_tacotron_decoder_grad_workspace_bytes, in any state: no word is read before this call wrote it), status (4 x int32,
+ *      zeroed), stream.
+ * Out: mel_out       (batch, steps * r, num_mels): with NULL masks the teacher-forced twv_tacotron_forward_targets mel up to summation order
+ *      grad_blob     the layout of blob: zeroed, then the gradient of every decoder-side tensor (memory_layer/kernel .. decoder/
+ *                    output_projection_wrapper/bias) written at the tensor's place; every other tensor reads 0
+ *      d_memory      (batch, t_in, 2 * enc_rnn_size), exactly 0 past each length; d_init (batch, AS + layers * DR)
+ * One workgroup per utterance runs the recurrence and no workgroup waits for another; no atomics: two runs give the same bits, and an
+ * utterance's d_memory / d_init rows are the same bits alone and inside a batch. */
+int twv_tacotron_decoder_grad_run(twv_tacotron_decoder_grad* g, const float* blob, const float* memory, const float* decoder_init,
+                                  const int32_t* lengths, const float* mel_targets, const float* d_mel, const float* mask1,
+                                  const float* mask2, void* workspace, int32_t* status, void* stream, float* mel_out,
+                                  float* grad_blob, float* d_memory, float* d_init);
+/* measurement: with timing on, a run records events at its phase boundaries; twv_tacotron_decoder_grad_phase_ms waits for the last run and
+ * gives ms3 = milliseconds of the recording forward, the backward through time, the weight-gradient products (TWV_E_INVALID before such a run) */
+int twv_tacotron_decoder_grad_set_timing(twv_tacotron_decoder_grad* g, int on);
+int twv_tacotron_decoder_grad_phase_ms(twv_tacotron_decoder_grad* g, double* ms3);
+/* the derivative of add_loss's mel term (tacotron.py:258-282) with respect to mel: d_mel = sign(mel - mel_targets) * loss_coeff[n] /
+ * (batch * t_out * num_mels), 0 where the difference is 0.  All of (batch, t_out, num_mels) but loss_coeff (batch). */
+int twv_tacotron_mel_loss_grad(const float* mel, const float* mel_targets, const float* loss_coeff, int batch, int t_out, int num_mels,
+                               float* d_mel, void* stream);
+
 /* launch geometry (performance only, results are bit-identical): "decoder_groups" = 0 auto (the XCD-resident decoder kernel wherever it
  * fits -- batch <= 32, t_in <= 512, 256 CUs, decoder widths divisible by 4, not model_type 'simple', attention_type bah_mon_norm -- else the split kernel with 16 / 8 / 4
  * workgroups per utterance), 1/2/4/8/16 = the split kernel with that many workgroups per utterance, 32 = the XCD-resident kernel or an

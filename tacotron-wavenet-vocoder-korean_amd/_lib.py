@@ -251,6 +251,15 @@ def lib():
     L.twv_tacotron_infer.argtypes = [vp, vp, ip, ip, ip, C.c_int, C.c_int, vp, fp, fp, fp, ip, vp]
     L.twv_tacotron_forward_targets.argtypes = [vp, vp, ip, ip, ip, C.c_int, C.c_int, fp, C.c_int, C.c_int, vp, fp, fp, fp, ip, vp]
     L.twv_tacotron_loss.argtypes = [fp, fp, fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, dp, vp]
+    L.twv_tacotron_workspace_view.argtypes = [vp, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+    L.twv_tacotron_decoder_grad_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    L.twv_tacotron_decoder_grad_destroy.argtypes = [vp]; L.twv_tacotron_decoder_grad_destroy.restype = None
+    L.twv_tacotron_decoder_grad_workspace_bytes.argtypes = [vp]; L.twv_tacotron_decoder_grad_workspace_bytes.restype = C.c_size_t
+    L.twv_tacotron_decoder_grad_route.argtypes = [vp]; L.twv_tacotron_decoder_grad_route.restype = C.c_char_p
+    L.twv_tacotron_decoder_grad_run.argtypes = [vp, fp, fp, fp, ip, fp, fp, fp, fp, vp, ip, vp, fp, fp, fp, fp]
+    L.twv_tacotron_decoder_grad_set_timing.argtypes = [vp, C.c_int]
+    L.twv_tacotron_decoder_grad_phase_ms.argtypes = [vp, C.POINTER(C.c_double)]
+    L.twv_tacotron_mel_loss_grad.argtypes =[fp, fp, fp, C.c_int, C.c_int, C.c_int, fp, vp]
     L.twv_tacotron_set_profile_buffer.argtypes = [vp, vp]
     L.twv_tacotron_set_option.argtypes = [vp, C.c_char_p, C.c_int]
     L.twv_tacotron_gemm_stats.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]
@@ -297,7 +306,10 @@ EXPORTS = ["twv_last_error", "twv_version", "twv_wavenet_create", "twv_wavenet_d
            "twv_resample_workspace_bytes", "twv_resample_filter_host", "twv_resample_kernel_name", "twv_resample_rounds", "twv_resample",
            "twv_griffin_lim_create_ragged", "twv_griffin_lim_total_frames", "twv_griffin_lim_total_samples", "twv_griffin_lim_offsets",
            "twv_wavenet_score_create", "twv_wavenet_score_destroy", "twv_wavenet_score_workspace_bytes", "twv_wavenet_score_output_width",
-           "twv_wavenet_score_route", "twv_wavenet_score_windows", "twv_wavenet_score_reduce", "twv_wavenet_score_view", "twv_wavenet_train_create_w"]
+           "twv_wavenet_score_route", "twv_wavenet_score_windows", "twv_wavenet_score_reduce", "twv_wavenet_score_view", "twv_wavenet_train_create_w",
+           "twv_tacotron_workspace_view", "twv_tacotron_decoder_grad_create", "twv_tacotron_decoder_grad_destroy",
+           "twv_tacotron_decoder_grad_workspace_bytes", "twv_tacotron_decoder_grad_route", "twv_tacotron_decoder_grad_run",
+           "twv_tacotron_decoder_grad_set_timing", "twv_tacotron_decoder_grad_phase_ms", "twv_tacotron_mel_loss_grad"]
 
 
 class TacoDims(C.Structure):

@@ -22,6 +22,7 @@
 #include "../../include/twv_amd.h"
 #include "twv_dev.hpp"
 #include "twv_dpp.hpp"
+#include "twv_tacotron_blob.hpp"
 
 // "gemm_timing" option (measurement aid, bench.py's `tacotron.roofline`): every GEMM launch is bracketed by a pair of HIP events on
 // its stream and its useful FLOPs (2 * rows * K * N, unpadded) are counted; twv_tacotron_gemm_stats sums both since the option was set.
@@ -2875,6 +2876,7 @@ struct TacoCarve {
     float *semb, *sv[8], *dinit;                                // speaker embedding rows, one piece per dense output, the decoder's initial states
     float *exch, *xexch, *stabf;    // exchange granules of the split ([N][2][kExN]) and the XCD-local ([8][2][kXU * 512]) decoder; stage tables
     int *tickets, *xtickets; long long exch_floats, xexch_floats;    // the role tickets behind either area; granules + tickets: what a launch clears
+    long long o_memo, o_keys, o_dinit;                          // where memo / keys / dinit start (floats from the base): twv_tacotron_workspace_view
 };
 static long long taco_carve(const twv_tacotron* h, int N, int T, float* base, TacoCarve& c)
 {
@@ -2887,7 +2889,7 @@ static long long taco_carve(const twv_tacotron* h, int N, int T, float* base, Ta
     c.bankbuf = take(rmax * CB); c.poolbuf = take(rmax * CB);                           // bank output, maxpool output
     c.ra = take(rmax * 512); c.rb = take(rmax * 512); c.rc = take(rmax * 512); c.rd = take(rmax * 512);      // generic row buffers (<= 512 wide)
     c.gx = take(rmax * 512); c.cx = take(rmax * 256);                                   // Gx (2 dirs x 256), Cx (2 x 128)
-    c.memo = take(rowsE * 2 * d.enc_rnn_size); c.keys = take(rowsE * 256);              // (attention_size <= 256)
+    c.o_memo = used; c.memo = take(rowsE * 2 * d.enc_rnn_size); c.o_keys = used; c.keys = take(rowsE * 256);      // (attention_size <= 256)
     // speaker-dependent vectors: every piece has its real size.  The three areas are never smaller than the N * 64, N * 1984 and N * 2048
     // floats they had as fixed offsets of one N * 4096 block, so a model that fit those has the workspace size it always had.
     const long long SE = d.num_speakers > 1 ? d.speaker_embedding_size : 0, ninit = d.attention_state_size + (long long)d.dec_layer_num * d.dec_rnn_size;
@@ -2895,7 +2897,7 @@ static long long taco_carve(const twv_tacotron* h, int N, int T, float* base, Ta
     long long dsum = 0;
     for (int i = 0; i < 8; ++i) { c.sv[i] = i < h->ndense ? take((long long)N * h->dn[i]) : nullptr; dsum += i < h->ndense ? h->dn[i] : 0; }
     if (dsum < 1984) take(N * (1984 - dsum));
-    c.dinit = take(N * (ninit > 2048 ? ninit : 2048));
+    c.o_dinit = used; c.dinit = take(N * (ninit > 2048 ? ninit : 2048));
     c.postout = take(rowsP * 2 * d.post_rnn_size);
     c.exch_floats = (long long)N * 2 * kExN * 2 + 16; c.xexch_floats = 8LL * 2 * kXU * 512 * 2 + 64;   // 8-byte granules + 8 (16 words) / 64 tickets
     c.exch = take(c.exch_floats); c.tickets = base ? reinterpret_cast<int*>(c.exch + (c.exch_floats - 16)) : nullptr;
@@ -2904,6 +2906,47 @@ static long long taco_carve(const twv_tacotron* h, int N, int T, float* base, Ta
     return used;
 }
 extern "C" size_t twv_tacotron_workspace_bytes(const twv_tacotron* h, int batch, int t_in) { TacoCarve c; return (size_t)taco_carve(h, batch, t_in, nullptr, c) * 4; }
+
+// The carve's answer for the pieces of the workspace a pass leaves behind for the decoder gradient (host only): the encoder output
+// "memory" [batch][t_in][2 * enc_rnn_size], its "keys" [batch][t_in][attention_size] and the decoder's initial states "decoder_init"
+// [batch][attention_state_size + dec_layer_num * dec_rnn_size], as (offset, count) in floats from the workspace's start.
+extern "C" int twv_tacotron_workspace_view(const twv_tacotron* h, int batch, int t_in, const char* which, long long* offset_floats, long long* floats)
+{
+    if (!h || !which || !offset_floats || !floats) return twv_fail(TWV_E_INVALID, "null argument");
+    if (batch < 1 || t_in < 1 || t_in > 1024) return twv_fail(TWV_E_INVALID, "batch >= 1 and 1 <= t_in <= 1024 required");
+    TacoCarve c;
+    taco_carve(h, batch, t_in, nullptr, c);
+    const twv_tacotron_dims& d = h->d;
+    const long long rows = (long long)batch * t_in;
+    if (!strcmp(which, "memory")) { *offset_floats = c.o_memo; *floats = rows * 2 * d.enc_rnn_size; }
+    else if (!strcmp(which, "keys")) { *offset_floats = c.o_keys; *floats = rows * d.attention_size; }
+    else if (!strcmp(which, "decoder_init")) { *offset_floats = c.o_dinit; *floats = (long long)batch * (d.attention_state_size + (long long)d.dec_layer_num * d.dec_rnn_size); }
+    else return twv_fail(TWV_E_INVALID, std::string("twv_tacotron_workspace_view: no piece named '") + which + "' (memory, keys, decoder_init)");
+    return TWV_OK;
+}
+
+// twv_tacotron_blob.hpp: the handle's dims and where the decoder-side tensors lie in the canonical blob (each packed item remembers its source)
+const twv_tacotron_dims& taco_dims(const twv_tacotron* h) { return h->d; }
+void taco_decoder_blob(const twv_tacotron* h, TacoDecoderBlob& b)
+{
+    auto src = [&](long long dst, bool present) -> long long {
+        if (present) for (const auto& it : h->items) if (it.dst == dst) return it.src;
+        return -1;
+    };
+    const int at = h->d.attention_type;
+    const bool bah = at == TWV_ATT_BAH_MON_NORM || at == TWV_ATT_BAH_MON || at == TWV_ATT_BAH_NORM || at == TWV_ATT_BAH, norm = at == TWV_ATT_BAH_MON_NORM || at == TWV_ATT_BAH_NORM;
+    b.Wm = src(h->Wm.off, true); b.Wq = src(h->Wq.off, bah); b.av = src(h->av.off, bah); b.ag = src(h->ag.off, norm); b.ab = src(h->ab.off, norm);
+    b.asb = src(h->asb.off, at == TWV_ATT_BAH_MON_NORM || at == TWV_ATT_BAH_MON);
+    b.dpW1 = src(h->dpW1.off, true); b.dpb1 = src(h->dpb1.off, true); b.dpW2 = src(h->dpW2.off, true); b.dpb2 = src(h->dpb2.off, true);
+    b.aWg = src(h->aWgm.off, true); b.abg = src(h->abg.off, true); b.aWc = src(h->aWcm.off, true); b.abc = src(h->abc.off, true);
+    b.cW = src(h->cW.off, true); b.cb = src(h->cb.off, true);
+    for (int i = 0; i < 4; ++i) {
+        const bool on = i < h->d.dec_layer_num;
+        b.rWg[i] = src(h->rWg[i].off, on); b.rbg[i] = src(h->rbg[i].off, on); b.rWc[i] = src(h->rWc[i].off, on); b.rbc[i] = src(h->rbc[i].off, on);
+    }
+    b.oW = src(h->oW.off, true); b.ob = src(h->ob.off, true);
+    b.blob_floats = h->blob_floats;
+}
 
 static inline int tgrid(long long n) { long long g = (n + 255) / 256; return (int)(g < 1 ? 1 : (g > 16384 ? 16384 : g)); }
 

@@ -144,6 +144,24 @@ def flatten(specs, tensors):
     return np.concatenate(parts).astype(np.float32)
 
 
+DECODER_FIRST, DECODER_LAST = "memory_layer/kernel", "decoder/output_projection_wrapper/bias"
+
+
+def decoder_grad_layout(specs):
+    """(name, offset in the canonical blob, shape) of the decoder-side tensors: memory_layer/kernel .. the output projection's bias --
+    what Tacotron.decoder_grad returns a gradient for"""
+    out, off, on = [], 0, False
+    for n, shp in specs:
+        size = 2 * shp[1] if n.endswith("batch_normalization") else int(np.prod(shp))     # (flatten: the derived (inv, shift) pair)
+        on = on or n == DECODER_FIRST
+        if on:
+            out.append((n, off, tuple(shp)))
+        off += size
+        if n == DECODER_LAST:
+            break
+    return out
+
+
 def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
@@ -209,6 +227,7 @@ class Tacotron(object):
 
     def __del__(self):
         try:
+            self._drop_grad_handle()
             if getattr(self, "_h", None):
                 self._L.twv_tacotron_destroy(self._h)
                 self._h = None
@@ -219,7 +238,7 @@ class Tacotron(object):
         blob = flatten(self.specs, tensors)
         assert blob.size == self._L.twv_tacotron_blob_floats(self._h), (blob.size, self._L.twv_tacotron_blob_floats(self._h))
         with torch.cuda.device(self.device):
-            dblob = torch.from_numpy(blob).to(self.device)
+            dblob = self._blob = torch.from_numpy(blob).to(self.device)     # kept: decoder_grad differentiates the canonical tensors
             self._packed = torch.empty(self._L.twv_tacotron_packed_bytes(self._h) // 4, dtype=torch.float32, device=self.device)
             _lib.check(self._L.twv_tacotron_pack(self._h, _ptr(dblob), _ptr(self._packed), _stream()))
             torch.cuda.current_stream().synchronize()
@@ -283,7 +302,93 @@ class Tacotron(object):
                                                             _ptr(status), _stream()))
         self.inputs, self.input_lengths, self.speaker_id = tok, ln, sp
         self.mel_outputs, self.linear_outputs, self.alignments, self.mel_targets = mel, lin, al, tgt
+        self._teacher_forced = bool(teacher_forced)
         return mel, lin, al
+
+    def _forced_pass(self, what):
+        if getattr(self, "mel_targets", None) is None or not getattr(self, "_teacher_forced", False):
+            raise ValueError("%s needs a forward_targets pass with teacher_forced=True first" % what)
+        return self.mel_outputs, self.mel_targets
+
+    def mel_loss_cotangent(self, loss_coeff=None):
+        """d(mel term of add_loss) / d mel_outputs on the last teacher-forced forward_targets pass (tacotron.py:258-282):
+        sign(mel - target) * loss_coeff[n] / (N * T_out * num_mels), a (N, T_out, num_mels) tensor on the device."""
+        mel, tgt = self._forced_pass("mel_loss_cotangent")
+        N, TO, M = (int(v) for v in mel.shape)
+        co = np.ones(N, np.float32) if loss_coeff is None else np.asarray(loss_coeff, np.float32).reshape(-1)
+        if co.shape != (N,):
+            raise ValueError("loss_coeff must hold one factor per utterance (%d), got shape %s" % (N, co.shape))
+        with torch.cuda.device(self.device):
+            co = torch.from_numpy(co).to(self.device)
+            out = torch.empty_like(mel)
+            _lib.check(self._L.twv_tacotron_mel_loss_grad(_ptr(mel), _ptr(tgt), _ptr(co), N, TO, M, _ptr(out), _stream()))
+        return out
+
+    def workspace_view(self, batch, t_in, which):
+        """the piece `which` ("memory", "keys", "decoder_init") of the workspace the last pass of (batch, t_in) used, as a flat view"""
+        off, n = C.c_longlong(), C.c_longlong()
+        _lib.check(self._L.twv_tacotron_workspace_view(self._h, int(batch), int(t_in), which.encode(), C.byref(off), C.byref(n)))
+        return self._ws[off.value:off.value + n.value]
+
+    def decoder_grad(self, d_mel, prenet_masks=None):
+        """The vector-Jacobian product of the teacher-forced decoder of the last forward_targets(teacher_forced=True) pass: d_mel
+        (N, T_out, num_mels) is the cotangent on the mel output; memory and the initial states are read from that pass's workspace.
+        prenet_masks: None (the evaluation graph) or two (N, steps, dec_prenet_sizes[i]) arrays of multipliers applied after the decoder
+        prenet's relus (dropout: 0 or 1 / keep_prob).  Returns a dict: every decoder-side checkpoint tensor's gradient by name (TF scalars
+        as (1,)), "d_memory" (N, T_in, 2 * enc_rnn_size), "d_init" (N, attention_state_size + dec_layer_num * dec_rnn_size) and "mel", the
+        recorded forward's output -- device tensors."""
+        hp = self._hparams
+        mel, tgt = self._forced_pass("decoder_grad")
+        if getattr(self, "_blob", None) is None:
+            raise ValueError("decoder_grad needs load_weights first")
+        N, TO, M = (int(v) for v in tgt.shape)
+        T = int(self.inputs.shape[1])
+        steps = TO // hp.reduction_factor
+        D = hp.dec_prenet_sizes
+        with torch.cuda.device(self.device):
+            if not torch.is_tensor(d_mel):
+                d_mel = torch.from_numpy(np.ascontiguousarray(d_mel, np.float32))
+            dm = d_mel.to(device=self.device, dtype=torch.float32).contiguous()
+            if tuple(dm.shape) != (N, TO, M):
+                raise ValueError("d_mel must be %s, got %s" % ((N, TO, M), tuple(dm.shape)))
+            masks = [None, None]
+            if prenet_masks is not None:
+                for i in range(2):
+                    m = prenet_masks[i]
+                    m = m if torch.is_tensor(m) else torch.from_numpy(np.ascontiguousarray(m, np.float32))
+                    masks[i] = m.to(device=self.device, dtype=torch.float32).contiguous()
+                    if tuple(masks[i].shape) != (N, steps, D[i]):
+                        raise ValueError("prenet_masks[%d] must be %s, got %s" % (i, (N, steps, D[i]), tuple(masks[i].shape)))
+            key = (N, T, steps)
+            if getattr(self, "_grad_key", None) != key:
+                self._drop_grad_handle()
+                g = C.c_void_p()
+                _lib.check(self._L.twv_tacotron_decoder_grad_create(self._h, N, T, steps, C.byref(g)))
+                self._grad, self._grad_key = g, key
+                self._grad_ws = torch.empty(self._L.twv_tacotron_decoder_grad_workspace_bytes(g) // 4, dtype=torch.float32, device=self.device)
+            ENC, ninit = 2 * hp.enc_rnn_size, hp.attention_state_size + hp.dec_layer_num * hp.dec_rnn_size
+            memory, init = self.workspace_view(N, T, "memory"), self.workspace_view(N, T, "decoder_init")
+            mel_out = torch.empty((N, TO, M), dtype=torch.float32, device=self.device)
+            grad = torch.empty_like(self._blob)
+            d_memory = torch.empty((N, T, ENC), dtype=torch.float32, device=self.device)
+            d_init = torch.empty((N, ninit), dtype=torch.float32, device=self.device)
+            status = torch.zeros(4, dtype=torch.int32, device=self.device)
+            _lib.check(self._L.twv_tacotron_decoder_grad_run(self._grad, _ptr(self._blob), _ptr(memory), _ptr(init), _ptr(self.input_lengths),
+                                                             _ptr(tgt), _ptr(dm), _ptr(masks[0]), _ptr(masks[1]), _ptr(self._grad_ws),
+                                                             _ptr(status), _stream(), _ptr(mel_out), _ptr(grad), _ptr(d_memory), _ptr(d_init)))
+        out = {"d_memory": d_memory, "d_init": d_init, "mel": mel_out}
+        for name, off, shp in decoder_grad_layout(self.specs):
+            out[name] = grad[off:off + int(np.prod(shp))].view(*shp)
+        return out
+
+    def decoder_grad_route(self):
+        """the label of the gradient kernels of the last decoder_grad call ('' before one)"""
+        return self._L.twv_tacotron_decoder_grad_route(self._grad).decode() if getattr(self, "_grad", None) else ""
+
+    def _drop_grad_handle(self):
+        if getattr(self, "_grad", None):
+            self._L.twv_tacotron_decoder_grad_destroy(self._grad)
+        self._grad, self._grad_key = None, None
 
     def add_loss(self, linear_targets, loss_coeff=None):
         """tacotron.py:258-282 on the outputs of the last forward_targets pass: sets `.loss`, `.mel_loss`, `.linear_loss` and
