@@ -151,6 +151,40 @@ __device__ __forceinline__ void nap_until(unsigned long long target)
     for (int i = 0; i < 4096 && __builtin_amdgcn_s_memtime() < target; ++i) __builtin_amdgcn_s_sleep(8);
 }
 
+// LDS byte address of 8-byte word i of lds[] (for an instruction written out by hand)
+__device__ __forceinline__ unsigned lds_byte_addr_u64(int i)
+{
+    return (unsigned)(unsigned long)(&((__attribute__((address_space(3))) unsigned long long*)lds)[i]);
+}
+// Spin on ONE tagged 8-byte LDS word {value, tag} until every lane sees `tag` (tags only grow within a launch, so "tag or later" is the
+// test: one 64-bit compare against {0, tag}), at most 4096 looks; `left` = 0 when they ran out.  Written out by hand because it is a
+// hop of the skip workgroups' relay: with the watchdog's bookkeeping inside the loop the compiler's control flow made an iteration
+// five taken branches and a hop 0.24 us -- more than a layer of the stack takes, so the relay never caught up (8.62 instead of
+// 8.03 us per step, docs/history.md).  The whole wave must be active (s_cmp_eq_u64 vcc, exec).
+__device__ __forceinline__ unsigned long long lds_spin_tag(unsigned byte_addr, unsigned tag, unsigned& left)
+{
+    unsigned long long q;
+    unsigned n;
+    const unsigned long long need = (unsigned long long)tag << 32;
+    asm volatile(
+        "s_movk_i32 %1, 0x1000\n"
+        "1:\n"
+        "ds_read_b64 %0, %2\n"
+        "s_waitcnt lgkmcnt(0)\n"
+        "v_cmp_le_u64 vcc, %3, %0\n"
+        "s_cmp_eq_u64 vcc, exec\n"
+        "s_cbranch_scc1 2f\n"
+        "s_sub_u32 %1, %1, 1\n"
+        "s_cmp_lg_u32 %1, 0\n"
+        "s_cbranch_scc1 1b\n"
+        "2:"
+        : "=&v"(q), "=&s"(n)
+        : "v"(byte_addr), "s"(need)
+        : "vcc", "scc", "memory");
+    left = n;
+    return q;
+}
+
 // chain lane that holds z[k] / x[j] in the granule arrays (twv_dpp.hpp layouts)
 __device__ __forceinline__ int lane_of_z(int k) { return ((k & 2) ? 16 : 0) + 2 * (k >> 2) + (k & 1); }
 __device__ __forceinline__ int lane_of_x(int j) { return j < 16 ? j : 16 + j; }
@@ -878,7 +912,8 @@ __device__ __forceinline__ void service_role(const XArgs& xa, int b, rsrc_t rs)
 
 // =====================================================================================================================
 //  SKIP workgroup g: model.py:94-96 skip 1x1 of every layer for output block g, model.py:154 sum over the layers in layer
-//  order, model.py:157 relu.  Wave v owns layers v, v+8, ...; the wave that owns the last layer adds the values up as they appear.
+//  order, model.py:157 relu.  Wave v owns layers v, v+8, ...; the running sum is handed from the owner of layer l-1 to the owner of
+//  layer l through a tagged LDS word (a relay, as in skip_many_role); the owner of the last served layer publishes it.
 // =====================================================================================================================
 // BIG (more than 32 layers; hparams.py's default has 50): a wave holds FIVE tiles in registers -- the layers NLDS + v + 8i, the late
 // ones, whose values are needed soonest after they appear -- and the tiles of the first NLDS = NL - 40 layers (v, v + 8) sit in LDS
@@ -925,38 +960,36 @@ __device__ __forceinline__ void skip_role(const XArgs& xa, const XStreams<NS>& s
             if (use_bias) bs[j] = a.P[lb + LayerOff::SK + (long long)L.NSJ * kTile + g * 64 + lane];
         }
     }
-    // the wave that owns the last layer adds a stream's values up.  With three or four streams per XCD that wave was the busiest of the
-    // kernel (it set the step time at B = 32), so the streams from the third on are summed by a SECOND wave, the owner of layer NL-2,
-    // which keeps a copy of the last layer's tile for them.
-    constexpr bool SPLIT = NS >= 3 && !BIG;
-    // (Round 6, measured dead end: a DEDICATED summing wave -- every wave only fills the LDS slots, the wave whose own layers end first
-    // spins on them in layer order and publishes -- was 0.75-0.88 us from the last layer's z to the published sum against 0.64 us for the
-    // owner of the last layer summing between its polls: 9.0-9.1 instead of 8.5 us per step at batch 8.)
-    const int vA = (NL - 1 - NLDS) & 7, vB = (SPLIT && NL >= 2) ? ((NL - 2) & 7) : -1;
-    const bool sumA = v == vA, sumB = v == vB, anysum = sumA || sumB;
-    Tile wx;                                                      // wave B: the last layer's tile
-    float bx = 0.0f;
-    if (SPLIT && sumB) {
-        const long long lb = L.off_layer0 + (long long)(NL - 1) * L.layer_stride;
-        load_tile(wx, a.P + lb + LayerOff::SK + (long long)g * kTile, lane);
-        if (use_bias) bx = a.P[lb + LayerOff::SK + (long long)L.NSJ * kTile + g * 64 + lane];
-    }
+    // model.py:154 sum(outputs), in layer order, as a RELAY through the waves (the scheme of skip_many_role): LDS slot l of a stream holds
+    // the running total of layers 0 .. l, written by the owner of layer l.  The owner of layer l takes slot l-1, adds its value and
+    // writes slot l; the owner of the last served layer publishes instead.  One add per wave, layer and stream; the same adds in the
+    // same order as a single summing wave: the same bits.
+    // No deadlock: a wave walks its (layer, stream) pairs in ascending order and waits only on the total of (l-1, k), which is earlier in
+    // that order for its owner too, so by induction over (layer, stream) every wait ends (z itself comes from the chain, which does not
+    // depend on this role within a step).  No overwrite: slot l of step t is read before step t's sum is published (every later total
+    // is built on it), and z_l of step t+1 -- hence the next write of slot l -- does not exist until that sum has been published and
+    // the sample drawn from it.  Tags are step + 1 and the slots start at zero in every launch.
+    // What a hop may cost: the chain's first five waves store their z granules five layers at a time, behind their hand-off, so the
+    // totals of five layers are wanted at once and the relay runs behind after every such burst; it catches up only if a hop (LDS
+    // write -> the next wave's look -> add -> LDS write) is well under the 0.2 us a layer of the stack takes.  Measured per-layer stamps:
+    // 0.24 us per hop with the waiting loop the compiler made of a poll_tick loop (8.62 instead of 8.03 us per step), hence lds_spin_tag.
+    // (Before, the owner of the last layer collected the other waves' VALUES from LDS in layer order between its polls and after its
+    // dot: 0.31 us from the second-to-last layer's z to the published sum, of which the dot is 0.07.  A DEDICATED summing wave had
+    // measured 0.75-0.88 us.  docs/history.md.)
     const int n16 = lane & 15;
     const int zc_lane = lane_of_z((lane < 32 ? 0 : 16) + n16);
-    unsigned long long seen[kSlots + 1], period = 0;              // arrival times of the own layers (first stream served) in the previous step
+    unsigned long long seen[kSlots], period = 0;                  // arrival times of the own layers (first stream served) in the previous step
 #pragma unroll
-    for (int i = 0; i < kSlots + 1; ++i) seen[i] = 0;
+    for (int i = 0; i < kSlots; ++i) seen[i] = 0;
     for (int t = 0; t < T && !pl.dead; ++t) {
         asm volatile(".p2align 6");                        // (XALIGN, see chain_many_role)
         const unsigned tag = (unsigned)t + 1u;
-        int nextl[NS];
-        float tot[NS];
-#pragma unroll
-        for (int k = 0; k < NS; ++k) { nextl[k] = 0; tot[k] = 0.0f; }
         // one own layer: `dot` multiplies by a register tile or (BIG, early layers) by a tile in LDS
-        auto own_layer = [&](auto&& dot, const float bias, const int l, const int si, const int k0, const int k1) __attribute__((always_inline)) {
+        auto own_layer = [&](auto&& dot, const float bias, const int l, const int si) __attribute__((always_inline)) {
             {
-                if (!anysum && period) nap_until(seen[si] + period - (period >> 3));
+                if (period) nap_until(seen[si] + period - (period >> 3));
+                const bool last = l == NL - 1;                            // the only layer of this role on the sample path
+                const int lp = l > 0 ? l - 1 : 0;
                 // the XCD's streams in a fixed order (they settle a fraction of a microsecond apart).  Measured alternatives: polling all
                 // the streams still missing in one round and serving whichever arrived (every extra load of a polling round adds to
                 // its round trip: B = 32 ran at 16.5 instead of 13 us/step); requesting the next stream's granules while this stream's
@@ -964,53 +997,25 @@ __device__ __forceinline__ void skip_role(const XArgs& xa, const XStreams<NS>& s
 #pragma unroll
                 for (int k = 0; k < NS; ++k) {
                     if (pl.dead) break;
-                    if (k < k0 || k >= k1) continue;                       // the last layer is served by two waves (see SPLIT)
-                    const bool summer = (SPLIT && vB >= 0) ? (k < 2 ? sumA : sumB) : sumA;     // of stream k
                     const rsrc_t rs = sx.rs[k];
                     const int b = sx.b[k];
                     pl.rs = rs;
-                    // model.py:154 sum(outputs), in layer order: the values of layers nextl .. l-1 come from the other waves through LDS;
-                    // eight slots per LDS round trip (one at a time, the 30 reads of a step cost the wave 1.5 us per stream: with four
-                    // streams per XCD that was the step time); consumed strictly in layer order, up to the first one not yet there.
-                    // Inside the z poll (non-blocking) the wide form lengthens the polling round: measured on one box, one slot per
-                    // round is better up to two streams per XCD (10.47 against 10.67 us/step at B = 8), eight from three on (11.96
-                    // against 13.5 us/step at B = 32)
-                    constexpr int kNb = NS >= 3 ? 8 : 1;
-                    auto drain = [&](bool blocking) __attribute__((always_inline)) {
-                        pl.it = 0;
-                        while (nextl[k] < l && !pl.dead) {
-                            const int base = nextl[k];
-                            unsigned long long q[8];
-#pragma unroll
-                            for (int j = 0; j < 8; ++j)
-                                if (blocking || j < kNb) q[j] = LDSU64(k * SW + (base + j < NL ? base + j : NL - 1) * 64 + lane);
-                            bool go = true;
-#pragma unroll
-                            for (int j = 0; j < 8; ++j) {
-                                if (!blocking && j >= kNb) break;
-                                go = go && (base + j < l) && __all(g_tag(q[j]) == tag);
-                                if (go) { tot[k] = (base + j == 0) ? g_val(q[j]) : tot[k] + g_val(q[j]); nextl[k] = base + j + 1; }
-                            }
-                            if (nextl[k] == base) {
-                                if (!blocking) return;
-                                if (!poll_tick(pl, 52)) return;
-                            }
-                        }
-                    };
                     XMARK(ROLE_SKIP0 + g, 10 + si);
                     // ONE load per round (every load of a polling round adds to its round trip): lanes 0-31 fetch z[0..15] twice, lanes
-                    // 32-63 z[16..31] twice; v_permlane32_swap makes the two dot operands of it
-                    unsigned long long qz;
+                    // 32-63 z[16..31] twice; v_permlane32_swap makes the two dot operands of it.  While it is in flight: one look at the
+                    // running total of the layers below (a total that has arrived stays until this layer's z of the NEXT step exists, so
+                    // the look of the last round is the one that counts)
+                    unsigned long long qz, qp = 0;
                     pl.it = 0;
                     // (Round 6, measured dead end: keeping three polls in flight here and two rounds in the conv1 workgroups' poll -- a new load
                     // issued whenever the oldest comes back unsuccessful -- to sample the L2 more often than once per round trip: 8.59 against
                     // 8.52 us per step at batch 8.  Polling loads do not pipeline: the extra loads lengthen every round trip.)
                     for (;;) {
                         qz = xb_load(rs, (int)XcdExch::ZX + l * 128, zc_lane * 2);
-                        if (summer) drain(false);                          // while the load is in flight: add what has arrived
+                        qp = LDSU64(k * SW + lp * 64 + lane);
                         if (__all(g_tag(qz) == tag)) break;
                         if (!poll_tick(pl, 51)) break;
-                        if (!summer) __builtin_amdgcn_s_sleep(1);
+                        if (!last) __builtin_amdgcn_s_sleep(1);
                     }
                     if ((INSTR & 1) && pl.dead && g == 0 && lane == 0) {   // bring-up: what the abandoned poll last saw
                         xb_store(rs, (int)XcdExch::MARK + 176 + v * 4, 0, g_tag(qz), __uint_as_float(g_tag(qz)));
@@ -1018,26 +1023,40 @@ __device__ __forceinline__ void skip_role(const XArgs& xa, const XStreams<NS>& s
                         xb_store(rs, (int)XcdExch::MARK + 178 + v * 4, 0, tag, __uint_as_float((unsigned)si));
                     }
                     // (no exit here on a watchdog abort: see the chain role; the loops end at their heads)
-                    if (!anysum && k == 0) {
-                        const unsigned long long now = __builtin_amdgcn_s_memtime();
-                        if (si == 0) { const unsigned long long d = now - seen[0]; period = (seen[0] != 0 && d < (1ull << 18)) ? d : 0; }
-                        seen[si] = now;
-                    }
-                    XSTAMP(g == 0 && summer && l == NL - 1, 20);
+                    XSTAMP(g == 0 && last, 20);
                     const auto sw = __builtin_amdgcn_permlane32_swap((unsigned)qz, (unsigned)qz, false, false);   // [lo, lo], [hi, hi]
                     float val = dot(__uint_as_float(sw[0]), __uint_as_float(sw[1]));                             // model.py:96
                     if (use_bias) val = val + bias;
-                    if (!summer) {
-                        LDSU64(k * SW + l * 64 + lane) = ((unsigned long long)tag << 32) | (unsigned long long)__float_as_uint(val);
-                    } else {
-                        drain(true);                                       // whatever is still missing below this layer
-                        tot[k] = (l == 0) ? val : tot[k] + val;
-                        nextl[k] = l + 1;
-                        if (l == NL - 1 && !pl.dead) {                     // this stream's sum is complete: out it goes before the next stream's turn
-                            const float h = (KF > 0 || tot[k] > 0.0f) ? tot[k] : 0.0f;           // model.py:157 (KF: the sum is not complete yet)
-                            xb_store(rs, (int)XcdExch::H1 + g * 64, lane, tag, h);
-                            XSTAMP(g == 0, 21);
+                    float tot = val;
+                    if (l > 0) {
+                        asm volatile("" : "+v"(val));                      // (the dot's last adds stay in front of the wait)
+                        if (!__all(g_tag(qp) == tag)) {
+                            // the total below is not there yet: this wait is a HOP OF THE RELAY, so it spins on the slot and on nothing
+                            // else (lds_spin_tag); the watchdog takes over after 4096 looks
+                            unsigned left;
+                            qp = lds_spin_tag(lds_byte_addr_u64(k * SW + lp * 64 + lane), tag, left);
+                            if (left == 0) {
+                                pl.it = 0;
+                                while (!__all(g_tag(qp) == tag)) {
+                                    if (!poll_tick(pl, 52)) break;
+                                    qp = LDSU64(k * SW + lp * 64 + lane);
+                                }
+                            }
                         }
+                        tot = g_val(qp) + val;                             // model.py:154, layers 0 .. l
+                    }
+                    if (pl.dead) break;
+                    if (last) {                                            // this stream's sum is complete: out it goes before the next stream's turn
+                        const float h = (KF > 0 || tot > 0.0f) ? tot : 0.0f;                     // model.py:157 (KF: the sum is not complete yet)
+                        xb_store(rs, (int)XcdExch::H1 + g * 64, lane, tag, h);
+                        XSTAMP(g == 0, 21);
+                    } else {
+                        LDSU64(k * SW + l * 64 + lane) = ((unsigned long long)tag << 32) | (unsigned long long)__float_as_uint(tot);
+                    }
+                    if (k == 0) {                                          // the wave's clock for its naps: read behind the hand-off, off the relay's path
+                        const unsigned long long now = __builtin_amdgcn_s_memtime();
+                        if (si == 0) { const unsigned long long d = now - seen[0]; period = (seen[0] != 0 && d < (1ull << 18)) ? d : 0; }
+                        seen[si] = now;
                     }
                 }
             }
@@ -1045,18 +1064,13 @@ __device__ __forceinline__ void skip_role(const XArgs& xa, const XStreams<NS>& s
 #pragma unroll
         for (int j = 0; j < kLds; ++j) {
             if (j < nlds && !pl.dead)
-                own_layer([&](float xa_, float xb_) __attribute__((always_inline)) { return dot32_dpp_lds(o_tile4 + (v + 8 * j) * (kTile / 4), lane, xa_, xb_); }, bs[j], v + 8 * j, j, 0, NS);
+                own_layer([&](float xa_, float xb_) __attribute__((always_inline)) { return dot32_dpp_lds(o_tile4 + (v + 8 * j) * (kTile / 4), lane, xa_, xb_); }, bs[j], v + 8 * j, j);
         }
 #pragma unroll
         for (int i = 0; i < kReg; ++i) {
-            if (i < nown && !pl.dead) {
-                const int l = NLDS + v + 8 * i;
-                own_layer([&](float xa_, float xb_) __attribute__((always_inline)) { return dot32_dpp(ws[i].w, xa_, xb_); }, bs[kLds + i], l, kLds + i, 0,
-                          (SPLIT && vB >= 0 && l == NL - 1) ? 2 : NS);
-            }
+            if (i < nown && !pl.dead)
+                own_layer([&](float xa_, float xb_) __attribute__((always_inline)) { return dot32_dpp(ws[i].w, xa_, xb_); }, bs[kLds + i], NLDS + v + 8 * i, kLds + i);
         }
-        if (SPLIT && sumB && !pl.dead)
-            own_layer([&](float xa_, float xb_) __attribute__((always_inline)) { return dot32_dpp(wx.w, xa_, xb_); }, bx, NL - 1, kSlots, 2, NS);
     }
     if (pl.dead && lane == 0) {
 #pragma unroll
