@@ -167,6 +167,8 @@ int twv_wavenet_status(const int32_t* status, void* stream);
  * the generic kernel), "workers" =
  * worker waves per stream workgroup (4 | 3), "helpers" = 1 (default: conv1d_1 and conv1d_2's chunk partials run in one helper
  * workgroup per stream slice when twice the workgroups are co-resident) | 2 (conv1d_1 only) | 0 (none).
+ * "spin_looks" = 1 .. 65535 (default 4096): looks a wait on the XCD kernel's sample-to-sample path takes as a bare spin before its
+ * watchdog loop takes over; 1 sends every wait through the watchdog loop after one look (a test aid: same results, slower).
  * On a wide model ((R, D) != (32, 32)) all of these are accepted and have no effect: wn_wide_generate_kernel has one geometry. */
 int twv_wavenet_set_option(twv_wavenet* h, const char* name, int value);
 

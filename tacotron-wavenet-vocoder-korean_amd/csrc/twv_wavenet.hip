@@ -1298,6 +1298,7 @@ struct twv_wavenet {
                    // 2 = conv1d_1 only, 0 = never
     int xcd;       // 1 (default) = the XCD-per-stream kernel (twv_wavenet_xcd.hip) whenever model, batch and device qualify; 0 = never
     int xcd_many;  // 0 = the library chooses (the many-streams form from batch 21 on), 1 = the many-streams form at every batch, 2 = never below batch 33
+    int spin_looks; // XCD kernels: bare looks of a sample-path wait before its watchdog loop takes over (twv_wavenet_xcd.hip: lds_spin_tag / xb_spin_tag)
     unsigned long long* prof;
     int prof_steps;
     int wide;      // (R, D) != (32, 32): every generation call goes to wn_wide_generate_kernel (twv_wavenet_wide.hip); the launch-geometry
@@ -1455,6 +1456,7 @@ extern "C" int twv_wavenet_create(const twv_wavenet_dims* dims, twv_wavenet** ou
     h->groups = 0;
     h->xcd = 1;
     h->xcd_many = 0;
+    h->spin_looks = kXcdSpinLooks;
     h->prof = nullptr; h->prof_steps = 0;
     const int rc = build_layout(*dims, h);
     if (rc != TWV_OK) { delete h; return rc; }
@@ -1523,6 +1525,11 @@ extern "C" int twv_wavenet_set_option(twv_wavenet* h, const char* name, int valu
                                      // kernel at every batch, 2: the batch <= 32 kernel wherever it can run (tests, A/B)
         if (value < 0 || value > 2) return fail(TWV_E_INVALID, "xcd_many must be 0, 1 or 2");
         h->xcd_many = value;
+        return TWV_OK;
+    }
+    if (!strcmp(name, "spin_looks")) {   // 1: every wait of the sample path takes one bare look and then its watchdog loop (tests: the hand-over on every wait)
+        if (value < 1 || value > 65535) return fail(TWV_E_INVALID, "spin_looks must be 1 .. 65535");
+        h->spin_looks = value;
         return TWV_OK;
     }
     if (!strcmp(name, "groups")) {   // workgroups per stream; set BEFORE sizing / resetting the state buffer
@@ -1789,7 +1796,7 @@ static int generate_impl(const twv_wavenet* h, const void* packed, void* state, 
         x.uniforms = (const float*)uniforms; x.temperature = (float)temperature; x.out = (float*)out; x.status = status; x.dbg = debug; x.dbg_steps = a.dbg_steps;
         x.prof = a.prof; x.prof_steps = a.prof_steps;
         { const char* e = getenv("TWV_XCD_PROF_STREAM"); x.prof_stream = e ? atoi(e) : 0; if (x.prof_stream < 0 || x.prof_stream >= batch) x.prof_stream = 0; }
-        x.B = batch; x.T = n_steps; x.lay = L; x.many = h->xcd_many;
+        x.B = batch; x.T = n_steps; x.lay = L; x.many = h->xcd_many; x.spin_looks = h->spin_looks;
         unsigned char* xb = reinterpret_cast<unsigned char*>((float*)state + (size_t)L.state_stride * (size_t)batch) + (size_t)batch * 2 * L.S * 8;
         HIPCHK(hipMemsetAsync(xb, 0, xcd_exchange_bytes(batch), st));
         x.exch = reinterpret_cast<unsigned long long*>(xb);

@@ -156,31 +156,124 @@ __device__ __forceinline__ unsigned lds_byte_addr_u64(int i)
 {
     return (unsigned)(unsigned long)(&((__attribute__((address_space(3))) unsigned long long*)lds)[i]);
 }
-// Spin on ONE tagged 8-byte LDS word {value, tag} until every lane sees `tag` (tags only grow within a launch, so "tag or later" is the
-// test: one 64-bit compare against {0, tag}), at most 4096 looks; `left` = 0 when they ran out.  Written out by hand because it is a
-// hop of the skip workgroups' relay: with the watchdog's bookkeeping inside the loop the compiler's control flow made an iteration
-// five taken branches and a hop 0.24 us -- more than a layer of the stack takes, so the relay never caught up (8.62 instead of
-// 8.03 us per step, docs/history.md).  The whole wave must be active (s_cmp_eq_u64 vcc, exec).
-__device__ __forceinline__ unsigned long long lds_spin_tag(unsigned byte_addr, unsigned tag, unsigned& left)
+__device__ __forceinline__ unsigned lds_byte_addr_u32(int i)
+{
+    return (unsigned)(unsigned long)(&((__attribute__((address_space(3))) unsigned*)lds)[i]);
+}
+// THE WAIT OF THE SAMPLE PATH, written out by hand: spin on ONE tagged 8-byte word {value, tag} per lane until every lane sees `tag`, at
+// most `looks` looks (option "spin_looks", 4096 unless set); `left` = 0 when they ran out -- the caller then falls into its poll_tick
+// loop, so the watchdog (abort word, 2^TWV_WATCHDOG_LOG2 bound, status code) sits BEHIND the spin and every wait still ends.
+// Inside the spin: the load, its s_waitcnt, the compare, s_cmp_eq_u64 vcc, exec (the whole wave must be active), the exit branch and
+// the look counter.  A success leaves through ONE short forward branch.  Why by hand: with the watchdog's bookkeeping inside the loop
+// the compiler's control flow makes a failed look ~20 instructions with the exit flags threaded through as scalar moves, and a
+// success leaves through two or three taken branches; as a hop of the skip workgroups' relay that loop took
+// 0.24 us per hop, more than a layer of the stack takes (8.62 instead of 8.03 us per step, docs/history.md).
+//   SPIN_GE: "tag or later", one 64-bit compare against {0, tag} -- only for words that start at zero in every launch and whose tags
+//            only grow (the skip relay's totals);
+//   SPIN_EQ: the tag itself: {value, tag} >> 32 against {tag, 0} (a 64-bit shift in front of the compare: an inline-asm operand has no
+//            name for the upper half of a register pair).
+// Two forms: an LDS word (ds_read_b64) and an exchange granule (the load of xb_load: same descriptor, offsets and sc0 sc1, the
+// descriptor in scalar registers), plus the LDS form over a 32-bit counter (>=).
+enum { SPIN_EQ = 0, SPIN_GE = 1 };
+#define TWV_SPIN_TAIL                 \
+    "s_cmp_eq_u64 vcc, exec\n"        \
+    "s_cbranch_scc1 2f\n"             \
+    "s_sub_u32 %1, %1, 1\n"           \
+    "s_cmp_lg_u32 %1, 0\n"            \
+    "s_cbranch_scc1 1b\n"             \
+    "2:"
+template <int CMP>
+__device__ __forceinline__ unsigned long long lds_spin_tag(unsigned byte_addr, unsigned tag, unsigned looks, unsigned& left)
 {
     unsigned long long q;
     unsigned n;
-    const unsigned long long need = (unsigned long long)tag << 32;
+    if (CMP == SPIN_GE) {
+        const unsigned long long need = (unsigned long long)tag << 32;
+        asm volatile(
+            "s_mov_b32 %1, %4\n"
+            "1:\n"
+            "ds_read_b64 %0, %2\n"
+            "s_waitcnt lgkmcnt(0)\n"
+            "v_cmp_le_u64 vcc, %3, %0\n"
+            TWV_SPIN_TAIL
+            : "=&v"(q), "=&s"(n)
+            : "v"(byte_addr), "s"(need), "s"(looks)
+            : "vcc", "scc", "memory");
+    } else {
+        unsigned long long d;
+        const unsigned long long want = (unsigned long long)tag;
+        asm volatile(
+            "s_mov_b32 %1, %5\n"
+            "1:\n"
+            "ds_read_b64 %0, %3\n"
+            "s_waitcnt lgkmcnt(0)\n"
+            "v_lshrrev_b64 %2, 32, %0\n"
+            "v_cmp_eq_u64 vcc, %4, %2\n"
+            TWV_SPIN_TAIL
+            : "=&v"(q), "=&s"(n), "=&v"(d)
+            : "v"(byte_addr), "s"(want), "s"(looks)
+            : "vcc", "scc", "memory");
+    }
+    left = n;
+    return q;
+}
+// the same over the 32-bit LDS word at `byte_addr` (an arrival counter): until it is `need` or more
+__device__ __forceinline__ void lds_spin_count(unsigned byte_addr, unsigned need, unsigned looks, unsigned& left)
+{
+    unsigned c, n;
     asm volatile(
-        "s_movk_i32 %1, 0x1000\n"
+        "s_mov_b32 %1, %4\n"
         "1:\n"
-        "ds_read_b64 %0, %2\n"
+        "ds_read_b32 %0, %2\n"
         "s_waitcnt lgkmcnt(0)\n"
-        "v_cmp_le_u64 vcc, %3, %0\n"
-        "s_cmp_eq_u64 vcc, exec\n"
-        "s_cbranch_scc1 2f\n"
-        "s_sub_u32 %1, %1, 1\n"
-        "s_cmp_lg_u32 %1, 0\n"
-        "s_cbranch_scc1 1b\n"
-        "2:"
-        : "=&v"(q), "=&s"(n)
-        : "v"(byte_addr), "s"(need)
+        "v_cmp_le_u32 vcc, %3, %0\n"
+        TWV_SPIN_TAIL
+        : "=&v"(c), "=&s"(n)
+        : "v"(byte_addr), "s"(need), "s"(looks)
         : "vcc", "scc", "memory");
+    left = n;
+}
+// several tags against one: acc + (got ^ tag) stays zero only while every tag so far was `tag` (tags are step counts: no sum of a few
+// differences wraps to zero), so a polling round over several granules ends in ONE compare.  By hand: written in C the compiler turns
+// (a ^ t) | (b ^ t) == 0 back into a compare per tag and a chain of scalar ands.
+__device__ __forceinline__ unsigned tag_diff_acc(unsigned acc, unsigned got, unsigned tag)
+{
+    asm("v_xad_u32 %0, %1, %2, %0" : "+v"(acc) : "v"(got), "s"(tag));
+    return acc;
+}
+// the L2 form: granule (uword + lword) of the stream's exchange area, as xb_load fetches it
+template <int CMP>
+__device__ __forceinline__ unsigned long long xb_spin_tag(rsrc_t rs, int uword, int lword, unsigned tag, unsigned looks, unsigned& left)
+{
+    unsigned long long q;
+    unsigned n;
+    if (CMP == SPIN_GE) {
+        const unsigned long long need = (unsigned long long)tag << 32;
+        asm volatile(
+            "s_mov_b32 %1, %6\n"
+            "1:\n"
+            "buffer_load_dwordx2 %0, %2, %3, %4 offen sc0 sc1\n"
+            "s_waitcnt vmcnt(0)\n"
+            "v_cmp_le_u64 vcc, %5, %0\n"
+            TWV_SPIN_TAIL
+            : "=&v"(q), "=&s"(n)
+            : "v"(lword * 8), "s"(rs), "s"(uword * 8), "s"(need), "s"(looks)
+            : "vcc", "scc", "memory");
+    } else {
+        unsigned long long d;
+        const unsigned long long want = (unsigned long long)tag;
+        asm volatile(
+            "s_mov_b32 %1, %7\n"
+            "1:\n"
+            "buffer_load_dwordx2 %0, %3, %4, %5 offen sc0 sc1\n"
+            "s_waitcnt vmcnt(0)\n"
+            "v_lshrrev_b64 %2, 32, %0\n"
+            "v_cmp_eq_u64 vcc, %6, %2\n"
+            TWV_SPIN_TAIL
+            : "=&v"(q), "=&s"(n), "=&v"(d)
+            : "v"(lword * 8), "s"(rs), "s"(uword * 8), "s"(want), "s"(looks)
+            : "vcc", "scc", "memory");
+    }
     left = n;
     return q;
 }
@@ -304,7 +397,7 @@ constexpr int kConvLdsFloats = 16 * 64 + 64; // LDS floats per stream in a conv1
 // CONT: known at compile time that a later wave continues the stack: the wave may defer its granule stores (DEFER).
 constexpr int kChainLpw = 5;                                  // residual layers per chain wave (160 of a lane's 256 VGPRs hold tap-1 tiles)
 template <int INSTR, bool ALL, bool FORCED, bool SEG1, bool TWOSEG, int NC, bool ONEHOT = false, bool HEAD = false, bool CONT = false>
-__device__ __forceinline__ void chain_role(const XArgs& xa, int b, rsrc_t rs)
+__device__ __forceinline__ void chain_role(const XArgs& xa, int b, rsrc_t rs, const unsigned looks)
 {
     const XcdLaunch& a = xa.p;
     const Layout& L = a.lay;
@@ -424,12 +517,17 @@ __device__ __forceinline__ void chain_role(const XArgs& xa, int b, rsrc_t rs)
         // ---- wave 7, head of the step: new input sample -> causal layer -> wave 0.  On the sample-to-sample path: one fma, three adds.
         if (head) {
             if (forced && t > 0) {
-                pl.it = 0;
-                for (;;) {
-                    const unsigned long long q = two_seg ? xb_load(rs, (int)XcdExch::DONE, lane) : LDSU64(8 * 64 + lane);
-                    if (__all(g_tag(q) == (unsigned)t)) break;             // the tag of step t-1
-                    if (!poll_tick(pl, 35)) break;
-                    __builtin_amdgcn_s_sleep(2);
+                unsigned left = 0;                                         // the tag of step t-1
+                if (two_seg) (void)xb_spin_tag<SPIN_EQ>(rs, (int)XcdExch::DONE, lane, (unsigned)t, looks, left);
+                else (void)lds_spin_tag<SPIN_EQ>(lds_byte_addr_u64(8 * 64 + lane), (unsigned)t, looks, left);
+                if (__builtin_expect(left == 0, 0)) {
+                    pl.it = 0;
+                    for (;;) {
+                        const unsigned long long q = two_seg ? xb_load(rs, (int)XcdExch::DONE, lane) : LDSU64(8 * 64 + lane);
+                        if (__all(g_tag(q) == (unsigned)t)) break;
+                        if (!poll_tick(pl, 35)) break;
+                        __builtin_amdgcn_s_sleep(2);
+                    }
                 }
                 if (pl.dead) break;
             }
@@ -503,19 +601,28 @@ __device__ __forceinline__ void chain_role(const XArgs& xa, int b, rsrc_t rs)
                 const f32x4 v = LDS4((O_WH >> 2) + (w * 4 + k) * 64 + lane);
                 w0lo[4 * k] = v.x; w0lo[4 * k + 1] = v.y; w0lo[4 * k + 2] = v.z; w0lo[4 * k + 3] = v.w;
             }
+            // the bare spin (lds_spin_tag / xb_spin_tag); the watchdog's loop only after spin_looks looks
             unsigned long long q;
-            pl.it = 0;
-            if (SEG1 && w == 0) {
-                for (;;) {                                               // from wave 5 of the first chain workgroup: one L2 hop
-                    q = xb_load(rs, (int)XcdExch::SEG, lane);
-                    if (__all(g_tag(q) == tag)) break;
-                    if (!poll_tick(pl, 36)) break;
+            unsigned left = 0;
+            if (SEG1 && w == 0) {                                        // from wave 5 of the first chain workgroup: one L2 hop
+                q = xb_spin_tag<SPIN_EQ>(rs, (int)XcdExch::SEG, lane, tag, looks, left);
+                if (__builtin_expect(left == 0, 0)) {
+                    pl.it = 0;
+                    for (;;) {
+                        q = xb_load(rs, (int)XcdExch::SEG, lane);
+                        if (__all(g_tag(q) == tag)) break;
+                        if (!poll_tick(pl, 36)) break;
+                    }
                 }
             } else {
-                for (;;) {
-                    q = LDSU64(w * 64 + lane);
-                    if (__all(g_tag(q) == tag)) break;
-                    if (!poll_tick(pl, 33)) break;
+                q = lds_spin_tag<SPIN_EQ>(lds_byte_addr_u64(w * 64 + lane), tag, looks, left);
+                if (__builtin_expect(left == 0, 0)) {
+                    pl.it = 0;
+                    for (;;) {
+                        q = LDSU64(w * 64 + lane);
+                        if (__all(g_tag(q) == tag)) break;
+                        if (!poll_tick(pl, 33)) break;
+                    }
                 }
             }
             // (a watchdog abort ends the loop at its head: an exit here would make the compiler thread state flags through the hand-off path)
@@ -533,6 +640,8 @@ __device__ __forceinline__ void chain_role(const XArgs& xa, int b, rsrc_t rs)
         // waves that a later wave follows (CONT: waves 0..4 of a 30-layer stack) keep {z, input} in registers and store their granules
         // behind the hand-off to the next wave, off the sample-to-sample path.  The wave with the stack's last layers stores at once.
         constexpr bool DEFER = ALL && !FORCED && !SEG1 && NC > 0 && CONT;
+        // (Measured and dropped: the stack's last full wave storing {z, tag} alone inside the layer, 8 bytes, and its five {layer input,
+        // tag} halves behind the last layer: 7.702-7.707 us per step with it against 7.701-7.705 without, docs/history.md.)
         float zs[kChainLpw] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, xs[kChainLpw] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
         auto run_layers = [&](auto nc) {
             constexpr int N = decltype(nc)::value;
@@ -606,7 +715,7 @@ __device__ __forceinline__ void chain_role(const XArgs& xa, int b, rsrc_t rs)
             for (;;) {
                 d0 = xb_load2(rs, (int)XcdExch::QL, lane * 2);
                 d1 = xb_load2(rs, (int)XcdExch::QL, lane * 2 + 1);
-                if (__all(d0.y == tag && d0.w == tag && d1.y == tag && d1.w == tag)) break;
+                if (__all(tag_diff_acc(tag_diff_acc(tag_diff_acc(tag_diff_acc(0u, d0.y, tag), d0.w, tag), d1.y, tag), d1.w, tag) == 0u)) break;       // one compare for the four tags
                 if (!poll_tick(pl, 34)) break;
             }
             now_tab = __builtin_amdgcn_s_memtime();
@@ -640,15 +749,15 @@ __device__ __forceinline__ void chain_role(const XArgs& xa, int b, rsrc_t rs)
             unsigned long long q[8];
             pl.it = 0;
             for (;;) {
-                bool good = true;
+                unsigned diff = 0;                                     // the eight tags against `tag`: ONE compare decides the round
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     const u32x4s d = xb_load2(rs, (int)XcdExch::PT, (half * 4 + k) * 32 + (lane & 31));
                     q[2 * k] = ((unsigned long long)d.y << 32) | d.x;
                     q[2 * k + 1] = ((unsigned long long)d.w << 32) | d.z;
-                    good = good && d.y == tag && d.w == tag;
+                    diff = tag_diff_acc(tag_diff_acc(diff, d.y, tag), d.w, tag);
                 }
-                if (__all(good)) break;
+                if (__all(diff == 0u)) break;
                 if (!poll_tick(pl, 34)) break;
             }
             // (a watchdog abort ends the loop at its head: an exit here would make the compiler thread state flags through the hand-off path)
@@ -922,7 +1031,7 @@ __device__ __forceinline__ void service_role(const XArgs& xa, int b, rsrc_t rs)
 // those layers straight from the chain: the skip -> conv1 hop then only carries the running sum of the layers in front of them -- raw,
 // the relu follows the last add over there -- and leaves the path behind the last layer.
 template <int INSTR, int NS, bool BIG, int KF = 0>
-__device__ __forceinline__ void skip_role(const XArgs& xa, const XStreams<NS>& sx, int g)
+__device__ __forceinline__ void skip_role(const XArgs& xa, const XStreams<NS>& sx, int g, const unsigned looks)
 {
     const XcdLaunch& a = xa.p;
     const Layout& L = a.lay;
@@ -1010,12 +1119,27 @@ __device__ __forceinline__ void skip_role(const XArgs& xa, const XStreams<NS>& s
                     // (Round 6, measured dead end: keeping three polls in flight here and two rounds in the conv1 workgroups' poll -- a new load
                     // issued whenever the oldest comes back unsuccessful -- to sample the L2 more often than once per round trip: 8.59 against
                     // 8.52 us per step at batch 8.  Polling loads do not pipeline: the extra loads lengthen every round trip.)
+                    if (last) {
+                        // the last served layer is on the sample path: the bare spin on its z granule; the look at the total below
+                        // follows it and lands under the dot
+                        unsigned left = 0;
+                        qz = xb_spin_tag<SPIN_EQ>(rs, (int)XcdExch::ZX + l * 128, zc_lane * 2, tag, looks, left);
+                        if (__builtin_expect(left == 0, 0)) {
+                            pl.it = 0;
+                            for (;;) {
+                                qz = xb_load(rs, (int)XcdExch::ZX + l * 128, zc_lane * 2);
+                                if (__all(g_tag(qz) == tag)) break;
+                                if (!poll_tick(pl, 51)) break;
+                            }
+                        }
+                        qp = LDSU64(k * SW + lp * 64 + lane);
+                    } else
                     for (;;) {
                         qz = xb_load(rs, (int)XcdExch::ZX + l * 128, zc_lane * 2);
                         qp = LDSU64(k * SW + lp * 64 + lane);
                         if (__all(g_tag(qz) == tag)) break;
                         if (!poll_tick(pl, 51)) break;
-                        if (!last) __builtin_amdgcn_s_sleep(1);
+                        __builtin_amdgcn_s_sleep(1);
                     }
                     if ((INSTR & 1) && pl.dead && g == 0 && lane == 0) {   // bring-up: what the abandoned poll last saw
                         xb_store(rs, (int)XcdExch::MARK + 176 + v * 4, 0, g_tag(qz), __uint_as_float(g_tag(qz)));
@@ -1032,9 +1156,9 @@ __device__ __forceinline__ void skip_role(const XArgs& xa, const XStreams<NS>& s
                         asm volatile("" : "+v"(val));                      // (the dot's last adds stay in front of the wait)
                         if (!__all(g_tag(qp) == tag)) {
                             // the total below is not there yet: this wait is a HOP OF THE RELAY, so it spins on the slot and on nothing
-                            // else (lds_spin_tag); the watchdog takes over after 4096 looks
-                            unsigned left;
-                            qp = lds_spin_tag(lds_byte_addr_u64(k * SW + lp * 64 + lane), tag, left);
+                            // else (lds_spin_tag); the watchdog takes over after spin_looks looks
+                            unsigned left = 0;
+                            qp = lds_spin_tag<SPIN_GE>(lds_byte_addr_u64(k * SW + lp * 64 + lane), tag, looks, left);
                             if (left == 0) {
                                 pl.it = 0;
                                 while (!__all(g_tag(qp) == tag)) {
@@ -1088,27 +1212,40 @@ __device__ __forceinline__ void skip_role(const XArgs& xa, const XStreams<NS>& s
 // layers) next to the sum, has the last skip value ready when the sum comes in, and finishes the sum in layer order + relu itself.
 template <int KF, bool BAR>
 __device__ __forceinline__ unsigned long long conv1_fetch_h1(Poll& pl, const rsrc_t rs, const int v, const int lane, const unsigned tag, const int last_layer,
-                                                             const int zc_lane, const float (&wl)[32], const float bl, const bool use_bias, bool& saw_z)
+                                                             const int zc_lane, const float (&wl)[32], const float bl, const bool use_bias, bool& saw_z, const unsigned looks)
 {
     unsigned long long q;
     pl.it = 0;
     if (KF > 0) {
         unsigned long long qz;
         float val = 0.0f;
-        bool havez = false;
+        // Two phases.  Until z has been seen: a round of two loads (z, and the sum beside it: a load added to a round lengthens it, so
+        // the sum's granule is not asked for more often than this); the dot belongs to the round that sees z.  After that only the sum
+        // is missing and the wait is on the sample path: the bare spin on its granule (xb_spin_tag).
         for (;;) {
-            if (!havez) qz = xb_load_t<BAR>(rs, (int)XcdExch::ZX + last_layer * 128, zc_lane * 2);
+            qz = xb_load_t<BAR>(rs, (int)XcdExch::ZX + last_layer * 128, zc_lane * 2);
             q = xb_load_t<BAR>(rs, (int)XcdExch::H1 + v * 64, lane);
-            if (!havez && __all(g_tag(qz) == tag)) {
+            if (__all(g_tag(qz) == tag)) {
                 const auto sw = __builtin_amdgcn_permlane32_swap((unsigned)qz, (unsigned)qz, false, false);   // [lo, lo], [hi, hi]
                 val = dot32_dpp(wl, __uint_as_float(sw[0]), __uint_as_float(sw[1]));                        // model.py:96
                 if (use_bias) val = val + bl;
-                havez = true;
                 saw_z = true;
+                break;
             }
-            if (havez && __all(g_tag(q) == tag)) break;
             if (!poll_tick<BAR>(pl, 61)) break;
-            if (!havez) __builtin_amdgcn_s_sleep(1);
+            __builtin_amdgcn_s_sleep(1);
+        }
+        if (saw_z && !__all(g_tag(q) == tag)) {
+            unsigned left = 0;
+            q = xb_spin_tag<SPIN_EQ>(rs, (int)XcdExch::H1 + v * 64, lane, tag, looks, left);
+            if (__builtin_expect(left == 0, 0)) {
+                pl.it = 0;
+                for (;;) {
+                    q = xb_load_t<BAR>(rs, (int)XcdExch::H1 + v * 64, lane);
+                    if (__all(g_tag(q) == tag)) break;
+                    if (!poll_tick<BAR>(pl, 61)) break;
+                }
+            }
         }
         const float tot = g_val(q) + val;                                            // model.py:154: the last term of the sum
         const float h = tot > 0.0f ? tot : 0.0f;                                     // model.py:157
@@ -1155,7 +1292,7 @@ __device__ __forceinline__ float conv1d2_chunk_dpp(const float (&t2)[16], const 
 // KF: see conv1_fetch_h1.  The last layer's z -> skip workgroup -> dot / sum / publish -> conv1 path (0.31 + 0.33 + 0.25 us behind the last
 // layer) becomes z -> conv1 (0.31 us) in parallel with the second-to-last layer's trip through the skip workgroup.
 template <int INSTR, int NS, bool BAR = false, class SX = XStreams<NS>, int KF = 0>
-__device__ __forceinline__ void conv1_role(const XArgs& xa, const SX& sx, int g, const int ns_rt = NS, const int prof_slot = -1)
+__device__ __forceinline__ void conv1_role(const XArgs& xa, const SX& sx, int g, const int ns_rt, const int prof_slot, const unsigned looks)
 {
     const XcdLaunch& a = xa.p;
     const Layout& L = a.lay;
@@ -1203,7 +1340,7 @@ __device__ __forceinline__ void conv1_role(const XArgs& xa, const SX& sx, int g,
             // this wave's two chunks are exactly the 64 values skip workgroup v publishes: ONE granule per lane
             WACC_T0();
             bool saw_z = false;
-            const unsigned long long q = conv1_fetch_h1<KF, BAR>(pl, rs, v, lane, tag, L.NL - 1, zc_lane, wl.w, bl, use_bias, saw_z);
+            const unsigned long long q = conv1_fetch_h1<KF, BAR>(pl, rs, v, lane, tag, L.NL - 1, zc_lane, wl.w, bl, use_bias, saw_z, looks);
             (void)saw_z;
             WACC_T1(1);
             WTRACE(prof_slot >= 0 && k == 0, 400 + g * 8 + v);
@@ -1231,8 +1368,12 @@ __device__ __forceinline__ void conv1_role(const XArgs& xa, const SX& sx, int g,
             XMARK(ROLE_CONV0 + g, 2);
             if (summer) {
                 WACC_T0();
-                pl.it = 0;
-                while (LDSVI(ob + O_CNT) < 8 * (t + 1)) { if (!poll_tick<BAR>(pl, 62)) break; }
+                unsigned left = 0;
+                if (!BAR) lds_spin_count(lds_byte_addr_u32(ob + O_CNT), 8u * tag, looks, left);      // (the many-streams kernel keeps its loop)
+                if (__builtin_expect(left == 0, 0)) {
+                    pl.it = 0;
+                    while (LDSVI(ob + O_CNT) < 8 * (t + 1)) { if (!poll_tick<BAR>(pl, 62)) break; }
+                }
                 WACC_T1(2);
                 // (no exit here on a watchdog abort: see the chain role; the loops end at their heads)
                 asm volatile("" ::: "memory");
@@ -1272,7 +1413,7 @@ __device__ __forceinline__ void conv1_role(const XArgs& xa, const SX& sx, int g,
 //  ([lo, lo]) and of chunk 2v + 1 ([hi, hi]).  Same fmas, same chains, same order of the chunk sum as conv1_role: same bits.
 // =====================================================================================================================
 template <int INSTR, int KF>
-__device__ __forceinline__ void conv1_half_role(const XArgs& xa, const XStreams<1>& sx, const int g, const int hh)
+__device__ __forceinline__ void conv1_half_role(const XArgs& xa, const XStreams<1>& sx, const int g, const int hh, const unsigned looks)
 {
     static_assert(KF > 0, "the last layer's skip 1x1 runs here");
     const XcdLaunch& a = xa.p;
@@ -1310,7 +1451,7 @@ __device__ __forceinline__ void conv1_half_role(const XArgs& xa, const XStreams<
         if (period) nap_until(t_arr + period - (period >> 3));
         XMARK(ROLE_CONV0 + 2 * g + hh, 1);
         bool saw_z = false;
-        const unsigned long long q = conv1_fetch_h1<KF, false>(pl, rs, v, hl, tag, L.NL - 1, zc_lane, wl.w, bl, use_bias, saw_z);
+        const unsigned long long q = conv1_fetch_h1<KF, false>(pl, rs, v, hl, tag, L.NL - 1, zc_lane, wl.w, bl, use_bias, saw_z, looks);
         (void)saw_z;
         // (no exit here on a watchdog abort: see the chain role; the loops end at their heads)
         const unsigned long long now_arr = __builtin_amdgcn_s_memtime();       // read only: the arithmetic follows the dots (as in the chain)
@@ -1337,8 +1478,12 @@ __device__ __forceinline__ void conv1_half_role(const XArgs& xa, const XStreams<
         XSTAMP(g == 0 && hh == 0 && v == 0, 23);
         XMARK(ROLE_CONV0 + 2 * g + hh, 2);
         if (summer) {
-            pl.it = 0;
-            while (LDSVI(O_CNT) < 8 * (t + 1)) { if (!poll_tick(pl, 62)) break; }
+            unsigned left = 0;
+            lds_spin_count(lds_byte_addr_u32(O_CNT), 8u * tag, looks, left);
+            if (__builtin_expect(left == 0, 0)) {
+                pl.it = 0;
+                while (LDSVI(O_CNT) < 8 * (t + 1)) { if (!poll_tick(pl, 62)) break; }
+            }
             // (no exit here on a watchdog abort: see the chain role; the loops end at their heads)
             asm volatile("" ::: "memory");
             XSTAMP(g == 0 && hh == 0, 24);
@@ -1370,7 +1515,7 @@ __device__ __forceinline__ void conv1_half_role(const XArgs& xa, const XStreams<
 // =====================================================================================================================
 constexpr int kConvQLdsFloats = 16 * 64 + 64 + 8 * 64;   // LDS floats per stream: conv1d_1 chunk partials | two arrival counters | conv1d_2 chunk partials
 template <int INSTR, int NS, int KF = 0>
-__device__ __forceinline__ void conv1_onehot_role(const XArgs& xa, const XStreams<NS>& sx, int g)
+__device__ __forceinline__ void conv1_onehot_role(const XArgs& xa, const XStreams<NS>& sx, int g, const unsigned looks)
 {
     const XcdLaunch& a = xa.p;
     const Layout& L = a.lay;
@@ -1418,7 +1563,7 @@ __device__ __forceinline__ void conv1_onehot_role(const XArgs& xa, const XStream
             pl.rs = rs;
             // ---- model.py:158-160 conv1d_1 + relu for output block g, as in conv1_role
             bool saw_z = false;
-            unsigned long long q = conv1_fetch_h1<KF, false>(pl, rs, v, lane, tag, L.NL - 1, zc_lane, wl.w, bl, use_bias, saw_z);
+            unsigned long long q = conv1_fetch_h1<KF, false>(pl, rs, v, lane, tag, L.NL - 1, zc_lane, wl.w, bl, use_bias, saw_z, looks);
             (void)saw_z;
             unsigned long long now_arr = 0;
             if (k == 0) now_arr = __builtin_amdgcn_s_memtime();
@@ -1442,8 +1587,12 @@ __device__ __forceinline__ void conv1_onehot_role(const XArgs& xa, const XStream
             }
             XSTAMP(g == 0 && v == 0, 23);
             if (v == 0) {
-                pl.it = 0;
-                while (LDSVI(ob + O_CNT) < 8 * (t + 1)) { if (!poll_tick(pl, 62)) break; }
+                unsigned left = 0;
+                lds_spin_count(lds_byte_addr_u32(ob + O_CNT), 8u * tag, looks, left);
+                if (__builtin_expect(left == 0, 0)) {
+                    pl.it = 0;
+                    while (LDSVI(ob + O_CNT) < 8 * (t + 1)) { if (!poll_tick(pl, 62)) break; }
+                }
                 asm volatile("" ::: "memory");
                 XSTAMP(g == 0, 24);
                 float cp[16];
@@ -1459,12 +1608,18 @@ __device__ __forceinline__ void conv1_onehot_role(const XArgs& xa, const XStream
                 XSTAMP(g == 0, 25);
             }
             // ---- model.py:161-165 conv1d_2, classes 32g .. 32g+31: this wave's two chunks read block v of relu(conv1d_1)
-            pl.it = 0;
-            for (;;) {
-                q = xb_load(rs, (int)XcdExch::H2 + v * 64, lane);
-                if (__all(g_tag(q) == tag)) break;
-                if (!poll_tick(pl, 63)) break;
-                __builtin_amdgcn_s_sleep(1);
+            {
+                unsigned left = 0;
+                q = xb_spin_tag<SPIN_EQ>(rs, (int)XcdExch::H2 + v * 64, lane, tag, looks, left);
+                if (__builtin_expect(left == 0, 0)) {
+                    pl.it = 0;
+                    for (;;) {
+                        q = xb_load(rs, (int)XcdExch::H2 + v * 64, lane);
+                        if (__all(g_tag(q) == tag)) break;
+                        if (!poll_tick(pl, 63)) break;
+                        __builtin_amdgcn_s_sleep(1);
+                    }
+                }
             }
             XSTAMP(g == 0 && v == 1, 34);
             {
@@ -1477,8 +1632,12 @@ __device__ __forceinline__ void conv1_onehot_role(const XArgs& xa, const XStream
             if (lane == 0) __hip_atomic_fetch_add(&LDSI(ob + O_CNT + 1), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             XSTAMP(g == 0 && v == 1, 35);
             if (v == 1) {
-                pl.it = 0;
-                while (LDSVI(ob + O_CNT + 1) < 8 * (t + 1)) { if (!poll_tick(pl, 64)) break; }
+                unsigned left = 0;
+                lds_spin_count(lds_byte_addr_u32(ob + O_CNT + 1), 8u * tag, looks, left);
+                if (__builtin_expect(left == 0, 0)) {
+                    pl.it = 0;
+                    while (LDSVI(ob + O_CNT + 1) < 8 * (t + 1)) { if (!poll_tick(pl, 64)) break; }
+                }
                 asm volatile("" ::: "memory");
                 XSTAMP(g == 0, 36);
                 float cp[16];
@@ -1721,7 +1880,7 @@ __device__ __forceinline__ bool roles_resident(const XArgs& xa)
 // configuration ran at 13.3 instead of 10.4 us per step).
 // ONEHOT: the one-hot mu-law model (scalar_input False, 256 classes): its own kernel instantiations, the MoL kernels carry none of it.
 template <int INSTR, bool BIGK, bool ONE, bool ONEHOT = false>
-__global__ void __launch_bounds__(512) wn_xcd_generate_kernel(XArgs xa)
+__global__ void __launch_bounds__(512) wn_xcd_generate_kernel(XArgs xa, const unsigned looks)
 {
     const XcdLaunch& a = xa.p;
     // ---- role ticket of this workgroup's XCD (HIP promises nothing about workgroup -> XCD placement: ask the hardware)
@@ -1760,20 +1919,20 @@ __global__ void __launch_bounds__(512) wn_xcd_generate_kernel(XArgs xa)
                 const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
                 const int nlw = a.lay.NL - kChainLpw * wv;      // layers from this wave's first one on
                 if (wv == 7) {
-                    if (forced) chain_role<INSTR, true, true, false, BIGK, 0, ONEHOT, true>(xa, b, rs);
-                    else chain_role<INSTR, true, false, false, BIGK, 0, ONEHOT, true>(xa, b, rs);
+                    if (forced) chain_role<INSTR, true, true, false, BIGK, 0, ONEHOT, true>(xa, b, rs, looks);
+                    else chain_role<INSTR, true, false, false, BIGK, 0, ONEHOT, true>(xa, b, rs, looks);
                 }
                 else if (wv >= kXcdSeg0Layers / kChainLpw || nlw <= 0) {}
-                else if (forced) chain_role<INSTR, true, true, false, BIGK, -1, ONEHOT>(xa, b, rs);
-                else if (nlw > kChainLpw) chain_role<INSTR, true, false, false, BIGK, kChainLpw, ONEHOT, false, true>(xa, b, rs);
-                else if (nlw == kChainLpw) chain_role<INSTR, true, false, false, BIGK, kChainLpw, ONEHOT, false, false>(xa, b, rs);
-                else chain_role<INSTR, true, false, false, BIGK, -1, ONEHOT>(xa, b, rs);
+                else if (forced) chain_role<INSTR, true, true, false, BIGK, -1, ONEHOT>(xa, b, rs, looks);
+                else if (nlw > kChainLpw) chain_role<INSTR, true, false, false, BIGK, kChainLpw, ONEHOT, false, true>(xa, b, rs, looks);
+                else if (nlw == kChainLpw) chain_role<INSTR, true, false, false, BIGK, kChainLpw, ONEHOT, false, false>(xa, b, rs, looks);
+                else chain_role<INSTR, true, false, false, BIGK, -1, ONEHOT>(xa, b, rs, looks);
             } else if constexpr (BIGK) {
                 // (the second chain workgroup has no head: nothing of it depends on the input / output type)
                 const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-                if (forced) chain_role<INSTR, true, true, true, true, -1>(xa, b, rs);
-                else if (a.lay.NL - kXcdSeg0Layers - kChainLpw * wv >= kChainLpw) chain_role<INSTR, true, false, true, true, kChainLpw>(xa, b, rs);
-                else chain_role<INSTR, true, false, true, true, -1>(xa, b, rs);
+                if (forced) chain_role<INSTR, true, true, true, true, -1>(xa, b, rs, looks);
+                else if (a.lay.NL - kXcdSeg0Layers - kChainLpw * wv >= kChainLpw) chain_role<INSTR, true, false, true, true, kChainLpw>(xa, b, rs, looks);
+                else chain_role<INSTR, true, false, true, true, -1>(xa, b, rs, looks);
             }
         }
         else service_role<INSTR, BIGK>(xa, b, rs);
@@ -1795,8 +1954,8 @@ __global__ void __launch_bounds__(512) wn_xcd_generate_kernel(XArgs xa)
         const bool fold = KF > 0 && (a.lay.NL > KF || !kUnfolded);
         if (role < 8) {
             if (!forced) {
-                if (fold) skip_role<INSTR, NS, BIGK, KF>(xa, sx, role);
-                else if constexpr (kUnfolded) skip_role<INSTR, NS, BIGK, 0>(xa, sx, role);
+                if (fold) skip_role<INSTR, NS, BIGK, KF>(xa, sx, role, looks);
+                else if constexpr (kUnfolded) skip_role<INSTR, NS, BIGK, 0>(xa, sx, role, looks);
             }
         }
         else if (role < 8 + nc1) {
@@ -1804,14 +1963,14 @@ __global__ void __launch_bounds__(512) wn_xcd_generate_kernel(XArgs xa)
                 // sixteen workgroups (output block, output half) where xcd_launch says so: one stream per XCD, MoL, the fold applies
                 constexpr bool kHalf = !ONEHOT && !BIGK && NS == 1 && KF > 0 && (ONE || INSTR != 0);
                 if constexpr (kHalf) {
-                    if (nc1 == 16) { conv1_half_role<INSTR, KF>(xa, sx, (role - 8) >> 1, (role - 8) & 1); return; }
+                    if (nc1 == 16) { conv1_half_role<INSTR, KF>(xa, sx, (role - 8) >> 1, (role - 8) & 1, looks); return; }
                 }
                 if constexpr (ONEHOT) {
-                    if (fold) conv1_onehot_role<INSTR, NS, KF>(xa, sx, role - 8);
-                    else if constexpr (kUnfolded) conv1_onehot_role<INSTR, NS, 0>(xa, sx, role - 8);
+                    if (fold) conv1_onehot_role<INSTR, NS, KF>(xa, sx, role - 8, looks);
+                    else if constexpr (kUnfolded) conv1_onehot_role<INSTR, NS, 0>(xa, sx, role - 8, looks);
                 }
-                else if (fold) conv1_role<INSTR, NS, false, XStreams<NS>, KF>(xa, sx, role - 8);
-                else if constexpr (kUnfolded) conv1_role<INSTR, NS>(xa, sx, role - 8);
+                else if (fold) conv1_role<INSTR, NS, false, XStreams<NS>, KF>(xa, sx, role - 8, NS, -1, looks);
+                else if constexpr (kUnfolded) conv1_role<INSTR, NS>(xa, sx, role - 8, NS, -1, looks);
             }
         }
         else lc_role<INSTR, NS, BIGK>(xa, sx, role - 8 - nc1);
@@ -2734,7 +2893,7 @@ __global__ void __launch_bounds__(512) wn_xcd_many_kernel(XArgs xa)
     if (role < 16) {
         if (!forced) {
             const XStreamsLazy<kManyPerXcd> sx{{&a, (int)xcc, ns}, {(int)xcc, ns}};
-            conv1_role<(INSTR & 4), kManyPerXcd, true, XStreamsLazy<kManyPerXcd>>(xa, sx, role - 8, ns, xcc == 0 ? 16 + role - 8 : -1);
+            conv1_role<(INSTR & 4), kManyPerXcd, true, XStreamsLazy<kManyPerXcd>>(xa, sx, role - 8, ns, xcc == 0 ? 16 + role - 8 : -1, (unsigned)kXcdSpinLooks);
         }
     }
     else lc_many_role<INSTR>(xa, (int)xcc, ns, role - 16, xcc == 0 ? 24 + role - 16 : -1);
@@ -2834,11 +2993,12 @@ int xcd_launch(const XcdLaunch& p, hipStream_t st)
     const int grid = 2 * cus;
     // instrumented builds are separate instantiations: 1 = phase stamps / stage markers, 2 = per-layer dumps
     const int instr = (p.prof != nullptr ? 1 : 0) | (p.dbg != nullptr ? 2 : 0);
-    auto go = [&](auto kern) {
+    const unsigned looks = (unsigned)p.spin_looks;         // its own kernel argument: straight into a scalar register (see XcdLaunch)
+    auto go = [&](auto kern, auto... more) {
         // more than 64 KiB of dynamic LDS: say so (the runtime has accepted the launch without it; the attribute is the documented way)
         (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
         (void)hipGetLastError();
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), shm, st, xa);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), shm, st, xa, more...);
     };
     if (!many && instr != 0 && p.lay.NL <= TWV_XCD_KF)
         return twv_fail(TWV_E_UNSUPPORTED, "layer dumps / phase stamps of the XCD kernel need a model of at least two layers (set option \"xcd\" = 0 for the generic kernel)");
@@ -2855,24 +3015,24 @@ int xcd_launch(const XcdLaunch& p, hipStream_t st)
         if (p.B > (p.lay.NL > kXcdSeg0Layers ? kXcdStreams / 2 : kXcdStreams)) return twv_fail(TWV_E_UNSUPPORTED, "the one-hot XCD kernel takes at most 32 streams (16 above 30 layers)");
         if (instr == 3 || (instr != 0 && p.lay.NL > kXcdSeg0Layers))
             return twv_fail(TWV_E_UNSUPPORTED, "the one-hot XCD kernel has layer dumps OR phase stamps, up to 30 layers (set option \"xcd\" = 0 for the generic kernel)");
-        if (p.lay.NL > kXcdSeg0Layers) go(wn_xcd_generate_kernel<0, true, false, true>);
-        else if (instr == 2) go(wn_xcd_generate_kernel<2, false, false, true>);
-        else if (instr == 1) go(wn_xcd_generate_kernel<1, false, false, true>);
-        else if (p.B <= 8) go(wn_xcd_generate_kernel<0, false, true, true>);
-        else go(wn_xcd_generate_kernel<0, false, false, true>);
+        if (p.lay.NL > kXcdSeg0Layers) go(wn_xcd_generate_kernel<0, true, false, true>, looks);
+        else if (instr == 2) go(wn_xcd_generate_kernel<2, false, false, true>, looks);
+        else if (instr == 1) go(wn_xcd_generate_kernel<1, false, false, true>, looks);
+        else if (p.B <= 8) go(wn_xcd_generate_kernel<0, false, true, true>, looks);
+        else go(wn_xcd_generate_kernel<0, false, false, true>, looks);
     }
     else if (p.lay.NL > kXcdSeg0Layers) {
         if (instr != 0) return twv_fail(TWV_E_UNSUPPORTED, "layer dumps / phase stamps exist for the 30-layer XCD kernel only (set option \"xcd\" = 0 for the generic kernel)");
-        go(wn_xcd_generate_kernel<0, true, false>);
+        go(wn_xcd_generate_kernel<0, true, false>, looks);
     }
-    else if (instr == 3) go(wn_xcd_generate_kernel<3, false, false>);
-    else if (instr == 2) go(wn_xcd_generate_kernel<2, false, false>);
-    else if (instr == 1) go(wn_xcd_generate_kernel<1, false, false>);
+    else if (instr == 3) go(wn_xcd_generate_kernel<3, false, false>, looks);
+    else if (instr == 2) go(wn_xcd_generate_kernel<2, false, false>, looks);
+    else if (instr == 1) go(wn_xcd_generate_kernel<1, false, false>, looks);
     // ONE: batch <= 8 (one stream per XCD) without the multi-stream roles compiled into the kernel: the register allocation of the
     // sampling loop depends on what shares the kernel (measured on one box, interleaved: 10.42 against 10.59 us/step; specialising
     // further -- only the hparams-default sampling chain in the kernel -- gave 10.61 again: it is allocation luck, not a trend)
-    else if (p.B <= 8) go(wn_xcd_generate_kernel<0, false, true>);
-    else go(wn_xcd_generate_kernel<0, false, false>);
+    else if (p.B <= 8) go(wn_xcd_generate_kernel<0, false, true>, looks);
+    else go(wn_xcd_generate_kernel<0, false, false>, looks);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return twv_fail(TWV_E_HIP, std::string("xcd launch: ") + hipGetErrorString(e));
     return TWV_OK;

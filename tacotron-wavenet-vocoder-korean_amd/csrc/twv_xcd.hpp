@@ -15,6 +15,7 @@ constexpr int kXcdLs = 64;             // layer slots of the per-layer exchange 
 constexpr int kXcdStreams = 32;        // up to four streams per XCD (stream b runs on XCD b % 8), each with its own chain workgroup
 constexpr int kXcdManyFrom = 21;       // batch from which the many-streams kernel is the default choice (measured: B = 16 9.25 vs 9.57 us per step, B = 24 9.65 vs 9.54, B = 32 11.0 vs 9.60)
 constexpr int kXcdManyStreams = 96;    // the many-streams kernel (30 layers or fewer): up to twelve per XCD, two per chain workgroup
+constexpr int kXcdSpinLooks = 4096;    // looks a wait of the sample path takes as a bare spin before the watchdog's loop (0.1-0.2 ms: a wait that outlasts them is not on anybody's path)
 constexpr int kXcdLcRing = 16;         // steps of lc projections the lc workgroups may run ahead of the chain
 #ifndef TWV_MANY_LC_RING
 #define TWV_MANY_LC_RING 8
@@ -65,6 +66,10 @@ struct XcdLaunch {
     int prof_stream;               // the stream whose workgroups stamp (0; TWV_XCD_PROF_STREAM picks another one: tuning aid)
     int B, T;
     int many;                      // option "xcd_many": 0 = from batch kXcdManyFrom on, 1 = at every batch, 2 = only above batch 32
+    int spin_looks;                // option "spin_looks": bare looks of a sample-path wait before its watchdog loop takes over (1 .. 65535; kXcdSpinLooks unless set).
+                                   // Host side only: xcd_launch hands it to wn_xcd_generate_kernel as a kernel argument of its own (a scalar register).  READ from
+                                   // this struct inside the kernel, it made the compiler keep the whole argument block on the stack in the largest
+                                   // instantiation (dumps + stamps: 32 -> 704 bytes of scratch per lane, the stamps' pointers reloaded from it)
     unsigned long long* exch;      // [B][XcdExch::WORDS]
     int* roles;                    // [8] role tickets per XCD (zeroed before the launch)
     Layout lay;

@@ -155,7 +155,9 @@ class WaveNetModel(object):
     def set_option(self, name, value):
         """launch-geometry options of the C-ABI (twv_wavenet_set_option).  "xcd" / "xcd_many" / "groups" select the kernel and with it
         the SIZE and layout of the state buffer (the XCD kernels append their exchange area): the queues are re-created, i.e. reset as by
-        queue_initializer (generate.py:163) -- set such options before priming / generating, not between chunks of one utterance."""
+        queue_initializer (generate.py:163) -- set such options before priming / generating, not between chunks of one utterance.
+        "spin_looks" (1 .. 65535, default 4096) changes neither: the bare looks a wait of the XCD kernel's sample path takes before its
+        watchdog loop takes over (1: every wait goes through that loop; same results)."""
         _lib.check(self._L.twv_wavenet_set_option(self._h, name.encode(), int(value)))
         if name in ("xcd", "xcd_many", "groups") and self._state is not None:
             self.queue_initializer()
