@@ -310,6 +310,52 @@ int twv_tacotron_decoder_grad_phase_ms(twv_tacotron_decoder_grad* g, double* ms3
 int twv_tacotron_mel_loss_grad(const float* mel, const float* mel_targets, const float* loss_coeff, int batch, int t_out, int num_mels,
                                float* d_mel, void* stream);
 
+/* ---- Tacotron encoder and post-net gradients: the vector-Jacobian product of one CBHG, instantiated twice ----
+ * twv_tacotron_workspace_view also answers "before_highway" (batch, enc_prenet_sizes[1]) and "encoder_rnn_init" (batch, 2 * enc_rnn_size =
+ * [fw | bw]): the speaker-dependent pieces a multi-speaker 'deepvoice' pass leaves in its workspace (TWV_E_INVALID for a model without them).
+ *
+ * A handle for (model, which, batch, t): t = t_in for TWV_CBHG_ENCODER, T_out for TWV_CBHG_POST.  Host only; every refusal comes before the
+ * device is touched.  TWV_E_INVALID: null arguments, another `which`, batch < 1, t_in outside 1 .. 1024, T_out outside 1 .. max_iters * r.
+ * TWV_E_UNSUPPORTED: model_type 'simple', proj_width above 16 (the row kernel stages 8 + width - 1 rows).  The attention type is not looked at.
+ * twv_tacotron_cbhg_grad_route: a label ("kernel=cg_bigru side=encoder|post workgroups_per_utterance=2 threads=512 weights=registers ..."). */
+#define TWV_CBHG_ENCODER 0
+#define TWV_CBHG_POST 1
+typedef struct twv_tacotron_cbhg_grad twv_tacotron_cbhg_grad;
+int twv_tacotron_cbhg_grad_create(const twv_tacotron* h, int which, int batch, int t, twv_tacotron_cbhg_grad** out);
+void twv_tacotron_cbhg_grad_destroy(twv_tacotron_cbhg_grad* g);
+size_t twv_tacotron_cbhg_grad_workspace_bytes(const twv_tacotron_cbhg_grad* g);
+const char* twv_tacotron_cbhg_grad_route(const twv_tacotron_cbhg_grad* g);
+/* The encoder (embedding, prenet, encoder CBHG), recorded, and its backward.
+ * In:  blob            the canonical weights on the device; tokens (batch, t_in) int32, lengths (batch) int32
+ *      before_highway  (batch, enc_prenet_sizes[1]) and rnn_init (batch, 2 * enc_rnn_size), or NULL each (a single-speaker model)
+ *      mask1, mask2    NULL, or (batch, t_in, enc_prenet_sizes[i]) multipliers after each prenet relu (dropout); NULL = the evaluation graph
+ *      d_memory        (batch, t_in, 2 * enc_rnn_size): the cotangent on the encoder output; rows past a length are not read
+ * Scratch: workspace (twv_tacotron_cbhg_grad_workspace_bytes, in any state), status (4 x int32, zeroed), stream.
+ * Out: memory_out      the recorded encoder output, exactly 0 past each length
+ *      grad_blob       the layout of blob: zeroed, then the gradients of embedding (row 0 exactly 0: the forward reads the <PAD> row as
+ *                      zeros), prenet/ * and encoder_cbhg/ *; a batch_normalization slot holds (d_inv, d_shift) of the derived pair
+ *      d_before_highway, d_rnn_init   as their inputs (required where the input is given, not touched otherwise)
+ * Padded rows pass through the prenet and the convolutions like any other row (the reference does not mask them); only the GRUs are
+ * masked.  No atomics, no workgroup waits for another: two runs give the same bits, and an utterance's outputs are the same bits alone
+ * and inside a batch. */
+int twv_tacotron_encoder_grad_run(twv_tacotron_cbhg_grad* g, const float* blob, const int32_t* tokens, const int32_t* lengths,
+                                  const float* before_highway, const float* rnn_init, const float* mask1, const float* mask2,
+                                  const float* d_memory, void* workspace, int32_t* status, void* stream, float* memory_out,
+                                  float* grad_blob, float* d_before_highway, float* d_rnn_init);
+/* The post net (post CBHG, linear-spectrogram layer), recorded, and its backward.  mel (batch, t_out, num_mels), d_linear and linear_out
+ * (batch, t_out, num_freq); grad_blob as above with post_cbhg/ * and the linear layer; d_mel (batch, t_out, num_mels) the cotangent on mel. */
+int twv_tacotron_postnet_grad_run(twv_tacotron_cbhg_grad* g, const float* blob, const float* mel, const float* d_linear, void* workspace,
+                                  int32_t* status, void* stream, float* linear_out, float* grad_blob, float* d_mel);
+/* measurement, as for the decoder: ms4 = the recording forward, the GRUs' backward through time, the row-wise backward (pointwise kernels
+ * and dx products), the weight-gradient products */
+int twv_tacotron_cbhg_grad_set_timing(twv_tacotron_cbhg_grad* g, int on);
+int twv_tacotron_cbhg_grad_phase_ms(twv_tacotron_cbhg_grad* g, double* ms4);
+/* the derivative of add_loss's linear term (tacotron.py:258-282) with respect to linear_outputs: s = sign(linear - target) * loss_coeff[n]
+ * (0 where the difference is 0); d_linear = s / (N T F), or with prioritize_loss s * (0.5 / (N T F) + [lo <= f < hi] * 0.5 / (N T (hi - lo)))
+ * with the band of twv_tacotron_loss. */
+int twv_tacotron_linear_loss_grad(const float* linear, const float* linear_targets, const float* loss_coeff, int batch, int t_out,
+                                  int num_freq, int prioritize_loss, double sample_rate, float* d_linear, void* stream);
+
 /* launch geometry (performance only, results are bit-identical): "decoder_groups" = 0 auto (the XCD-resident decoder kernel wherever it
  * fits -- batch <= 32, t_in <= 512, 256 CUs, decoder widths divisible by 4, not model_type 'simple', attention_type bah_mon_norm -- else the split kernel with 16 / 8 / 4
  * workgroups per utterance), 1/2/4/8/16 = the split kernel with that many workgroups per utterance, 32 = the XCD-resident kernel or an

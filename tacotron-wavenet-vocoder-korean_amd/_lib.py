@@ -260,6 +260,15 @@ def lib():
     L.twv_tacotron_decoder_grad_set_timing.argtypes = [vp, C.c_int]
     L.twv_tacotron_decoder_grad_phase_ms.argtypes = [vp, C.POINTER(C.c_double)]
     L.twv_tacotron_mel_loss_grad.argtypes =[fp, fp, fp, C.c_int, C.c_int, C.c_int, fp, vp]
+    L.twv_tacotron_cbhg_grad_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    L.twv_tacotron_cbhg_grad_destroy.argtypes = [vp]; L.twv_tacotron_cbhg_grad_destroy.restype = None
+    L.twv_tacotron_cbhg_grad_workspace_bytes.argtypes = [vp]; L.twv_tacotron_cbhg_grad_workspace_bytes.restype = C.c_size_t
+    L.twv_tacotron_cbhg_grad_route.argtypes = [vp]; L.twv_tacotron_cbhg_grad_route.restype = C.c_char_p
+    L.twv_tacotron_encoder_grad_run.argtypes = [vp, fp, ip, ip, fp, fp, fp, fp, fp, vp, ip, vp, fp, fp, fp, fp]
+    L.twv_tacotron_postnet_grad_run.argtypes = [vp, fp, fp, fp, vp, ip, vp, fp, fp, fp]
+    L.twv_tacotron_cbhg_grad_set_timing.argtypes = [vp, C.c_int]
+    L.twv_tacotron_cbhg_grad_phase_ms.argtypes = [vp, C.POINTER(C.c_double)]
+    L.twv_tacotron_linear_loss_grad.argtypes = [fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, fp, vp]
     L.twv_tacotron_set_profile_buffer.argtypes = [vp, vp]
     L.twv_tacotron_set_option.argtypes = [vp, C.c_char_p, C.c_int]
     L.twv_tacotron_gemm_stats.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]
@@ -309,7 +318,10 @@ EXPORTS = ["twv_last_error", "twv_version", "twv_wavenet_create", "twv_wavenet_d
            "twv_wavenet_score_route", "twv_wavenet_score_windows", "twv_wavenet_score_reduce", "twv_wavenet_score_view", "twv_wavenet_train_create_w",
            "twv_tacotron_workspace_view", "twv_tacotron_decoder_grad_create", "twv_tacotron_decoder_grad_destroy",
            "twv_tacotron_decoder_grad_workspace_bytes", "twv_tacotron_decoder_grad_route", "twv_tacotron_decoder_grad_run",
-           "twv_tacotron_decoder_grad_set_timing", "twv_tacotron_decoder_grad_phase_ms", "twv_tacotron_mel_loss_grad"]
+           "twv_tacotron_decoder_grad_set_timing", "twv_tacotron_decoder_grad_phase_ms", "twv_tacotron_mel_loss_grad",
+           "twv_tacotron_cbhg_grad_create", "twv_tacotron_cbhg_grad_destroy", "twv_tacotron_cbhg_grad_workspace_bytes",
+           "twv_tacotron_cbhg_grad_route", "twv_tacotron_encoder_grad_run", "twv_tacotron_postnet_grad_run",
+           "twv_tacotron_cbhg_grad_set_timing", "twv_tacotron_cbhg_grad_phase_ms", "twv_tacotron_linear_loss_grad"]
 
 
 class TacoDims(C.Structure):

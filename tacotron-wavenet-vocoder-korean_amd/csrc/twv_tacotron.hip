@@ -2877,6 +2877,7 @@ struct TacoCarve {
     float *exch, *xexch, *stabf;    // exchange granules of the split ([N][2][kExN]) and the XCD-local ([8][2][kXU * 512]) decoder; stage tables
     int *tickets, *xtickets; long long exch_floats, xexch_floats;    // the role tickets behind either area; granules + tickets: what a launch clears
     long long o_memo, o_keys, o_dinit;                          // where memo / keys / dinit start (floats from the base): twv_tacotron_workspace_view
+    long long o_sv[2];                                          // sv[0] (before_highway) and sv[1] (the encoder GRUs' initial states), -1 without them
 };
 static long long taco_carve(const twv_tacotron* h, int N, int T, float* base, TacoCarve& c)
 {
@@ -2895,7 +2896,11 @@ static long long taco_carve(const twv_tacotron* h, int N, int T, float* base, Ta
     const long long SE = d.num_speakers > 1 ? d.speaker_embedding_size : 0, ninit = d.attention_state_size + (long long)d.dec_layer_num * d.dec_rnn_size;
     c.semb = take(N * (SE > 64 ? SE : 64));
     long long dsum = 0;
-    for (int i = 0; i < 8; ++i) { c.sv[i] = i < h->ndense ? take((long long)N * h->dn[i]) : nullptr; dsum += i < h->ndense ? h->dn[i] : 0; }
+    c.o_sv[0] = c.o_sv[1] = -1;
+    for (int i = 0; i < 8; ++i) {
+        if (i < 2 && i < h->ndense) c.o_sv[i] = used;
+        c.sv[i] = i < h->ndense ? take((long long)N * h->dn[i]) : nullptr; dsum += i < h->ndense ? h->dn[i] : 0;
+    }
     if (dsum < 1984) take(N * (1984 - dsum));
     c.o_dinit = used; c.dinit = take(N * (ninit > 2048 ? ninit : 2048));
     c.postout = take(rowsP * 2 * d.post_rnn_size);
@@ -2921,7 +2926,13 @@ extern "C" int twv_tacotron_workspace_view(const twv_tacotron* h, int batch, int
     if (!strcmp(which, "memory")) { *offset_floats = c.o_memo; *floats = rows * 2 * d.enc_rnn_size; }
     else if (!strcmp(which, "keys")) { *offset_floats = c.o_keys; *floats = rows * d.attention_size; }
     else if (!strcmp(which, "decoder_init")) { *offset_floats = c.o_dinit; *floats = (long long)batch * (d.attention_state_size + (long long)d.dec_layer_num * d.dec_rnn_size); }
-    else return twv_fail(TWV_E_INVALID, std::string("twv_tacotron_workspace_view: no piece named '") + which + "' (memory, keys, decoder_init)");
+    else if (!strcmp(which, "before_highway") || !strcmp(which, "encoder_rnn_init")) {
+        // the speaker-dependent vectors the encoder CBHG reads (tacotron.py:63-86): the pieces of a multi-speaker 'deepvoice' pass only
+        const int i = which[0] == 'b' ? 0 : 1;
+        if (c.o_sv[i] < 0) return twv_fail(TWV_E_INVALID, std::string("twv_tacotron_workspace_view: this model has no '") + which + "' (single speaker or model_type 'simple')");
+        *offset_floats = c.o_sv[i]; *floats = (long long)batch * h->dn[i];
+    }
+    else return twv_fail(TWV_E_INVALID, std::string("twv_tacotron_workspace_view: no piece named '") + which + "' (memory, keys, decoder_init, before_highway, encoder_rnn_init)");
     return TWV_OK;
 }
 
@@ -2945,6 +2956,30 @@ void taco_decoder_blob(const twv_tacotron* h, TacoDecoderBlob& b)
         b.rWg[i] = src(h->rWg[i].off, on); b.rbg[i] = src(h->rbg[i].off, on); b.rWc[i] = src(h->rWc[i].off, on); b.rbc[i] = src(h->rbc[i].off, on);
     }
     b.oW = src(h->oW.off, true); b.ob = src(h->ob.off, true);
+    b.blob_floats = h->blob_floats;
+}
+
+void taco_cbhg_blob(const twv_tacotron* h, int which, TacoCbhgBlob& b)
+{
+    auto src = [&](long long dst) -> long long {
+        for (const auto& it : h->items) if (it.dst == dst) return it.src;
+        return -1;
+    };
+    const twv_tacotron_dims& d = h->d;
+    const TCbhg& c = which ? h->post : h->enc;
+    memset(&b, 0xff, sizeof(b));                    // every offset -1 until found
+    b.Cin = which ? d.num_mels : d.enc_prenet_sizes[1];
+    b.bank = which ? d.post_bank_size : d.enc_bank_size; b.bch = which ? d.post_bank_channel_size : d.enc_bank_channel_size;
+    for (int i = 0; i < 2; ++i) b.proj[i] = which ? d.post_proj_sizes[i] : d.enc_proj_sizes[i];
+    b.pw = which ? d.post_proj_width : d.enc_proj_width; b.depth = which ? d.post_highway_depth : d.enc_highway_depth;
+    b.rnn = which ? d.post_rnn_size : d.enc_rnn_size; b.has_dense = c.has_dense;
+    for (int k = 1; k <= b.bank; ++k) { b.W[k] = src(c.W[k].off); b.b[k] = src(c.b[k].off); b.bn[k] = src(c.inv[k].off); }
+    for (int i = 0; i < 2; ++i) { b.pW[i] = src(c.pW[i].off); b.pb[i] = src(c.pb[i].off); b.pbn[i] = src(c.pinv[i].off); }
+    if (c.has_dense) { b.dW = src(c.dW.off); b.db = src(c.db.off); }
+    for (int i = 0; i < b.depth; ++i) { b.hH[i] = src(c.hH[i].off); b.hHb[i] = src(c.hHb[i].off); b.hT[i] = src(c.hT[i].off); b.hTb[i] = src(c.hTb[i].off); }
+    for (int dr = 0; dr < 2; ++dr) { b.gWg[dr] = src(c.gWgx[dr].off); b.gbg[dr] = src(c.gbg[dr].off); b.gWc[dr] = src(c.gWcx[dr].off); b.gbc[dr] = src(c.gbc[dr].off); }
+    if (which) { b.lW = src(h->lW.off); b.lb = src(h->lb.off); }
+    else { b.emb = src(h->emb.off); b.pW1 = src(h->pW1.off); b.pb1 = src(h->pb1.off); b.pW2 = src(h->pW2.off); b.pb2 = src(h->pb2.off); }
     b.blob_floats = h->blob_floats;
 }
 

@@ -14,5 +14,21 @@ struct TacoDecoderBlob {
     long long blob_floats;
 };
 
+// The same for one CBHG (twv_tacotron_cbhg_grad.hip): which = 0 the encoder's (with the embedding and the encoder prenet in front of it),
+// 1 the post net's (with the linear-spectrogram layer behind it).  A batch_normalization entry is the derived (inv, shift) pair of
+// tacotron.flatten: inv at `bn`, shift at `bn` + channels.
+struct TacoCbhgBlob {
+    int Cin, bank, bch, proj[2], pw, depth, rnn, has_dense;
+    long long W[17], b[17], bn[17];                 // conv_bank/conv1d_k, k = 1 .. bank: kernel (k, Cin, bch), bias, batch norm pair
+    long long pW[2], pb[2], pbn[2];                 // proj_1, proj_2: kernel (pw, cin, proj[i]), bias, batch norm pair
+    long long dW, db;                               // scope/dense (has_dense)
+    long long hH[8], hHb[8], hT[8], hTb[8];         // highway layers
+    long long gWg[2], gbg[2], gWc[2], gbc[2];       // fw / bw GRU: gates / candidate kernel (rows [x | h]) and bias
+    long long emb, pW1, pb1, pW2, pb2;              // encoder only: embedding table, prenet
+    long long lW, lb;                               // post net only: the linear-spectrogram layer
+    long long blob_floats;
+};
+
 const twv_tacotron_dims& taco_dims(const twv_tacotron* h);
 void taco_decoder_blob(const twv_tacotron* h, TacoDecoderBlob& b);
+void taco_cbhg_blob(const twv_tacotron* h, int which, TacoCbhgBlob& b);

@@ -1,0 +1,923 @@
+// Tacotron encoder and post-net gradients (gfx950): the vector-Jacobian product of one CBHG (modules.py:25-74), instantiated twice
+// (DESIGN 3b-h).
+//
+//   encoder:  d_memory  ->  the gradient of embedding, prenet/* and encoder_cbhg/*  + d_before_highway + d_rnn_init
+//   post net: d_linear  ->  the gradient of post_cbhg/* and the linear-spectrogram layer + d_mel (the cotangent on the post net's input)
+//
+// The pass is (a) a recording forward -- every product over all N * T rows, then cg_gru_forward_kernel, ONE workgroup of 512 threads per
+// (utterance, direction), whose recurrent weights (the h rows of gates/kernel and candidate/kernel, 49 152 floats) stay in registers for
+// the whole launch; the input halves x . W_x of both GRU kernels are products over all rows made before the loop; (b) cg_gru_backward_kernel,
+// the same geometry with the same 49 152 values in the layout of the transposed products, walking each direction's steps backwards with
+// dh in LDS and writing the pre-activation deltas per row; (c) the row-wise backward: dx = delta . W_x^T as products over all rows, the
+// highway layers, the projections' and the conv bank's batch norm / relu / max-pool backward as fused pointwise kernels with per-channel
+// partial sums; (d) every kernel gradient as a product X^T . delta (rocBLAS, atomics off; a convolution as one product per tap against a
+// delta whose rows that would read across an utterance boundary are zeroed) and every bias gradient as a column sum.
+// No workgroup waits for another one: no exchange areas, tickets or grid barriers.  No atomics: two runs give the same bits.  Whatever lies
+// on the path to d_x / d_before_highway / d_rnn_init / the recorded output goes through this file's own row kernel, whose order of additions
+// for a row does not depend on how many rows there are: an utterance's outputs are the same bits alone and inside a batch.
+#include <hip/hip_runtime.h>
+#include <rocblas/rocblas.h>
+#include <stdint.h>
+#include <string.h>
+#include <string>
+#include "../../include/twv_amd.h"
+#include "twv_dev.hpp"
+#include "twv_tacotron_blob.hpp"
+
+namespace cg {
+
+constexpr int kU = 128;                              // GRU / highway width: twv_tacotron_create accepts no other enc_rnn_size / post_rnn_size
+constexpr int kGruThreads = 512;
+constexpr int kRB = 8, kKC = 128, kMaxKw = 16;       // the row kernel: rows a block, K chunk in LDS, widest convolution
+constexpr int kChunk = 128;                          // rows per block of the column-statistics kernels
+
+__device__ inline float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
+// a workgroup barrier that orders LDS only: __syncthreads() also waits for every global load and store in flight (vmcnt(0)), which in the
+// recurrent kernels are the tape writes and the next step's prefetch
+__device__ inline void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// ---- the row kernel: products over all rows, a convolution of width kw as kw shifted products accumulated in tap order
+//   z[r][j] = bias[j] + sum_tap sum_k X[r + tap - left][k] * W[(tap * Cin + k) * ldw + j]        (rows of another utterance read as zeros)
+//   act 1: v = max(z, 0) * mask, gate_out = z > 0 ? mask : 0 (mask null = ones);  act 2: v = sigmoid(z);  v *= gate_in
+//   C = (add ? C : 0) + v;   Y = v * inv[j] + shift[j] (inv null: v) + add1[r][j] + add2[r / T][j]
+// float64 accumulators, one order of additions per (row, column) whatever the number of rows.
+struct RowsArgs {
+    const float *X, *W, *bias, *mask, *gate_in, *inv, *shift, *add1, *add2;
+    float *C, *gate_out, *Y;
+    int ldx, ldw, ldc, ldy, ld1, ld2, rows, T, Cin, kw, left, ncols, act, add;
+};
+__global__ void __launch_bounds__(256) cg_rows_kernel(RowsArgs a)
+{
+    __shared__ double xs[(kRB + kMaxKw) * kKC];       // rows r0 - left .. r0 + kRB - 1 + right of the chunk, then one row of zeros
+    __shared__ int idx[kRB * kMaxKw];
+    const int tid = threadIdx.x, r0 = blockIdx.x * kRB, nr = min(kRB, a.rows - r0), kw = a.kw, nstage = kRB + kw - 1, zrow = nstage;
+    const int j = blockIdx.y * 256 + tid;
+    for (int i = tid; i < kRB * kw; i += 256) {
+        const int r = i / kw, tap = i - r * kw, row = r0 + r, src = row + tap - a.left;
+        const bool ok = r < nr && src >= 0 && src < a.rows && src / a.T == row / a.T;
+        idx[r * kMaxKw + tap] = (ok ? r + tap : zrow) * kKC;
+    }
+    if (tid < kKC) xs[zrow * kKC + tid] = 0.0;
+    double acc[kRB];
+#pragma unroll
+    for (int r = 0; r < kRB; ++r) acc[r] = 0.0;
+    for (int k0 = 0; k0 < a.Cin; k0 += kKC) {
+        const int kc = min(kKC, a.Cin - k0);
+        __syncthreads();
+        for (int i = tid; i < nstage * kKC; i += 256) {
+            const int s = i / kKC, k = i - s * kKC, src = r0 - a.left + s;
+            xs[i] = (src >= 0 && src < a.rows && k < kc) ? (double)a.X[(long long)src * a.ldx + k0 + k] : 0.0;
+        }
+        __syncthreads();
+        if (j < a.ncols) {
+            for (int tap = 0; tap < kw; ++tap) {
+                int o[kRB];
+#pragma unroll
+                for (int r = 0; r < kRB; ++r) o[r] = idx[r * kMaxKw + tap];
+                const float* wp = a.W + ((long long)tap * a.Cin + k0) * a.ldw + j;
+                for (int k = 0; k < kc; ++k) {
+                    const double w = (double)wp[(long long)k * a.ldw];
+#pragma unroll
+                    for (int r = 0; r < kRB; ++r) acc[r] = fma(w, xs[o[r] + k], acc[r]);
+                }
+            }
+        }
+    }
+    if (j >= a.ncols) return;
+#pragma unroll
+    for (int r = 0; r < kRB; ++r) {
+        if (r >= nr) continue;
+        const long long row = r0 + r;
+        float v = (float)(acc[r] + (a.bias ? (double)a.bias[j] : 0.0));
+        if (a.act == 1) {
+            const float m = a.mask ? a.mask[row * a.ncols + j] : 1.0f;
+            if (a.gate_out) a.gate_out[row * a.ncols + j] = v > 0.0f ? m : 0.0f;
+            v = fmaxf(v, 0.0f) * m;
+        } else if (a.act == 2) v = sigmoidf_(v);
+        if (a.gate_in) v *= a.gate_in[row * a.ncols + j];
+        if (a.C) { const long long o = row * a.ldc + j; a.C[o] = a.add ? a.C[o] + v : v; }
+        if (a.Y) {
+            float y = a.inv ? v * a.inv[j] + a.shift[j] : v;
+            if (a.add1) y = y + a.add1[row * a.ld1 + j];
+            if (a.add2) y = y + a.add2[(row / a.T) * a.ld2 + j];
+            a.Y[row * a.ldy + j] = y;
+        }
+    }
+}
+
+// the kernel of the transposed convolution: Wt[(tap' * ncols + j) * Cin + k] = W[((kw - 1 - tap') * Cin + k) * ldw + j]
+__global__ void cg_transpose_kernel(const float* W, int kw, int Cin, int ncols, int ldw, float* Wt)
+{
+    const long long total = (long long)kw * Cin * ncols;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int k = (int)(i % Cin); const long long q = i / Cin; const int j = (int)(q % ncols), tp = (int)(q / ncols);
+        Wt[i] = W[((long long)(kw - 1 - tp) * Cin + k) * ldw + j];
+    }
+}
+
+// ---- small row-wise kernels
+// tacotron.py:51-60: the <PAD> row of the table reads as zeros
+__global__ void cg_embed_kernel(const float* table, const int32_t* tokens, int rows, int E, int nsym, float* out)
+{
+    const long long total = (long long)rows * E;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int row = (int)(i / E), c = (int)(i - (long long)row * E), tok = tokens[row];
+        out[i] = (tok <= 0 || tok >= nsym) ? 0.0f : table[(long long)tok * E + c];
+    }
+}
+// d embedding: a segmented sum, one workgroup per symbol walking the token rows in order (float64 inside); row 0 is exactly zero, as the
+// forward never reads it
+__global__ void __launch_bounds__(256) cg_embed_grad_kernel(const float* dE, const int32_t* tokens, int rows, int E, float* out)
+{
+    const int s = blockIdx.x;
+    for (int c = threadIdx.x; c < E; c += 256) {
+        double acc = 0.0;
+        if (s > 0) for (int r = 0; r < rows; ++r) if (tokens[r] == s) acc += (double)dE[(long long)r * E + c];
+        out[(long long)s * E + c] = (float)acc;
+    }
+}
+// per-group vectors of the conv bank (one batch norm per convolution): channel c belongs to group c / gs
+struct Groups { long long inv[17], shift[17]; int gs; };
+// modules.py:38 max_pooling1d(2, stride 1, 'same') on BN(a): out[t] = max(y[t], y[t+1]) inside each utterance
+__global__ void cg_pool_kernel(const float* A, const float* blob, Groups g, int rows, int T, int Cn, float* out)
+{
+    const long long total = (long long)rows * Cn;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int row = (int)(i / Cn), c = (int)(i - (long long)row * Cn), q = c / g.gs, cc = c - q * g.gs;
+        const float inv = blob[g.inv[q] + cc], sh = blob[g.shift[q] + cc];
+        const float y = A[i] * inv + sh;
+        float m = y;
+        if (row % T + 1 < T) { const float yn = A[i + Cn] * inv + sh; m = yn > y ? yn : y; }
+        out[i] = m;
+    }
+}
+// batch norm (inference form y = a * inv + shift) and relu backward, with the max pool in front of it when pool is set:
+//   pool: dy[t] = dP[t] where y[t+1] does not beat y[t] (a tie goes to the earlier position)  +  dP[t-1] where y[t] beats y[t-1]
+//   dz = dy * inv, 0 where relu and a <= 0;  partial sums over the block's rows of d_inv = dy * a and d_shift = dy (float64)
+// grid (column blocks of 64, row chunks of kChunk); a thread walks every fourth row of its column, the four are added in order.
+__global__ void __launch_bounds__(256) cg_bn_bwd_kernel(const float* dY, int ldy, const float* A, int lda, const float* blob, Groups g, int rows, int T,
+                                                        int Cn, int pool, int relu, float* dZ, int ldz, double* partial)
+{
+    __shared__ double red[2][4][64];
+    const int c = blockIdx.x * 64 + (threadIdx.x & 63), q4 = threadIdx.x >> 6, ra = blockIdx.y * kChunk, rb = min(rows, ra + kChunk);
+    double si = 0.0, ss = 0.0;
+    if (c < Cn) {
+        const int q = c / g.gs, cc = c - q * g.gs;
+        const float inv = blob[g.inv[q] + cc], sh = blob[g.shift[q] + cc];
+        for (int r = ra + q4; r < rb; r += 4) {
+            const float av = A[(long long)r * lda + c];
+            float dy;
+            if (pool) {
+                const int t = r % T;
+                const float y = av * inv + sh;
+                dy = 0.0f;
+                bool mine = true;
+                if (t + 1 < T) { const float yn = A[(long long)(r + 1) * lda + c] * inv + sh; mine = !(yn > y); }
+                if (mine) dy += dY[(long long)r * ldy + c];
+                if (t > 0) { const float yp = A[(long long)(r - 1) * lda + c] * inv + sh; if (y > yp) dy += dY[(long long)(r - 1) * ldy + c]; }
+            } else dy = dY[(long long)r * ldy + c];
+            float dz = dy * inv;
+            if (relu && !(av > 0.0f)) dz = 0.0f;
+            dZ[(long long)r * ldz + c] = dz;
+            si += (double)dy * (double)av; ss += (double)dy;
+        }
+    }
+    red[0][q4][threadIdx.x & 63] = si; red[1][q4][threadIdx.x & 63] = ss;
+    __syncthreads();
+    if (q4 == 0 && c < Cn) {
+        const int l = threadIdx.x;
+        partial[((long long)blockIdx.y * 2 + 0) * Cn + c] = ((red[0][0][l] + red[0][1][l]) + red[0][2][l]) + red[0][3][l];
+        partial[((long long)blockIdx.y * 2 + 1) * Cn + c] = ((red[1][0][l] + red[1][1][l]) + red[1][2][l]) + red[1][3][l];
+    }
+}
+// column sums (bias gradients), the same grid: partial[chunk][0][c]
+__global__ void __launch_bounds__(256) cg_colsum_kernel(const float* D, int ld, int rows, int Cn, double* partial)
+{
+    __shared__ double red[4][64];
+    const int c = blockIdx.x * 64 + (threadIdx.x & 63), q4 = threadIdx.x >> 6, ra = blockIdx.y * kChunk, rb = min(rows, ra + kChunk);
+    double s = 0.0;
+    if (c < Cn) for (int r = ra + q4; r < rb; r += 4) s += (double)D[(long long)r * ld + c];
+    red[q4][threadIdx.x & 63] = s;
+    __syncthreads();
+    if (q4 == 0 && c < Cn) { const int l = threadIdx.x; partial[(long long)blockIdx.y * Cn + c] = ((red[0][l] + red[1][l]) + red[2][l]) + red[3][l]; }
+}
+// the chunks' partial sums in chunk order: stat s of channel c goes to grad[off[s][c / gs] + c % gs]
+struct FinishArgs { long long off[2][17]; int gs, nstat, Cn, nchunk; };
+__global__ void cg_finish_kernel(const double* partial, FinishArgs f, float* grad)
+{
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= f.Cn) return;
+    const int q = c / f.gs, cc = c - q * f.gs;
+    for (int s = 0; s < f.nstat; ++s) {
+        double v = 0.0;
+        for (int k = 0; k < f.nchunk; ++k) v += partial[((long long)k * f.nstat + s) * f.Cn + c];
+        grad[f.off[s][q] + cc] = (float)v;
+    }
+}
+// highway layer: y = relu(h) * sigmoid(t) + x * (1 - sigmoid(t));  H, Tg hold relu(h) and sigmoid(t)
+__global__ void cg_highway_kernel(const float* x, const float* H, const float* Tg, long long total, float* y)
+{
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x)
+        y[i] = H[i] * Tg[i] + x[i] * (1.0f - Tg[i]);
+}
+// its backward in one pass: D[r] = [dh~ | dt~] (pre-activation deltas, 2 * kU a row), dx = the carry term dy * (1 - sigmoid(t))
+__global__ void cg_highway_bwd_kernel(const float* dy, const float* x, const float* H, const float* Tg, long long total, float* D, float* dx)
+{
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const long long r = i / kU; const int j = (int)(i - r * kU);
+        const float d = dy[i], h = H[i], t = Tg[i];
+        D[r * 2 * kU + j] = h > 0.0f ? d * t : 0.0f;
+        D[r * 2 * kU + kU + j] = d * (h - x[i]) * t * (1.0f - t);
+        dx[i] = d * (1.0f - t);
+    }
+}
+__global__ void cg_mul_kernel(float* x, const float* g, long long total)
+{
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) x[i] *= g[i];
+}
+// out[n][j] = sum_t D[n * T + t][j], t in order (float64 inside): d_before_highway
+__global__ void cg_utterance_sum_kernel(const float* D, int N, int T, int Cn, float* out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N * Cn) return;
+    const int n = i / Cn, j = i - n * Cn;
+    double s = 0.0;
+    for (int t = 0; t < T; ++t) s += (double)D[((long long)n * T + t) * Cn + j];
+    out[i] = (float)s;
+}
+// Ds[r][j] = D[r][j] where row r + shift lies in r's utterance, else 0: the delta of one tap of a convolution's kernel gradient
+__global__ void cg_shift_mask_kernel(const float* D, int ld, int rows, int T, int Cn, int shift, float* Ds)
+{
+    const long long total = (long long)rows * Cn;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int r = (int)(i / Cn), j = (int)(i - (long long)r * Cn), t = r % T + shift;
+        Ds[i] = (t >= 0 && t < T) ? D[(long long)r * ld + j] : 0.0f;
+    }
+}
+__global__ void cg_linear_loss_grad_kernel(const float* lin, const float* tgt, const float* coeff, long long per, int F, int lo, int hi, float w0,
+                                           float w1, long long total, float* out)
+{
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int f = (int)(i % F);
+        const float d = lin[i] - tgt[i], s = coeff[i / per] * ((f >= lo && f < hi) ? w0 + w1 : w0);
+        out[i] = d > 0.0f ? s : (d < 0.0f ? -s : 0.0f);
+    }
+}
+
+// ---- the bidirectional GRU: blockIdx.x = 2 * utterance + direction, 512 threads
+struct GruArgs {
+    const float *Wg[2], *Wc[2];          // gates/kernel (2 kU x 2 kU), candidate/kernel (2 kU x kU), rows [x | h]
+    const float *GX, *CX;                // x . W_x + bias of all rows: [row][dir][2 kU], [row][dir][kU]
+    const float* init;                   // (N, 2 kU) = [fw | bw] or null
+    const int32_t* lengths;              // null: every row is live (the post net)
+    float* out;                          // (rows, 2 kU), zero past each length
+    float *HP[2], *RU[2], *CC[2], *RH[2];   // tape per direction: h_{t-1}, [r | u], c, r * h_{t-1}
+    const float* dOut;
+    float *DG[2], *DC[2], *dinit;        // [dr~ | du~], dc~ per row (zero past each length); d_rnn_init (N, 2 kU) or null
+    int N, T;
+};
+// LDS of the two recurrent kernels, in floats: one carve for the kernels and for the launch
+struct GruLds { int h, g, rh, red, total; };
+__host__ __device__ inline GruLds gru_lds()
+{
+    GruLds c; int u = 0;
+    auto take = [&](int n) { const int o = u; u += (n + 3) & ~3; return o; };
+    c.h = take(kU); c.g = take(2 * kU); c.rh = take(kU); c.red = take(kGruThreads); c.total = u;
+    return c;
+}
+__device__ inline float sum4(const float* red, int i) { return (red[i] + red[kU + i]) + (red[2 * kU + i] + red[3 * kU + i]); }
+
+// dot of n (a multiple of 16) register weights with an LDS vector, four chains
+template <int n>
+__device__ inline float dot_reg(const float (&w)[n], const float* v)
+{
+    float p0 = 0.0f, p1 = 0.0f, p2 = 0.0f, p3 = 0.0f;
+    const float4* v4 = reinterpret_cast<const float4*>(v);
+#pragma unroll
+    for (int i = 0; i < n / 4; ++i) {
+        const float4 x = v4[i];
+        p0 = fmaf(w[4 * i], x.x, p0); p1 = fmaf(w[4 * i + 1], x.y, p1); p2 = fmaf(w[4 * i + 2], x.z, p2); p3 = fmaf(w[4 * i + 3], x.w, p3);
+    }
+    return (p0 + p1) + (p2 + p3);
+}
+
+__global__ void __launch_bounds__(kGruThreads) cg_gru_forward_kernel(GruArgs a)
+{
+    extern __shared__ float lds[];
+    const GruLds c = gru_lds();
+    float *hs = lds + c.h, *gs = lds + c.g, *rhs = lds + c.rh, *red = lds + c.red;
+    const int n = blockIdx.x >> 1, dir = blockIdx.x & 1, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, T = a.T;
+    // gates: column jg, k in [64 hg, 64 hg + 64); candidate: column jc, k in [32 qc, 32 qc + 32).  A wave shares its k range, so its LDS
+    // reads of the state are broadcasts.
+    const int jg = (wv >> 1) * 64 + lane, hg = wv & 1, jc = (wv & 1) * 64 + lane, qc = wv >> 1;
+    float wg[64], wc[32];
+    {
+        const float* Wg = a.Wg[dir] + (long long)(kU + 64 * hg) * 2 * kU + jg;
+        const float* Wc = a.Wc[dir] + (long long)(kU + 32 * qc) * kU + jc;
+#pragma unroll
+        for (int i = 0; i < 64; ++i) wg[i] = Wg[i * 2 * kU];
+#pragma unroll
+        for (int i = 0; i < 32; ++i) wc[i] = Wc[i * kU];
+    }
+    const int len = a.lengths ? min(max(a.lengths[n], 0), T) : T;
+    float *HP = a.HP[dir], *RU = a.RU[dir], *CC = a.CC[dir], *RH = a.RH[dir];
+    if (tid < kU) hs[tid] = a.init ? a.init[(long long)n * 2 * kU + dir * kU + tid] : 0.0f;
+    lds_barrier();
+    for (int s = 0; s < len; ++s) {
+        const long long row = (long long)n * T + (dir ? len - 1 - s : s);
+        const float gx = tid < 2 * kU ? a.GX[row * 4 * kU + dir * 2 * kU + tid] : 0.0f;
+        const float cx = tid < kU ? a.CX[row * 2 * kU + dir * kU + tid] : 0.0f;
+        red[hg * 2 * kU + jg] = dot_reg<64>(wg, hs + 64 * hg);
+        lds_barrier();
+        if (tid < 2 * kU) {
+            const float g = sigmoidf_(gx + (red[tid] + red[2 * kU + tid]));
+            gs[tid] = g; RU[row * 2 * kU + tid] = g;
+            if (tid < kU) rhs[tid] = g * hs[tid];
+        }
+        lds_barrier();
+        red[qc * kU + jc] = dot_reg<32>(wc, rhs + 32 * qc);
+        lds_barrier();
+        if (tid < kU) {
+            const float cc = tanhf(cx + sum4(red, tid)), u = gs[kU + tid], h = hs[tid], hn = u * h + (1.0f - u) * cc;
+            HP[row * kU + tid] = h; CC[row * kU + tid] = cc; RH[row * kU + tid] = rhs[tid];
+            a.out[row * 2 * kU + dir * kU + tid] = hn;
+            hs[tid] = hn;
+        }
+        lds_barrier();
+    }
+    // past the length: outputs are zeros (bidirectional_dynamic_rnn), and so is the tape, which the weight products read for every row
+    for (int t = len; t < T; ++t) {
+        const long long row = (long long)n * T + t;
+        if (tid < kU) { a.out[row * 2 * kU + dir * kU + tid] = 0.0f; HP[row * kU + tid] = 0.0f; CC[row * kU + tid] = 0.0f; RH[row * kU + tid] = 0.0f; }
+        if (tid < 2 * kU) RU[row * 2 * kU + tid] = 0.0f;
+    }
+}
+
+// backward through time.  Given dh' : dc~ = dh' (1 - u)(1 - c^2), du~ = dh' (h - c) u (1 - u), d(r h) = W_ch dc~, dr~ = d(r h) h r (1 - r),
+// dh = dh' u + d(r h) r + W_gh [dr~ | du~]
+__global__ void __launch_bounds__(kGruThreads) cg_gru_backward_kernel(GruArgs a)
+{
+    extern __shared__ float lds[];
+    const GruLds c = gru_lds();
+    float *dhs = lds + c.h, *dgs = lds + c.g, *dcs = lds + c.rh, *red = lds + c.red;
+    const int n = blockIdx.x >> 1, dir = blockIdx.x & 1, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, T = a.T;
+    // thread (k, q) holds row k of the h rows of both kernels: columns [64 q, 64 q + 64) of gates, [32 q, 32 q + 32) of candidate
+    const int k = (wv & 1) * 64 + lane, q = wv >> 1;
+    float wg[64], wc[32];
+    {
+        // (single floats: a tensor's place in the canonical blob is a multiple of 4 bytes, not of 16)
+        const float* Wg = a.Wg[dir] + (long long)(kU + k) * 2 * kU + 64 * q;
+        const float* Wc = a.Wc[dir] + (long long)(kU + k) * kU + 32 * q;
+#pragma unroll
+        for (int i = 0; i < 64; ++i) wg[i] = Wg[i];
+#pragma unroll
+        for (int i = 0; i < 32; ++i) wc[i] = Wc[i];
+    }
+    const int len = a.lengths ? min(max(a.lengths[n], 0), T) : T;
+    const float *HP = a.HP[dir], *RU = a.RU[dir], *CC = a.CC[dir];
+    float *DG = a.DG[dir], *DC = a.DC[dir];
+    if (tid < kU) dhs[tid] = 0.0f;
+    // the tape values of a step are fetched one step ahead
+    float nu = 0.0f, nr = 0.0f, ncc = 0.0f, nh = 0.0f, nd = 0.0f;
+    auto fetch = [&](int s) {
+        if (tid < kU && s < len) {
+            const long long row = (long long)n * T + (dir ? s : len - 1 - s);
+            nr = RU[row * 2 * kU + tid]; nu = RU[row * 2 * kU + kU + tid]; ncc = CC[row * kU + tid]; nh = HP[row * kU + tid];
+            nd = a.dOut[row * 2 * kU + dir * kU + tid];
+        }
+    };
+    fetch(0);
+    for (int s = 0; s < len; ++s) {
+        const long long row = (long long)n * T + (dir ? s : len - 1 - s);       // the direction's own order, reversed
+        const float u = nu, r = nr, cc = ncc, h = nh;
+        float dhp = 0.0f;
+        if (tid < kU) {
+            dhp = dhs[tid] + nd;
+            const float dc = dhp * (1.0f - u) * (1.0f - cc * cc), du = dhp * (h - cc) * u * (1.0f - u);
+            dcs[tid] = dc; dgs[kU + tid] = du;
+            DC[row * kU + tid] = dc; DG[row * 2 * kU + kU + tid] = du;
+        }
+        fetch(s + 1);
+        lds_barrier();
+        red[q * kU + k] = dot_reg<32>(wc, dcs + 32 * q);
+        lds_barrier();
+        float base = 0.0f;
+        if (tid < kU) {
+            const float drh = sum4(red, tid), dr = drh * h * r * (1.0f - r);
+            dgs[tid] = dr; DG[row * 2 * kU + tid] = dr;
+            base = dhp * u + drh * r;
+        }
+        lds_barrier();
+        red[q * kU + k] = dot_reg<64>(wg, dgs + 64 * q);
+        lds_barrier();
+        if (tid < kU) dhs[tid] = base + sum4(red, tid);
+    }
+    if (a.dinit && tid < kU) a.dinit[(long long)n * 2 * kU + dir * kU + tid] = dhs[tid];
+    for (int t = len; t < T; ++t) {
+        const long long row = (long long)n * T + t;
+        if (tid < kU) DC[row * kU + tid] = 0.0f;
+        if (tid < 2 * kU) DG[row * 2 * kU + tid] = 0.0f;
+    }
+}
+
+inline int grid_for(long long n) { const long long g = (n + 255) / 256; return (int)(g < 1 ? 1 : (g > 8192 ? 8192 : g)); }
+
+}  // namespace cg
+using namespace cg;
+
+// ---- the workspace of one handle: ONE carve, which also sizes it
+struct CgCarve {
+    float *E, *H1, *G1, *X, *G2;                        // encoder: embedded tokens, prenet (outputs and relu gates); X = the CBHG input
+    float *bankA, *pool, *A1, *Y1, *A2, *HW0, *hw[9], *Hh[8], *Tg[8], *GX, *CX, *out;
+    float *HP[2], *RU[2], *CC[2], *RH[2];
+    float *dOut, *DG[2], *DC[2], *dhw, *dhw2, *DHT[8], *dHW0, *dZ2, *dY1, *dZ1, *dpool, *dZb, *dX, *dH1, *dE, *Ds;
+    float *wT;                                          // transposed kernels
+    double* partial;
+};
+struct twv_tacotron_cbhg_grad {
+    twv_tacotron_dims d;
+    TacoCbhgBlob w;
+    int which, N, T, E, P0, F;
+    long long ws_floats, wT_floats;
+    int lds;                       // bytes, both recurrent kernels
+    rocblas_handle blas = nullptr;
+    std::string route;
+    int timing = 0;
+    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+};
+
+static long long cg_carve(const twv_tacotron_cbhg_grad* g, float* base, CgCarve& c)
+{
+    const TacoCbhgBlob& w = g->w;
+    const long long rows = (long long)g->N * g->T;
+    const int CB = w.bank * w.bch, Cin = w.Cin, P0 = w.proj[0], P1 = w.proj[1];
+    long long used = 0;
+    auto take = [&](long long n) { float* p = base ? base + used : nullptr; used += (n + 3) / 4 * 4; return p; };
+    memset(&c, 0, sizeof(c));
+    if (g->which == 0) {
+        c.E = take(rows * g->E); c.H1 = take(rows * g->P0); c.G1 = take(rows * g->P0); c.X = take(rows * Cin); c.G2 = take(rows * Cin);
+        c.dH1 = take(rows * g->P0); c.dE = take(rows * g->E);
+    }
+    c.bankA = take(rows * CB); c.pool = take(rows * CB); c.A1 = take(rows * P0); c.Y1 = take(rows * P0); c.A2 = take(rows * P1); c.HW0 = take(rows * P1);
+    for (int i = 0; i <= w.depth; ++i) c.hw[i] = (i == 0 && !w.has_dense) ? c.HW0 : take(rows * kU);
+    for (int i = 0; i < w.depth; ++i) { c.Hh[i] = take(rows * kU); c.Tg[i] = take(rows * kU); c.DHT[i] = take(rows * 2 * kU); }
+    c.GX = take(rows * 4 * kU); c.CX = take(rows * 2 * kU); c.out = take(rows * 2 * kU);
+    for (int dr = 0; dr < 2; ++dr) {
+        c.HP[dr] = take(rows * kU); c.RU[dr] = take(rows * 2 * kU); c.CC[dr] = take(rows * kU); c.RH[dr] = take(rows * kU);
+        c.DG[dr] = take(rows * 2 * kU); c.DC[dr] = take(rows * kU);
+    }
+    c.dOut = take(rows * 2 * kU); c.dhw = take(rows * kU); c.dhw2 = take(rows * kU); c.dHW0 = take(rows * P1); c.dZ2 = take(rows * P1);
+    c.dY1 = take(rows * P0); c.dZ1 = take(rows * P0); c.dpool = take(rows * CB); c.dZb = take(rows * CB); c.dX = take(rows * Cin);
+    int widest = w.bch > P0 ? w.bch : P0; widest = widest > P1 ? widest : P1;
+    c.Ds = take(rows * widest);
+    c.wT = take(g->wT_floats);
+    const long long nchunk = (rows + kChunk - 1) / kChunk;
+    int cmax = 2 * kU;                                  // the widest matrix a column-statistics kernel is run on
+    for (int v : {CB, P0, P1, Cin, g->P0, g->F, g->E}) cmax = cmax > v ? cmax : v;
+    used = (used + 1) / 2 * 2;
+    c.partial = reinterpret_cast<double*>(take(nchunk * 2 * cmax * 2));
+    return used;
+}
+
+static const char* const kCgBuilt = "the CBHG gradient is built for single-speaker and 'deepvoice' models, enc_rnn_size = post_rnn_size = 128 and projection widths up to 16";
+
+extern "C" int twv_tacotron_cbhg_grad_create(const twv_tacotron* h, int which, int batch, int t, twv_tacotron_cbhg_grad** out)
+{
+    if (!h || !out) return twv_fail(TWV_E_INVALID, "null argument");
+    const twv_tacotron_dims& d = taco_dims(h);
+    if (which != TWV_CBHG_ENCODER && which != TWV_CBHG_POST) return twv_fail(TWV_E_INVALID, "which must be TWV_CBHG_ENCODER (0) or TWV_CBHG_POST (1)");
+    if (batch < 1) return twv_fail(TWV_E_INVALID, "batch >= 1 required");
+    if (which == TWV_CBHG_ENCODER && (t < 1 || t > 1024)) return twv_fail(TWV_E_INVALID, "encoder: 1 <= t_in <= 1024 required");
+    if (which == TWV_CBHG_POST && (t < 1 || t > d.max_iters * d.reduction_factor)) return twv_fail(TWV_E_INVALID, "post net: 1 <= t_out <= max_iters * r required");
+    if ((long long)batch * t > (1LL << 24)) return twv_fail(TWV_E_INVALID, "batch * t above 2^24 rows");
+    if (d.num_speakers > 1 && d.model_simple && d.speaker_embedding_size != 1)
+        return twv_fail(TWV_E_UNSUPPORTED, std::string("model_type 'simple': ") + kCgBuilt);
+    twv_tacotron_cbhg_grad* g = new twv_tacotron_cbhg_grad();
+    g->d = d; g->which = which; g->N = batch; g->T = t;
+    taco_cbhg_blob(h, which, g->w);
+    const TacoCbhgBlob& w = g->w;
+    // the row kernel stages kRB + kw - 1 rows of a K chunk: convolutions up to kMaxKw wide (the bank's are bounded by twv_tacotron_create)
+    if (w.pw < 1 || w.pw > kMaxKw || w.bank > kMaxKw || w.rnn != kU) {
+        delete g;
+        return twv_fail(TWV_E_UNSUPPORTED, std::string("proj_width above 16: ") + kCgBuilt);
+    }
+    g->E = which ? 0 : d.embedding_size; g->P0 = which ? 0 : d.enc_prenet_sizes[0]; g->F = which ? d.num_freq : 0;
+    const int CB = w.bank * w.bch;
+    long long wt = 0;
+    for (int k = 1; k <= w.bank; ++k) wt += (long long)k * w.Cin * w.bch;
+    wt += (long long)w.pw * CB * w.proj[0] + (long long)w.pw * w.proj[0] * w.proj[1] + (w.has_dense ? (long long)w.proj[1] * kU : 0);
+    wt += (long long)w.depth * 2 * kU * kU + 2LL * (2 * kU * kU + kU * kU);
+    if (which) wt += (long long)2 * kU * d.num_freq; else wt += (long long)d.enc_prenet_sizes[0] * d.enc_prenet_sizes[1] + (long long)d.embedding_size * d.enc_prenet_sizes[0];
+    g->wT_floats = wt + 64;
+    CgCarve c;
+    g->ws_floats = cg_carve(g, nullptr, c);
+    g->lds = gru_lds().total * 4;
+    g->route = std::string("kernel=cg_bigru side=") + (which ? "post" : "encoder") + " workgroups_per_utterance=2 threads=512 weights=registers bank=" +
+               std::to_string(w.bank) + " bank_channels=" + std::to_string(w.bch) + " highway=" + std::to_string(w.depth) + " dense=" +
+               std::to_string(w.has_dense) + " lds=" + std::to_string(g->lds) + " wgrad=rocblas";
+    *out = g;
+    return TWV_OK;
+}
+extern "C" void twv_tacotron_cbhg_grad_destroy(twv_tacotron_cbhg_grad* g)
+{
+    if (g && g->blas) rocblas_destroy_handle(g->blas);
+    if (g) for (hipEvent_t e : g->ev) if (e) (void)hipEventDestroy(e);
+    delete g;
+}
+extern "C" int twv_tacotron_cbhg_grad_set_timing(twv_tacotron_cbhg_grad* g, int on)
+{
+    if (!g) return twv_fail(TWV_E_INVALID, "null argument");
+    g->timing = on ? 1 : 0;
+    return TWV_OK;
+}
+extern "C" size_t twv_tacotron_cbhg_grad_workspace_bytes(const twv_tacotron_cbhg_grad* g) { return g ? (size_t)g->ws_floats * 4 : 0; }
+extern "C" const char* twv_tacotron_cbhg_grad_route(const twv_tacotron_cbhg_grad* g) { return g ? g->route.c_str() : ""; }
+
+#define CG_HIPCHK(expr)                                                                                          \
+    do {                                                                                                          \
+        hipError_t e_ = (expr);                                                                                   \
+        if (e_ != hipSuccess) return twv_fail(TWV_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));     \
+    } while (0)
+#define CG_BLASCHK(expr)                                                                                         \
+    do {                                                                                                          \
+        rocblas_status s_ = (expr);                                                                               \
+        if (s_ != rocblas_status_success) return twv_fail(TWV_E_HIP, std::string(#expr) + ": " + rocblas_status_to_string(s_)); \
+    } while (0)
+
+namespace {
+
+// one run's launches: the stream, the sizes and the helpers the encoder and the post net share
+struct CgRun {
+    twv_tacotron_cbhg_grad* g;
+    hipStream_t st;
+    const float* blob;
+    float* grad;
+    CgCarve c;
+    int rows, T;
+    long long wt_used = 0;
+
+    RowsArgs rows_args(const float* X, int ldx, int Cin, int kw, int left, const float* W, int ldw, int ncols, const float* bias) const
+    {
+        RowsArgs a;
+        memset(&a, 0, sizeof(a));
+        a.X = X; a.ldx = ldx; a.Cin = Cin; a.kw = kw; a.left = left; a.W = W; a.ldw = ldw; a.ncols = ncols; a.bias = bias; a.rows = rows; a.T = T;
+        return a;
+    }
+    void launch(const RowsArgs& a) const
+    {
+        hipLaunchKernelGGL(cg_rows_kernel, dim3((rows + kRB - 1) / kRB, (a.ncols + 255) / 256), dim3(256), 0, st, a);
+    }
+    // C (ldc) = (add ? C : 0) + D (rows x ncols, ldd) (*) W^T: the backward of a convolution / dense layer W (kw, Cin, ncols; row stride ldw)
+    // with respect to its input.  The transposed, tap-reversed kernel is laid down in the workspace first.
+    void data_grad(const float* D, int ldd, int ncols, const float* W, int ldw, int Cin, int kw, float* C, int ldc, int add, const float* gate_in = nullptr)
+    {
+        float* Wt = c.wT + wt_used;
+        wt_used += (long long)kw * Cin * ncols;
+        hipLaunchKernelGGL(cg_transpose_kernel, dim3(grid_for((long long)kw * Cin * ncols)), dim3(256), 0, st, W, kw, Cin, ncols, ldw, Wt);
+        RowsArgs a = rows_args(D, ldd, ncols, kw, (kw - 1) - (kw - 1) / 2, Wt, Cin, Cin, nullptr);
+        a.C = C; a.ldc = ldc; a.add = add; a.gate_in = gate_in;
+        launch(a);
+    }
+    // grad[off .. off + K * Nc) = X^T (K x rows) . D (rows x Nc): row-major = rocBLAS (Nc x K) = D-as-stored . X^T
+    rocblas_status wgrad(const float* X, int ldx, int K, const float* D, int ldd, int Nc, long long off, long long nrows) const
+    {
+        const float one = 1.0f, zero = 0.0f;
+        return rocblas_sgemm(g->blas, rocblas_operation_none, rocblas_operation_transpose, Nc, K, (int)nrows, &one, D, ldd, X, ldx, &zero, grad + off, Nc);
+    }
+    // the kernel gradient of a convolution: tap by tap, dW[tap] = X[r + tap - left]^T . D[r] over the rows whose shifted row lies in the same
+    // utterance (the others are zeroed in a copy of D)
+    rocblas_status conv_wgrad(const float* X, int ldx, int Cin, const float* D, int ldd, int Nc, int kw, long long off) const
+    {
+        const int left = (kw - 1) / 2;
+        for (int tap = 0; tap < kw; ++tap) {
+            const int s = tap - left;
+            const long long o = off + (long long)tap * Cin * Nc;
+            if (s <= -T || s >= T) { if (hipMemsetAsync(grad + o, 0, (size_t)Cin * Nc * 4, st) != hipSuccess) return rocblas_status_internal_error; continue; }
+            const float* Dp = D; int ld = ldd;
+            if (s != 0) {
+                hipLaunchKernelGGL(cg_shift_mask_kernel, dim3(grid_for((long long)rows * Nc)), dim3(256), 0, st, D, ldd, rows, T, Nc, s, c.Ds);
+                Dp = c.Ds; ld = Nc;
+            }
+            const long long n = rows - (s < 0 ? -s : s);
+            const rocblas_status rs = s >= 0 ? wgrad(X + (long long)s * ldx, ldx, Cin, Dp, ld, Nc, o, n) : wgrad(X, ldx, Cin, Dp + (long long)(-s) * ld, ld, Nc, o, n);
+            if (rs != rocblas_status_success) return rs;
+        }
+        return rocblas_status_success;
+    }
+    void colsum(const float* D, int ld, int Nc, long long off) const
+    {
+        const int nchunk = (rows + kChunk - 1) / kChunk;
+        hipLaunchKernelGGL(cg_colsum_kernel, dim3((Nc + 63) / 64, nchunk), dim3(256), 0, st, D, ld, rows, Nc, c.partial);
+        FinishArgs f;
+        memset(&f, 0, sizeof(f));
+        f.off[0][0] = off; f.gs = Nc; f.nstat = 1; f.Cn = Nc; f.nchunk = nchunk;
+        hipLaunchKernelGGL(cg_finish_kernel, dim3((Nc + 63) / 64), dim3(64), 0, st, c.partial, f, grad);
+    }
+    // dZ = batch norm / relu (/ max pool) backward of dY against the tape A; the (d_inv, d_shift) pairs land in the groups' blob slots
+    void bn_bwd(const float* dY, int ldy, const float* A, int lda, const Groups& gr, int Cn, int pool, int relu, float* dZ, int ldz) const
+    {
+        const int nchunk = (rows + kChunk - 1) / kChunk;
+        hipLaunchKernelGGL(cg_bn_bwd_kernel, dim3((Cn + 63) / 64, nchunk), dim3(256), 0, st, dY, ldy, A, lda, blob, gr, rows, T, Cn, pool, relu, dZ, ldz, c.partial);
+        FinishArgs f;
+        memset(&f, 0, sizeof(f));
+        for (int q = 0; q < 17; ++q) { f.off[0][q] = gr.inv[q]; f.off[1][q] = gr.shift[q]; }
+        f.gs = gr.gs; f.nstat = 2; f.Cn = Cn; f.nchunk = nchunk;
+        hipLaunchKernelGGL(cg_finish_kernel, dim3((Cn + 63) / 64), dim3(64), 0, st, c.partial, f, grad);
+    }
+    hipError_t mark(int i) const
+    {
+        if (!g->timing) return hipSuccess;
+        if (!g->ev[i]) { const hipError_t e = hipEventCreate(&g->ev[i]); if (e != hipSuccess) return e; }
+        return hipEventRecord(g->ev[i], st);
+    }
+};
+
+Groups one_group(long long bn, int Cn)
+{
+    Groups gr;
+    memset(&gr, 0, sizeof(gr));
+    gr.inv[0] = bn; gr.shift[0] = bn + Cn; gr.gs = Cn;
+    return gr;
+}
+
+// the CBHG forward from r.c.X-or-`x` (rows x Cin) to r.c.out, recording; `bh` (N, proj[1]) and `init` (N, 2 kU) may be null
+int cbhg_forward(CgRun& r, const float* x, const float* bh, const float* init, const int32_t* lengths)
+{
+    const TacoCbhgBlob& w = r.g->w;
+    const CgCarve& c = r.c;
+    const float* B = r.blob;
+    const int Cin = w.Cin, CB = w.bank * w.bch, P0 = w.proj[0], P1 = w.proj[1], pl = (w.pw - 1) / 2;
+    const long long rows = r.rows;
+    Groups bank;
+    memset(&bank, 0, sizeof(bank));
+    bank.gs = w.bch;
+    for (int k = 1; k <= w.bank; ++k) {
+        bank.inv[k - 1] = w.bn[k]; bank.shift[k - 1] = w.bn[k] + w.bch;
+        RowsArgs a = r.rows_args(x, Cin, Cin, k, (k - 1) / 2, B + w.W[k], w.bch, w.bch, B + w.b[k]);
+        a.act = 1; a.C = c.bankA + (long long)(k - 1) * w.bch; a.ldc = CB;
+        r.launch(a);
+    }
+    hipLaunchKernelGGL(cg_pool_kernel, dim3(grid_for(rows * CB)), dim3(256), 0, r.st, c.bankA, B, bank, r.rows, r.T, CB, c.pool);
+    {
+        RowsArgs a = r.rows_args(c.pool, CB, CB, w.pw, pl, B + w.pW[0], P0, P0, B + w.pb[0]);
+        a.act = 1; a.C = c.A1; a.ldc = P0; a.Y = c.Y1; a.ldy = P0; a.inv = B + w.pbn[0]; a.shift = B + w.pbn[0] + P0;
+        r.launch(a);
+    }
+    {   // second projection + residual: (proj + inputs) + before_highway
+        RowsArgs a = r.rows_args(c.Y1, P0, P0, w.pw, pl, B + w.pW[1], P1, P1, B + w.pb[1]);
+        a.C = c.A2; a.ldc = P1; a.Y = c.HW0; a.ldy = P1; a.inv = B + w.pbn[1]; a.shift = B + w.pbn[1] + P1;
+        a.add1 = x; a.ld1 = Cin; a.add2 = bh; a.ld2 = P1;
+        r.launch(a);
+    }
+    if (w.has_dense) {
+        RowsArgs a = r.rows_args(c.HW0, P1, P1, 1, 0, B + w.dW, kU, kU, B + w.db);
+        a.C = c.hw[0]; a.ldc = kU;
+        r.launch(a);
+    }
+    for (int i = 0; i < w.depth; ++i) {
+        RowsArgs a = r.rows_args(c.hw[i], kU, kU, 1, 0, B + w.hH[i], kU, kU, B + w.hHb[i]);
+        a.act = 1; a.C = c.Hh[i]; a.ldc = kU;
+        r.launch(a);
+        a = r.rows_args(c.hw[i], kU, kU, 1, 0, B + w.hT[i], kU, kU, B + w.hTb[i]);
+        a.act = 2; a.C = c.Tg[i]; a.ldc = kU;
+        r.launch(a);
+        hipLaunchKernelGGL(cg_highway_kernel, dim3(grid_for(rows * kU)), dim3(256), 0, r.st, c.hw[i], c.Hh[i], c.Tg[i], rows * kU, c.hw[i + 1]);
+    }
+    const float* top = c.hw[w.depth];
+    for (int dr = 0; dr < 2; ++dr) {      // the input halves of both GRU kernels, all rows at once
+        RowsArgs a = r.rows_args(top, kU, kU, 1, 0, B + w.gWg[dr], 2 * kU, 2 * kU, B + w.gbg[dr]);
+        a.C = c.GX + dr * 2 * kU; a.ldc = 4 * kU;
+        r.launch(a);
+        a = r.rows_args(top, kU, kU, 1, 0, B + w.gWc[dr], kU, kU, B + w.gbc[dr]);
+        a.C = c.CX + dr * kU; a.ldc = 2 * kU;
+        r.launch(a);
+    }
+    GruArgs ga;
+    memset(&ga, 0, sizeof(ga));
+    for (int dr = 0; dr < 2; ++dr) {
+        ga.Wg[dr] = B + w.gWg[dr]; ga.Wc[dr] = B + w.gWc[dr];
+        ga.HP[dr] = c.HP[dr]; ga.RU[dr] = c.RU[dr]; ga.CC[dr] = c.CC[dr]; ga.RH[dr] = c.RH[dr]; ga.DG[dr] = c.DG[dr]; ga.DC[dr] = c.DC[dr];
+    }
+    ga.GX = c.GX; ga.CX = c.CX; ga.init = init; ga.lengths = lengths; ga.out = c.out; ga.N = r.g->N; ga.T = r.T;
+    hipLaunchKernelGGL(cg_gru_forward_kernel, dim3(2 * r.g->N), dim3(kGruThreads), (size_t)r.g->lds, r.st, ga);
+    return TWV_OK;
+}
+
+// the CBHG backward from r.c.dOut (rows x 2 kU) to r.c.dX (rows x Cin); phases: marks 1 .. 2 the GRUs, 2 .. 3 the row-wise backward
+int cbhg_backward_data(CgRun& r, const float* x, const int32_t* lengths, float* d_bh, float* d_init)
+{
+    const TacoCbhgBlob& w = r.g->w;
+    const CgCarve& c = r.c;
+    const float* B = r.blob;
+    const int Cin = w.Cin, CB = w.bank * w.bch, P0 = w.proj[0], P1 = w.proj[1];
+    const long long rows = r.rows;
+    GruArgs ga;
+    memset(&ga, 0, sizeof(ga));
+    for (int dr = 0; dr < 2; ++dr) {
+        ga.Wg[dr] = B + w.gWg[dr]; ga.Wc[dr] = B + w.gWc[dr];
+        ga.HP[dr] = c.HP[dr]; ga.RU[dr] = c.RU[dr]; ga.CC[dr] = c.CC[dr]; ga.RH[dr] = c.RH[dr]; ga.DG[dr] = c.DG[dr]; ga.DC[dr] = c.DC[dr];
+    }
+    ga.lengths = lengths; ga.dOut = c.dOut; ga.dinit = d_init; ga.N = r.g->N; ga.T = r.T;
+    hipLaunchKernelGGL(cg_gru_backward_kernel, dim3(2 * r.g->N), dim3(kGruThreads), (size_t)r.g->lds, r.st, ga);
+    CG_HIPCHK(hipGetLastError());
+    CG_HIPCHK(r.mark(2));
+    // dx = delta . W_x^T of both kernels and both directions, products over all rows
+    float* dcur = (w.depth & 1) ? c.dhw2 : c.dhw;       // (ping-pong so that the bottom of the highway stack lands in c.dhw)
+    for (int dr = 0; dr < 2; ++dr) {
+        r.data_grad(c.DG[dr], 2 * kU, 2 * kU, B + w.gWg[dr], 2 * kU, kU, 1, dcur, kU, dr);
+        r.data_grad(c.DC[dr], kU, kU, B + w.gWc[dr], kU, kU, 1, dcur, kU, 1);
+    }
+    for (int i = w.depth - 1; i >= 0; --i) {
+        float* dnext = dcur == c.dhw ? c.dhw2 : c.dhw;
+        hipLaunchKernelGGL(cg_highway_bwd_kernel, dim3(grid_for(rows * kU)), dim3(256), 0, r.st, dcur, c.hw[i], c.Hh[i], c.Tg[i], rows * kU, c.DHT[i], dnext);
+        r.data_grad(c.DHT[i], 2 * kU, kU, B + w.hH[i], kU, kU, 1, dnext, kU, 1);
+        r.data_grad(c.DHT[i] + kU, 2 * kU, kU, B + w.hT[i], kU, kU, 1, dnext, kU, 1);
+        dcur = dnext;
+    }
+    // dcur == c.dhw: the cotangent of the highway stack's input
+    const float* dHW0 = c.dhw;
+    if (w.has_dense) { r.data_grad(c.dhw, kU, kU, B + w.dW, kU, P1, 1, c.dHW0, P1, 0); dHW0 = c.dHW0; }
+    if (d_bh) hipLaunchKernelGGL(cg_utterance_sum_kernel, dim3((r.g->N * P1 + 255) / 256), dim3(256), 0, r.st, dHW0, r.g->N, r.T, P1, d_bh);
+    r.bn_bwd(dHW0, P1, c.A2, P1, one_group(w.pbn[1], P1), P1, 0, 0, c.dZ2, P1);
+    r.data_grad(c.dZ2, P1, P1, B + w.pW[1], P1, P0, w.pw, c.dY1, P0, 0);
+    r.bn_bwd(c.dY1, P0, c.A1, P0, one_group(w.pbn[0], P0), P0, 0, 1, c.dZ1, P0);
+    r.data_grad(c.dZ1, P0, P0, B + w.pW[0], P0, CB, w.pw, c.dpool, CB, 0);
+    Groups bank;
+    memset(&bank, 0, sizeof(bank));
+    bank.gs = w.bch;
+    for (int k = 1; k <= w.bank; ++k) { bank.inv[k - 1] = w.bn[k]; bank.shift[k - 1] = w.bn[k] + w.bch; }
+    r.bn_bwd(c.dpool, CB, c.bankA, CB, bank, CB, 1, 1, c.dZb, CB);
+    // d_x: the residual's share, then the bank's convolutions in order
+    CG_HIPCHK(hipMemcpy2DAsync(c.dX, (size_t)Cin * 4, dHW0, (size_t)P1 * 4, (size_t)Cin * 4, (size_t)rows, hipMemcpyDeviceToDevice, r.st));
+    for (int k = 1; k <= w.bank; ++k) r.data_grad(c.dZb + (long long)(k - 1) * w.bch, CB, w.bch, B + w.W[k], w.bch, Cin, k, c.dX, Cin, 1);
+    (void)x;
+    CG_HIPCHK(hipGetLastError());
+    return TWV_OK;
+}
+
+// every kernel / bias gradient of the CBHG from the tape and the deltas
+int cbhg_weight_grads(CgRun& r, const float* x)
+{
+    const TacoCbhgBlob& w = r.g->w;
+    const CgCarve& c = r.c;
+    const int Cin = w.Cin, CB = w.bank * w.bch, P0 = w.proj[0], P1 = w.proj[1];
+    const long long rows = r.rows;
+    const float* top = c.hw[w.depth];
+    for (int dr = 0; dr < 2; ++dr) {
+        CG_BLASCHK(r.wgrad(top, kU, kU, c.DG[dr], 2 * kU, 2 * kU, w.gWg[dr], rows));
+        CG_BLASCHK(r.wgrad(c.HP[dr], kU, kU, c.DG[dr], 2 * kU, 2 * kU, w.gWg[dr] + (long long)kU * 2 * kU, rows));
+        r.colsum(c.DG[dr], 2 * kU, 2 * kU, w.gbg[dr]);
+        CG_BLASCHK(r.wgrad(top, kU, kU, c.DC[dr], kU, kU, w.gWc[dr], rows));
+        CG_BLASCHK(r.wgrad(c.RH[dr], kU, kU, c.DC[dr], kU, kU, w.gWc[dr] + (long long)kU * kU, rows));
+        r.colsum(c.DC[dr], kU, kU, w.gbc[dr]);
+    }
+    for (int i = 0; i < w.depth; ++i) {
+        CG_BLASCHK(r.wgrad(c.hw[i], kU, kU, c.DHT[i], 2 * kU, kU, w.hH[i], rows)); r.colsum(c.DHT[i], 2 * kU, kU, w.hHb[i]);
+        CG_BLASCHK(r.wgrad(c.hw[i], kU, kU, c.DHT[i] + kU, 2 * kU, kU, w.hT[i], rows)); r.colsum(c.DHT[i] + kU, 2 * kU, kU, w.hTb[i]);
+    }
+    if (w.has_dense) { CG_BLASCHK(r.wgrad(c.HW0, P1, P1, c.dhw, kU, kU, w.dW, rows)); r.colsum(c.dhw, kU, kU, w.db); }
+    CG_BLASCHK(r.conv_wgrad(c.Y1, P0, P0, c.dZ2, P1, P1, w.pw, w.pW[1])); r.colsum(c.dZ2, P1, P1, w.pb[1]);
+    CG_BLASCHK(r.conv_wgrad(c.pool, CB, CB, c.dZ1, P0, P0, w.pw, w.pW[0])); r.colsum(c.dZ1, P0, P0, w.pb[0]);
+    for (int k = 1; k <= w.bank; ++k) {
+        const float* D = c.dZb + (long long)(k - 1) * w.bch;
+        CG_BLASCHK(r.conv_wgrad(x, Cin, Cin, D, CB, w.bch, k, w.W[k])); r.colsum(D, CB, w.bch, w.b[k]);
+    }
+    CG_HIPCHK(hipGetLastError());
+    return TWV_OK;
+}
+
+int cg_begin(twv_tacotron_cbhg_grad* g, CgRun& r, const float* blob, void* workspace, int32_t* status, void* stream, float* grad_blob)
+{
+    r.g = g; r.st = (hipStream_t)stream; r.blob = blob; r.grad = grad_blob; r.rows = g->N * g->T; r.T = g->T;
+    if (!g->blas) {
+        CG_BLASCHK(rocblas_create_handle(&g->blas));
+        CG_BLASCHK(rocblas_set_atomics_mode(g->blas, rocblas_atomics_not_allowed));     // the same bits on every run
+    }
+    CG_BLASCHK(rocblas_set_stream(g->blas, r.st));
+    CG_BLASCHK(rocblas_set_pointer_mode(g->blas, rocblas_pointer_mode_host));
+    cg_carve(g, (float*)workspace, r.c);
+    CG_HIPCHK(hipMemsetAsync(status, 0, 16, r.st));
+    CG_HIPCHK(hipMemsetAsync(grad_blob, 0, (size_t)g->w.blob_floats * 4, r.st));
+    CG_HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(cg_gru_forward_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, g->lds));
+    CG_HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(cg_gru_backward_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, g->lds));
+    return TWV_OK;
+}
+
+}  // namespace
+
+extern "C" int twv_tacotron_encoder_grad_run(twv_tacotron_cbhg_grad* g, const float* blob, const int32_t* tokens, const int32_t* lengths,
+                                             const float* before_highway, const float* rnn_init, const float* mask1, const float* mask2,
+                                             const float* d_memory, void* workspace, int32_t* status, void* stream, float* memory_out,
+                                             float* grad_blob, float* d_before_highway, float* d_rnn_init)
+{
+    if (!g || !blob || !tokens || !lengths || !d_memory || !workspace || !status || !memory_out || !grad_blob) return twv_fail(TWV_E_INVALID, "null argument");
+    if (g->which != TWV_CBHG_ENCODER) return twv_fail(TWV_E_INVALID, "the handle was created for the post net");
+    if ((before_highway && !d_before_highway) || (rnn_init && !d_rnn_init)) return twv_fail(TWV_E_INVALID, "null argument: before_highway / rnn_init need their d_ outputs");
+    CgRun r;
+    const int rc = cg_begin(g, r, blob, workspace, status, stream, grad_blob);
+    if (rc != TWV_OK) return rc;
+    const TacoCbhgBlob& w = g->w;
+    const CgCarve& c = r.c;
+    const int E = g->E, P0 = g->P0, P1 = w.Cin, rows = r.rows;
+    // ---- (a) recording forward
+    CG_HIPCHK(r.mark(0));
+    hipLaunchKernelGGL(cg_embed_kernel, dim3(grid_for((long long)rows * E)), dim3(256), 0, r.st, blob + w.emb, tokens, rows, E, g->d.n_symbols, c.E);
+    {
+        RowsArgs a = r.rows_args(c.E, E, E, 1, 0, blob + w.pW1, P0, P0, blob + w.pb1);
+        a.act = 1; a.mask = mask1; a.gate_out = c.G1; a.C = c.H1; a.ldc = P0;
+        r.launch(a);
+        a = r.rows_args(c.H1, P0, P0, 1, 0, blob + w.pW2, P1, P1, blob + w.pb2);
+        a.act = 1; a.mask = mask2; a.gate_out = c.G2; a.C = c.X; a.ldc = P1;
+        r.launch(a);
+    }
+    int e = cbhg_forward(r, c.X, before_highway, rnn_init, lengths);
+    if (e != TWV_OK) return e;
+    CG_HIPCHK(hipMemcpyAsync(memory_out, c.out, (size_t)rows * 2 * kU * 4, hipMemcpyDeviceToDevice, r.st));
+    CG_HIPCHK(hipGetLastError());
+    // ---- (b) the GRUs backward through time, (c) the row-wise backward
+    CG_HIPCHK(r.mark(1));
+    CG_HIPCHK(hipMemcpyAsync(c.dOut, d_memory, (size_t)rows * 2 * kU * 4, hipMemcpyDeviceToDevice, r.st));
+    e = cbhg_backward_data(r, c.X, lengths, before_highway ? d_before_highway : nullptr, rnn_init ? d_rnn_init : nullptr);
+    if (e != TWV_OK) return e;
+    hipLaunchKernelGGL(cg_mul_kernel, dim3(grid_for((long long)rows * P1)), dim3(256), 0, r.st, c.dX, c.G2, (long long)rows * P1);
+    r.data_grad(c.dX, P1, P1, blob + w.pW2, P1, P0, 1, c.dH1, P0, 0, c.G1);
+    r.data_grad(c.dH1, P0, P0, blob + w.pW1, P0, E, 1, c.dE, E, 0);
+    CG_HIPCHK(hipGetLastError());
+    CG_HIPCHK(r.mark(3));
+    // ---- (d) weight gradients
+    e = cbhg_weight_grads(r, c.X);
+    if (e != TWV_OK) return e;
+    CG_BLASCHK(r.wgrad(c.H1, P0, P0, c.dX, P1, P1, w.pW2, rows)); r.colsum(c.dX, P1, P1, w.pb2);
+    CG_BLASCHK(r.wgrad(c.E, E, E, c.dH1, P0, P0, w.pW1, rows)); r.colsum(c.dH1, P0, P0, w.pb1);
+    hipLaunchKernelGGL(cg_embed_grad_kernel, dim3(g->d.n_symbols), dim3(256), 0, r.st, c.dE, tokens, rows, E, grad_blob + w.emb);
+    CG_HIPCHK(hipGetLastError());
+    CG_HIPCHK(r.mark(4));
+    return TWV_OK;
+}
+
+extern "C" int twv_tacotron_postnet_grad_run(twv_tacotron_cbhg_grad* g, const float* blob, const float* mel, const float* d_linear, void* workspace,
+                                             int32_t* status, void* stream, float* linear_out, float* grad_blob, float* d_mel)
+{
+    if (!g || !blob || !mel || !d_linear || !workspace || !status || !linear_out || !grad_blob || !d_mel) return twv_fail(TWV_E_INVALID, "null argument");
+    if (g->which != TWV_CBHG_POST) return twv_fail(TWV_E_INVALID, "the handle was created for the encoder");
+    CgRun r;
+    const int rc = cg_begin(g, r, blob, workspace, status, stream, grad_blob);
+    if (rc != TWV_OK) return rc;
+    const TacoCbhgBlob& w = g->w;
+    const CgCarve& c = r.c;
+    const int F = g->F, M = w.Cin, rows = r.rows;
+    CG_HIPCHK(r.mark(0));
+    int e = cbhg_forward(r, mel, nullptr, nullptr, nullptr);
+    if (e != TWV_OK) return e;
+    {
+        RowsArgs a = r.rows_args(c.out, 2 * kU, 2 * kU, 1, 0, blob + w.lW, F, F, blob + w.lb);
+        a.C = linear_out; a.ldc = F;
+        r.launch(a);
+    }
+    CG_HIPCHK(hipGetLastError());
+    CG_HIPCHK(r.mark(1));
+    r.data_grad(d_linear, F, F, blob + w.lW, F, 2 * kU, 1, c.dOut, 2 * kU, 0);
+    e = cbhg_backward_data(r, mel, nullptr, nullptr, nullptr);
+    if (e != TWV_OK) return e;
+    CG_HIPCHK(hipMemcpyAsync(d_mel, c.dX, (size_t)rows * M * 4, hipMemcpyDeviceToDevice, r.st));
+    CG_HIPCHK(r.mark(3));
+    e = cbhg_weight_grads(r, mel);
+    if (e != TWV_OK) return e;
+    CG_BLASCHK(r.wgrad(c.out, 2 * kU, 2 * kU, d_linear, F, F, w.lW, rows)); r.colsum(d_linear, F, F, w.lb);
+    CG_HIPCHK(hipGetLastError());
+    CG_HIPCHK(r.mark(4));
+    return TWV_OK;
+}
+
+// after a run with timing on: waits for it and gives the milliseconds of (a) the recording forward, (b) the GRUs' backward through time,
+// (c) the row-wise backward (pointwise kernels and the dx products), (d) the weight-gradient products
+extern "C" int twv_tacotron_cbhg_grad_phase_ms(twv_tacotron_cbhg_grad* g, double* ms4)
+{
+    if (!g || !ms4) return twv_fail(TWV_E_INVALID, "null argument");
+    if (!g->ev[4]) return twv_fail(TWV_E_INVALID, "no run with timing on (twv_tacotron_cbhg_grad_set_timing) has been made");
+    CG_HIPCHK(hipEventSynchronize(g->ev[4]));
+    for (int i = 0; i < 4; ++i) { float ms = 0.0f; CG_HIPCHK(hipEventElapsedTime(&ms, g->ev[i], g->ev[i + 1])); ms4[i] = (double)ms; }
+    return TWV_OK;
+}
+
+extern "C" int twv_tacotron_linear_loss_grad(const float* linear, const float* linear_targets, const float* loss_coeff, int batch, int t_out,
+                                             int num_freq, int prioritize_loss, double sample_rate, float* d_linear, void* stream)
+{
+    if (!linear || !linear_targets || !loss_coeff || !d_linear) return twv_fail(TWV_E_INVALID, "null argument");
+    if (batch < 1 || t_out < 1 || num_freq < 1) return twv_fail(TWV_E_INVALID, "batch, t_out and num_freq must be >= 1");
+    if (prioritize_loss && !(sample_rate > 0.0)) return twv_fail(TWV_E_INVALID, "prioritize_loss needs sample_rate > 0");
+    const long long per = (long long)t_out * num_freq, total = per * batch;
+    int lo = 0, hi = 0;
+    double w0 = 1.0 / (double)total, w1 = 0.0;
+    if (prioritize_loss) {              // tacotron.py:269-272, the band exactly as twv_tacotron_loss computes it
+        const int hi_ = (int)(5000 / (sample_rate * 0.5) * num_freq), lo_ = (int)(165 / (sample_rate * 0.5) * num_freq);
+        lo = lo_ < 0 ? 0 : (lo_ > num_freq ? num_freq : lo_);
+        hi = hi_ < lo ? lo : (hi_ > num_freq ? num_freq : hi_);
+        w0 = 0.5 / (double)total;
+        w1 = hi > lo ? 0.5 / ((double)batch * t_out * (hi - lo)) : 0.0;
+    }
+    hipLaunchKernelGGL(cg_linear_loss_grad_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, linear, linear_targets, loss_coeff, per,
+                       num_freq, lo, hi, (float)w0, (float)w1, total, d_linear);
+    CG_HIPCHK(hipGetLastError());
+    return TWV_OK;
+}

@@ -162,6 +162,28 @@ def decoder_grad_layout(specs):
     return out
 
 
+def _grad_layout(specs, pick):
+    out, off = [], 0
+    for i, (n, shp) in enumerate(specs):
+        bn = n.endswith("batch_normalization")
+        size = 2 * shp[1] if bn else int(np.prod(shp))
+        if pick(i, n):
+            out.append((n, off, (2, shp[1]) if bn else tuple(shp)))
+        off += size
+    return out
+
+
+def encoder_grad_layout(specs):
+    """(name, offset in the canonical blob, shape) of the tensors Tacotron.encoder_grad differentiates: embedding, prenet/*, encoder_cbhg/*.
+    A batch_normalization entry is the (2, C) slot of the derived (inv, shift) pair (flatten); encoder_grad turns it into (d_gamma, d_beta)."""
+    return _grad_layout(specs, lambda i, n: n == "embedding" or n.startswith("prenet/") or n.startswith("encoder_cbhg/"))
+
+
+def postnet_grad_layout(specs):
+    """the same for Tacotron.postnet_grad: post_cbhg/* and the linear-spectrogram layer (the last dense layer of the spec list)"""
+    return _grad_layout(specs, lambda i, n: n.startswith("post_cbhg/") or i >= len(specs) - 2)
+
+
 def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
@@ -228,6 +250,8 @@ class Tacotron(object):
     def __del__(self):
         try:
             self._drop_grad_handle()
+            for which in (0, 1):
+                self._drop_cbhg_handle(which)
             if getattr(self, "_h", None):
                 self._L.twv_tacotron_destroy(self._h)
                 self._h = None
@@ -236,6 +260,8 @@ class Tacotron(object):
 
     def load_weights(self, tensors):
         blob = flatten(self.specs, tensors)
+        # the raw (4, C) batch norm tensors: encoder_grad / postnet_grad turn the derived pair's gradient into (d_gamma, d_beta) with them
+        self._bn_raw = {n: np.asarray(tensors[n], np.float64) for n, _ in self.specs if n.endswith("batch_normalization")}
         assert blob.size == self._L.twv_tacotron_blob_floats(self._h), (blob.size, self._L.twv_tacotron_blob_floats(self._h))
         with torch.cuda.device(self.device):
             dblob = self._blob = torch.from_numpy(blob).to(self.device)     # kept: decoder_grad differentiates the canonical tensors
@@ -325,7 +351,7 @@ class Tacotron(object):
         return out
 
     def workspace_view(self, batch, t_in, which):
-        """the piece `which` ("memory", "keys", "decoder_init") of the workspace the last pass of (batch, t_in) used, as a flat view"""
+        """the piece `which` ("memory", "keys", "decoder_init"; "before_highway", "encoder_rnn_init" of a multi-speaker model) of the workspace the last pass of (batch, t_in) used, as a flat view"""
         off, n = C.c_longlong(), C.c_longlong()
         _lib.check(self._L.twv_tacotron_workspace_view(self._h, int(batch), int(t_in), which.encode(), C.byref(off), C.byref(n)))
         return self._ws[off.value:off.value + n.value]
@@ -389,6 +415,160 @@ class Tacotron(object):
         if getattr(self, "_grad", None):
             self._L.twv_tacotron_decoder_grad_destroy(self._grad)
         self._grad, self._grad_key = None, None
+
+    def _drop_cbhg_handle(self, which):
+        g = getattr(self, "_cbhg", None)
+        if g and g[which][1]:
+            self._L.twv_tacotron_cbhg_grad_destroy(g[which][1])
+            g[which] = [None, None, None]
+
+    def _cbhg_handle(self, which, N, T):
+        """the gradient handle and workspace of (encoder / post net, batch, rows an utterance), kept until the sizes change"""
+        if getattr(self, "_cbhg", None) is None:
+            self._cbhg = [[None, None, None], [None, None, None]]
+        if self._cbhg[which][0] != (N, T):
+            self._drop_cbhg_handle(which)
+            g = C.c_void_p()
+            _lib.check(self._L.twv_tacotron_cbhg_grad_create(self._h, which, N, T, C.byref(g)))
+            ws = torch.empty(self._L.twv_tacotron_cbhg_grad_workspace_bytes(g) // 4, dtype=torch.float32, device=self.device)
+            self._cbhg[which] = [(N, T), g, ws]
+        return self._cbhg[which][1], self._cbhg[which][2]
+
+    def cbhg_grad_route(self, which):
+        """the label of the gradient kernels of the last encoder_grad (which = "encoder") / postnet_grad ("post") call ('' before one)"""
+        g = getattr(self, "_cbhg", None)
+        i = {"encoder": 0, "post": 1}[which]
+        return self._L.twv_tacotron_cbhg_grad_route(g[i][1]).decode() if g and g[i][1] else ""
+
+    def _named_grads(self, grad, layout):
+        """the blob-shaped gradient as a dict by checkpoint name; a batch norm's (d_inv, d_shift) becomes (d_gamma, d_beta), float64 inside:
+        inv = gamma rsqrt(var + eps), shift = beta - mean inv  =>  d_gamma = rsqrt(var + eps) (d_inv - mean d_shift), d_beta = d_shift"""
+        out = {}
+        for name, off, shp in layout:
+            t = grad[off:off + int(np.prod(shp))].view(*shp)
+            if name.endswith("batch_normalization"):
+                raw = self._bn_raw[name]
+                pair = t.cpu().numpy().astype(np.float64)
+                rs = 1.0 / np.sqrt(raw[3] + np.float64(BN_EPS))
+                gb = np.stack([rs * (pair[0] - raw[2] * pair[1]), pair[1]])
+                t = torch.from_numpy(gb.astype(np.float32)).to(self.device)
+            out[name] = t
+        return out
+
+    def linear_loss_cotangent(self, linear_targets, loss_coeff=None):
+        """d(linear term of add_loss) / d linear_outputs on the last teacher-forced forward_targets pass (tacotron.py:258-282), a
+        (N, T_out, num_freq) device tensor: sign(linear - target) * loss_coeff[n] / (N T_out F), with hp.prioritize_loss half of it
+        once more over the priority band (reads hp.prioritize_loss, hp.sample_rate, hp.num_freq as add_loss does)."""
+        hp = self._hparams
+        self._forced_pass("linear_loss_cotangent")
+        lin = getattr(self, "linear_outputs", None)
+        if lin is None:
+            raise ValueError("linear_loss_cotangent needs a forward_targets pass with teacher_forced=True and want_linear=True first")
+        N, TO, F = (int(v) for v in lin.shape)
+        co = np.ones(N, np.float32) if loss_coeff is None else np.asarray(loss_coeff, np.float32).reshape(-1)
+        if co.shape != (N,):
+            raise ValueError("loss_coeff must hold one factor per utterance (%d), got shape %s" % (N, co.shape))
+        with torch.cuda.device(self.device):
+            if not torch.is_tensor(linear_targets):
+                linear_targets = torch.from_numpy(np.ascontiguousarray(linear_targets, np.float32))
+            lt = linear_targets.to(device=self.device, dtype=torch.float32).contiguous()
+            if tuple(lt.shape) != (N, TO, F):
+                raise ValueError("linear_targets must be %s, got %s" % ((N, TO, F), tuple(lt.shape)))
+            co = torch.from_numpy(co).to(self.device)
+            out = torch.empty_like(lin)
+            _lib.check(self._L.twv_tacotron_linear_loss_grad(_ptr(lin), _ptr(lt), _ptr(co), N, TO, F, 1 if hp.prioritize_loss else 0,
+                                                             float(hp.sample_rate), _ptr(out), _stream()))
+        return out
+
+    def postnet_grad(self, d_linear, mel=None):
+        """The vector-Jacobian product of the post net (post CBHG + the linear-spectrogram layer): d_linear (N, T_out, num_freq) is the
+        cotangent on linear_outputs; mel (N, T_out, num_mels) the post net's input, by default the mel_outputs of the last teacher-forced
+        forward_targets pass.  Returns a dict: the gradient of every post_cbhg/* tensor and of the linear layer by name (batch norms as
+        (2, C) = d_gamma, d_beta), "d_mel" (the cotangent on mel) and "linear", the recorded forward's output."""
+        hp = self._hparams
+        mel0, _ = self._forced_pass("postnet_grad")
+        if getattr(self, "_blob", None) is None:
+            raise ValueError("postnet_grad needs load_weights first")
+        with torch.cuda.device(self.device):
+            mel = mel0 if mel is None else (mel if torch.is_tensor(mel) else torch.from_numpy(np.ascontiguousarray(mel, np.float32)))
+            mel = mel.to(device=self.device, dtype=torch.float32).contiguous()
+            N, TO, M = (int(v) for v in mel.shape)
+            if not torch.is_tensor(d_linear):
+                d_linear = torch.from_numpy(np.ascontiguousarray(d_linear, np.float32))
+            dl = d_linear.to(device=self.device, dtype=torch.float32).contiguous()
+            if M != hp.num_mels or tuple(dl.shape) != (N, TO, hp.num_freq):
+                raise ValueError("mel must be (N, T_out, %d) and d_linear (N, T_out, %d), got %s and %s" % (hp.num_mels, hp.num_freq, tuple(mel.shape), tuple(dl.shape)))
+            g, ws = self._cbhg_handle(1, N, TO)
+            lin = torch.empty((N, TO, hp.num_freq), dtype=torch.float32, device=self.device)
+            grad = torch.empty_like(self._blob)
+            d_mel = torch.empty_like(mel)
+            status = torch.zeros(4, dtype=torch.int32, device=self.device)
+            _lib.check(self._L.twv_tacotron_postnet_grad_run(g, _ptr(self._blob), _ptr(mel), _ptr(dl), _ptr(ws), _ptr(status), _stream(),
+                                                             _ptr(lin), _ptr(grad), _ptr(d_mel)))
+            out = self._named_grads(grad, postnet_grad_layout(self.specs))
+        out["d_mel"], out["linear"] = d_mel, lin
+        return out
+
+    def encoder_grad(self, d_memory, prenet_masks=None):
+        """The vector-Jacobian product of the encoder (embedding, prenet, encoder CBHG) of the last forward_targets(teacher_forced=True)
+        pass: d_memory (N, T_in, 2 * enc_rnn_size) is the cotangent on the encoder output (decoder_grad's "d_memory"); tokens, lengths and,
+        for a multi-speaker model, before_highway and the GRUs' initial states are read from that pass.  prenet_masks: None (the evaluation
+        graph) or two (N, T_in, enc_prenet_sizes[i]) arrays of multipliers after the prenet's relus.  Returns a dict: the gradient of
+        embedding, prenet/* and encoder_cbhg/* by name (batch norms as (2, C) = d_gamma, d_beta), "memory" (the recorded output) and, for a
+        multi-speaker model, "d_before_highway" (N, enc_prenet_sizes[1]) and "d_encoder_rnn_init" (N, 2 * enc_rnn_size)."""
+        hp = self._hparams
+        self._forced_pass("encoder_grad")
+        if getattr(self, "_blob", None) is None:
+            raise ValueError("encoder_grad needs load_weights first")
+        N, T = (int(v) for v in self.inputs.shape)
+        ENC, P = 2 * hp.enc_rnn_size, hp.enc_prenet_sizes
+        with torch.cuda.device(self.device):
+            if not torch.is_tensor(d_memory):
+                d_memory = torch.from_numpy(np.ascontiguousarray(d_memory, np.float32))
+            dm = d_memory.to(device=self.device, dtype=torch.float32).contiguous()
+            if tuple(dm.shape) != (N, T, ENC):
+                raise ValueError("d_memory must be %s, got %s" % ((N, T, ENC), tuple(dm.shape)))
+            masks = [None, None]
+            if prenet_masks is not None:
+                for i in range(2):
+                    m = prenet_masks[i]
+                    m = m if torch.is_tensor(m) else torch.from_numpy(np.ascontiguousarray(m, np.float32))
+                    masks[i] = m.to(device=self.device, dtype=torch.float32).contiguous()
+                    if tuple(masks[i].shape) != (N, T, P[i]):
+                        raise ValueError("prenet_masks[%d] must be %s, got %s" % (i, (N, T, P[i]), tuple(masks[i].shape)))
+            bh = init = d_bh = d_init = None
+            if self.num_speakers > 1:
+                bh, init = self.workspace_view(N, T, "before_highway"), self.workspace_view(N, T, "encoder_rnn_init")
+                d_bh = torch.empty((N, P[1]), dtype=torch.float32, device=self.device)
+                d_init = torch.empty((N, ENC), dtype=torch.float32, device=self.device)
+            g, ws = self._cbhg_handle(0, N, T)
+            memory = torch.empty((N, T, ENC), dtype=torch.float32, device=self.device)
+            grad = torch.empty_like(self._blob)
+            status = torch.zeros(4, dtype=torch.int32, device=self.device)
+            _lib.check(self._L.twv_tacotron_encoder_grad_run(g, _ptr(self._blob), _ptr(self.inputs), _ptr(self.input_lengths), _ptr(bh), _ptr(init),
+                                                             _ptr(masks[0]), _ptr(masks[1]), _ptr(dm), _ptr(ws), _ptr(status), _stream(),
+                                                             _ptr(memory), _ptr(grad), _ptr(d_bh), _ptr(d_init)))
+            out = self._named_grads(grad, encoder_grad_layout(self.specs))
+        out["memory"] = memory
+        if d_bh is not None:
+            out["d_before_highway"], out["d_encoder_rnn_init"] = d_bh, d_init
+        return out
+
+    def loss_gradients(self, linear_targets, loss_coeff=None):
+        """The gradient of add_loss's `loss` (tacotron.py:258-282) on the last forward_targets(teacher_forced=True) pass, in the evaluation
+        graph (inference-mode batch norm, no dropout): linear_loss_cotangent -> postnet_grad -> d_mel = mel_loss_cotangent + the post
+        net's d_mel -> decoder_grad -> encoder_grad.  Returns one dict: every checkpoint tensor's gradient by name (batch norms as (2, C) =
+        d_gamma, d_beta; the speaker table and its dense layers are not differentiated and absent), "d_init" and, for a multi-speaker
+        model, "d_before_highway" and "d_encoder_rnn_init": what the speaker side's gradient starts from."""
+        d_linear = self.linear_loss_cotangent(linear_targets, loss_coeff)
+        post = self.postnet_grad(d_linear)
+        d_mel = self.mel_loss_cotangent(loss_coeff) + post["d_mel"]
+        dec = self.decoder_grad(d_mel)
+        enc = self.encoder_grad(dec["d_memory"])
+        out = {}
+        for part in (enc, dec, post):
+            out.update({k: v for k, v in part.items() if k not in ("memory", "mel", "linear", "d_mel", "d_memory")})
+        return out
 
     def add_loss(self, linear_targets, loss_coeff=None):
         """tacotron.py:258-282 on the outputs of the last forward_targets pass: sets `.loss`, `.mel_loss`, `.linear_loss` and
