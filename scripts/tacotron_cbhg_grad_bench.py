@@ -98,7 +98,7 @@ for N in [int(b) for b in args.batches.split(",")]:
     lnd = torch.from_numpy(ln.astype(np.int64)).cuda()
     for side, which, run, Tn in (("encoder", 0, lambda: m.encoder_grad(d_mem), T), ("post net", 1, lambda: m.postnet_grad(d_lin), TO)):
         got = run()
-        g = m._cbhg[which][1]
+        g = m._grad_cache["encoder" if which == 0 else "post"][1]
         _lib.check(L.twv_tacotron_cbhg_grad_set_timing(g, 1))
         phases = []
 

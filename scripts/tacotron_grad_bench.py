@@ -94,13 +94,13 @@ for N in [int(b) for b in args.batches.split(",")]:
     forced_ms = med(lambda: m.forward_targets(tok, ln, spk, tg, teacher_forced=True), args.passes)
     cot = m.mel_loss_cotangent()
     got = m.decoder_grad(cot)
-    _lib.check(L.twv_tacotron_decoder_grad_set_timing(m._grad, 1))
+    _lib.check(L.twv_tacotron_decoder_grad_set_timing(m._grad_cache["decoder"][1], 1))
     phases = []
 
     def one():
         m.decoder_grad(cot)
         ms = (C.c_double * 3)()
-        _lib.check(L.twv_tacotron_decoder_grad_phase_ms(m._grad, ms))
+        _lib.check(L.twv_tacotron_decoder_grad_phase_ms(m._grad_cache["decoder"][1], ms))
         phases.append(list(ms))
     call_ms = med(one, args.passes)
     ph = np.median(np.asarray(phases[-args.passes:]), axis=0)

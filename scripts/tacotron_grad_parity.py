@@ -1,13 +1,14 @@
 #!/usr/bin/env python
 """Per-tensor error of the Tacotron decoder gradients against the float64 autograd checker (tests/torch_tacotron_grad_ref.py), for every
-case of tests/test_tacotron_grad_gpu.py: e = max|g - g64| / max|g64| for the HIP pass (e_hip) and for the float32 autograd run of the same
+case of tests/tacotron_grad_cases.py: e = max|g - g64| / max|g64| for the HIP pass (e_hip) and for the float32 autograd run of the same
 lines (e_t32), their ratio, and whether the floor of the bar was needed.  Writes --out (default profiles/tacotron_decoder_grad_parity.txt).
 Needs the GPU."""
 import argparse, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np, torch
-import test_tacotron_grad_gpu as TG
+import test_tacotron_grad_gpu as TG        # the device side of a case (_case) and RTOL; the table itself is tests/tacotron_grad_cases.py
+from tacotron_grad_cases import CASES
 from train_cases import FLOOR, RATIO
 from twvk_amd import _lib
 
@@ -17,11 +18,11 @@ args = ap.parse_args()
 assert torch.cuda.is_available(), "a measurement needs the GPU"
 
 lines = ["Tacotron decoder gradients (tg_forward_kernel / tg_backward_kernel + rocBLAS weight products) against the float64 autograd checker",
-         "(scripts/tacotron_grad_parity.py; the cases of tests/test_tacotron_grad_gpu.py)",
+         "(scripts/tacotron_grad_parity.py; the cases of tests/tacotron_grad_cases.py)",
          "library %s on %s" % (_lib.lib().twv_version().decode(), torch.cuda.get_device_name(0)),
          "e = max|g - g64| / max|g64| per tensor; bar e_hip <= max(%g * e_t32, %g); 'floor' = e_hip > %g * e_t32 (the floor carried the tensor)" % (RATIO, FLOOR, RATIO), ""]
 summary = []
-for name in sorted(TG.CASES):
+for name in sorted(CASES):
     c = TG._case(name)
     mel64, g64, rec = c.checker("float64")
     _, g32, _ = c.checker("float32")

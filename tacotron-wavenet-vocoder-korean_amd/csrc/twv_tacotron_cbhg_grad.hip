@@ -15,95 +15,20 @@
 // No workgroup waits for another one: no exchange areas, tickets or grid barriers.  No atomics: two runs give the same bits.  Whatever lies
 // on the path to d_x / d_before_highway / d_rnn_init / the recorded output goes through this file's own row kernel, whose order of additions
 // for a row does not depend on how many rows there are: an utterance's outputs are the same bits alone and inside a batch.
-#include <hip/hip_runtime.h>
-#include <rocblas/rocblas.h>
-#include <stdint.h>
-#include <string.h>
-#include <string>
-#include "../../include/twv_amd.h"
-#include "twv_dev.hpp"
 #include "twv_tacotron_blob.hpp"
+#include "twv_tacotron_grad_common.hpp"
 
 namespace cg {
 
+using namespace tgrad;
+
 constexpr int kU = 128;                              // GRU / highway width: twv_tacotron_create accepts no other enc_rnn_size / post_rnn_size
 constexpr int kGruThreads = 512;
-constexpr int kRB = 8, kKC = 128, kMaxKw = 16;       // the row kernel: rows a block, K chunk in LDS, widest convolution
 constexpr int kChunk = 128;                          // rows per block of the column-statistics kernels
 
-__device__ inline float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 // a workgroup barrier that orders LDS only: __syncthreads() also waits for every global load and store in flight (vmcnt(0)), which in the
 // recurrent kernels are the tape writes and the next step's prefetch
 __device__ inline void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// ---- the row kernel: products over all rows, a convolution of width kw as kw shifted products accumulated in tap order
-//   z[r][j] = bias[j] + sum_tap sum_k X[r + tap - left][k] * W[(tap * Cin + k) * ldw + j]        (rows of another utterance read as zeros)
-//   act 1: v = max(z, 0) * mask, gate_out = z > 0 ? mask : 0 (mask null = ones);  act 2: v = sigmoid(z);  v *= gate_in
-//   C = (add ? C : 0) + v;   Y = v * inv[j] + shift[j] (inv null: v) + add1[r][j] + add2[r / T][j]
-// float64 accumulators, one order of additions per (row, column) whatever the number of rows.
-struct RowsArgs {
-    const float *X, *W, *bias, *mask, *gate_in, *inv, *shift, *add1, *add2;
-    float *C, *gate_out, *Y;
-    int ldx, ldw, ldc, ldy, ld1, ld2, rows, T, Cin, kw, left, ncols, act, add;
-};
-__global__ void __launch_bounds__(256) cg_rows_kernel(RowsArgs a)
-{
-    __shared__ double xs[(kRB + kMaxKw) * kKC];       // rows r0 - left .. r0 + kRB - 1 + right of the chunk, then one row of zeros
-    __shared__ int idx[kRB * kMaxKw];
-    const int tid = threadIdx.x, r0 = blockIdx.x * kRB, nr = min(kRB, a.rows - r0), kw = a.kw, nstage = kRB + kw - 1, zrow = nstage;
-    const int j = blockIdx.y * 256 + tid;
-    for (int i = tid; i < kRB * kw; i += 256) {
-        const int r = i / kw, tap = i - r * kw, row = r0 + r, src = row + tap - a.left;
-        const bool ok = r < nr && src >= 0 && src < a.rows && src / a.T == row / a.T;
-        idx[r * kMaxKw + tap] = (ok ? r + tap : zrow) * kKC;
-    }
-    if (tid < kKC) xs[zrow * kKC + tid] = 0.0;
-    double acc[kRB];
-#pragma unroll
-    for (int r = 0; r < kRB; ++r) acc[r] = 0.0;
-    for (int k0 = 0; k0 < a.Cin; k0 += kKC) {
-        const int kc = min(kKC, a.Cin - k0);
-        __syncthreads();
-        for (int i = tid; i < nstage * kKC; i += 256) {
-            const int s = i / kKC, k = i - s * kKC, src = r0 - a.left + s;
-            xs[i] = (src >= 0 && src < a.rows && k < kc) ? (double)a.X[(long long)src * a.ldx + k0 + k] : 0.0;
-        }
-        __syncthreads();
-        if (j < a.ncols) {
-            for (int tap = 0; tap < kw; ++tap) {
-                int o[kRB];
-#pragma unroll
-                for (int r = 0; r < kRB; ++r) o[r] = idx[r * kMaxKw + tap];
-                const float* wp = a.W + ((long long)tap * a.Cin + k0) * a.ldw + j;
-                for (int k = 0; k < kc; ++k) {
-                    const double w = (double)wp[(long long)k * a.ldw];
-#pragma unroll
-                    for (int r = 0; r < kRB; ++r) acc[r] = fma(w, xs[o[r] + k], acc[r]);
-                }
-            }
-        }
-    }
-    if (j >= a.ncols) return;
-#pragma unroll
-    for (int r = 0; r < kRB; ++r) {
-        if (r >= nr) continue;
-        const long long row = r0 + r;
-        float v = (float)(acc[r] + (a.bias ? (double)a.bias[j] : 0.0));
-        if (a.act == 1) {
-            const float m = a.mask ? a.mask[row * a.ncols + j] : 1.0f;
-            if (a.gate_out) a.gate_out[row * a.ncols + j] = v > 0.0f ? m : 0.0f;
-            v = fmaxf(v, 0.0f) * m;
-        } else if (a.act == 2) v = sigmoidf_(v);
-        if (a.gate_in) v *= a.gate_in[row * a.ncols + j];
-        if (a.C) { const long long o = row * a.ldc + j; a.C[o] = a.add ? a.C[o] + v : v; }
-        if (a.Y) {
-            float y = a.inv ? v * a.inv[j] + a.shift[j] : v;
-            if (a.add1) y = y + a.add1[row * a.ld1 + j];
-            if (a.add2) y = y + a.add2[(row / a.T) * a.ld2 + j];
-            a.Y[row * a.ldy + j] = y;
-        }
-    }
-}
 
 // the kernel of the transposed convolution: Wt[(tap' * ncols + j) * Cin + k] = W[((kw - 1 - tap') * Cin + k) * ldw + j]
 __global__ void cg_transpose_kernel(const float* W, int kw, int Cin, int ncols, int ldw, float* Wt)
@@ -231,10 +156,6 @@ __global__ void cg_highway_bwd_kernel(const float* dy, const float* x, const flo
         dx[i] = d * (1.0f - t);
     }
 }
-__global__ void cg_mul_kernel(float* x, const float* g, long long total)
-{
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) x[i] *= g[i];
-}
 // out[n][j] = sum_t D[n * T + t][j], t in order (float64 inside): d_before_highway
 __global__ void cg_utterance_sum_kernel(const float* D, int N, int T, int Cn, float* out)
 {
@@ -280,9 +201,8 @@ struct GruArgs {
 struct GruLds { int h, g, rh, red, total; };
 __host__ __device__ inline GruLds gru_lds()
 {
-    GruLds c; int u = 0;
-    auto take = [&](int n) { const int o = u; u += (n + 3) & ~3; return o; };
-    c.h = take(kU); c.g = take(2 * kU); c.rh = take(kU); c.red = take(kGruThreads); c.total = u;
+    GruLds c; Take<int> take;
+    c.h = take(kU); c.g = take(2 * kU); c.rh = take(kU); c.red = take(kGruThreads); c.total = take.used;
     return c;
 }
 __device__ inline float sum4(const float* red, int i) { return (red[i] + red[kU + i]) + (red[2 * kU + i] + red[3 * kU + i]); }
@@ -420,8 +340,6 @@ __global__ void __launch_bounds__(kGruThreads) cg_gru_backward_kernel(GruArgs a)
     }
 }
 
-inline int grid_for(long long n) { const long long g = (n + 255) / 256; return (int)(g < 1 ? 1 : (g > 8192 ? 8192 : g)); }
-
 }  // namespace cg
 using namespace cg;
 
@@ -434,25 +352,21 @@ struct CgCarve {
     float *wT;                                          // transposed kernels
     double* partial;
 };
-struct twv_tacotron_cbhg_grad {
+struct twv_tacotron_cbhg_grad : Handle {
     twv_tacotron_dims d;
     TacoCbhgBlob w;
     int which, N, T, E, P0, F;
-    long long ws_floats, wT_floats;
+    long long wT_floats;
     int lds;                       // bytes, both recurrent kernels
-    rocblas_handle blas = nullptr;
-    std::string route;
-    int timing = 0;
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
 };
+using Cg = twv_tacotron_cbhg_grad;
 
 static long long cg_carve(const twv_tacotron_cbhg_grad* g, float* base, CgCarve& c)
 {
     const TacoCbhgBlob& w = g->w;
     const long long rows = (long long)g->N * g->T;
     const int CB = w.bank * w.bch, Cin = w.Cin, P0 = w.proj[0], P1 = w.proj[1];
-    long long used = 0;
-    auto take = [&](long long n) { float* p = base ? base + used : nullptr; used += (n + 3) / 4 * 4; return p; };
+    TakeFloats take{base};
     memset(&c, 0, sizeof(c));
     if (g->which == 0) {
         c.E = take(rows * g->E); c.H1 = take(rows * g->P0); c.G1 = take(rows * g->P0); c.X = take(rows * Cin); c.G2 = take(rows * Cin);
@@ -474,9 +388,8 @@ static long long cg_carve(const twv_tacotron_cbhg_grad* g, float* base, CgCarve&
     const long long nchunk = (rows + kChunk - 1) / kChunk;
     int cmax = 2 * kU;                                  // the widest matrix a column-statistics kernel is run on
     for (int v : {CB, P0, P1, Cin, g->P0, g->F, g->E}) cmax = cmax > v ? cmax : v;
-    used = (used + 1) / 2 * 2;
-    c.partial = reinterpret_cast<double*>(take(nchunk * 2 * cmax * 2));
-    return used;
+    c.partial = reinterpret_cast<double*>(take(nchunk * 2 * cmax * 2));      // (every piece starts at a multiple of four floats)
+    return take.off.used;
 }
 
 static const char* const kCgBuilt = "the CBHG gradient is built for single-speaker and 'deepvoice' models, enc_rnn_size = post_rnn_size = 128 and projection widths up to 16";
@@ -518,31 +431,10 @@ extern "C" int twv_tacotron_cbhg_grad_create(const twv_tacotron* h, int which, i
     *out = g;
     return TWV_OK;
 }
-extern "C" void twv_tacotron_cbhg_grad_destroy(twv_tacotron_cbhg_grad* g)
-{
-    if (g && g->blas) rocblas_destroy_handle(g->blas);
-    if (g) for (hipEvent_t e : g->ev) if (e) (void)hipEventDestroy(e);
-    delete g;
-}
-extern "C" int twv_tacotron_cbhg_grad_set_timing(twv_tacotron_cbhg_grad* g, int on)
-{
-    if (!g) return twv_fail(TWV_E_INVALID, "null argument");
-    g->timing = on ? 1 : 0;
-    return TWV_OK;
-}
+extern "C" void twv_tacotron_cbhg_grad_destroy(twv_tacotron_cbhg_grad* g) { delete g; }
+extern "C" int twv_tacotron_cbhg_grad_set_timing(twv_tacotron_cbhg_grad* g, int on) { return g ? g->set_timing(on) : twv_fail(TWV_E_INVALID, "null argument"); }
 extern "C" size_t twv_tacotron_cbhg_grad_workspace_bytes(const twv_tacotron_cbhg_grad* g) { return g ? (size_t)g->ws_floats * 4 : 0; }
 extern "C" const char* twv_tacotron_cbhg_grad_route(const twv_tacotron_cbhg_grad* g) { return g ? g->route.c_str() : ""; }
-
-#define CG_HIPCHK(expr)                                                                                          \
-    do {                                                                                                          \
-        hipError_t e_ = (expr);                                                                                   \
-        if (e_ != hipSuccess) return twv_fail(TWV_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));     \
-    } while (0)
-#define CG_BLASCHK(expr)                                                                                         \
-    do {                                                                                                          \
-        rocblas_status s_ = (expr);                                                                               \
-        if (s_ != rocblas_status_success) return twv_fail(TWV_E_HIP, std::string(#expr) + ": " + rocblas_status_to_string(s_)); \
-    } while (0)
 
 namespace {
 
@@ -558,15 +450,9 @@ struct CgRun {
 
     RowsArgs rows_args(const float* X, int ldx, int Cin, int kw, int left, const float* W, int ldw, int ncols, const float* bias) const
     {
-        RowsArgs a;
-        memset(&a, 0, sizeof(a));
-        a.X = X; a.ldx = ldx; a.Cin = Cin; a.kw = kw; a.left = left; a.W = W; a.ldw = ldw; a.ncols = ncols; a.bias = bias; a.rows = rows; a.T = T;
-        return a;
+        return tgrad::rows_args(X, ldx, rows, T, Cin, kw, left, W, ldw, ncols, bias);
     }
-    void launch(const RowsArgs& a) const
-    {
-        hipLaunchKernelGGL(cg_rows_kernel, dim3((rows + kRB - 1) / kRB, (a.ncols + 255) / 256), dim3(256), 0, st, a);
-    }
+    void launch(const RowsArgs& a) const { launch_rows<Cg>(st, a); }
     // C (ldc) = (add ? C : 0) + D (rows x ncols, ldd) (*) W^T: the backward of a convolution / dense layer W (kw, Cin, ncols; row stride ldw)
     // with respect to its input.  The transposed, tap-reversed kernel is laid down in the workspace first.
     void data_grad(const float* D, int ldd, int ncols, const float* W, int ldw, int Cin, int kw, float* C, int ldc, int add, const float* gate_in = nullptr)
@@ -578,31 +464,24 @@ struct CgRun {
         a.C = C; a.ldc = ldc; a.add = add; a.gate_in = gate_in;
         launch(a);
     }
-    // grad[off .. off + K * Nc) = X^T (K x rows) . D (rows x Nc): row-major = rocBLAS (Nc x K) = D-as-stored . X^T
-    rocblas_status wgrad(const float* X, int ldx, int K, const float* D, int ldd, int Nc, long long off, long long nrows) const
-    {
-        const float one = 1.0f, zero = 0.0f;
-        return rocblas_sgemm(g->blas, rocblas_operation_none, rocblas_operation_transpose, Nc, K, (int)nrows, &one, D, ldd, X, ldx, &zero, grad + off, Nc);
-    }
     // the kernel gradient of a convolution: tap by tap, dW[tap] = X[r + tap - left]^T . D[r] over the rows whose shifted row lies in the same
     // utterance (the others are zeroed in a copy of D)
-    rocblas_status conv_wgrad(const float* X, int ldx, int Cin, const float* D, int ldd, int Nc, int kw, long long off) const
+    int conv_wgrad(const float* X, int ldx, int Cin, const float* D, int ldd, int Nc, int kw, long long off) const
     {
         const int left = (kw - 1) / 2;
         for (int tap = 0; tap < kw; ++tap) {
             const int s = tap - left;
             const long long o = off + (long long)tap * Cin * Nc;
-            if (s <= -T || s >= T) { if (hipMemsetAsync(grad + o, 0, (size_t)Cin * Nc * 4, st) != hipSuccess) return rocblas_status_internal_error; continue; }
+            if (s <= -T || s >= T) { GRAD_HIPCHK(hipMemsetAsync(grad + o, 0, (size_t)Cin * Nc * 4, st)); continue; }
             const float* Dp = D; int ld = ldd;
             if (s != 0) {
                 hipLaunchKernelGGL(cg_shift_mask_kernel, dim3(grid_for((long long)rows * Nc)), dim3(256), 0, st, D, ldd, rows, T, Nc, s, c.Ds);
                 Dp = c.Ds; ld = Nc;
             }
             const long long n = rows - (s < 0 ? -s : s);
-            const rocblas_status rs = s >= 0 ? wgrad(X + (long long)s * ldx, ldx, Cin, Dp, ld, Nc, o, n) : wgrad(X, ldx, Cin, Dp + (long long)(-s) * ld, ld, Nc, o, n);
-            if (rs != rocblas_status_success) return rs;
+            GRAD_CHK(s >= 0 ? g->wgrad(X + (long long)s * ldx, ldx, Cin, Dp, ld, Nc, o, n) : g->wgrad(X, ldx, Cin, Dp + (long long)(-s) * ld, ld, Nc, o, n));
         }
-        return rocblas_status_success;
+        return TWV_OK;
     }
     void colsum(const float* D, int ld, int Nc, long long off) const
     {
@@ -623,12 +502,6 @@ struct CgRun {
         for (int q = 0; q < 17; ++q) { f.off[0][q] = gr.inv[q]; f.off[1][q] = gr.shift[q]; }
         f.gs = gr.gs; f.nstat = 2; f.Cn = Cn; f.nchunk = nchunk;
         hipLaunchKernelGGL(cg_finish_kernel, dim3((Cn + 63) / 64), dim3(64), 0, st, c.partial, f, grad);
-    }
-    hipError_t mark(int i) const
-    {
-        if (!g->timing) return hipSuccess;
-        if (!g->ev[i]) { const hipError_t e = hipEventCreate(&g->ev[i]); if (e != hipSuccess) return e; }
-        return hipEventRecord(g->ev[i], st);
     }
 };
 
@@ -704,7 +577,7 @@ int cbhg_forward(CgRun& r, const float* x, const float* bh, const float* init, c
 }
 
 // the CBHG backward from r.c.dOut (rows x 2 kU) to r.c.dX (rows x Cin); phases: marks 1 .. 2 the GRUs, 2 .. 3 the row-wise backward
-int cbhg_backward_data(CgRun& r, const float* x, const int32_t* lengths, float* d_bh, float* d_init)
+int cbhg_backward_data(CgRun& r, const int32_t* lengths, float* d_bh, float* d_init)
 {
     const TacoCbhgBlob& w = r.g->w;
     const CgCarve& c = r.c;
@@ -719,8 +592,8 @@ int cbhg_backward_data(CgRun& r, const float* x, const int32_t* lengths, float* 
     }
     ga.lengths = lengths; ga.dOut = c.dOut; ga.dinit = d_init; ga.N = r.g->N; ga.T = r.T;
     hipLaunchKernelGGL(cg_gru_backward_kernel, dim3(2 * r.g->N), dim3(kGruThreads), (size_t)r.g->lds, r.st, ga);
-    CG_HIPCHK(hipGetLastError());
-    CG_HIPCHK(r.mark(2));
+    GRAD_HIPCHK(hipGetLastError());
+    GRAD_CHK(r.g->mark(2));
     // dx = delta . W_x^T of both kernels and both directions, products over all rows
     float* dcur = (w.depth & 1) ? c.dhw2 : c.dhw;       // (ping-pong so that the bottom of the highway stack lands in c.dhw)
     for (int dr = 0; dr < 2; ++dr) {
@@ -748,10 +621,9 @@ int cbhg_backward_data(CgRun& r, const float* x, const int32_t* lengths, float* 
     for (int k = 1; k <= w.bank; ++k) { bank.inv[k - 1] = w.bn[k]; bank.shift[k - 1] = w.bn[k] + w.bch; }
     r.bn_bwd(c.dpool, CB, c.bankA, CB, bank, CB, 1, 1, c.dZb, CB);
     // d_x: the residual's share, then the bank's convolutions in order
-    CG_HIPCHK(hipMemcpy2DAsync(c.dX, (size_t)Cin * 4, dHW0, (size_t)P1 * 4, (size_t)Cin * 4, (size_t)rows, hipMemcpyDeviceToDevice, r.st));
+    GRAD_HIPCHK(hipMemcpy2DAsync(c.dX, (size_t)Cin * 4, dHW0, (size_t)P1 * 4, (size_t)Cin * 4, (size_t)rows, hipMemcpyDeviceToDevice, r.st));
     for (int k = 1; k <= w.bank; ++k) r.data_grad(c.dZb + (long long)(k - 1) * w.bch, CB, w.bch, B + w.W[k], w.bch, Cin, k, c.dX, Cin, 1);
-    (void)x;
-    CG_HIPCHK(hipGetLastError());
+    GRAD_HIPCHK(hipGetLastError());
     return TWV_OK;
 }
 
@@ -764,42 +636,35 @@ int cbhg_weight_grads(CgRun& r, const float* x)
     const long long rows = r.rows;
     const float* top = c.hw[w.depth];
     for (int dr = 0; dr < 2; ++dr) {
-        CG_BLASCHK(r.wgrad(top, kU, kU, c.DG[dr], 2 * kU, 2 * kU, w.gWg[dr], rows));
-        CG_BLASCHK(r.wgrad(c.HP[dr], kU, kU, c.DG[dr], 2 * kU, 2 * kU, w.gWg[dr] + (long long)kU * 2 * kU, rows));
+        GRAD_CHK(r.g->wgrad(top, kU, kU, c.DG[dr], 2 * kU, 2 * kU, w.gWg[dr], rows));
+        GRAD_CHK(r.g->wgrad(c.HP[dr], kU, kU, c.DG[dr], 2 * kU, 2 * kU, w.gWg[dr] + (long long)kU * 2 * kU, rows));
         r.colsum(c.DG[dr], 2 * kU, 2 * kU, w.gbg[dr]);
-        CG_BLASCHK(r.wgrad(top, kU, kU, c.DC[dr], kU, kU, w.gWc[dr], rows));
-        CG_BLASCHK(r.wgrad(c.RH[dr], kU, kU, c.DC[dr], kU, kU, w.gWc[dr] + (long long)kU * kU, rows));
+        GRAD_CHK(r.g->wgrad(top, kU, kU, c.DC[dr], kU, kU, w.gWc[dr], rows));
+        GRAD_CHK(r.g->wgrad(c.RH[dr], kU, kU, c.DC[dr], kU, kU, w.gWc[dr] + (long long)kU * kU, rows));
         r.colsum(c.DC[dr], kU, kU, w.gbc[dr]);
     }
     for (int i = 0; i < w.depth; ++i) {
-        CG_BLASCHK(r.wgrad(c.hw[i], kU, kU, c.DHT[i], 2 * kU, kU, w.hH[i], rows)); r.colsum(c.DHT[i], 2 * kU, kU, w.hHb[i]);
-        CG_BLASCHK(r.wgrad(c.hw[i], kU, kU, c.DHT[i] + kU, 2 * kU, kU, w.hT[i], rows)); r.colsum(c.DHT[i] + kU, 2 * kU, kU, w.hTb[i]);
+        GRAD_CHK(r.g->wgrad(c.hw[i], kU, kU, c.DHT[i], 2 * kU, kU, w.hH[i], rows)); r.colsum(c.DHT[i], 2 * kU, kU, w.hHb[i]);
+        GRAD_CHK(r.g->wgrad(c.hw[i], kU, kU, c.DHT[i] + kU, 2 * kU, kU, w.hT[i], rows)); r.colsum(c.DHT[i] + kU, 2 * kU, kU, w.hTb[i]);
     }
-    if (w.has_dense) { CG_BLASCHK(r.wgrad(c.HW0, P1, P1, c.dhw, kU, kU, w.dW, rows)); r.colsum(c.dhw, kU, kU, w.db); }
-    CG_BLASCHK(r.conv_wgrad(c.Y1, P0, P0, c.dZ2, P1, P1, w.pw, w.pW[1])); r.colsum(c.dZ2, P1, P1, w.pb[1]);
-    CG_BLASCHK(r.conv_wgrad(c.pool, CB, CB, c.dZ1, P0, P0, w.pw, w.pW[0])); r.colsum(c.dZ1, P0, P0, w.pb[0]);
+    if (w.has_dense) { GRAD_CHK(r.g->wgrad(c.HW0, P1, P1, c.dhw, kU, kU, w.dW, rows)); r.colsum(c.dhw, kU, kU, w.db); }
+    GRAD_CHK(r.conv_wgrad(c.Y1, P0, P0, c.dZ2, P1, P1, w.pw, w.pW[1])); r.colsum(c.dZ2, P1, P1, w.pb[1]);
+    GRAD_CHK(r.conv_wgrad(c.pool, CB, CB, c.dZ1, P0, P0, w.pw, w.pW[0])); r.colsum(c.dZ1, P0, P0, w.pb[0]);
     for (int k = 1; k <= w.bank; ++k) {
         const float* D = c.dZb + (long long)(k - 1) * w.bch;
-        CG_BLASCHK(r.conv_wgrad(x, Cin, Cin, D, CB, w.bch, k, w.W[k])); r.colsum(D, CB, w.bch, w.b[k]);
+        GRAD_CHK(r.conv_wgrad(x, Cin, Cin, D, CB, w.bch, k, w.W[k])); r.colsum(D, CB, w.bch, w.b[k]);
     }
-    CG_HIPCHK(hipGetLastError());
+    GRAD_HIPCHK(hipGetLastError());
     return TWV_OK;
 }
 
 int cg_begin(twv_tacotron_cbhg_grad* g, CgRun& r, const float* blob, void* workspace, int32_t* status, void* stream, float* grad_blob)
 {
     r.g = g; r.st = (hipStream_t)stream; r.blob = blob; r.grad = grad_blob; r.rows = g->N * g->T; r.T = g->T;
-    if (!g->blas) {
-        CG_BLASCHK(rocblas_create_handle(&g->blas));
-        CG_BLASCHK(rocblas_set_atomics_mode(g->blas, rocblas_atomics_not_allowed));     // the same bits on every run
-    }
-    CG_BLASCHK(rocblas_set_stream(g->blas, r.st));
-    CG_BLASCHK(rocblas_set_pointer_mode(g->blas, rocblas_pointer_mode_host));
+    GRAD_CHK(g->begin(r.st, status, grad_blob, g->w.blob_floats));
     cg_carve(g, (float*)workspace, r.c);
-    CG_HIPCHK(hipMemsetAsync(status, 0, 16, r.st));
-    CG_HIPCHK(hipMemsetAsync(grad_blob, 0, (size_t)g->w.blob_floats * 4, r.st));
-    CG_HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(cg_gru_forward_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, g->lds));
-    CG_HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(cg_gru_backward_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, g->lds));
+    GRAD_HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(cg_gru_forward_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, g->lds));
+    GRAD_HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(cg_gru_backward_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, g->lds));
     return TWV_OK;
 }
 
@@ -814,13 +679,12 @@ extern "C" int twv_tacotron_encoder_grad_run(twv_tacotron_cbhg_grad* g, const fl
     if (g->which != TWV_CBHG_ENCODER) return twv_fail(TWV_E_INVALID, "the handle was created for the post net");
     if ((before_highway && !d_before_highway) || (rnn_init && !d_rnn_init)) return twv_fail(TWV_E_INVALID, "null argument: before_highway / rnn_init need their d_ outputs");
     CgRun r;
-    const int rc = cg_begin(g, r, blob, workspace, status, stream, grad_blob);
-    if (rc != TWV_OK) return rc;
+    GRAD_CHK(cg_begin(g, r, blob, workspace, status, stream, grad_blob));
     const TacoCbhgBlob& w = g->w;
     const CgCarve& c = r.c;
     const int E = g->E, P0 = g->P0, P1 = w.Cin, rows = r.rows;
     // ---- (a) recording forward
-    CG_HIPCHK(r.mark(0));
+    GRAD_CHK(r.g->mark(0));
     hipLaunchKernelGGL(cg_embed_kernel, dim3(grid_for((long long)rows * E)), dim3(256), 0, r.st, blob + w.emb, tokens, rows, E, g->d.n_symbols, c.E);
     {
         RowsArgs a = r.rows_args(c.E, E, E, 1, 0, blob + w.pW1, P0, P0, blob + w.pb1);
@@ -830,28 +694,25 @@ extern "C" int twv_tacotron_encoder_grad_run(twv_tacotron_cbhg_grad* g, const fl
         a.act = 1; a.mask = mask2; a.gate_out = c.G2; a.C = c.X; a.ldc = P1;
         r.launch(a);
     }
-    int e = cbhg_forward(r, c.X, before_highway, rnn_init, lengths);
-    if (e != TWV_OK) return e;
-    CG_HIPCHK(hipMemcpyAsync(memory_out, c.out, (size_t)rows * 2 * kU * 4, hipMemcpyDeviceToDevice, r.st));
-    CG_HIPCHK(hipGetLastError());
+    GRAD_CHK(cbhg_forward(r, c.X, before_highway, rnn_init, lengths));
+    GRAD_HIPCHK(hipMemcpyAsync(memory_out, c.out, (size_t)rows * 2 * kU * 4, hipMemcpyDeviceToDevice, r.st));
+    GRAD_HIPCHK(hipGetLastError());
     // ---- (b) the GRUs backward through time, (c) the row-wise backward
-    CG_HIPCHK(r.mark(1));
-    CG_HIPCHK(hipMemcpyAsync(c.dOut, d_memory, (size_t)rows * 2 * kU * 4, hipMemcpyDeviceToDevice, r.st));
-    e = cbhg_backward_data(r, c.X, lengths, before_highway ? d_before_highway : nullptr, rnn_init ? d_rnn_init : nullptr);
-    if (e != TWV_OK) return e;
-    hipLaunchKernelGGL(cg_mul_kernel, dim3(grid_for((long long)rows * P1)), dim3(256), 0, r.st, c.dX, c.G2, (long long)rows * P1);
+    GRAD_CHK(r.g->mark(1));
+    GRAD_HIPCHK(hipMemcpyAsync(c.dOut, d_memory, (size_t)rows * 2 * kU * 4, hipMemcpyDeviceToDevice, r.st));
+    GRAD_CHK(cbhg_backward_data(r, lengths, before_highway ? d_before_highway : nullptr, rnn_init ? d_rnn_init : nullptr));
+    launch_mul<Cg>(r.st, c.dX, c.G2, (long long)rows * P1);
     r.data_grad(c.dX, P1, P1, blob + w.pW2, P1, P0, 1, c.dH1, P0, 0, c.G1);
     r.data_grad(c.dH1, P0, P0, blob + w.pW1, P0, E, 1, c.dE, E, 0);
-    CG_HIPCHK(hipGetLastError());
-    CG_HIPCHK(r.mark(3));
+    GRAD_HIPCHK(hipGetLastError());
+    GRAD_CHK(r.g->mark(3));
     // ---- (d) weight gradients
-    e = cbhg_weight_grads(r, c.X);
-    if (e != TWV_OK) return e;
-    CG_BLASCHK(r.wgrad(c.H1, P0, P0, c.dX, P1, P1, w.pW2, rows)); r.colsum(c.dX, P1, P1, w.pb2);
-    CG_BLASCHK(r.wgrad(c.E, E, E, c.dH1, P0, P0, w.pW1, rows)); r.colsum(c.dH1, P0, P0, w.pb1);
+    GRAD_CHK(cbhg_weight_grads(r, c.X));
+    GRAD_CHK(r.g->wgrad(c.H1, P0, P0, c.dX, P1, P1, w.pW2, rows)); r.colsum(c.dX, P1, P1, w.pb2);
+    GRAD_CHK(r.g->wgrad(c.E, E, E, c.dH1, P0, P0, w.pW1, rows)); r.colsum(c.dH1, P0, P0, w.pb1);
     hipLaunchKernelGGL(cg_embed_grad_kernel, dim3(g->d.n_symbols), dim3(256), 0, r.st, c.dE, tokens, rows, E, grad_blob + w.emb);
-    CG_HIPCHK(hipGetLastError());
-    CG_HIPCHK(r.mark(4));
+    GRAD_HIPCHK(hipGetLastError());
+    GRAD_CHK(r.g->mark(4));
     return TWV_OK;
 }
 
@@ -861,31 +722,27 @@ extern "C" int twv_tacotron_postnet_grad_run(twv_tacotron_cbhg_grad* g, const fl
     if (!g || !blob || !mel || !d_linear || !workspace || !status || !linear_out || !grad_blob || !d_mel) return twv_fail(TWV_E_INVALID, "null argument");
     if (g->which != TWV_CBHG_POST) return twv_fail(TWV_E_INVALID, "the handle was created for the encoder");
     CgRun r;
-    const int rc = cg_begin(g, r, blob, workspace, status, stream, grad_blob);
-    if (rc != TWV_OK) return rc;
+    GRAD_CHK(cg_begin(g, r, blob, workspace, status, stream, grad_blob));
     const TacoCbhgBlob& w = g->w;
     const CgCarve& c = r.c;
     const int F = g->F, M = w.Cin, rows = r.rows;
-    CG_HIPCHK(r.mark(0));
-    int e = cbhg_forward(r, mel, nullptr, nullptr, nullptr);
-    if (e != TWV_OK) return e;
+    GRAD_CHK(r.g->mark(0));
+    GRAD_CHK(cbhg_forward(r, mel, nullptr, nullptr, nullptr));
     {
         RowsArgs a = r.rows_args(c.out, 2 * kU, 2 * kU, 1, 0, blob + w.lW, F, F, blob + w.lb);
         a.C = linear_out; a.ldc = F;
         r.launch(a);
     }
-    CG_HIPCHK(hipGetLastError());
-    CG_HIPCHK(r.mark(1));
+    GRAD_HIPCHK(hipGetLastError());
+    GRAD_CHK(r.g->mark(1));
     r.data_grad(d_linear, F, F, blob + w.lW, F, 2 * kU, 1, c.dOut, 2 * kU, 0);
-    e = cbhg_backward_data(r, mel, nullptr, nullptr, nullptr);
-    if (e != TWV_OK) return e;
-    CG_HIPCHK(hipMemcpyAsync(d_mel, c.dX, (size_t)rows * M * 4, hipMemcpyDeviceToDevice, r.st));
-    CG_HIPCHK(r.mark(3));
-    e = cbhg_weight_grads(r, mel);
-    if (e != TWV_OK) return e;
-    CG_BLASCHK(r.wgrad(c.out, 2 * kU, 2 * kU, d_linear, F, F, w.lW, rows)); r.colsum(d_linear, F, F, w.lb);
-    CG_HIPCHK(hipGetLastError());
-    CG_HIPCHK(r.mark(4));
+    GRAD_CHK(cbhg_backward_data(r, nullptr, nullptr, nullptr));
+    GRAD_HIPCHK(hipMemcpyAsync(d_mel, c.dX, (size_t)rows * M * 4, hipMemcpyDeviceToDevice, r.st));
+    GRAD_CHK(r.g->mark(3));
+    GRAD_CHK(cbhg_weight_grads(r, mel));
+    GRAD_CHK(r.g->wgrad(c.out, 2 * kU, 2 * kU, d_linear, F, F, w.lW, rows)); r.colsum(d_linear, F, F, w.lb);
+    GRAD_HIPCHK(hipGetLastError());
+    GRAD_CHK(r.g->mark(4));
     return TWV_OK;
 }
 
@@ -894,10 +751,7 @@ extern "C" int twv_tacotron_postnet_grad_run(twv_tacotron_cbhg_grad* g, const fl
 extern "C" int twv_tacotron_cbhg_grad_phase_ms(twv_tacotron_cbhg_grad* g, double* ms4)
 {
     if (!g || !ms4) return twv_fail(TWV_E_INVALID, "null argument");
-    if (!g->ev[4]) return twv_fail(TWV_E_INVALID, "no run with timing on (twv_tacotron_cbhg_grad_set_timing) has been made");
-    CG_HIPCHK(hipEventSynchronize(g->ev[4]));
-    for (int i = 0; i < 4; ++i) { float ms = 0.0f; CG_HIPCHK(hipEventElapsedTime(&ms, g->ev[i], g->ev[i + 1])); ms4[i] = (double)ms; }
-    return TWV_OK;
+    return g->phase_ms(4, ms4, "twv_tacotron_cbhg_grad_set_timing");
 }
 
 extern "C" int twv_tacotron_linear_loss_grad(const float* linear, const float* linear_targets, const float* loss_coeff, int batch, int t_out,
@@ -918,6 +772,6 @@ extern "C" int twv_tacotron_linear_loss_grad(const float* linear, const float* l
     }
     hipLaunchKernelGGL(cg_linear_loss_grad_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, linear, linear_targets, loss_coeff, per,
                        num_freq, lo, hi, (float)w0, (float)w1, total, d_linear);
-    CG_HIPCHK(hipGetLastError());
+    GRAD_HIPCHK(hipGetLastError());
     return TWV_OK;
 }

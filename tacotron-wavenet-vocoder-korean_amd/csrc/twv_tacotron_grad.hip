@@ -13,19 +13,16 @@
 //   (c) every kernel / bias gradient as ONE product (rocBLAS, atomics off) or column sum of saved inputs against saved deltas.
 // No workgroup waits for another one anywhere: no exchange areas, tickets or grid barriers, so the pass cannot deadlock; the price is that
 // each utterance's workgroup re-reads the decoder weights from L2 every step.  No atomics: two runs give the same bits.  Whatever feeds the
-// recurrence (prenet, keys, d_mel through the output projection) goes through this file's own row kernels, whose summation order for a row
+// recurrence (prenet, keys, d_mel through the output projection) goes through row kernels -- the gradient passes' shared grad_rows_kernel
+// (twv_tacotron_grad_common.hpp) and, for the transposed products, this file's tg_rows_nt_kernel -- whose summation order for a row
 // does not depend on how many rows there are: an utterance's d_memory / d_init are the same bits alone and inside a batch.
 // Dot products accumulate in float64 (the kernels wait on L2, not on the VALU); tape and deltas are float32.
-#include <hip/hip_runtime.h>
-#include <rocblas/rocblas.h>
-#include <stdint.h>
-#include <string.h>
-#include <string>
-#include "../../include/twv_amd.h"
-#include "twv_dev.hpp"
 #include "twv_tacotron_blob.hpp"
+#include "twv_tacotron_grad_common.hpp"
 
 namespace tg {       // (helper names such as wave_sum exist in other files of the library with other bodies)
+
+using namespace tgrad;
 
 constexpr int kThreads = 512, kWaves = kThreads / 64;
 constexpr float kTiny = 1.17549435e-38f;          // np.finfo(np.float32).tiny: safe_cumprod's lower clip
@@ -37,7 +34,6 @@ __device__ inline double wave_sum(double v)
     for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
     return v;
 }
-__device__ inline float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 __device__ inline float clampf_(float x, float lo, float hi) { return fminf(fmaxf(x, lo), hi); }
 
 // out[j] = bias[j] + sum_k in(k) * W[k * ld + j], j < ncols <= 512; in(k) = k < split ? a[k] : b[k - split] (LDS).  512 / ncols threads share
@@ -154,24 +150,22 @@ struct TgArgs {
 struct TgFwdLds { int red, x, g, xc, qb, vh, xr, gr, dech, al, pc, cp, ss, total; };
 __host__ __device__ inline TgFwdLds tg_fwd_lds(int T, int D1, int ENC, int A, int AS, int DR, int L)
 {
-    TgFwdLds c; int u = 0; const int Tp = (T + 3) & ~3;
-    auto take = [&](int n) { const int o = u; u += (n + 3) & ~3; return o; };
+    TgFwdLds c; Take<int> take; const int Tp = (T + 3) & ~3;
     c.red = take(2 * kThreads); c.x = take(D1 + ENC + 2 * AS); c.g = take(3 * AS); c.xc = take(AS + ENC); c.qb = take(A); c.vh = take(A);
     c.xr = take(3 * DR); c.gr = take(3 * DR); c.dech = take(L * DR); c.al = take(Tp); c.pc = take(Tp); c.cp = take(Tp); c.ss = take(Tp);
-    c.total = u;
+    c.total = take.used;
     return c;
 }
 struct TgBwdLds { int acc, dha, dctx, ddech, dy, dhl, dcl, dgl, dxh, dxh2, dx, tmp, vh, qb, dq, wp, dal, t1, t2, de, total; };
 __host__ __device__ inline TgBwdLds tg_bwd_lds(int T, int D1, int ENC, int A, int AS, int DR, int L)
 {
-    TgBwdLds c; int u = 0; const int Tp = (T + 3) & ~3;
+    TgBwdLds c; Take<int> take; const int Tp = (T + 3) & ~3;
     const int U = AS > DR ? AS : DR, KX = (D1 + ENC + AS) > 2 * DR ? (D1 + ENC + AS) : 2 * DR;
-    auto take = [&](int n) { const int o = u; u += (n + 3) & ~3; return o; };
     c.acc = take(4 * A);                           // two arrays of A doubles: the utterance's sums for attention_v-hat and attention_b
     c.dha = take(AS); c.dctx = take(ENC); c.ddech = take(L * DR); c.dy = take(DR); c.dhl = take(U); c.dcl = take(U); c.dgl = take(2 * U);
     c.dxh = take(KX); c.dxh2 = take(KX); c.dx = take(KX); c.tmp = take(AS + ENC); c.vh = take(A); c.qb = take(A); c.dq = take(A);
     c.wp = take(2 * kWaves * A); c.dal = take(Tp); c.t1 = take(Tp); c.t2 = take(Tp); c.de = take(Tp);
-    c.total = u;
+    c.total = take.used;
     return c;
 }
 
@@ -445,50 +439,15 @@ __global__ void __launch_bounds__(kThreads) tg_backward_kernel(TgArgs a)
     if (tid == 0) a.psb[n] = (float)accsb;
 }
 
-// ---- products over rows whose order of additions for a row does not depend on the number of rows
-struct RowsArgs {
-    const float *X, *W, *bias, *mask, *gate_in;
-    float *C, *gate_out;
-    int ldx, ldw, ldc, rows, K, ncols, relu, add;
-};
-constexpr int kRB = 8, kRowsK = 512;
+// ---- the decoder's own products over rows.  Everything not transposed goes through the shared row kernel (grad_rows_kernel).
+constexpr int kRowsK = 512;        // the widest row tg_rows_nt_kernel stages
 
-// C[r][j] = f(bias[j] + sum_k X[r][k] W[k][j]); relu: C = max(z, 0) * mask[r][j], gate_out = z > 0 ? mask : 0 (mask null = ones)
-__global__ void __launch_bounds__(256) tg_rows_nn_kernel(RowsArgs a)
-{
-    __shared__ float xs[kRB * kRowsK];
-    const int tid = threadIdx.x, r0 = blockIdx.x * kRB, nr = min(kRB, a.rows - r0), K = a.K;
-    for (int i = tid; i < kRB * K; i += 256) { const int r = i / K, k = i - r * K; xs[i] = r < nr ? a.X[(long long)(r0 + r) * a.ldx + k] : 0.0f; }
-    __syncthreads();
-    for (int j = tid; j < a.ncols; j += 256) {
-        double acc[kRB];
-#pragma unroll
-        for (int r = 0; r < kRB; ++r) acc[r] = 0.0;
-        for (int k = 0; k < K; ++k) {
-            const double w = (double)a.W[(long long)k * a.ldw + j];
-#pragma unroll
-            for (int r = 0; r < kRB; ++r) acc[r] = fma(w, (double)xs[r * K + k], acc[r]);
-        }
-#pragma unroll
-        for (int r = 0; r < kRB; ++r) {
-            if (r >= nr) continue;
-            const long long o = (long long)(r0 + r) * a.ldc + j;
-            float z = (float)(acc[r] + (a.bias ? (double)a.bias[j] : 0.0));
-            if (a.relu) {
-                const float m = a.mask ? a.mask[(long long)(r0 + r) * a.ncols + j] : 1.0f;
-                if (a.gate_out) a.gate_out[o] = z > 0.0f ? m : 0.0f;
-                z = fmaxf(z, 0.0f) * m;
-            }
-            a.C[o] = z;
-        }
-    }
-}
-
+// Not the CBHG's transpose + row kernel (k in order): here the lanes stride over k and a butterfly adds them, another order of additions.
 // C[r][j] (+)= gate_in[r][j] * sum_k X[r][k] W[j][k]  (the product with the transposed kernel; W is (ncols, K) row-major)
 __global__ void __launch_bounds__(256) tg_rows_nt_kernel(RowsArgs a)
 {
     __shared__ float xs[kRB * kRowsK];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, r0 = blockIdx.x * kRB, nr = min(kRB, a.rows - r0), K = a.K;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, r0 = blockIdx.x * kRB, nr = min(kRB, a.rows - r0), K = a.Cin;
     for (int i = tid; i < kRB * K; i += 256) { const int r = i / K, k = i - r * K; xs[i] = r < nr ? a.X[(long long)(r0 + r) * a.ldx + k] : 0.0f; }
     __syncthreads();
     for (int j = wv; j < a.ncols; j += 4) {
@@ -522,11 +481,8 @@ __global__ void tg_fed_frames_kernel(const float* tgt, int N, int steps, int R, 
         F[i] = t == 0 ? 0.0f : tgt[((n * steps * R) + (long long)t * R - 1) * M + m];
     }
 }
-__global__ void tg_mul_kernel(float* x, const float* g, long long total)
-{
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) x[i] *= g[i];
-}
 // out[j] = sum over rows of D[row][j], rows in order (float64 inside)
+// Not the CBHG's cg_colsum_kernel + cg_finish_kernel (chunks of 128 rows, four strided partial sums each): another order of additions.
 __global__ void tg_colsum_kernel(const float* D, long long rows, int ld, int ncols, float* out)
 {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
@@ -574,8 +530,6 @@ __global__ void tg_mel_loss_grad_kernel(const float* mel, const float* tgt, cons
     }
 }
 
-inline int grid_for(long long n) { const long long g = (n + 255) / 256; return (int)(g < 1 ? 1 : (g > 8192 ? 8192 : g)); }
-
 }  // namespace tg
 using namespace tg;
 
@@ -584,17 +538,13 @@ struct TgCarve {
     float *F, *H1, *G1, *P, *G2, *keys, *XA, *GA, *XC, *QB, *PCH, *CP, *S, *AL, *XR[4], *GR[4], *YF;
     float *dYF, *DAg, *DAc, *DQ, *DY0, *DRg[4], *DRc[4], *DP, *dH1, *dkeys, *pv, *pb, *psb;
 };
-struct twv_tacotron_decoder_grad {
+struct twv_tacotron_decoder_grad : Handle {
     twv_tacotron_dims d;
     TacoDecoderBlob w;
     int N, T, steps;
-    long long ws_floats;
     int lds_fwd, lds_bwd;          // bytes
-    rocblas_handle blas = nullptr;
-    std::string route;
-    int timing = 0;                // twv_tacotron_decoder_grad_set_timing: events at the phase boundaries of the next runs
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
 };
+using Tg = twv_tacotron_decoder_grad;
 
 static long long tg_carve(const twv_tacotron_decoder_grad* g, float* base, TgCarve& c)
 {
@@ -602,8 +552,7 @@ static long long tg_carve(const twv_tacotron_decoder_grad* g, float* base, TgCar
     const long long rows = (long long)g->N * g->steps, rowsE = (long long)g->N * g->T;
     const int D0 = d.dec_prenet_sizes[0], D1 = d.dec_prenet_sizes[1], ENC = 2 * d.enc_rnn_size, A = d.attention_size, AS = d.attention_state_size,
               DR = d.dec_rnn_size, M = d.num_mels, L = d.dec_layer_num;
-    long long used = 0;
-    auto take = [&](long long n) { float* p = base ? base + used : nullptr; used += (n + 3) / 4 * 4; return p; };
+    TakeFloats take{base};
     c.F = take(rows * M); c.H1 = take(rows * D0); c.G1 = take(rows * D0); c.P = take(rows * D1); c.G2 = take(rows * D1);
     c.keys = take(rowsE * A);
     c.XA = take(rows * (D1 + ENC + 2 * AS)); c.GA = take(rows * 3 * AS); c.XC = take(rows * (AS + ENC)); c.QB = take(rows * A);
@@ -614,7 +563,7 @@ static long long tg_carve(const twv_tacotron_decoder_grad* g, float* base, TgCar
     for (int l = 0; l < 4; ++l) { c.DRg[l] = l < L ? take(rows * 2 * DR) : nullptr; c.DRc[l] = l < L ? take(rows * DR) : nullptr; }
     c.DP = take(rows * D1); c.dH1 = take(rows * D0); c.dkeys = take(rowsE * A);
     c.pv = take((long long)g->N * A); c.pb = take((long long)g->N * A); c.psb = take(g->N);
-    return used;
+    return take.off.used;
 }
 
 static const char* const kTgBuilt = "the decoder gradient is built for attention_type 'bah_mon_norm' and 'bah_mon', single-speaker and 'deepvoice' models";
@@ -647,39 +596,27 @@ extern "C" int twv_tacotron_decoder_grad_create(const twv_tacotron* h, int batch
     *out = g;
     return TWV_OK;
 }
-extern "C" void twv_tacotron_decoder_grad_destroy(twv_tacotron_decoder_grad* g)
-{
-    if (g && g->blas) rocblas_destroy_handle(g->blas);
-    if (g) for (hipEvent_t e : g->ev) if (e) (void)hipEventDestroy(e);
-    delete g;
-}
-extern "C" int twv_tacotron_decoder_grad_set_timing(twv_tacotron_decoder_grad* g, int on)
-{
-    if (!g) return twv_fail(TWV_E_INVALID, "null argument");
-    g->timing = on ? 1 : 0;
-    return TWV_OK;
-}
+extern "C" void twv_tacotron_decoder_grad_destroy(twv_tacotron_decoder_grad* g) { delete g; }
+extern "C" int twv_tacotron_decoder_grad_set_timing(twv_tacotron_decoder_grad* g, int on) { return g ? g->set_timing(on) : twv_fail(TWV_E_INVALID, "null argument"); }
 extern "C" size_t twv_tacotron_decoder_grad_workspace_bytes(const twv_tacotron_decoder_grad* g) { return g ? (size_t)g->ws_floats * 4 : 0; }
 extern "C" const char* twv_tacotron_decoder_grad_route(const twv_tacotron_decoder_grad* g) { return g ? g->route.c_str() : ""; }
 
-#define TG_HIPCHK(expr)                                                                                          \
-    do {                                                                                                          \
-        hipError_t e_ = (expr);                                                                                   \
-        if (e_ != hipSuccess) return twv_fail(TWV_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));     \
-    } while (0)
-#define TG_BLASCHK(expr)                                                                                         \
-    do {                                                                                                          \
-        rocblas_status s_ = (expr);                                                                               \
-        if (s_ != rocblas_status_success) return twv_fail(TWV_E_HIP, std::string(#expr) + ": " + rocblas_status_to_string(s_)); \
-    } while (0)
-
-static void tg_rows(bool nt, hipStream_t st, const float* X, int ldx, int rows, int K, const float* W, int ldw, int ncols, const float* bias,
-                    float* C, int ldc, int relu = 0, const float* mask = nullptr, float* gate_out = nullptr, const float* gate_in = nullptr, int add = 0)
+// C (rows x ncols) = X (rows x K) . W (K x ncols) + bias through the shared row kernel, every matrix dense; the caller adds the relu's
+// mask and gate to the arguments
+static RowsArgs tg_nn(const float* X, int rows, int K, const float* W, int ncols, const float* bias, float* C)
 {
-    RowsArgs a{X, W, bias, mask, gate_in, C, gate_out, ldx, ldw, ldc, rows, K, ncols, relu, add};
-    if (nt) hipLaunchKernelGGL(tg_rows_nt_kernel, dim3((rows + kRB - 1) / kRB), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(tg_rows_nn_kernel, dim3((rows + kRB - 1) / kRB), dim3(256), 0, st, a);
+    RowsArgs a = rows_args(X, K, rows, rows, K, 1, 0, W, ncols, ncols, bias);
+    a.C = C; a.ldc = ncols;
+    return a;
 }
+// C (rows x ncols) = X (rows x K) . W^T, W (ncols x K); the caller sets gate_in / add
+static RowsArgs tg_nt(const float* X, int rows, int K, const float* W, int ncols, float* C)
+{
+    RowsArgs a = rows_args(X, K, rows, rows, K, 1, 0, W, K, ncols, nullptr);
+    a.C = C; a.ldc = ncols;
+    return a;
+}
+static void tg_launch_nt(hipStream_t st, const RowsArgs& a) { hipLaunchKernelGGL(tg_rows_nt_kernel, dim3((a.rows + kRB - 1) / kRB), dim3(256), 0, st, a); }
 
 extern "C" int twv_tacotron_decoder_grad_run(twv_tacotron_decoder_grad* g, const float* blob, const float* memory, const float* decoder_init,
                                              const int32_t* lengths, const float* mel_targets, const float* d_mel, const float* mask1,
@@ -696,27 +633,21 @@ extern "C" int twv_tacotron_decoder_grad_run(twv_tacotron_decoder_grad* g, const
     const int D0 = d.dec_prenet_sizes[0], D1 = d.dec_prenet_sizes[1], ENC = 2 * d.enc_rnn_size, A = d.attention_size, AS = d.attention_state_size,
               DR = d.dec_rnn_size, M = d.num_mels, R = d.reduction_factor, L = d.dec_layer_num, MR = M * R, ain = D1 + ENC, XW = ain + 2 * AS;
     const int norm = d.attention_type == TWV_ATT_BAH_MON_NORM ? 1 : 0;
-    if (!g->blas) {
-        TG_BLASCHK(rocblas_create_handle(&g->blas));
-        TG_BLASCHK(rocblas_set_atomics_mode(g->blas, rocblas_atomics_not_allowed));     // the same bits on every run
-    }
-    TG_BLASCHK(rocblas_set_stream(g->blas, st));
-    TG_BLASCHK(rocblas_set_pointer_mode(g->blas, rocblas_pointer_mode_host));
+    GRAD_CHK(g->begin(st, status, grad_blob, w.blob_floats));
     TgCarve c;
     tg_carve(g, (float*)workspace, c);
-    TG_HIPCHK(hipMemsetAsync(status, 0, 16, st));
-    TG_HIPCHK(hipMemsetAsync(grad_blob, 0, (size_t)w.blob_floats * 4, st));
-    auto mark = [&](int i) -> hipError_t {
-        if (!g->timing) return hipSuccess;
-        if (!g->ev[i]) { const hipError_t e = hipEventCreate(&g->ev[i]); if (e != hipSuccess) return e; }
-        return hipEventRecord(g->ev[i], st);
-    };
     // ---- (a) recording forward
-    TG_HIPCHK(mark(0));
+    GRAD_CHK(g->mark(0));
     hipLaunchKernelGGL(tg_fed_frames_kernel, dim3(grid_for((long long)rows * M)), dim3(256), 0, st, mel_targets, N, steps, R, M, c.F);
-    tg_rows(false, st, c.F, M, rows, M, blob + w.dpW1, D0, D0, blob + w.dpb1, c.H1, D0, 1, mask1, c.G1);
-    tg_rows(false, st, c.H1, D0, rows, D0, blob + w.dpW2, D1, D1, blob + w.dpb2, c.P, D1, 1, mask2, c.G2);
-    tg_rows(false, st, memory, ENC, rowsE, ENC, blob + w.Wm, A, A, nullptr, c.keys, A);
+    {
+        RowsArgs p = tg_nn(c.F, rows, M, blob + w.dpW1, D0, blob + w.dpb1, c.H1);
+        p.act = 1; p.mask = mask1; p.gate_out = c.G1;
+        launch_rows<Tg>(st, p);
+        p = tg_nn(c.H1, rows, D0, blob + w.dpW2, D1, blob + w.dpb2, c.P);
+        p.act = 1; p.mask = mask2; p.gate_out = c.G2;
+        launch_rows<Tg>(st, p);
+        launch_rows<Tg>(st, tg_nn(memory, rowsE, ENC, blob + w.Wm, A, nullptr, c.keys));
+    }
     TgArgs a;
     memset(&a, 0, sizeof(a));
     a.blob = blob; a.memory = memory; a.init = decoder_init; a.keys = c.keys; a.lengths = lengths; a.w = w;
@@ -725,47 +656,48 @@ extern "C" int twv_tacotron_decoder_grad_run(twv_tacotron_decoder_grad* g, const
     for (int l = 0; l < 4; ++l) { a.XR[l] = c.XR[l]; a.GR[l] = c.GR[l]; a.DRg[l] = c.DRg[l]; a.DRc[l] = c.DRc[l]; }
     a.dYF = c.dYF; a.DAg = c.DAg; a.DAc = c.DAc; a.DQ = c.DQ; a.DY0 = c.DY0; a.DP = c.DP; a.dkeys = c.dkeys; a.dmem = d_memory; a.dinit = d_init;
     a.pv = c.pv; a.pb = c.pb; a.psb = c.psb;
-    TG_HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(tg_forward_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, g->lds_fwd));
-    TG_HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(tg_backward_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, g->lds_bwd));
+    GRAD_HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(tg_forward_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, g->lds_fwd));
+    GRAD_HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(tg_backward_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, g->lds_bwd));
     hipLaunchKernelGGL(tg_forward_kernel, dim3(N), dim3(kThreads), (size_t)g->lds_fwd, st, a);
-    tg_rows(false, st, c.YF, DR, rows, DR, blob + w.oW, MR, MR, blob + w.ob, mel_out, MR);
+    launch_rows<Tg>(st, tg_nn(c.YF, rows, DR, blob + w.oW, MR, blob + w.ob, mel_out));
     // ---- (b) backward through time
-    TG_HIPCHK(mark(1));
-    tg_rows(true, st, d_mel, MR, rows, MR, blob + w.oW, MR, DR, nullptr, c.dYF, DR);
+    GRAD_CHK(g->mark(1));
+    tg_launch_nt(st, tg_nt(d_mel, rows, MR, blob + w.oW, DR, c.dYF));
     hipLaunchKernelGGL(tg_backward_kernel, dim3(N), dim3(kThreads), (size_t)g->lds_bwd, st, a);
-    tg_rows(true, st, c.dkeys, A, rowsE, A, blob + w.Wm, A, ENC, nullptr, d_memory, ENC, 0, nullptr, nullptr, nullptr, 1);   // d_values += d_keys . Wm^T
-    hipLaunchKernelGGL(tg_mul_kernel, dim3(grid_for((long long)rows * D1)), dim3(256), 0, st, c.DP, c.G2, (long long)rows * D1);
-    tg_rows(true, st, c.DP, D1, rows, D1, blob + w.dpW2, D1, D0, nullptr, c.dH1, D0, 0, nullptr, nullptr, c.G1);
-    TG_HIPCHK(hipGetLastError());
-    TG_HIPCHK(mark(2));
+    {
+        RowsArgs p = tg_nt(c.dkeys, rowsE, A, blob + w.Wm, ENC, d_memory);
+        p.add = 1;                                                                   // d_values += d_keys . Wm^T
+        tg_launch_nt(st, p);
+        launch_mul<Tg>(st, c.DP, c.G2, (long long)rows * D1);
+        p = tg_nt(c.DP, rows, D1, blob + w.dpW2, D0, c.dH1);
+        p.gate_in = c.G1;
+        tg_launch_nt(st, p);
+    }
+    GRAD_HIPCHK(hipGetLastError());
+    GRAD_CHK(g->mark(2));
     // ---- (c) weight gradients: grad[K x N] = X^T (K x rows) . delta (rows x N), row-major = rocBLAS (N x K) = delta^T-as-stored . X
-    const float one = 1.0f, zero = 0.0f;
-    auto wgrad = [&](const float* X, int ldx, int K, const float* D, int ldd, int Nc, long long off, long long nrows) {
-        return rocblas_sgemm(g->blas, rocblas_operation_none, rocblas_operation_transpose, Nc, K, (int)nrows, &one, D, ldd, X, ldx, &zero,
-                             grad_blob + off, Nc);
-    };
     auto colsum = [&](const float* D, int ld, int Nc, long long off, long long nrows) {
         hipLaunchKernelGGL(tg_colsum_kernel, dim3((Nc + 63) / 64), dim3(64), 0, st, D, nrows, ld, Nc, grad_blob + off);
     };
-    TG_BLASCHK(wgrad(c.YF, DR, DR, d_mel, MR, MR, w.oW, rows)); colsum(d_mel, MR, MR, w.ob, rows);
+    GRAD_CHK(g->wgrad(c.YF, DR, DR, d_mel, MR, MR, w.oW, rows)); colsum(d_mel, MR, MR, w.ob, rows);
     for (int l = 0; l < L; ++l) {
-        TG_BLASCHK(wgrad(c.XR[l], 3 * DR, 2 * DR, c.DRg[l], 2 * DR, 2 * DR, w.rWg[l], rows)); colsum(c.DRg[l], 2 * DR, 2 * DR, w.rbg[l], rows);
-        TG_BLASCHK(wgrad(c.XR[l], 3 * DR, DR, c.DRc[l], DR, DR, w.rWc[l], rows));
-        TG_BLASCHK(wgrad(c.XR[l] + 2 * DR, 3 * DR, DR, c.DRc[l], DR, DR, w.rWc[l] + (long long)DR * DR, rows));
+        GRAD_CHK(g->wgrad(c.XR[l], 3 * DR, 2 * DR, c.DRg[l], 2 * DR, 2 * DR, w.rWg[l], rows)); colsum(c.DRg[l], 2 * DR, 2 * DR, w.rbg[l], rows);
+        GRAD_CHK(g->wgrad(c.XR[l], 3 * DR, DR, c.DRc[l], DR, DR, w.rWc[l], rows));
+        GRAD_CHK(g->wgrad(c.XR[l] + 2 * DR, 3 * DR, DR, c.DRc[l], DR, DR, w.rWc[l] + (long long)DR * DR, rows));
         colsum(c.DRc[l], DR, DR, w.rbc[l], rows);
     }
-    TG_BLASCHK(wgrad(c.XC, AS + ENC, AS + ENC, c.DY0, DR, DR, w.cW, rows)); colsum(c.DY0, DR, DR, w.cb, rows);
-    TG_BLASCHK(wgrad(c.XC, AS + ENC, AS, c.DQ, A, A, w.Wq, rows));
-    TG_BLASCHK(wgrad(c.XA, XW, ain + AS, c.DAg, 2 * AS, 2 * AS, w.aWg, rows)); colsum(c.DAg, 2 * AS, 2 * AS, w.abg, rows);
-    TG_BLASCHK(wgrad(c.XA, XW, ain, c.DAc, AS, AS, w.aWc, rows));
-    TG_BLASCHK(wgrad(c.XA + ain + AS, XW, AS, c.DAc, AS, AS, w.aWc + (long long)ain * AS, rows));
+    GRAD_CHK(g->wgrad(c.XC, AS + ENC, AS + ENC, c.DY0, DR, DR, w.cW, rows)); colsum(c.DY0, DR, DR, w.cb, rows);
+    GRAD_CHK(g->wgrad(c.XC, AS + ENC, AS, c.DQ, A, A, w.Wq, rows));
+    GRAD_CHK(g->wgrad(c.XA, XW, ain + AS, c.DAg, 2 * AS, 2 * AS, w.aWg, rows)); colsum(c.DAg, 2 * AS, 2 * AS, w.abg, rows);
+    GRAD_CHK(g->wgrad(c.XA, XW, ain, c.DAc, AS, AS, w.aWc, rows));
+    GRAD_CHK(g->wgrad(c.XA + ain + AS, XW, AS, c.DAc, AS, AS, w.aWc + (long long)ain * AS, rows));
     colsum(c.DAc, AS, AS, w.abc, rows);
-    TG_BLASCHK(wgrad(c.H1, D0, D0, c.DP, D1, D1, w.dpW2, rows)); colsum(c.DP, D1, D1, w.dpb2, rows);
-    TG_BLASCHK(wgrad(c.F, M, M, c.dH1, D0, D0, w.dpW1, rows)); colsum(c.dH1, D0, D0, w.dpb1, rows);
-    TG_BLASCHK(wgrad(memory, ENC, ENC, c.dkeys, A, A, w.Wm, rowsE));
+    GRAD_CHK(g->wgrad(c.H1, D0, D0, c.DP, D1, D1, w.dpW2, rows)); colsum(c.DP, D1, D1, w.dpb2, rows);
+    GRAD_CHK(g->wgrad(c.F, M, M, c.dH1, D0, D0, w.dpW1, rows)); colsum(c.dH1, D0, D0, w.dpb1, rows);
+    GRAD_CHK(g->wgrad(memory, ENC, ENC, c.dkeys, A, A, w.Wm, rowsE));
     hipLaunchKernelGGL(tg_attention_finish_kernel, dim3(1), dim3(256), 0, st, blob, w, norm, N, A, c.pv, c.pb, c.psb, grad_blob);
-    TG_HIPCHK(hipGetLastError());
-    TG_HIPCHK(mark(3));
+    GRAD_HIPCHK(hipGetLastError());
+    GRAD_CHK(g->mark(3));
     return TWV_OK;
 }
 
@@ -774,10 +706,7 @@ extern "C" int twv_tacotron_decoder_grad_run(twv_tacotron_decoder_grad* g, const
 extern "C" int twv_tacotron_decoder_grad_phase_ms(twv_tacotron_decoder_grad* g, double* ms3)
 {
     if (!g || !ms3) return twv_fail(TWV_E_INVALID, "null argument");
-    if (!g->ev[3]) return twv_fail(TWV_E_INVALID, "no run with timing on (twv_tacotron_decoder_grad_set_timing) has been made");
-    TG_HIPCHK(hipEventSynchronize(g->ev[3]));
-    for (int i = 0; i < 3; ++i) { float ms = 0.0f; TG_HIPCHK(hipEventElapsedTime(&ms, g->ev[i], g->ev[i + 1])); ms3[i] = (double)ms; }
-    return TWV_OK;
+    return g->phase_ms(3, ms3, "twv_tacotron_decoder_grad_set_timing");
 }
 
 extern "C" int twv_tacotron_mel_loss_grad(const float* mel, const float* mel_targets, const float* loss_coeff, int batch, int t_out,
@@ -788,6 +717,6 @@ extern "C" int twv_tacotron_mel_loss_grad(const float* mel, const float* mel_tar
     const long long per = (long long)t_out * num_mels, total = per * batch;
     hipLaunchKernelGGL(tg_mel_loss_grad_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, mel, mel_targets, loss_coeff, per,
                        (float)total, total, d_mel);
-    TG_HIPCHK(hipGetLastError());
+    GRAD_HIPCHK(hipGetLastError());
     return TWV_OK;
 }

@@ -184,6 +184,19 @@ def postnet_grad_layout(specs):
     return _grad_layout(specs, lambda i, n: n.startswith("post_cbhg/") or i >= len(specs) - 2)
 
 
+def bn_grad_from_inference_pair(pair, raw):
+    """a batch norm's gradient as the checkpoint stores the layer: (d_inv, d_shift) of the derived pair (flatten) and the raw (4, C) tensor
+    -> (d_gamma, d_beta) as (2, C) float32, float64 inside:
+    inv = gamma rsqrt(var + eps), shift = beta - mean inv  =>  d_gamma = rsqrt(var + eps) (d_inv - mean d_shift), d_beta = d_shift"""
+    pair, raw = np.asarray(pair, np.float64), np.asarray(raw, np.float64)
+    rs = 1.0 / np.sqrt(raw[3] + np.float64(BN_EPS))
+    return np.stack([rs * (pair[0] - raw[2] * pair[1]), pair[1]]).astype(np.float32)
+
+
+# kind of gradient handle -> (prefix of its C entries, leading arguments of *_create after the model)
+_GRAD_KINDS = {"decoder": ("twv_tacotron_decoder_grad", ()), "encoder": ("twv_tacotron_cbhg_grad", (0,)), "post": ("twv_tacotron_cbhg_grad", (1,))}
+
+
 def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
@@ -249,9 +262,7 @@ class Tacotron(object):
 
     def __del__(self):
         try:
-            self._drop_grad_handle()
-            for which in (0, 1):
-                self._drop_cbhg_handle(which)
+            self._drop_grad_handles()
             if getattr(self, "_h", None):
                 self._L.twv_tacotron_destroy(self._h)
                 self._h = None
@@ -341,11 +352,8 @@ class Tacotron(object):
         sign(mel - target) * loss_coeff[n] / (N * T_out * num_mels), a (N, T_out, num_mels) tensor on the device."""
         mel, tgt = self._forced_pass("mel_loss_cotangent")
         N, TO, M = (int(v) for v in mel.shape)
-        co = np.ones(N, np.float32) if loss_coeff is None else np.asarray(loss_coeff, np.float32).reshape(-1)
-        if co.shape != (N,):
-            raise ValueError("loss_coeff must hold one factor per utterance (%d), got shape %s" % (N, co.shape))
         with torch.cuda.device(self.device):
-            co = torch.from_numpy(co).to(self.device)
+            co = self._loss_coeff(loss_coeff, N)
             out = torch.empty_like(mel)
             _lib.check(self._L.twv_tacotron_mel_loss_grad(_ptr(mel), _ptr(tgt), _ptr(co), N, TO, M, _ptr(out), _stream()))
         return out
@@ -370,28 +378,10 @@ class Tacotron(object):
         N, TO, M = (int(v) for v in tgt.shape)
         T = int(self.inputs.shape[1])
         steps = TO // hp.reduction_factor
-        D = hp.dec_prenet_sizes
         with torch.cuda.device(self.device):
-            if not torch.is_tensor(d_mel):
-                d_mel = torch.from_numpy(np.ascontiguousarray(d_mel, np.float32))
-            dm = d_mel.to(device=self.device, dtype=torch.float32).contiguous()
-            if tuple(dm.shape) != (N, TO, M):
-                raise ValueError("d_mel must be %s, got %s" % ((N, TO, M), tuple(dm.shape)))
-            masks = [None, None]
-            if prenet_masks is not None:
-                for i in range(2):
-                    m = prenet_masks[i]
-                    m = m if torch.is_tensor(m) else torch.from_numpy(np.ascontiguousarray(m, np.float32))
-                    masks[i] = m.to(device=self.device, dtype=torch.float32).contiguous()
-                    if tuple(masks[i].shape) != (N, steps, D[i]):
-                        raise ValueError("prenet_masks[%d] must be %s, got %s" % (i, (N, steps, D[i]), tuple(masks[i].shape)))
-            key = (N, T, steps)
-            if getattr(self, "_grad_key", None) != key:
-                self._drop_grad_handle()
-                g = C.c_void_p()
-                _lib.check(self._L.twv_tacotron_decoder_grad_create(self._h, N, T, steps, C.byref(g)))
-                self._grad, self._grad_key = g, key
-                self._grad_ws = torch.empty(self._L.twv_tacotron_decoder_grad_workspace_bytes(g) // 4, dtype=torch.float32, device=self.device)
+            dm = self._device_f32(d_mel, (N, TO, M), "d_mel must be %s, got %s")
+            masks = self._prenet_masks(prenet_masks, (N, steps), hp.dec_prenet_sizes)
+            g, ws = self._grad_handle("decoder", (N, T, steps))
             ENC, ninit = 2 * hp.enc_rnn_size, hp.attention_state_size + hp.dec_layer_num * hp.dec_rnn_size
             memory, init = self.workspace_view(N, T, "memory"), self.workspace_view(N, T, "decoder_init")
             mel_out = torch.empty((N, TO, M), dtype=torch.float32, device=self.device)
@@ -399,59 +389,74 @@ class Tacotron(object):
             d_memory = torch.empty((N, T, ENC), dtype=torch.float32, device=self.device)
             d_init = torch.empty((N, ninit), dtype=torch.float32, device=self.device)
             status = torch.zeros(4, dtype=torch.int32, device=self.device)
-            _lib.check(self._L.twv_tacotron_decoder_grad_run(self._grad, _ptr(self._blob), _ptr(memory), _ptr(init), _ptr(self.input_lengths),
-                                                             _ptr(tgt), _ptr(dm), _ptr(masks[0]), _ptr(masks[1]), _ptr(self._grad_ws),
+            _lib.check(self._L.twv_tacotron_decoder_grad_run(g, _ptr(self._blob), _ptr(memory), _ptr(init), _ptr(self.input_lengths),
+                                                             _ptr(tgt), _ptr(dm), _ptr(masks[0]), _ptr(masks[1]), _ptr(ws),
                                                              _ptr(status), _stream(), _ptr(mel_out), _ptr(grad), _ptr(d_memory), _ptr(d_init)))
-        out = {"d_memory": d_memory, "d_init": d_init, "mel": mel_out}
-        for name, off, shp in decoder_grad_layout(self.specs):
-            out[name] = grad[off:off + int(np.prod(shp))].view(*shp)
+            out = self._named_grads(grad, decoder_grad_layout(self.specs))       # (no batch norm on the decoder side)
+        out.update({"d_memory": d_memory, "d_init": d_init, "mel": mel_out})
         return out
 
     def decoder_grad_route(self):
         """the label of the gradient kernels of the last decoder_grad call ('' before one)"""
-        return self._L.twv_tacotron_decoder_grad_route(self._grad).decode() if getattr(self, "_grad", None) else ""
-
-    def _drop_grad_handle(self):
-        if getattr(self, "_grad", None):
-            self._L.twv_tacotron_decoder_grad_destroy(self._grad)
-        self._grad, self._grad_key = None, None
-
-    def _drop_cbhg_handle(self, which):
-        g = getattr(self, "_cbhg", None)
-        if g and g[which][1]:
-            self._L.twv_tacotron_cbhg_grad_destroy(g[which][1])
-            g[which] = [None, None, None]
-
-    def _cbhg_handle(self, which, N, T):
-        """the gradient handle and workspace of (encoder / post net, batch, rows an utterance), kept until the sizes change"""
-        if getattr(self, "_cbhg", None) is None:
-            self._cbhg = [[None, None, None], [None, None, None]]
-        if self._cbhg[which][0] != (N, T):
-            self._drop_cbhg_handle(which)
-            g = C.c_void_p()
-            _lib.check(self._L.twv_tacotron_cbhg_grad_create(self._h, which, N, T, C.byref(g)))
-            ws = torch.empty(self._L.twv_tacotron_cbhg_grad_workspace_bytes(g) // 4, dtype=torch.float32, device=self.device)
-            self._cbhg[which] = [(N, T), g, ws]
-        return self._cbhg[which][1], self._cbhg[which][2]
+        return self._grad_route("decoder")
 
     def cbhg_grad_route(self, which):
         """the label of the gradient kernels of the last encoder_grad (which = "encoder") / postnet_grad ("post") call ('' before one)"""
-        g = getattr(self, "_cbhg", None)
-        i = {"encoder": 0, "post": 1}[which]
-        return self._L.twv_tacotron_cbhg_grad_route(g[i][1]).decode() if g and g[i][1] else ""
+        if which not in ("encoder", "post"):
+            raise KeyError(which)
+        return self._grad_route(which)
+
+    # ---- what the gradient methods share
+    def _grad_handle(self, kind, sizes):
+        """(handle, workspace) of a kind of _GRAD_KINDS at `sizes` (the arguments of its *_create), kept until that kind's sizes change"""
+        cache = self.__dict__.setdefault("_grad_cache", {})
+        if kind not in cache or cache[kind][0] != sizes:
+            self._drop_grad_handles(kind)
+            prefix, lead = _GRAD_KINDS[kind]
+            g = C.c_void_p()
+            _lib.check(getattr(self._L, prefix + "_create")(self._h, *(lead + tuple(sizes) + (C.byref(g),))))
+            ws = torch.empty(getattr(self._L, prefix + "_workspace_bytes")(g) // 4, dtype=torch.float32, device=self.device)
+            cache[kind] = (sizes, g, ws)
+        return cache[kind][1:]
+
+    def _drop_grad_handles(self, kind=None):
+        cache = getattr(self, "_grad_cache", {})
+        for k in [k for k in list(cache) if kind in (None, k)]:
+            getattr(self._L, _GRAD_KINDS[k][0] + "_destroy")(cache.pop(k)[1])
+
+    def _grad_route(self, kind):
+        entry = getattr(self, "_grad_cache", {}).get(kind)
+        return getattr(self._L, _GRAD_KINDS[kind][0] + "_route")(entry[1]).decode() if entry else ""
+
+    def _device_f32(self, value, shape, message):
+        """array or tensor -> contiguous float32 tensor on the device; ValueError(message % (shape, its shape)) when a shape is given and is not its shape"""
+        if not torch.is_tensor(value):
+            value = torch.from_numpy(np.ascontiguousarray(value, np.float32))
+        t = value.to(device=self.device, dtype=torch.float32).contiguous()
+        if shape is not None and tuple(t.shape) != tuple(shape):
+            raise ValueError(message % (tuple(shape), tuple(t.shape)))
+        return t
+
+    def _prenet_masks(self, prenet_masks, lead, sizes):
+        """None, or the two dropout multipliers of a prenet as device tensors of lead + (sizes[i],)"""
+        if prenet_masks is None:
+            return [None, None]
+        return [self._device_f32(prenet_masks[i], lead + (sizes[i],), "prenet_masks[%d] must be %%s, got %%s" % i) for i in range(2)]
+
+    def _loss_coeff(self, loss_coeff, N):
+        """add_loss's per-utterance factors on the device (ones when None)"""
+        co = np.ones(N, np.float32) if loss_coeff is None else np.asarray(loss_coeff, np.float32).reshape(-1)
+        if co.shape != (N,):
+            raise ValueError("loss_coeff must hold one factor per utterance (%d), got shape %s" % (N, co.shape))
+        return torch.from_numpy(co).to(self.device)
 
     def _named_grads(self, grad, layout):
-        """the blob-shaped gradient as a dict by checkpoint name; a batch norm's (d_inv, d_shift) becomes (d_gamma, d_beta), float64 inside:
-        inv = gamma rsqrt(var + eps), shift = beta - mean inv  =>  d_gamma = rsqrt(var + eps) (d_inv - mean d_shift), d_beta = d_shift"""
+        """the blob-shaped gradient as a dict by checkpoint name, a batch norm's slot as (d_gamma, d_beta)"""
         out = {}
         for name, off, shp in layout:
             t = grad[off:off + int(np.prod(shp))].view(*shp)
             if name.endswith("batch_normalization"):
-                raw = self._bn_raw[name]
-                pair = t.cpu().numpy().astype(np.float64)
-                rs = 1.0 / np.sqrt(raw[3] + np.float64(BN_EPS))
-                gb = np.stack([rs * (pair[0] - raw[2] * pair[1]), pair[1]])
-                t = torch.from_numpy(gb.astype(np.float32)).to(self.device)
+                t = torch.from_numpy(bn_grad_from_inference_pair(t.cpu().numpy(), self._bn_raw[name])).to(self.device)
             out[name] = t
         return out
 
@@ -465,16 +470,9 @@ class Tacotron(object):
         if lin is None:
             raise ValueError("linear_loss_cotangent needs a forward_targets pass with teacher_forced=True and want_linear=True first")
         N, TO, F = (int(v) for v in lin.shape)
-        co = np.ones(N, np.float32) if loss_coeff is None else np.asarray(loss_coeff, np.float32).reshape(-1)
-        if co.shape != (N,):
-            raise ValueError("loss_coeff must hold one factor per utterance (%d), got shape %s" % (N, co.shape))
         with torch.cuda.device(self.device):
-            if not torch.is_tensor(linear_targets):
-                linear_targets = torch.from_numpy(np.ascontiguousarray(linear_targets, np.float32))
-            lt = linear_targets.to(device=self.device, dtype=torch.float32).contiguous()
-            if tuple(lt.shape) != (N, TO, F):
-                raise ValueError("linear_targets must be %s, got %s" % ((N, TO, F), tuple(lt.shape)))
-            co = torch.from_numpy(co).to(self.device)
+            co = self._loss_coeff(loss_coeff, N)
+            lt = self._device_f32(linear_targets, (N, TO, F), "linear_targets must be %s, got %s")
             out = torch.empty_like(lin)
             _lib.check(self._L.twv_tacotron_linear_loss_grad(_ptr(lin), _ptr(lt), _ptr(co), N, TO, F, 1 if hp.prioritize_loss else 0,
                                                              float(hp.sample_rate), _ptr(out), _stream()))
@@ -490,15 +488,12 @@ class Tacotron(object):
         if getattr(self, "_blob", None) is None:
             raise ValueError("postnet_grad needs load_weights first")
         with torch.cuda.device(self.device):
-            mel = mel0 if mel is None else (mel if torch.is_tensor(mel) else torch.from_numpy(np.ascontiguousarray(mel, np.float32)))
-            mel = mel.to(device=self.device, dtype=torch.float32).contiguous()
+            mel = self._device_f32(mel0 if mel is None else mel, None, "")
             N, TO, M = (int(v) for v in mel.shape)
-            if not torch.is_tensor(d_linear):
-                d_linear = torch.from_numpy(np.ascontiguousarray(d_linear, np.float32))
-            dl = d_linear.to(device=self.device, dtype=torch.float32).contiguous()
+            dl = self._device_f32(d_linear, None, "")
             if M != hp.num_mels or tuple(dl.shape) != (N, TO, hp.num_freq):
                 raise ValueError("mel must be (N, T_out, %d) and d_linear (N, T_out, %d), got %s and %s" % (hp.num_mels, hp.num_freq, tuple(mel.shape), tuple(dl.shape)))
-            g, ws = self._cbhg_handle(1, N, TO)
+            g, ws = self._grad_handle("post", (N, TO))
             lin = torch.empty((N, TO, hp.num_freq), dtype=torch.float32, device=self.device)
             grad = torch.empty_like(self._blob)
             d_mel = torch.empty_like(mel)
@@ -523,25 +518,14 @@ class Tacotron(object):
         N, T = (int(v) for v in self.inputs.shape)
         ENC, P = 2 * hp.enc_rnn_size, hp.enc_prenet_sizes
         with torch.cuda.device(self.device):
-            if not torch.is_tensor(d_memory):
-                d_memory = torch.from_numpy(np.ascontiguousarray(d_memory, np.float32))
-            dm = d_memory.to(device=self.device, dtype=torch.float32).contiguous()
-            if tuple(dm.shape) != (N, T, ENC):
-                raise ValueError("d_memory must be %s, got %s" % ((N, T, ENC), tuple(dm.shape)))
-            masks = [None, None]
-            if prenet_masks is not None:
-                for i in range(2):
-                    m = prenet_masks[i]
-                    m = m if torch.is_tensor(m) else torch.from_numpy(np.ascontiguousarray(m, np.float32))
-                    masks[i] = m.to(device=self.device, dtype=torch.float32).contiguous()
-                    if tuple(masks[i].shape) != (N, T, P[i]):
-                        raise ValueError("prenet_masks[%d] must be %s, got %s" % (i, (N, T, P[i]), tuple(masks[i].shape)))
+            dm = self._device_f32(d_memory, (N, T, ENC), "d_memory must be %s, got %s")
+            masks = self._prenet_masks(prenet_masks, (N, T), P)
             bh = init = d_bh = d_init = None
             if self.num_speakers > 1:
                 bh, init = self.workspace_view(N, T, "before_highway"), self.workspace_view(N, T, "encoder_rnn_init")
                 d_bh = torch.empty((N, P[1]), dtype=torch.float32, device=self.device)
                 d_init = torch.empty((N, ENC), dtype=torch.float32, device=self.device)
-            g, ws = self._cbhg_handle(0, N, T)
+            g, ws = self._grad_handle("encoder", (N, T))
             memory = torch.empty((N, T, ENC), dtype=torch.float32, device=self.device)
             grad = torch.empty_like(self._blob)
             status = torch.zeros(4, dtype=torch.int32, device=self.device)
@@ -583,15 +567,8 @@ class Tacotron(object):
             raise ValueError("outputs %s / %s and mel_targets %s do not belong to one forward_targets pass"
                              % (tuple(mel.shape), tuple(lin.shape), tuple(tgt.shape)))
         with torch.cuda.device(self.device):
-            if not torch.is_tensor(linear_targets):
-                linear_targets = torch.from_numpy(np.ascontiguousarray(linear_targets, np.float32))
-            lt = linear_targets.to(device=self.device, dtype=torch.float32).contiguous()
-            if tuple(lt.shape) != (N, TO, hp.num_freq):
-                raise ValueError("linear_targets must be %s, got %s" % ((N, TO, hp.num_freq), tuple(lt.shape)))
-            co = np.ones(N, np.float32) if loss_coeff is None else np.asarray(loss_coeff, np.float32).reshape(-1)
-            if co.shape != (N,):
-                raise ValueError("loss_coeff must hold one factor per utterance (%d), got shape %s" % (N, co.shape))
-            co = torch.from_numpy(co).to(self.device)
+            lt = self._device_f32(linear_targets, (N, TO, hp.num_freq), "linear_targets must be %s, got %s")
+            co = self._loss_coeff(loss_coeff, N)
             out = torch.empty(4, dtype=torch.float64, device=self.device)
             _lib.check(self._L.twv_tacotron_loss(_ptr(mel), _ptr(lin), _ptr(tgt), _ptr(lt), _ptr(co), N, TO, hp.num_mels, hp.num_freq,
                                                  1 if hp.prioritize_loss else 0, float(hp.sample_rate), _ptr(out), _stream()))

@@ -73,3 +73,52 @@ def sensitive_onehot(O, d, blob, U, gc, first_input, u0, temperature=1.0, prime=
     u, want, n = knife_edge_onehot(O, d, blob, U, gc, first_input, u0, temperature, prime, builder_workers(d, B, T))
     assert_onehot_inputs(u, want, n, d.Q)
     return u, want
+
+
+def assert_bar(label, got, g64, g32):
+    """the gradient bar of tests/train_cases.py, per tensor of g64: max|got - g64| <= max(RATIO * max|g32 - g64|, FLOOR * max|g64|), finite
+    and of g64's shape; prints every figure and returns the worst tensor as (name, e_got, e_g32)"""
+    from train_cases import FLOOR, RATIO
+    worst = ("", 0.0, 0.0)
+    for k in g64:
+        scale = max(float(np.abs(g64[k]).max()), 1e-30)
+        e_hip = float(np.abs(got[k].astype(np.float64) - g64[k]).max()) / scale
+        e_t32 = float(np.abs(g32[k].astype(np.float64) - g64[k]).max()) / scale
+        print("%s %-100s e_hip %.3e e_t32 %.3e ratio %6.2f%s" % (label, k, e_hip, e_t32, e_hip / max(e_t32, 1e-30), "  (floor)" if e_hip > RATIO * e_t32 else ""))
+        assert np.isfinite(got[k]).all(), (label, k)
+        assert got[k].shape == g64[k].shape, (label, k, got[k].shape, g64[k].shape)
+        assert e_hip <= max(RATIO * e_t32, FLOOR), ("%s %s: HIP %.3g vs torch-f32 %.3g (relative to the tensor's max, against float64)" % (label, k, e_hip, e_t32))
+        if e_hip > worst[1]:
+            worst = (k, e_hip, e_t32)
+    return worst
+
+
+def same_outputs(a, b, what, skip=()):
+    """two dicts of arrays hold the same bits (NaN equal to NaN), but for the keys of skip"""
+    for k in a:
+        if k not in skip:
+            assert first_mismatch(a[k], b[k]) is None, (what, k, first_mismatch(a[k], b[k]))
+
+
+def run_grad_handle(m, prefix, create_args, check_route, poison, call):
+    """One run of a Tacotron gradient entry on a handle of its own: <prefix>_create(model, *create_args), check_route(the route label as a
+    dict), a workspace filled with NaN (poison) or zeros, `call(g, ws, status, new)` -- which launches on the current stream and returns a
+    dict of device tensors, its outputs made with new(*shape) so that they carry the same fill -- then synchronise and destroy the handle.
+    Returns the dict as numpy arrays."""
+    import ctypes as C
+    import torch
+    from twvk_amd import _lib
+    L, dev, fill = m._L, m.device, float("nan") if poison else 0.0
+    g = C.c_void_p()
+    _lib.check(getattr(L, prefix + "_create")(m._h, *(tuple(create_args) + (C.byref(g),))))
+    try:
+        check_route(dict(kv.split("=", 1) for kv in getattr(L, prefix + "_route")(g).decode().split()))
+        ws = torch.full((getattr(L, prefix + "_workspace_bytes")(g) // 4,), fill, dtype=torch.float32, device=dev)
+        status = torch.zeros(4, dtype=torch.int32, device=dev)
+        new = lambda *shape: torch.full(shape, fill, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            out = call(g, ws, status, new)
+            torch.cuda.synchronize()
+        return {k: v.cpu().numpy() for k, v in out.items()}
+    finally:
+        getattr(L, prefix + "_destroy")(g)

@@ -1,6 +1,6 @@
 """The case table of the Tacotron encoder / post-net gradient tests (tests/test_tacotron_cbhg_grad_cpu.py proves the margin condition for
 every case on the host, tests/test_tacotron_cbhg_grad_gpu.py runs them on the device, scripts/tacotron_cbhg_grad_parity.py records them)
-and the host-only inputs of a case.  Sizes follow SMALL of tests/test_tacotron_grad_gpu.py: bank sizes 4 and 3 cover even and odd kernel
+and the host-only inputs of a case.  Sizes are SMALL of tests/tacotron_grad_cases.py: bank sizes 4 and 3 cover even and odd kernel
 widths and both sides of the SAME padding.
 
 Every input of both C entries is made on the host, so that the float64 / float32 checker runs the CPU test compares are the ones the
@@ -13,8 +13,8 @@ import functools
 
 import numpy as np
 
-R_ = 5
-SMALL = dict(enc_bank_size=4, post_bank_size=3, num_freq=129)
+from tacotron_grad_cases import R_, SMALL, hparams, padded_tokens      # noqa: F401 -- (the tests import SMALL and hparams from here)
+
 # The device's row products accumulate in float64, so one of its pre-activations (of size ~1 here) differs from the exact one by the float32
 # rounding of its inputs and of itself, a few 1e-7; a case's smallest |pre-activation| and pool gap must stay an order of magnitude clear of that.
 MARGIN = 1e-6
@@ -39,14 +39,6 @@ CHAIN_CASES = ("C-length-one", "E-single-speaker")
 CHAIN_E_T32 = 2e-6
 
 
-def hparams(**kw):
-    import twvk_amd
-    hp = twvk_amd.default_hparams()
-    for k, v in kw.items():
-        setattr(hp, k, v)
-    return hp
-
-
 class HostCase(object):
     """weights and inputs of a case, numpy float32 / int32, host only"""
 
@@ -65,10 +57,7 @@ class HostCase(object):
         self.dims = AR.Dims(self.hp, self.speakers)
         self.enc_names, self.post_names = CG.encoder_names(self.specs), CG.postnet_names(self.specs)
         rng = np.random.RandomState(seed + 1)
-        self.tok = rng.randint(2, 80, (self.N, self.T)).astype(np.int32)
-        for n, ln in enumerate(lengths):
-            self.tok[n, ln - 1] = 1
-            self.tok[n, ln:] = 0
+        self.tok = padded_tokens(rng, self.N, self.T, lengths)
         self.ln = np.asarray(lengths, np.int32)
         self.spk = (np.arange(self.N) % 2).astype(np.int32)
         f32 = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)

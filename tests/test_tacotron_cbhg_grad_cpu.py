@@ -174,7 +174,7 @@ def test_symbols_are_exported_and_declared():
     nm = subprocess.check_output(["nm", "-D", "--defined-only", _lib.LIB_PATH]).decode()
     for name in NEW_SYMBOLS:
         assert name in _lib.EXPORTS and hasattr(L, name) and name + "(" in header and (" T " + name + "\n") in nm, name
-    for kernel in ("cg_gru_forward_kernel", "cg_gru_backward_kernel", "cg_rows_kernel", "cg_bn_bwd_kernel", "cg_highway_bwd_kernel"):
+    for kernel in ("cg_gru_forward_kernel", "cg_gru_backward_kernel", "grad_rows_kernel", "cg_bn_bwd_kernel", "cg_highway_bwd_kernel"):
         assert kernel in nm, "the gfx950 kernel %s must be in the library" % kernel
 
 

@@ -6,15 +6,13 @@ the cotangent, per-utterance independence, repeatability on NaN-filled scratch, 
 
 The cases and their host-made inputs are tests/tacotron_cbhg_grad_cases.py (whose margin condition tests/test_tacotron_cbhg_grad_cpu.py
 proves); every case's device passes and checker passes are computed once and shared."""
-import ctypes as C
 import functools
 
 import numpy as np
 import pytest
 
-from helpers import first_mismatch
+from helpers import assert_bar, first_mismatch, run_grad_handle, same_outputs
 from tacotron_cbhg_grad_cases import CASES, CHAIN_CASES, MARGIN, host_case
-from train_cases import FLOOR, RATIO
 
 pytestmark = pytest.mark.gpu
 
@@ -32,25 +30,10 @@ class _Case(object):
         self.m = Tacotron(self.h.hp, num_speakers=self.h.speakers)
         self.m.load_weights(self.h.w)
 
-    def _run(self, which, call, t, fill):
-        """create the handle, NaN- or zero-filled workspace; `call(g, ws, status, new)` launches; returns its outputs as numpy"""
-        from twvk_amd import _lib
-        torch, m, dev = self.torch, self.m, self.m.device
-        g = C.c_void_p()
-        N = call.N
-        _lib.check(m._L.twv_tacotron_cbhg_grad_create(m._h, which, N, t, C.byref(g)))
-        try:
-            route = dict(kv.split("=", 1) for kv in m._L.twv_tacotron_cbhg_grad_route(g).decode().split())
+    def _run(self, which, N, t, poison, call):
+        def check_route(route):
             assert route["kernel"] == "cg_bigru" and route["side"] == ("post" if which else "encoder") and route["weights"] == "registers", route
-            ws = torch.full((m._L.twv_tacotron_cbhg_grad_workspace_bytes(g) // 4,), fill, dtype=torch.float32, device=dev)
-            status = torch.zeros(4, dtype=torch.int32, device=dev)
-            new = lambda *shape: torch.full(shape, fill, dtype=torch.float32, device=dev)
-            with torch.cuda.device(dev):
-                out = call(g, ws, status, new)
-                torch.cuda.synchronize()
-            return {k: v.cpu().numpy() for k, v in out.items()}
-        finally:
-            m._L.twv_tacotron_cbhg_grad_destroy(g)
+        return run_grad_handle(self.m, "twv_tacotron_cbhg_grad", (which, N, t), check_route, poison, call)
 
     def encoder(self, d_memory=None, masks="case", rows=None, poison=False):
         from twvk_amd import _lib
@@ -72,8 +55,7 @@ class _Case(object):
             if bh is not None:
                 out["d_before_highway"], out["d_rnn_init"] = d_bh, d_init
             return out
-        call.N = sl.stop - sl.start
-        out = self._run(0, call, h.T, float("nan") if poison else 0.0)
+        out = self._run(0, sl.stop - sl.start, h.T, poison, call)
         return self._named(out, encoder_grad_layout(m.specs))
 
     def postnet(self, d_linear=None, rows=None, poison=False):
@@ -90,21 +72,20 @@ class _Case(object):
             _lib.check(m._L.twv_tacotron_postnet_grad_run(g, _ptr(m._blob), _ptr(mel), _ptr(dl), _ptr(ws), _ptr(status), _stream(), _ptr(lin),
                                                           _ptr(grad), _ptr(d_mel)))
             return {"linear": lin, "blob": grad, "d_mel": d_mel}
-        call.N = sl.stop - sl.start
-        out = self._run(1, call, h.TO, float("nan") if poison else 0.0)
+        out = self._run(1, sl.stop - sl.start, h.TO, poison, call)
         return self._named(out, postnet_grad_layout(m.specs))
 
     def _named(self, out, layout):
-        """the tensors by name; a batch norm's (d_inv, d_shift) slot as (d_gamma, d_beta), float64 inside (Tacotron._named_grads' lines)"""
-        from twvk_amd.tacotron import BN_EPS
+        """the tensors by name; a batch norm's (d_inv, d_shift) slot as (d_gamma, d_beta) through tacotron.bn_grad_from_inference_pair, the
+        function Tacotron's methods use.  The checker side does not: tests/torch_tacotron_cbhg_grad_ref.py differentiates gamma and beta
+        themselves, so the expected values are computed independently of that function."""
+        from twvk_amd.tacotron import bn_grad_from_inference_pair
         inside = np.zeros(out["blob"].size, bool)
         for name, off, shp in layout:
             v = out["blob"][off:off + int(np.prod(shp))].reshape(shp)
             inside[off:off + v.size] = True
             if name.endswith("batch_normalization"):
-                raw = np.asarray(self.h.w[name], np.float64)
-                rs = 1.0 / np.sqrt(raw[3] + np.float64(BN_EPS))
-                v = np.stack([rs * (v[0].astype(np.float64) - raw[2] * v[1]), v[1].astype(np.float64)]).astype(np.float32)
+                v = bn_grad_from_inference_pair(v, self.h.w[name])
             out[name] = v
         out["inside"] = inside
         return out
@@ -133,23 +114,6 @@ def _case(name):
     return _Case(name)
 
 
-def _assert_bar(label, got, g64, g32):
-    """every gradient tensor: max|g_hip - g64| <= max(RATIO * max|g32 - g64|, FLOOR * max|g64|)"""
-    for k in g64:
-        scale = max(float(np.abs(g64[k]).max()), 1e-30)
-        e_hip = float(np.abs(got[k].astype(np.float64) - g64[k]).max()) / scale
-        e_t32 = float(np.abs(g32[k].astype(np.float64) - g64[k]).max()) / scale
-        print("%s %-70s e_hip %.3e e_t32 %.3e ratio %6.2f%s" % (label, k, e_hip, e_t32, e_hip / max(e_t32, 1e-30), "  (floor)" if e_hip > RATIO * e_t32 else ""))
-        assert np.isfinite(got[k]).all(), (label, k)
-        assert got[k].shape == g64[k].shape, (label, k, got[k].shape, g64[k].shape)
-        assert e_hip <= max(RATIO * e_t32, FLOOR), ("%s %s: HIP %.3g vs torch-f32 %.3g (relative to the tensor's max, against float64)" % (label, k, e_hip, e_t32))
-
-
-def _same_outputs(a, b, what):
-    for k in a:
-        assert first_mismatch(a[k], b[k]) is None, (what, k, first_mismatch(a[k], b[k]))
-
-
 @pytest.mark.parametrize("name", sorted(CASES))
 def test_encoder_gradients_meet_the_bar(name):
     c = _case(name)
@@ -158,7 +122,7 @@ def test_encoder_gradients_meet_the_bar(name):
     assert rec["relu_margin"] > MARGIN and rec["pool_gap"] > MARGIN, rec["relu_margin"]
     _, g32, _ = h.encoder_checker("float32")
     got = c.encoder_hip()
-    _assert_bar(name + " encoder", got, g64, g32)
+    assert_bar(name + " encoder", got, g64, g32)
     scale = float(np.abs(mem64).max())
     assert float(np.abs(got["memory"] - mem64).max()) <= RTOL * scale
     if h.forced and h.masks is None:
@@ -178,7 +142,7 @@ def test_postnet_gradients_meet_the_bar(name):
     assert rec["relu_margin"] > MARGIN and rec["pool_gap"] > MARGIN, rec["relu_margin"]
     _, g32, _ = h.postnet_checker("float32")
     got = c.postnet_hip()
-    _assert_bar(name + " post", got, g64, g32)
+    assert_bar(name + " post", got, g64, g32)
     scale = float(np.abs(lin64).max())
     assert float(np.abs(got["linear"] - lin64).max()) <= RTOL * scale
     if h.forced:
@@ -215,16 +179,16 @@ def test_two_runs_give_the_same_bits_also_on_nan_filled_scratch():
     for name in ("A-masked-tails", "I-dropout-masks", "E-single-speaker"):
         c = _case(name)
         for first, run in ((c.encoder_hip(), c.encoder), (c.postnet_hip(), c.postnet)):
-            _same_outputs(first, run(), name + " second run")
+            same_outputs(first, run(), name + " second run")
             poisoned = run(poison=True)
             assert all(np.isfinite(v).all() for v in poisoned.values()), name
-            _same_outputs(first, poisoned, name + " NaN-filled workspace and outputs")
+            same_outputs(first, poisoned, name + " NaN-filled workspace and outputs")
 
 
 def test_masks_of_ones_are_no_masks():
     c = _case("A-masked-tails")
     ones = [np.ones((c.h.N, c.h.T, d), np.float32) for d in c.h.hp.enc_prenet_sizes]
-    _same_outputs(c.encoder_hip(), c.encoder(masks=ones), "masks of ones")
+    same_outputs(c.encoder_hip(), c.encoder(masks=ones), "masks of ones")
 
 
 @pytest.mark.parametrize("name", ["A-masked-tails", "C-length-one", "B-nine-utterances"])
@@ -236,7 +200,7 @@ def test_a_cotangent_past_a_length_changes_nothing(name):
     for n, ln in enumerate(h.ln):
         d[n, ln:] = rng.randn(*d[n, ln:].shape).astype(np.float32)
     assert first_mismatch(d, h.d_memory) is not None
-    _same_outputs(c.encoder_hip(), c.encoder(d_memory=d), "cotangent past the lengths")
+    same_outputs(c.encoder_hip(), c.encoder(d_memory=d), "cotangent past the lengths")
 
 
 @pytest.mark.parametrize("prioritize", [False, True])
@@ -287,7 +251,7 @@ def test_the_chain_from_the_loss_to_every_tensor(name):
     assert set(got) == set(g64), set(got) ^ set(g64)
     # every output is within RTOL of its maximum, and the loss a coeff-weighted mean of |output - target| of each side
     assert abs(loss - l64) <= RTOL * float(h.coeff.max()) * (float(np.abs(mel64).max()) + float(np.abs(lin64).max()))
-    _assert_bar(name + " chain", got, g64, res[torch.float32][3])
+    assert_bar(name + " chain", got, g64, res[torch.float32][3])
     m.forward_targets(h.tok, h.ln, h.spk, h.tgt, teacher_forced=False)
     for call in (lambda: m.loss_gradients(h.lin_tgt), lambda: m.encoder_grad(h.d_memory), lambda: m.postnet_grad(h.d_linear),
                  lambda: m.linear_loss_cotangent(h.lin_tgt)):

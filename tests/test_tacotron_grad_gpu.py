@@ -3,74 +3,32 @@ autograd checker tests/torch_tacotron_grad_ref.py, held to the project's gradien
 8 x the float32 autograd run's own distance from float64, floor 5e-6 of the tensor's maximum), and the exact properties of the pass:
 linearity in d_mel, causality of the tape, masking, per-utterance independence, repeatability on NaN-filled scratch, masks of ones.
 
-Default decoder widths, small encoder / post banks (SMALL of tests/test_tacotron_targets_gpu.py).  Every case's device pass and checker
-passes are computed once and shared."""
-import ctypes as C
+The cases and their host-made inputs are tests/tacotron_grad_cases.py (default decoder widths, small encoder / post banks); every case's
+device pass and checker passes are computed once and shared."""
 import functools
 
 import numpy as np
 import pytest
 
-from helpers import first_mismatch
-from train_cases import FLOOR, RATIO
+from helpers import assert_bar, first_mismatch, run_grad_handle, same_outputs
+from tacotron_grad_cases import CASES, R_, HostCase
 
 pytestmark = pytest.mark.gpu
 
 RTOL = 5e-5          # float32 kernel vs float64 restatement, per output, relative to its maximum (tests/test_tacotron_targets_gpu.py)
-R_ = 5
-SMALL = dict(enc_bank_size=4, post_bank_size=3, num_freq=129)
 TINY = float(np.finfo(np.float32).tiny)
-# id -> (N, T_in, lengths, steps, hparams overrides, masks, seed)
-CASES = {
-    "A-masked-tails": (3, 19, (19, 12, 7), 8, {}, False, 131),
-    "B-clamp": (2, 40, (40, 33), 12, {}, False, 141),
-    "C-nine-utterances": (9, 23, (23, 20, 17, 14, 11, 8, 5, 23, 2), 5, {}, False, 151),
-    "D-one-step": (3, 19, (19, 12, 7), 1, {}, False, 161),
-    "E-length-one": (3, 19, (19, 1, 7), 4, {}, False, 171),
-    "F-one-layer": (3, 19, (19, 12, 7), 4, dict(dec_layer_num=1), False, 181),
-    "G-bah_mon": (3, 19, (19, 12, 7), 4, dict(attention_type="bah_mon"), False, 191),
-    "H-dropout-masks": (3, 19, (19, 12, 7), 8, {}, True, 131),
-}
 
 
-def _hp(**kw):
-    import twvk_amd
-    hp = twvk_amd.default_hparams()
-    for k, v in kw.items():
-        setattr(hp, k, v)
-    return hp
-
-
-class _Case(object):
-    """a model with its weights on the device, a teacher-forced pass (which leaves memory and the initial states in the workspace), and the
-    C entry on copies of those"""
+class _Case(HostCase):
+    """a host case with its model on the device, a teacher-forced pass (which leaves memory and the initial states in the workspace), and
+    the C entry on copies of those"""
 
     def __init__(self, name):
         import torch
-        import torch_attention_ref as AR
-        import torch_tacotron_grad_ref as G
         from twvk_amd.tacotron import Tacotron
-        self.name = name
-        self.N, self.T, lengths, self.steps, kw, with_masks, seed = CASES[name]
-        self.hp = _hp(max_iters=max(self.steps, 8), **dict(SMALL, **kw))
-        self.at = self.hp.attention_type
+        HostCase.__init__(self, name)
         self.m = Tacotron(self.hp, num_speakers=2)
-        self.w = AR.random_tensors(self.m.specs, seed=seed)
         self.m.load_weights(self.w)
-        self.dims, self.names = AR.Dims(self.hp, 2), G.decoder_names(self.m.specs)
-        rng = np.random.RandomState(seed + 1)
-        self.tok = rng.randint(2, 80, (self.N, self.T)).astype(np.int32)
-        for n, ln in enumerate(lengths):
-            self.tok[n, ln - 1] = 1
-            self.tok[n, ln:] = 0
-        self.ln = np.asarray(lengths, np.int32)
-        self.spk = (np.arange(self.N) % 2).astype(np.int32)
-        M, TO = self.hp.num_mels, self.steps * R_
-        self.tgt = rng.uniform(-4.0, 4.0, (self.N, TO, M)).astype(np.float32)
-        self.d_mel = (rng.randn(self.N, TO, M) / (self.N * TO * M)).astype(np.float32)
-        self.masks = None
-        if with_masks:          # dropout at keep_prob 0.5: multipliers 0 or 2
-            self.masks = [(2.0 * rng.randint(0, 2, (self.N, self.steps, d))).astype(np.float32) for d in self.hp.dec_prenet_sizes]
         self.fwd_mel = self.m.forward_targets(self.tok, self.ln, self.spk, self.tgt, teacher_forced=True)[0].cpu().numpy()
         self.memory = self.m.workspace_view(self.N, self.T, "memory").clone().view(self.N, self.T, -1)
         self.init = self.m.workspace_view(self.N, self.T, "decoder_init").clone().view(self.N, -1)
@@ -90,29 +48,21 @@ class _Case(object):
         m1, m2 = (up(mk[0]), up(mk[1])) if mk is not None else (None, None)
         ln = up(self.ln)
         memory, init = self.memory[sl].contiguous(), self.init[sl].contiguous()
-        g = C.c_void_p()
-        _lib.check(m._L.twv_tacotron_decoder_grad_create(m._h, N, self.T, self.steps, C.byref(g)))
-        try:
-            route = dict(kv.split("=", 1) for kv in m._L.twv_tacotron_decoder_grad_route(g).decode().split())
+
+        def check_route(route):
             assert route["kernel"] == "tg_bptt" and route["attention"] == self.at and route["layers"] == str(self.hp.dec_layer_num), route
-            fill = float("nan") if poison else 0.0
-            ws = torch.full((m._L.twv_tacotron_decoder_grad_workspace_bytes(g) // 4,), fill, dtype=torch.float32, device=dev)
-            new = lambda *shape: torch.full(shape, fill, dtype=torch.float32, device=dev)
+
+        def call(g, ws, status, new):
             mel, grad = new(N, self.steps * R_, self.hp.num_mels), new(m._blob.numel())
             d_memory, d_init = new(N, self.T, memory.shape[2]), new(N, init.shape[1])
-            status = torch.zeros(4, dtype=torch.int32, device=dev)
-            with torch.cuda.device(dev):
-                _lib.check(m._L.twv_tacotron_decoder_grad_run(g, _ptr(m._blob), _ptr(memory), _ptr(init), _ptr(ln), _ptr(tg), _ptr(dm), _ptr(m1),
-                                                              _ptr(m2), _ptr(ws), _ptr(status), _stream(), _ptr(mel), _ptr(grad), _ptr(d_memory),
-                                                              _ptr(d_init)))
-                torch.cuda.synchronize()
-            flat = grad.cpu().numpy()
-            out = {"d_memory": d_memory.cpu().numpy(), "d_init": d_init.cpu().numpy(), "mel": mel.cpu().numpy(), "blob": flat}
-            for name, off, shp in decoder_grad_layout(m.specs):
-                out[name] = flat[off:off + int(np.prod(shp))].reshape(shp)
-            return out
-        finally:
-            m._L.twv_tacotron_decoder_grad_destroy(g)
+            _lib.check(m._L.twv_tacotron_decoder_grad_run(g, _ptr(m._blob), _ptr(memory), _ptr(init), _ptr(ln), _ptr(tg), _ptr(dm), _ptr(m1),
+                                                          _ptr(m2), _ptr(ws), _ptr(status), _stream(), _ptr(mel), _ptr(grad), _ptr(d_memory),
+                                                          _ptr(d_init)))
+            return {"d_memory": d_memory, "d_init": d_init, "mel": mel, "blob": grad}
+        out = run_grad_handle(m, "twv_tacotron_decoder_grad", (N, self.T, self.steps), check_route, poison, call)
+        for name, off, shp in decoder_grad_layout(m.specs):
+            out[name] = out["blob"][off:off + int(np.prod(shp))].reshape(shp)
+        return out
 
     @functools.lru_cache(maxsize=None)
     def hip(self):
@@ -132,28 +82,6 @@ def _case(name):
     return _Case(name)
 
 
-def _assert_bar(label, got, g64, g32):
-    """every gradient tensor, d_memory and d_init: max|g_hip - g64| <= max(RATIO * max|g32 - g64|, FLOOR * max|g64|)"""
-    worst = ("", 0.0, 0.0)
-    for k in g64:
-        scale = max(float(np.abs(g64[k]).max()), 1e-30)
-        e_hip = float(np.abs(got[k].astype(np.float64) - g64[k]).max()) / scale
-        e_t32 = float(np.abs(g32[k].astype(np.float64) - g64[k]).max()) / scale
-        print("%s %-100s e_hip %.3e e_t32 %.3e ratio %6.2f%s" % (label, k, e_hip, e_t32, e_hip / max(e_t32, 1e-30), "  (floor)" if e_hip > RATIO * e_t32 else ""))
-        assert np.isfinite(got[k]).all(), (label, k)
-        assert got[k].shape == g64[k].shape, (label, k, got[k].shape, g64[k].shape)
-        assert e_hip <= max(RATIO * e_t32, FLOOR), ("%s %s: HIP %.3g vs torch-f32 %.3g (relative to the tensor's max, against float64)" % (label, k, e_hip, e_t32))
-        if e_hip > worst[1]:
-            worst = (k, e_hip, e_t32)
-    return worst
-
-
-def _same_outputs(a, b, what, skip=()):
-    for k in a:
-        if k not in skip:
-            assert first_mismatch(a[k], b[k]) is None, (what, k, first_mismatch(a[k], b[k]))
-
-
 @pytest.mark.parametrize("name", sorted(CASES))
 def test_gradients_meet_the_bar_and_the_recorded_forward_is_the_forward(name):
     c = _case(name)
@@ -164,7 +92,7 @@ def test_gradients_meet_the_bar_and_the_recorded_forward_is_the_forward(name):
         assert rec["clamp_engaged"], "case B is there for the 1e-10 clamp"
     _, g32, _ = c.checker("float32")
     got = c.hip()
-    _assert_bar(name, got, g64, g32)
+    assert_bar(name, got, g64, g32)
     scale = float(np.abs(mel64).max())
     assert float(np.abs(got["mel"] - mel64).max()) <= RTOL * scale
     if c.masks is None:
@@ -198,7 +126,7 @@ def test_tape_is_causal():
     a, b = c.run(d_mel=d_mel), c.run(d_mel=d_mel, tgt=tgt)
     assert first_mismatch(a["mel"], b["mel"]) is not None, "the changed targets must reach the later steps"
     assert first_mismatch(a["mel"][:, :(k + 1) * R_], b["mel"][:, :(k + 1) * R_]) is None
-    _same_outputs(a, b, "causality", skip=("mel",))
+    same_outputs(a, b, "causality", skip=("mel",))
     assert a["d_memory"].any() and a["d_init"].any()
 
 
@@ -224,16 +152,16 @@ def test_two_runs_give_the_same_bits_also_on_nan_filled_scratch():
     for name in ("A-masked-tails", "H-dropout-masks"):
         c = _case(name)
         first = c.hip()
-        _same_outputs(first, c.run(), name + " second run")
+        same_outputs(first, c.run(), name + " second run")
         poisoned = c.run(poison=True)
         assert all(np.isfinite(v).all() for v in poisoned.values()), name
-        _same_outputs(first, poisoned, name + " NaN-filled workspace and outputs")
+        same_outputs(first, poisoned, name + " NaN-filled workspace and outputs")
 
 
 def test_masks_of_ones_are_no_masks():
     c = _case("A-masked-tails")
     ones = [np.ones((c.N, c.steps, d), np.float32) for d in c.hp.dec_prenet_sizes]
-    _same_outputs(c.hip(), c.run(masks=ones), "masks of ones")
+    same_outputs(c.hip(), c.run(masks=ones), "masks of ones")
 
 
 def test_end_to_end_from_tokens():
@@ -257,7 +185,7 @@ def test_end_to_end_from_tokens():
         res[dt] = G.decoder_vjp(c.w, c.names, c.dims, memory, init, c.ln, c.at, c.tgt, cot_np, dtype=dt)
     mel64, g64, rec = res[torch.float64]
     assert rec["cumprod_margin"] > 1e-3 and rec["min_one_minus_p"] >= TINY, rec
-    _assert_bar("end-to-end", got, g64, res[torch.float32][1])
+    assert_bar("end-to-end", got, g64, res[torch.float32][1])
     assert float(np.abs(got["mel"] - mel64).max()) <= RTOL * float(np.abs(mel64).max())
     # the methods need a teacher-forced pass
     c.m.forward_targets(c.tok, c.ln, c.spk, c.tgt, teacher_forced=False)
