@@ -356,6 +356,35 @@ int twv_tacotron_cbhg_grad_phase_ms(twv_tacotron_cbhg_grad* g, double* ms4);
 int twv_tacotron_linear_loss_grad(const float* linear, const float* linear_targets, const float* loss_coeff, int batch, int t_out,
                                   int num_freq, int prioritize_loss, double sample_rate, float* d_linear, void* stream);
 
+/* ---- Tacotron training step: the speaker side's gradient and the training vector ----
+ * The gradient of the speaker tensors from the three cotangents the other passes hand back: d_before_highway (batch, enc_prenet_sizes[1])
+ * and d_encoder_rnn_init (batch, 2 * enc_rnn_size) of twv_tacotron_encoder_grad_run, d_init (batch, attention_state_size + dec_layer_num *
+ * dec_rnn_size) of twv_tacotron_decoder_grad_run.
+ * 'deepvoice' with a speaker embedding: per dense layer i (0 <- d_before_highway, 1 <- d_encoder_rnn_init, 2 .. <- the column blocks of
+ * d_init) z_i = e W_i + b_i is recomputed from blob and the rows e = speaker_embedding[speaker_ids]; dz_i = dy_i / (1 + |z_i|)^2 (softsign),
+ * dW_i = e^T dz_i, db_i = the column sum of dz_i, d_e = sum_i dz_i W_i^T, d speaker_embedding[s] = the sum of d_e[n] over speaker_ids[n] = s.
+ * speaker_embedding_size 1: the five get_embed tables, d table_i[s] = the sum of the cotangent's rows of speaker s.
+ * Only the speaker tensors' ranges of grad_blob (the layout of blob) are written.  scratch: twv_tacotron_speaker_grad_scratch_bytes of the
+ * caller's, in any state.  No atomics; every sum over utterances runs in utterance order, in float64, rounded once: equal inputs give equal
+ * bits, and a speaker no utterance names gets a row of exact zeros (an id outside 0 .. num_speakers - 1 names nobody).
+ * Host-side refusals, before the device is touched: null arguments or batch < 1 TWV_E_INVALID; a single-speaker model TWV_E_INVALID (it
+ * has no speaker tensors); model_type 'simple' TWV_E_UNSUPPORTED. */
+size_t twv_tacotron_speaker_grad_scratch_bytes(const twv_tacotron* h, int batch);
+int twv_tacotron_speaker_grad(const twv_tacotron* h, const float* blob, const int32_t* speaker_ids, int batch,
+                              const float* d_before_highway, const float* d_encoder_rnn_init, const float* d_init, void* scratch,
+                              float* grad_blob, void* stream);
+/* The training vector: every tensor of tacotron_specs in canonical order, a batch_normalization entry as its (4, C) checkpoint tensor
+ * (gamma, beta, moving_mean, moving_variance) where the blob holds the derived (inv, shift) pair: twv_tacotron_train_floats =
+ * twv_tacotron_blob_floats + 2 C per batch norm.
+ * twv_tacotron_refold: variables -> blob, the bits of tacotron.flatten (inv = (1 / sqrt(var + 1e-3)) * gamma, shift = beta - mean * inv, every
+ * operation rounded to float32 in that order); re-pack (twv_tacotron_pack) before the next pass.
+ * twv_tacotron_grad_convert: a blob-shaped gradient -> the gradient of the training vector: (d_inv, d_shift) -> d_gamma = rsqrt(var + 1e-3)
+ * (d_inv - mean d_shift), d_beta = d_shift (float64 inside), exact zeros for the moving statistics, every other range copied.
+ * Null arguments: TWV_E_INVALID. */
+size_t twv_tacotron_train_floats(const twv_tacotron* h);
+int twv_tacotron_refold(const twv_tacotron* h, const float* variables, float* blob, void* stream);
+int twv_tacotron_grad_convert(const twv_tacotron* h, const float* variables, const float* grad_blob, float* grad_variables, void* stream);
+
 /* launch geometry (performance only, results are bit-identical): "decoder_groups" = 0 auto (the XCD-resident decoder kernel wherever it
  * fits -- batch <= 32, t_in <= 512, 256 CUs, decoder widths divisible by 4, not model_type 'simple', attention_type bah_mon_norm -- else the split kernel with 16 / 8 / 4
  * workgroups per utterance), 1/2/4/8/16 = the split kernel with that many workgroups per utterance, 32 = the XCD-resident kernel or an

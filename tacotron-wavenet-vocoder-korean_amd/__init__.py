@@ -17,6 +17,9 @@ def __getattr__(name):
     if name in ("WaveNetTrainer",):
         from .train import WaveNetTrainer
         return WaveNetTrainer
+    if name in ("TacotronTrainer",):
+        from .tacotron_train import TacotronTrainer
+        return TacotronTrainer
     if name in ("text_to_wave", "texts_to_waves"):
         from . import e2e
         return getattr(e2e, name)

@@ -269,6 +269,11 @@ def lib():
     L.twv_tacotron_cbhg_grad_set_timing.argtypes = [vp, C.c_int]
     L.twv_tacotron_cbhg_grad_phase_ms.argtypes = [vp, C.POINTER(C.c_double)]
     L.twv_tacotron_linear_loss_grad.argtypes = [fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, fp, vp]
+    L.twv_tacotron_speaker_grad_scratch_bytes.argtypes = [vp, C.c_int]; L.twv_tacotron_speaker_grad_scratch_bytes.restype = C.c_size_t
+    L.twv_tacotron_speaker_grad.argtypes = [vp, fp, ip, C.c_int, fp, fp, fp, vp, fp, vp]
+    L.twv_tacotron_train_floats.argtypes = [vp]; L.twv_tacotron_train_floats.restype = C.c_size_t
+    L.twv_tacotron_refold.argtypes = [vp, fp, fp, vp]
+    L.twv_tacotron_grad_convert.argtypes = [vp, fp, fp, fp, vp]
     L.twv_tacotron_set_profile_buffer.argtypes = [vp, vp]
     L.twv_tacotron_set_option.argtypes = [vp, C.c_char_p, C.c_int]
     L.twv_tacotron_gemm_stats.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]
@@ -321,7 +326,9 @@ EXPORTS = ["twv_last_error", "twv_version", "twv_wavenet_create", "twv_wavenet_d
            "twv_tacotron_decoder_grad_set_timing", "twv_tacotron_decoder_grad_phase_ms", "twv_tacotron_mel_loss_grad",
            "twv_tacotron_cbhg_grad_create", "twv_tacotron_cbhg_grad_destroy", "twv_tacotron_cbhg_grad_workspace_bytes",
            "twv_tacotron_cbhg_grad_route", "twv_tacotron_encoder_grad_run", "twv_tacotron_postnet_grad_run",
-           "twv_tacotron_cbhg_grad_set_timing", "twv_tacotron_cbhg_grad_phase_ms", "twv_tacotron_linear_loss_grad"]
+           "twv_tacotron_cbhg_grad_set_timing", "twv_tacotron_cbhg_grad_phase_ms", "twv_tacotron_linear_loss_grad",
+           "twv_tacotron_speaker_grad_scratch_bytes", "twv_tacotron_speaker_grad", "twv_tacotron_train_floats", "twv_tacotron_refold",
+           "twv_tacotron_grad_convert"]
 
 
 class TacoDims(C.Structure):

@@ -184,6 +184,35 @@ def postnet_grad_layout(specs):
     return _grad_layout(specs, lambda i, n: n.startswith("post_cbhg/") or i >= len(specs) - 2)
 
 
+def speaker_grad_layout(specs):
+    """the same for Tacotron.speaker_grad: what lies between embedding and prenet/dense_1/kernel -- the speaker table and its dense layers,
+    or the five tables of speaker_embedding_size 1 (nothing for a single speaker)"""
+    names = [n for n, _ in specs]
+    first, last = names.index("embedding") + 1, names.index("prenet/dense_1/kernel")
+    return _grad_layout(specs, lambda i, n: first <= i < last)
+
+
+def training_layout(specs):
+    """(name, offset, shape) of every tensor in the training vector (twv_tacotron_train_floats): the canonical order with a
+    batch_normalization entry as its (4, C) checkpoint tensor"""
+    out, off = [], 0
+    for n, shp in specs:
+        out.append((n, off, tuple(shp)))
+        off += int(np.prod(shp))
+    return out
+
+
+def flatten_variables(specs, tensors):
+    """the training vector of these tensors (flatten without the batch norm folding)"""
+    parts = []
+    for n, shp in specs:
+        a = np.asarray(tensors[n], np.float32)
+        if tuple(a.shape) != tuple(shp):
+            raise ValueError("tensor %s has shape %s, expected %s" % (n, a.shape, shp))
+        parts.append(a.reshape(-1))
+    return np.concatenate(parts).astype(np.float32)
+
+
 def bn_grad_from_inference_pair(pair, raw):
     """a batch norm's gradient as the checkpoint stores the layer: (d_inv, d_shift) of the derived pair (flatten) and the raw (4, C) tensor
     -> (d_gamma, d_beta) as (2, C) float32, float64 inside:
@@ -371,6 +400,14 @@ class Tacotron(object):
         prenet's relus (dropout: 0 or 1 / keep_prob).  Returns a dict: every decoder-side checkpoint tensor's gradient by name (TF scalars
         as (1,)), "d_memory" (N, T_in, 2 * enc_rnn_size), "d_init" (N, attention_state_size + dec_layer_num * dec_rnn_size) and "mel", the
         recorded forward's output -- device tensors."""
+        grad, d_memory, d_init, mel_out = self._decoder_grad_blob(d_mel, prenet_masks)
+        with torch.cuda.device(self.device):
+            out = self._named_grads(grad, decoder_grad_layout(self.specs))       # (no batch norm on the decoder side)
+        out.update({"d_memory": d_memory, "d_init": d_init, "mel": mel_out})
+        return out
+
+    def _decoder_grad_blob(self, d_mel, prenet_masks=None):
+        """decoder_grad's pass with the gradient as the C entry leaves it: (blob-shaped gradient, d_memory, d_init, mel)"""
         hp = self._hparams
         mel, tgt = self._forced_pass("decoder_grad")
         if getattr(self, "_blob", None) is None:
@@ -392,9 +429,7 @@ class Tacotron(object):
             _lib.check(self._L.twv_tacotron_decoder_grad_run(g, _ptr(self._blob), _ptr(memory), _ptr(init), _ptr(self.input_lengths),
                                                              _ptr(tgt), _ptr(dm), _ptr(masks[0]), _ptr(masks[1]), _ptr(ws),
                                                              _ptr(status), _stream(), _ptr(mel_out), _ptr(grad), _ptr(d_memory), _ptr(d_init)))
-            out = self._named_grads(grad, decoder_grad_layout(self.specs))       # (no batch norm on the decoder side)
-        out.update({"d_memory": d_memory, "d_init": d_init, "mel": mel_out})
-        return out
+        return grad, d_memory, d_init, mel_out
 
     def decoder_grad_route(self):
         """the label of the gradient kernels of the last decoder_grad call ('' before one)"""
@@ -483,6 +518,14 @@ class Tacotron(object):
         cotangent on linear_outputs; mel (N, T_out, num_mels) the post net's input, by default the mel_outputs of the last teacher-forced
         forward_targets pass.  Returns a dict: the gradient of every post_cbhg/* tensor and of the linear layer by name (batch norms as
         (2, C) = d_gamma, d_beta), "d_mel" (the cotangent on mel) and "linear", the recorded forward's output."""
+        grad, d_mel, lin = self._postnet_grad_blob(d_linear, mel)
+        with torch.cuda.device(self.device):
+            out = self._named_grads(grad, postnet_grad_layout(self.specs))
+        out["d_mel"], out["linear"] = d_mel, lin
+        return out
+
+    def _postnet_grad_blob(self, d_linear, mel=None):
+        """postnet_grad's pass with the gradient as the C entry leaves it: (blob-shaped gradient, d_mel, linear)"""
         hp = self._hparams
         mel0, _ = self._forced_pass("postnet_grad")
         if getattr(self, "_blob", None) is None:
@@ -500,9 +543,7 @@ class Tacotron(object):
             status = torch.zeros(4, dtype=torch.int32, device=self.device)
             _lib.check(self._L.twv_tacotron_postnet_grad_run(g, _ptr(self._blob), _ptr(mel), _ptr(dl), _ptr(ws), _ptr(status), _stream(),
                                                              _ptr(lin), _ptr(grad), _ptr(d_mel)))
-            out = self._named_grads(grad, postnet_grad_layout(self.specs))
-        out["d_mel"], out["linear"] = d_mel, lin
-        return out
+        return grad, d_mel, lin
 
     def encoder_grad(self, d_memory, prenet_masks=None):
         """The vector-Jacobian product of the encoder (embedding, prenet, encoder CBHG) of the last forward_targets(teacher_forced=True)
@@ -511,6 +552,16 @@ class Tacotron(object):
         graph) or two (N, T_in, enc_prenet_sizes[i]) arrays of multipliers after the prenet's relus.  Returns a dict: the gradient of
         embedding, prenet/* and encoder_cbhg/* by name (batch norms as (2, C) = d_gamma, d_beta), "memory" (the recorded output) and, for a
         multi-speaker model, "d_before_highway" (N, enc_prenet_sizes[1]) and "d_encoder_rnn_init" (N, 2 * enc_rnn_size)."""
+        grad, memory, d_bh, d_init = self._encoder_grad_blob(d_memory, prenet_masks)
+        with torch.cuda.device(self.device):
+            out = self._named_grads(grad, encoder_grad_layout(self.specs))
+        out["memory"] = memory
+        if d_bh is not None:
+            out["d_before_highway"], out["d_encoder_rnn_init"] = d_bh, d_init
+        return out
+
+    def _encoder_grad_blob(self, d_memory, prenet_masks=None):
+        """encoder_grad's pass with the gradient as the C entry leaves it: (blob-shaped gradient, memory, d_before_highway, d_encoder_rnn_init)"""
         hp = self._hparams
         self._forced_pass("encoder_grad")
         if getattr(self, "_blob", None) is None:
@@ -532,11 +583,7 @@ class Tacotron(object):
             _lib.check(self._L.twv_tacotron_encoder_grad_run(g, _ptr(self._blob), _ptr(self.inputs), _ptr(self.input_lengths), _ptr(bh), _ptr(init),
                                                              _ptr(masks[0]), _ptr(masks[1]), _ptr(dm), _ptr(ws), _ptr(status), _stream(),
                                                              _ptr(memory), _ptr(grad), _ptr(d_bh), _ptr(d_init)))
-            out = self._named_grads(grad, encoder_grad_layout(self.specs))
-        out["memory"] = memory
-        if d_bh is not None:
-            out["d_before_highway"], out["d_encoder_rnn_init"] = d_bh, d_init
-        return out
+        return grad, memory, d_bh, d_init
 
     def loss_gradients(self, linear_targets, loss_coeff=None):
         """The gradient of add_loss's `loss` (tacotron.py:258-282) on the last forward_targets(teacher_forced=True) pass, in the evaluation
@@ -552,6 +599,49 @@ class Tacotron(object):
         out = {}
         for part in (enc, dec, post):
             out.update({k: v for k, v in part.items() if k not in ("memory", "mel", "linear", "d_mel", "d_memory")})
+        return out
+
+    def _speaker_grad_blob(self, d_before_highway, d_encoder_rnn_init, d_init, grad=None):
+        """twv_tacotron_speaker_grad on the speaker ids of the last pass: the speaker tensors' ranges of `grad` (a new blob-shaped buffer,
+        other ranges unwritten, when None) are written; returns it"""
+        hp = self._hparams
+        if getattr(self, "_blob", None) is None:
+            raise ValueError("speaker_grad needs load_weights first")
+        sp = getattr(self, "speaker_id", None)
+        if self.num_speakers > 1 and sp is None:
+            raise ValueError("speaker_grad needs a pass (infer / forward_targets) first: it reads that pass's speaker ids")
+        N = int(sp.shape[0]) if sp is not None else int(np.shape(d_init)[0])
+        if sp is None:          # a single-speaker model: the library refuses it in its own words
+            sp = torch.zeros(N, dtype=torch.int32, device=self.device)
+        ninit = hp.attention_state_size + hp.dec_layer_num * hp.dec_rnn_size
+        with torch.cuda.device(self.device):
+            d_bh = self._device_f32(d_before_highway, (N, hp.enc_prenet_sizes[1]), "d_before_highway must be %s, got %s")
+            d_ei = self._device_f32(d_encoder_rnn_init, (N, 2 * hp.enc_rnn_size), "d_encoder_rnn_init must be %s, got %s")
+            d_di = self._device_f32(d_init, (N, ninit), "d_init must be %s, got %s")
+            if grad is None:
+                grad = torch.empty_like(self._blob)
+            need = max(self._L.twv_tacotron_speaker_grad_scratch_bytes(self._h, N) // 4, 4)
+            scratch = self.__dict__.get("_speaker_scratch")
+            if scratch is None or scratch.numel() < need:
+                scratch = self._speaker_scratch = torch.empty(need, dtype=torch.float32, device=self.device)
+            _lib.check(self._L.twv_tacotron_speaker_grad(self._h, _ptr(self._blob), _ptr(sp), N, _ptr(d_bh), _ptr(d_ei), _ptr(d_di), _ptr(scratch),
+                                                         _ptr(grad), _stream()))
+        return grad
+
+    def speaker_grad(self, d_before_highway, d_encoder_rnn_init, d_init):
+        """The gradient of the speaker side of a multi-speaker 'deepvoice' model from the three cotangents loss_gradients hands back
+        (encoder_grad's "d_before_highway" and "d_encoder_rnn_init", decoder_grad's "d_init"), for the speaker ids of the last pass.
+        Returns a dict by checkpoint name: speaker_embedding and dense* kernel / bias, or the five tables of speaker_embedding_size 1
+        (tacotron.py:64-84).  A single-speaker model and model_type 'simple' are refused by the library."""
+        grad = self._speaker_grad_blob(d_before_highway, d_encoder_rnn_init, d_init)
+        return self._named_grads(grad, speaker_grad_layout(self.specs))
+
+    def variable_gradients(self, linear_targets, loss_coeff=None):
+        """loss_gradients plus the speaker tensors: the gradient of add_loss's `loss` with respect to every trainable checkpoint tensor of the
+        model, in the evaluation graph (moving-average batch norm, no dropout).  Keeps loss_gradients' hand-off entries."""
+        out = self.loss_gradients(linear_targets, loss_coeff)
+        if self.num_speakers > 1:
+            out.update(self.speaker_grad(out["d_before_highway"], out["d_encoder_rnn_init"], out["d_init"]))
         return out
 
     def add_loss(self, linear_targets, loss_coeff=None):

@@ -1,0 +1,245 @@
+"""Host-side mirror of the reference's Tacotron update rule (tacotron/tacotron.py:285-313 `add_optimizer`) over the HIP C-ABI, on the
+EVALUATION graph:
+
+    model = Tacotron(hparams, num_speakers); model.load_weights(tensors)
+    trainer = TacotronTrainer(model, randomly_initialized=True)
+    losses = trainer.step(inputs, input_lengths, speaker_id, mel_targets, linear_targets)     # == sess.run([model.loss, model.optimize])
+
+One step is forward_targets(teacher_forced=True) -> add_loss -> the three gradient passes and the speaker side -> the gradient of the
+training vector -> tf.clip_by_global_norm(gradients, 1.0) -> AdamOptimizer(lr, adam_beta1, adam_beta2) -> the new inference blob, all on
+the device; the only device -> host traffic is add_loss's four numbers.
+
+What this is NOT: the reference trains with batch-statistics batch norm and dropout (is_training=True).  Those change the forward graph
+of all three gradient passes and are not built; here the moving statistics are frozen and there is no dropout -- a fine-tuning step with
+frozen batch norm.  The moving statistics ride along in the flat Adam call with a zero gradient and zero moments, which leaves them
+untouched bit for bit (TensorFlow does not hand non-trainable variables to the optimiser at all).  A data feeder, a `train_tacotron`
+command line and the gradient all-reduce are not built either.
+PyTorch is used for device memory and streams only."""
+import os
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import checkpoint as ckpt
+from .tacotron import _ptr, _stream, flatten_variables, training_layout
+
+CLIP_NORM = 1.0          # tacotron.py:306 tf.clip_by_global_norm(gradients, 1.0)
+ADAM_EPSILON = 1e-8      # tf.train.AdamOptimizer's default
+SCOPE = "model/inference/"
+
+
+def learning_rate(lr0, step, mode=0, randomly_initialized=True):
+    """tacotron.py:292-303 with step = global_step + 1.  mode 0: lr0 * w^0.5 * min(step * w^-1.5, step^-0.5), w = 4000 warm-up steps for a
+    randomly initialised model and 40000 otherwise (the peak lr0 is reached at step = w); mode 1: lr0 * 0.95^(step / 3000)"""
+    step = float(step)
+    if mode == 0:
+        w = 4000.0 if randomly_initialized else 40000.0
+        return float(lr0) * w ** 0.5 * min(step * w ** -1.5, step ** -0.5)
+    if mode == 1:
+        return float(lr0) * 0.95 ** (step / 3000.0)
+    raise ValueError("decay_learning_rate_mode must be 0 or 1, got %r" % (mode,))
+
+
+def _copy_runs(specs, picks):
+    """[(first float, one past the last)] of the maximal runs of blob floats whose tensor satisfies pick(i, name)"""
+    runs, off = [], 0
+    for i, (n, shp) in enumerate(specs):
+        size = 2 * shp[1] if n.endswith("batch_normalization") else int(np.prod(shp))
+        if picks(i, n):
+            if runs and runs[-1][1] == off:
+                runs[-1][1] = off + size
+            else:
+                runs.append([off, off + size])
+        off += size
+    return [tuple(r) for r in runs]
+
+
+class TacotronTrainer(object):
+    def __init__(self, model, randomly_initialized=True):
+        """model: a Tacotron, with weights loaded or to be given its weights by `restore`; the trainer updates the model's blob in place, so
+        `infer` and `forward_targets` see the new weights after every step.  randomly_initialized: tacotron.py:296-299, the warm-up of
+        learning-rate mode 0."""
+        hp = model._hparams
+        self.model, self.device, self._L = model, model.device, model._L
+        self.randomly_initialized = bool(randomly_initialized)
+        self.lr0, self.mode = hp.tacotron_initial_learning_rate, hp.decay_learning_rate_mode
+        learning_rate(self.lr0, 1, self.mode, self.randomly_initialized)         # (refuses another mode here, not at the first step)
+        self.beta1, self.beta2, self.epsilon = hp.adam_beta1, hp.adam_beta2, ADAM_EPSILON
+        self.max_checkpoints = getattr(hp, "max_checkpoints", 3)
+        self.layout = training_layout(model.specs)
+        self.n_variables = int(self._L.twv_tacotron_train_floats(model._h))
+        assert self.n_variables == sum(int(np.prod(s)) for _, _, s in self.layout), self.n_variables
+        names = [n for n, _ in model.specs]
+        first, last = names.index("embedding") + 1, names.index("prenet/dense_1/kernel")
+        dec0, dec1 = names.index("memory_layer/kernel"), names.index("decoder/output_projection_wrapper/bias")
+        # each of the three gradient passes zeroes the whole blob-shaped buffer it is given before it writes its own range (tgrad::Handle::
+        # begin), so one buffer cannot serve all three: each writes a buffer of its own and its range is copied into the step's gradient
+        self._runs = {"encoder": _copy_runs(model.specs, lambda i, n: not first <= i < last and i < dec0),
+                      "decoder": _copy_runs(model.specs, lambda i, n: dec0 <= i <= dec1),
+                      "post": _copy_runs(model.specs, lambda i, n: i > dec1)}
+        self._speaker = model.num_speakers > 1
+        self.global_step = 0
+        self.vars = None
+        if getattr(model, "_blob", None) is not None:
+            self._set_variables(self._model_tensors())
+
+    # ---- variables
+    def _model_tensors(self):
+        """the checkpoint tensors the model holds: the blob's ranges, and the raw (4, C) tensors load_weights kept of every batch norm"""
+        m = self.model
+        blob, out, off = m._blob.cpu().numpy(), {}, 0
+        for n, shp in m.specs:
+            if n.endswith("batch_normalization"):
+                out[n] = np.asarray(m._bn_raw[n], np.float32)
+                off += 2 * shp[1]
+            else:
+                size = int(np.prod(shp))
+                out[n] = blob[off:off + size].reshape(shp).copy()
+                off += size
+        return out
+
+    def _set_variables(self, tensors, m=None, v=None):
+        flat = flatten_variables(self.model.specs, tensors)
+        assert flat.size == self.n_variables, (flat.size, self.n_variables)
+        with torch.cuda.device(self.device):
+            self.vars = torch.from_numpy(flat).to(self.device)
+            self.m = torch.zeros_like(self.vars) if m is None else torch.from_numpy(m).to(self.device)
+            self.v = torch.zeros_like(self.vars) if v is None else torch.from_numpy(v).to(self.device)
+            self._shadow = self.vars.clone()                # twv_adam_ema_step's shadow: written, never read
+            self.grads = torch.zeros_like(self.vars)
+            self._gblob = torch.zeros_like(self.model._blob)
+            self._clip_scratch = torch.empty(self.n_variables + 2048, dtype=torch.float32, device=self.device)
+
+    def _named(self, flat):
+        host = flat.detach().cpu().numpy()
+        return {n: host[off:off + int(np.prod(shp))].reshape(shp).copy() for n, off, shp in self.layout}
+
+    def variables(self):
+        """every checkpoint tensor by tacotron_specs name (batch norms as (4, C)), numpy"""
+        return self._named(self.vars)
+
+    def gradients(self):
+        """the last step's gradient of the training vector as Adam saw it (after the clip), by name"""
+        return self._named(self.grads)
+
+    def learning_rate(self, step):
+        """the schedule at step = global_step + 1 (tacotron.py:292-303)"""
+        return learning_rate(self.lr0, step, self.mode, self.randomly_initialized)
+
+    # ---- compute_gradients
+    def loss_and_gradients(self, inputs, input_lengths, speaker_id, mel_targets, linear_targets, loss_coeff=None):
+        """forward_targets(teacher_forced=True), add_loss and d loss / d (training vector) into self.grads (unclipped); returns add_loss's dict"""
+        m = self.model
+        if self.vars is None:
+            raise RuntimeError("no weights: give the model its weights (load_weights) before the trainer is made, or call restore")
+        m.forward_targets(inputs, input_lengths, speaker_id, mel_targets, teacher_forced=True)
+        out = m.add_loss(linear_targets, loss_coeff)
+        self._forward_done()
+        with torch.cuda.device(self.device):
+            g = self._gblob
+            post, d_mel_post, _ = m._postnet_grad_blob(m.linear_loss_cotangent(linear_targets, loss_coeff))
+            self._collect(g, post, "post")
+            dec, d_memory, d_init, _ = m._decoder_grad_blob(m.mel_loss_cotangent(loss_coeff) + d_mel_post)
+            self._collect(g, dec, "decoder")
+            enc, _, d_bh, d_ei = m._encoder_grad_blob(d_memory)
+            self._collect(g, enc, "encoder")
+            self._passes_done()
+            if self._speaker:
+                m._speaker_grad_blob(d_bh, d_ei, d_init, grad=g)
+            self._speaker_done()
+            _lib.check(self._L.twv_tacotron_grad_convert(m._h, _ptr(self.vars), _ptr(g), _ptr(self.grads), _stream()))
+        return out
+
+    def _collect(self, grad, part, which):
+        for a, b in self._runs[which]:
+            grad[a:b].copy_(part[a:b])
+
+    # (phase boundaries: scripts/tacotron_train_bench.py records events here)
+    def _forward_done(self):
+        pass
+
+    def _passes_done(self):
+        pass
+
+    def _speaker_done(self):
+        pass
+
+    # ---- clip_by_global_norm + apply_gradients
+    def apply_gradients(self):
+        m = self.model
+        lr = self.learning_rate(self.global_step + 1)
+        with torch.cuda.device(self.device):
+            _lib.check(self._L.twv_clip_by_global_norm(_ptr(self.grads), self.n_variables, 1.0, CLIP_NORM, _ptr(self._clip_scratch), _stream()))
+            _lib.check(self._L.twv_adam_ema_step(_ptr(self.vars), _ptr(self.grads), _ptr(self.m), _ptr(self.v), _ptr(self._shadow),
+                                                self.n_variables, lr, self.beta1, self.beta2, self.epsilon, self.global_step + 1, 0.0, 1.0,
+                                                _stream()))
+            self._refold()
+        self.global_step += 1
+        return lr
+
+    def _refold(self):
+        """the training vector -> the model's blob and packed weights (the moving statistics never move, so the mean and variance the model
+        keeps on the host for bn_grad_from_inference_pair stay those of the blob)"""
+        m = self.model
+        _lib.check(self._L.twv_tacotron_refold(m._h, _ptr(self.vars), _ptr(m._blob), _stream()))
+        _lib.check(self._L.twv_tacotron_pack(m._h, _ptr(m._blob), _ptr(m._packed), _stream()))
+
+    def step(self, inputs, input_lengths, speaker_id, mel_targets, linear_targets, loss_coeff=None):
+        """one sess.run([model.loss, model.optimize]) on the evaluation graph; returns add_loss's dict (the loss BEFORE the update) and
+        advances global_step.  `last_learning_rate` is the rate the update used."""
+        out = self.loss_and_gradients(inputs, input_lengths, speaker_id, mel_targets, linear_targets, loss_coeff)
+        self.last_learning_rate = self.apply_gradients()
+        return out
+
+    # ---- saver.save / restore
+    def save(self, logdir, step=None, include_optimizer=True, max_to_keep=None):
+        """writes `logdir/model.ckpt-<step>` as a TensorFlow V2 bundle + the `checkpoint` state file: the variables under
+        'model/inference/' (checkpoint.tacotron_variables; Synthesizer.load reads them), `global_step`, and with include_optimizer the Adam
+        moments of the trainable variables under `optimizer/<variable>/Adam`, `/Adam_1` and `optimizer/beta{1,2}_power` ([RECALLED-TF] slot
+        naming, unverified, as WaveNetTrainer.save)."""
+        step = self.global_step if step is None else int(step)
+        var = ckpt.tacotron_variables(self.variables(), SCOPE)
+        var["global_step"] = np.asarray(step, np.int32)
+        if include_optimizer:
+            for suffix, flat in (("/Adam", self.m), ("/Adam_1", self.v)):
+                for k, a in ckpt.tacotron_variables(self._named(flat), SCOPE).items():
+                    if not k.endswith(("/moving_mean", "/moving_variance")):         # (not trainable: no slots)
+                        var["optimizer/" + k + suffix] = a
+            var["optimizer/beta1_power"] = np.asarray(self.beta1 ** (self.global_step + 1), np.float32)
+            var["optimizer/beta2_power"] = np.asarray(self.beta2 ** (self.global_step + 1), np.float32)
+        prefix = os.path.join(logdir, "model.ckpt-%d" % step)
+        ckpt.write_bundle(prefix, var)
+        if max_to_keep is None:
+            max_to_keep = self.max_checkpoints
+        kept = [q for q in ckpt.all_checkpoint_paths(logdir) if q != prefix and os.path.exists(q + ".index")] + [prefix]
+        while max_to_keep and len(kept) > max_to_keep:
+            ckpt.delete_bundle(kept.pop(0))
+        ckpt.write_checkpoint_state(logdir, prefix, kept)
+        return prefix
+
+    def restore(self, path, verify=False):
+        """logdir or bundle prefix -> global step.  The variables are required and go into the model too (load_weights); the Adam moments
+        are taken when the bundle has them all (else zeros, a fresh optimizer)."""
+        prefix = ckpt.resolve(path)
+        var = ckpt.read_bundle(prefix, verify=verify)
+        specs = self.model.specs
+        tensors = ckpt.tacotron_tensors(var, specs, SCOPE)
+        self.model.load_weights(tensors)
+
+        def slots(suffix):
+            got = {}
+            for k in ckpt.tacotron_variables(tensors, SCOPE):
+                if k.endswith(("/moving_mean", "/moving_variance")):
+                    got[k] = np.zeros_like(var[k], dtype=np.float32)
+                elif "optimizer/" + k + suffix in var:
+                    got[k] = var["optimizer/" + k + suffix]
+                else:
+                    return None
+            return flatten_variables(specs, ckpt.tacotron_tensors(got, specs, SCOPE))
+        m, v = slots("/Adam"), slots("/Adam_1")
+        if m is None or v is None:
+            m = v = None
+        self._set_variables(tensors, m, v)
+        self.global_step = int(var["global_step"]) if "global_step" in var else ckpt.checkpoint_step(prefix)
+        return self.global_step
