@@ -301,6 +301,15 @@ int twv_tacotron_decoder_grad_run(twv_tacotron_decoder_grad* g, const float* blo
                                   const int32_t* lengths, const float* mel_targets, const float* d_mel, const float* mask1,
                                   const float* mask2, void* workspace, int32_t* status, void* stream, float* mel_out,
                                   float* grad_blob, float* d_memory, float* d_init);
+/* The two halves of twv_tacotron_decoder_grad_run as calls of their own (a training step runs every forward before any backward): the
+ * arguments are the run's.  The tape stays in `workspace` between the two, so the backward is given the forward's workspace, blob, memory,
+ * decoder_init and lengths.  _run is _forward followed by _backward.  _backward on a handle with no forward since create: TWV_E_INVALID. */
+int twv_tacotron_decoder_grad_forward(twv_tacotron_decoder_grad* g, const float* blob, const float* memory, const float* decoder_init,
+                                      const int32_t* lengths, const float* mel_targets, const float* mask1, const float* mask2,
+                                      void* workspace, int32_t* status, void* stream, float* mel_out);
+int twv_tacotron_decoder_grad_backward(twv_tacotron_decoder_grad* g, const float* blob, const float* memory, const float* decoder_init,
+                                       const int32_t* lengths, const float* d_mel, void* workspace, int32_t* status, void* stream,
+                                       float* grad_blob, float* d_memory, float* d_init);
 /* measurement: with timing on, a run records events at its phase boundaries; twv_tacotron_decoder_grad_phase_ms waits for the last run and
  * gives ms3 = milliseconds of the recording forward, the backward through time, the weight-gradient products (TWV_E_INVALID before such a run) */
 int twv_tacotron_decoder_grad_set_timing(twv_tacotron_decoder_grad* g, int on);
@@ -346,6 +355,34 @@ int twv_tacotron_encoder_grad_run(twv_tacotron_cbhg_grad* g, const float* blob, 
  * (batch, t_out, num_freq); grad_blob as above with post_cbhg/ * and the linear layer; d_mel (batch, t_out, num_mels) the cotangent on mel. */
 int twv_tacotron_postnet_grad_run(twv_tacotron_cbhg_grad* g, const float* blob, const float* mel, const float* d_linear, void* workspace,
                                   int32_t* status, void* stream, float* linear_out, float* grad_blob, float* d_mel);
+/* The halves of the two runs as calls of their own, as for the decoder: the run's arguments; the backward is given the forward's workspace,
+ * blob and inputs (tokens and lengths; mel), and d_before_highway / d_rnn_init where the forward was given their inputs.  A backward on a
+ * handle with no forward since create or set_mode, or on a handle of the other kind: TWV_E_INVALID. */
+int twv_tacotron_encoder_grad_forward(twv_tacotron_cbhg_grad* g, const float* blob, const int32_t* tokens, const int32_t* lengths,
+                                      const float* before_highway, const float* rnn_init, const float* mask1, const float* mask2,
+                                      void* workspace, int32_t* status, void* stream, float* memory_out);
+int twv_tacotron_encoder_grad_backward(twv_tacotron_cbhg_grad* g, const float* blob, const int32_t* tokens, const int32_t* lengths,
+                                       const float* d_memory, void* workspace, int32_t* status, void* stream, float* grad_blob,
+                                       float* d_before_highway, float* d_rnn_init);
+int twv_tacotron_postnet_grad_forward(twv_tacotron_cbhg_grad* g, const float* blob, const float* mel, void* workspace, int32_t* status,
+                                      void* stream, float* linear_out);
+int twv_tacotron_postnet_grad_backward(twv_tacotron_cbhg_grad* g, const float* blob, const float* mel, const float* d_linear, void* workspace,
+                                       int32_t* status, void* stream, float* grad_blob, float* d_mel);
+/* The batch norm of a handle's passes.  TWV_BN_INFERENCE, the default: y = a * inv + shift with the blob's pair (the moving
+ * statistics).  TWV_BN_BATCH: tf.layers.batch_normalization(training=True) -- each of the bank + 2 batch norms takes the mean and the biased
+ * variance of its input over ALL batch * t rows (padded rows too; float64 sums in a fixed order, each statistic rounded once to float32),
+ * derives its pair from them and from gamma and beta in twv_tacotron_refold's rounding sequence, and the backward goes through the
+ * statistics.  `variables` is the training vector on the device (twv_tacotron_train_floats; gamma and beta are read from it at every
+ * forward, so it must outlive the mode); it is not looked at in inference mode.  In batch mode a batch_normalization slot of grad_blob holds
+ * (d_gamma, d_beta) themselves (twv_tacotron_grad_convert_batch), and an utterance's outputs depend on the whole batch.
+ * twv_tacotron_cbhg_grad_batch_stats copies the statistics of the last batch-mode forward to `out` on the device:
+ * twv_tacotron_cbhg_grad_batch_stats_floats floats, per batch norm in the order bank 1 .. K, proj_1, proj_2 a (2, C) piece = (mean, variance).
+ * TWV_E_INVALID: another mode, batch mode without variables, statistics before a batch-mode forward. */
+#define TWV_BN_INFERENCE 0
+#define TWV_BN_BATCH 1
+int twv_tacotron_cbhg_grad_set_mode(twv_tacotron_cbhg_grad* g, int mode, const float* variables);
+size_t twv_tacotron_cbhg_grad_batch_stats_floats(const twv_tacotron_cbhg_grad* g);
+int twv_tacotron_cbhg_grad_batch_stats(const twv_tacotron_cbhg_grad* g, float* out, void* stream);
 /* measurement, as for the decoder: ms4 = the recording forward, the GRUs' backward through time, the row-wise backward (pointwise kernels
  * and dx products), the weight-gradient products */
 int twv_tacotron_cbhg_grad_set_timing(twv_tacotron_cbhg_grad* g, int on);
@@ -384,6 +421,20 @@ int twv_tacotron_speaker_grad(const twv_tacotron* h, const float* blob, const in
 size_t twv_tacotron_train_floats(const twv_tacotron* h);
 int twv_tacotron_refold(const twv_tacotron* h, const float* variables, float* blob, void* stream);
 int twv_tacotron_grad_convert(const twv_tacotron* h, const float* variables, const float* grad_blob, float* grad_variables, void* stream);
+/* The training-mode step's own pieces.
+ * twv_tacotron_grad_convert_batch: twv_tacotron_grad_convert for a gradient whose batch_normalization slots hold (d_gamma, d_beta) already
+ * (passes in TWV_BN_BATCH mode): they are copied, the moving statistics get exact zeros.
+ * twv_tacotron_moving_update: tf's assign_moving_average without zero-debias on the moving mean and variance of every batch norm of both
+ * CBHGs in the training vector: m <- m - (m - batch) * (float)(1 - momentum), each operation rounded to float32 (the reference's momentum is
+ * 0.99); encoder_stats / post_stats are twv_tacotron_cbhg_grad_batch_stats of the two handles.
+ * twv_dropout_mask: n dropout multipliers from a counter-based generator -- element i depends on (seed, step, site, i) alone:
+ * key = mix(seed + G (4 step + site)), z = mix(key + G (i + 1)), u = (z >> 40) 2^-24, with mix the splitmix64 finaliser and G =
+ * 0x9E3779B97F4A7C15; out[i] = (float)(1 / (1 - rate)) where u >= (float)rate, else 0.  site 0 .. 3 = encoder prenet 1, 2, decoder prenet 1, 2.
+ * TWV_E_INVALID: null arguments, momentum outside [0, 1], n < 1, step < 0, another site, rate outside [0, 1). */
+int twv_tacotron_grad_convert_batch(const twv_tacotron* h, const float* grad_blob, float* grad_variables, void* stream);
+int twv_tacotron_moving_update(const twv_tacotron* h, float* variables, const float* encoder_stats, const float* post_stats, double momentum,
+                               void* stream);
+int twv_dropout_mask(float* out, int64_t n, uint64_t seed, int64_t step, int site, double rate, void* stream);
 
 /* launch geometry (performance only, results are bit-identical): "decoder_groups" = 0 auto (the XCD-resident decoder kernel wherever it
  * fits -- batch <= 32, t_in <= 512, 256 CUs, decoder widths divisible by 4, not model_type 'simple', attention_type bah_mon_norm -- else the split kernel with 16 / 8 / 4

@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """Bit identity of what existed before the training step, one build against another: `infer`, `forward_targets` (free-running and
-teacher-forced) and `loss_gradients` on every case of tests/tacotron_cbhg_grad_cases.py.
+teacher-forced) and `loss_gradients` on every case of tests/tacotron_cbhg_grad_cases.py, and one `TacotronTrainer.step` with the
+constructor's defaults on the whole-model cases of tests/tacotron_train_cases.py (the losses and every variable after the update).
 
     python scripts/tacotron_train_identity.py --root PARENT_CHECKOUT --dump parent.json      # a checkout WITH its built library
     python scripts/tacotron_train_identity.py --dump new.json
@@ -20,6 +21,8 @@ def dump(root, path):
     assert os.path.dirname(os.path.dirname(os.path.abspath(twvk_amd.__file__))) == root, twvk_amd.__file__
     from twvk_amd.tacotron import Tacotron
     from tacotron_cbhg_grad_cases import CASES, host_case
+    import torch
+    torch_of = lambda a: torch.from_numpy(np.ascontiguousarray(a))
     digest = lambda t: (int(t.numel()), hashlib.sha256(np.ascontiguousarray(t.detach().cpu().numpy()).tobytes()).hexdigest())
     out = {"library": twvk_amd._lib.lib().twv_version().decode(), "entries": {}}
     for name in sorted(CASES):
@@ -34,6 +37,19 @@ def dump(root, path):
             out["entries"]["%s %s" % (label, name)] = {k: digest(t) for k, t in zip(("mel", "linear", "alignments"), run())}
         if h.forced:        # (the last pass above is the teacher-forced one)
             out["entries"]["loss_gradients %s" % name] = {k: digest(t) for k, t in sorted(m.loss_gradients(h.lin_tgt, h.coeff).items())}
+    # one TacotronTrainer step with the constructor's defaults (the evaluation graph) on the whole-model cases of tests/tacotron_train_cases.py:
+    # the losses and every variable after the update
+    from tacotron_train_cases import WHOLE, whole_case
+    from twvk_amd.tacotron_train import TacotronTrainer
+    for name in sorted(WHOLE):
+        h = whole_case(name)
+        m = Tacotron(h.hp, num_speakers=h.speakers)
+        m.load_weights(h.w)
+        t = TacotronTrainer(m)
+        losses = t.step(h.tok, h.ln, h.spk, h.tgt, h.lin_tgt, h.coeff)
+        entry = {k: digest(torch_of(v)) for k, v in sorted(t.variables().items())}
+        entry["losses"] = (4, hashlib.sha256(repr(sorted(losses.items())).encode()).hexdigest())
+        out["entries"]["TacotronTrainer.step %s" % name] = entry
     with open(path, "w") as fh:
         json.dump(out, fh)
     print("wrote", path, len(out["entries"]), "entries,", out["library"])
@@ -41,8 +57,8 @@ def dump(root, path):
 
 def compare(a_path, b_path, out_path):
     a, b = json.load(open(a_path)), json.load(open(b_path))
-    lines = ["Bit identity of `infer`, `forward_targets` and `loss_gradients`, parent build against this tree: every case of",
-             "tests/tacotron_cbhg_grad_cases.py CASES (scripts/tacotron_train_identity.py).  Two processes on one MI355X, each the Python package and the",
+    lines = ["Bit identity of `infer`, `forward_targets`, `loss_gradients` and one `TacotronTrainer.step`, parent build against this tree: every case of",
+             "tests/tacotron_cbhg_grad_cases.py CASES and tests/tacotron_train_cases.py WHOLE (scripts/tacotron_train_identity.py).  Two processes on one MI355X, each the Python package and the",
              "library of one commit; every output tensor's bytes compared by SHA-256.  The condition: 0 differing tensors everywhere.",
              "parent: %s" % a["library"], "new:    %s" % b["library"], ""]
     tensors = elements = differing = 0

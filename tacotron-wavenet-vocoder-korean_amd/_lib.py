@@ -274,6 +274,18 @@ def lib():
     L.twv_tacotron_train_floats.argtypes = [vp]; L.twv_tacotron_train_floats.restype = C.c_size_t
     L.twv_tacotron_refold.argtypes = [vp, fp, fp, vp]
     L.twv_tacotron_grad_convert.argtypes = [vp, fp, fp, fp, vp]
+    L.twv_tacotron_decoder_grad_forward.argtypes = [vp, fp, fp, fp, ip, fp, fp, fp, vp, ip, vp, fp]
+    L.twv_tacotron_decoder_grad_backward.argtypes = [vp, fp, fp, fp, ip, fp, vp, ip, vp, fp, fp, fp]
+    L.twv_tacotron_encoder_grad_forward.argtypes = [vp, fp, ip, ip, fp, fp, fp, fp, vp, ip, vp, fp]
+    L.twv_tacotron_encoder_grad_backward.argtypes = [vp, fp, ip, ip, fp, vp, ip, vp, fp, fp, fp]
+    L.twv_tacotron_postnet_grad_forward.argtypes = [vp, fp, fp, vp, ip, vp, fp]
+    L.twv_tacotron_postnet_grad_backward.argtypes = [vp, fp, fp, fp, vp, ip, vp, fp, fp]
+    L.twv_tacotron_cbhg_grad_set_mode.argtypes = [vp, C.c_int, fp]
+    L.twv_tacotron_cbhg_grad_batch_stats_floats.argtypes = [vp]; L.twv_tacotron_cbhg_grad_batch_stats_floats.restype = C.c_size_t
+    L.twv_tacotron_cbhg_grad_batch_stats.argtypes = [vp, fp, vp]
+    L.twv_tacotron_grad_convert_batch.argtypes = [vp, fp, fp, vp]
+    L.twv_tacotron_moving_update.argtypes = [vp, fp, fp, fp, C.c_double, vp]
+    L.twv_dropout_mask.argtypes = [fp, C.c_int64, C.c_uint64, C.c_int64, C.c_int, C.c_double, vp]
     L.twv_tacotron_set_profile_buffer.argtypes = [vp, vp]
     L.twv_tacotron_set_option.argtypes = [vp, C.c_char_p, C.c_int]
     L.twv_tacotron_gemm_stats.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]
@@ -328,7 +340,10 @@ EXPORTS = ["twv_last_error", "twv_version", "twv_wavenet_create", "twv_wavenet_d
            "twv_tacotron_cbhg_grad_route", "twv_tacotron_encoder_grad_run", "twv_tacotron_postnet_grad_run",
            "twv_tacotron_cbhg_grad_set_timing", "twv_tacotron_cbhg_grad_phase_ms", "twv_tacotron_linear_loss_grad",
            "twv_tacotron_speaker_grad_scratch_bytes", "twv_tacotron_speaker_grad", "twv_tacotron_train_floats", "twv_tacotron_refold",
-           "twv_tacotron_grad_convert"]
+           "twv_tacotron_grad_convert", "twv_tacotron_decoder_grad_forward", "twv_tacotron_decoder_grad_backward",
+           "twv_tacotron_encoder_grad_forward", "twv_tacotron_encoder_grad_backward", "twv_tacotron_postnet_grad_forward",
+           "twv_tacotron_postnet_grad_backward", "twv_tacotron_cbhg_grad_set_mode", "twv_tacotron_cbhg_grad_batch_stats_floats",
+           "twv_tacotron_cbhg_grad_batch_stats", "twv_tacotron_grad_convert_batch", "twv_tacotron_moving_update", "twv_dropout_mask"]
 
 
 class TacoDims(C.Structure):

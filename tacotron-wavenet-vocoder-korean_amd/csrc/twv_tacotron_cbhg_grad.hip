@@ -139,6 +139,129 @@ __global__ void cg_finish_kernel(const double* partial, FinishArgs f, float* gra
         grad[f.off[s][q] + cc] = (float)v;
     }
 }
+// ---- batch-statistics batch norm (tf.layers.batch_normalization(training=True)).  A handle in batch mode keeps, per batch
+// norm and in the order bank 1 .. K, proj_1, proj_2, a (2, C) piece of two buffers of its own: `stats` = (mean, variance) of the last
+// forward over ALL rows, `pairs` = the (inv, shift) pair derived from them.  Batch norm q of a launch has its pieces at pair[q] of both
+// buffers and its (4, C) tensor (gamma, beta first) at var[q] of the training vector.
+const float kCgBnEps = 1e-3f;        // tf.layers.batch_normalization's default epsilon
+struct BatchGroups { long long pair[17], var[17]; int gs; };
+// column sums of a and a * a (float64), the grid of cg_bn_bwd_kernel: partial[chunk][0 | 1][c]
+__global__ void __launch_bounds__(256) cg_stats_kernel(const float* A, int lda, int rows, int Cn, double* partial)
+{
+    __shared__ double red[2][4][64];
+    const int c = blockIdx.x * 64 + (threadIdx.x & 63), q4 = threadIdx.x >> 6, ra = blockIdx.y * kChunk, rb = min(rows, ra + kChunk);
+    double s1 = 0.0, s2 = 0.0;
+    if (c < Cn) for (int r = ra + q4; r < rb; r += 4) { const double av = (double)A[(long long)r * lda + c]; s1 += av; s2 += av * av; }
+    red[0][q4][threadIdx.x & 63] = s1; red[1][q4][threadIdx.x & 63] = s2;
+    __syncthreads();
+    if (q4 == 0 && c < Cn) {
+        const int l = threadIdx.x;
+        partial[((long long)blockIdx.y * 2 + 0) * Cn + c] = ((red[0][0][l] + red[0][1][l]) + red[0][2][l]) + red[0][3][l];
+        partial[((long long)blockIdx.y * 2 + 1) * Cn + c] = ((red[1][0][l] + red[1][1][l]) + red[1][2][l]) + red[1][3][l];
+    }
+}
+// the chunks in order: mean = sum a / R, variance = sum a^2 / R - mean^2 (biased, float64, clamped at 0), each rounded once to float32; then
+// the pair from the float32 statistics in the rounding sequence of tt_refold_kernel / tacotron.bn_inference_vectors
+__global__ void cg_stats_finish_kernel(const double* partial, BatchGroups b, int Cn, int nchunk, int rows, const float* variables, float* stats,
+                                       float* pairs)
+{
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= Cn) return;
+    const int q = c / b.gs, cc = c - q * b.gs;
+    double s1 = 0.0, s2 = 0.0;
+    for (int k = 0; k < nchunk; ++k) { s1 += partial[((long long)k * 2 + 0) * Cn + c]; s2 += partial[((long long)k * 2 + 1) * Cn + c]; }
+    const double mu = s1 / (double)rows;
+    double v = s2 / (double)rows - mu * mu;
+    if (!(v > 0.0)) v = 0.0;
+    const float mean = (float)mu, variance = (float)v;
+    const float gamma = variables[b.var[q] + cc], beta = variables[b.var[q] + b.gs + cc];
+    const float root = (float)sqrt((double)__fadd_rn(variance, kCgBnEps));
+    const float inv = __fmul_rn((float)(1.0 / (double)root), gamma);
+    stats[b.pair[q] + cc] = mean; stats[b.pair[q] + b.gs + cc] = variance;
+    pairs[b.pair[q] + cc] = inv; pairs[b.pair[q] + b.gs + cc] = __fsub_rn(beta, __fmul_rn(mean, inv));
+}
+// Y = A * inv + shift (+ add1[r] + add2[r / T]): what the row kernel fuses into a projection in inference mode, the same expression in the
+// same order (the statistics need all of A first)
+__global__ void cg_bn_apply_kernel(const float* A, const float* inv, const float* shift, const float* add1, int ld1, const float* add2, int ld2,
+                                   int rows, int T, int Cn, float* Y)
+{
+    const long long total = (long long)rows * Cn;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const long long row = i / Cn; const int j = (int)(i - row * Cn);
+        const float v = A[i];
+        float y = v * inv[j] + shift[j];
+        if (add1) y = y + add1[row * ld1 + j];
+        if (add2) y = y + add2[(row / T) * ld2 + j];
+        Y[i] = y;
+    }
+}
+// backward, the sums phase: cg_bn_bwd_kernel's routing through the max pool (on the batch pair) and its partial sums of dy * a and dy, but
+// dZ receives dy itself -- the elementwise phase needs the finished sums
+__global__ void __launch_bounds__(256) cg_bn_batch_sums_kernel(const float* dY, int ldy, const float* A, int lda, const float* pairs, Groups g, int rows,
+                                                               int T, int Cn, int pool, float* dZ, int ldz, double* partial)
+{
+    __shared__ double red[2][4][64];
+    const int c = blockIdx.x * 64 + (threadIdx.x & 63), q4 = threadIdx.x >> 6, ra = blockIdx.y * kChunk, rb = min(rows, ra + kChunk);
+    double si = 0.0, ss = 0.0;
+    if (c < Cn) {
+        const int q = c / g.gs, cc = c - q * g.gs;
+        const float inv = pairs[g.inv[q] + cc], sh = pairs[g.shift[q] + cc];
+        for (int r = ra + q4; r < rb; r += 4) {
+            const float av = A[(long long)r * lda + c];
+            float dy;
+            if (pool) {
+                const int t = r % T;
+                const float y = av * inv + sh;
+                dy = 0.0f;
+                bool mine = true;
+                if (t + 1 < T) { const float yn = A[(long long)(r + 1) * lda + c] * inv + sh; mine = !(yn > y); }
+                if (mine) dy += dY[(long long)r * ldy + c];
+                if (t > 0) { const float yp = A[(long long)(r - 1) * lda + c] * inv + sh; if (y > yp) dy += dY[(long long)(r - 1) * ldy + c]; }
+            } else dy = dY[(long long)r * ldy + c];
+            dZ[(long long)r * ldz + c] = dy;
+            si += (double)dy * (double)av; ss += (double)dy;
+        }
+    }
+    red[0][q4][threadIdx.x & 63] = si; red[1][q4][threadIdx.x & 63] = ss;
+    __syncthreads();
+    if (q4 == 0 && c < Cn) {
+        const int l = threadIdx.x;
+        partial[((long long)blockIdx.y * 2 + 0) * Cn + c] = ((red[0][0][l] + red[0][1][l]) + red[0][2][l]) + red[0][3][l];
+        partial[((long long)blockIdx.y * 2 + 1) * Cn + c] = ((red[1][0][l] + red[1][1][l]) + red[1][2][l]) + red[1][3][l];
+    }
+}
+// the chunks in order: S1 = sum dy, S2 = sum dy * a.  With rs = rsqrt(var + eps): sum dy * xhat = rs (S2 - mean S1), so
+// d_gamma = rs (S2 - mean S1) and d_beta = S1 go to the pair's slots of the gradient (gr), and the elementwise phase gets
+// coef[0][c] = S1 / R, coef[1][c] = rs^2 (S2 - mean S1) / R
+__global__ void cg_bn_batch_finish_kernel(const double* partial, BatchGroups b, Groups gr, int Cn, int nchunk, int rows, const float* stats, double* coef,
+                                          float* grad)
+{
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= Cn) return;
+    const int q = c / b.gs, cc = c - q * b.gs;
+    double s2 = 0.0, s1 = 0.0;
+    for (int k = 0; k < nchunk; ++k) { s2 += partial[((long long)k * 2 + 0) * Cn + c]; s1 += partial[((long long)k * 2 + 1) * Cn + c]; }
+    const double mu = (double)stats[b.pair[q] + cc], rs = 1.0 / sqrt((double)stats[b.pair[q] + b.gs + cc] + (double)kCgBnEps);
+    const double t = s2 - mu * s1;
+    grad[gr.inv[q] + cc] = (float)(rs * t);
+    grad[gr.shift[q] + cc] = (float)s1;
+    coef[c] = s1 / (double)rows;
+    coef[Cn + c] = rs * rs * t / (double)rows;
+}
+// the elementwise phase, in place on dZ = dy: da = inv (dy - S1 / R - (a - mean) rs^2 (S2 - mean S1) / R), 0 where relu and a <= 0
+__global__ void cg_bn_batch_bwd_kernel(float* dZ, int ldz, const float* A, int lda, const float* pairs, const float* stats, BatchGroups b,
+                                       const double* coef, int rows, int Cn, int relu)
+{
+    const long long total = (long long)rows * Cn;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const long long r = i / Cn; const int c = (int)(i - r * Cn), q = c / b.gs, cc = c - q * b.gs;
+        const float av = A[r * lda + c];
+        const double d = ((double)dZ[r * ldz + c] - coef[c]) - ((double)av - (double)stats[b.pair[q] + cc]) * coef[Cn + c];
+        float dz = (float)((double)pairs[b.pair[q] + cc] * d);
+        if (relu && !(av > 0.0f)) dz = 0.0f;
+        dZ[r * ldz + c] = dz;
+    }
+}
 // highway layer: y = relu(h) * sigmoid(t) + x * (1 - sigmoid(t));  H, Tg hold relu(h) and sigmoid(t)
 __global__ void cg_highway_kernel(const float* x, const float* H, const float* Tg, long long total, float* y)
 {
@@ -358,6 +481,19 @@ struct twv_tacotron_cbhg_grad : Handle {
     int which, N, T, E, P0, F;
     long long wT_floats;
     int lds;                       // bytes, both recurrent kernels
+    // the batch norms in the order bank 1 .. K, proj_1, proj_2: channels, the pair's place in the blob, the (4, C) tensor's place in the
+    // training vector, the (2, C) piece's place in `pairs` and `stats`
+    int n_bn, bn_ch[18];
+    long long bn_blob[18], bn_var[18], bn_pair[18], pair_floats;
+    int mode = TWV_BN_INFERENCE;   // twv_tacotron_cbhg_grad_set_mode
+    const float* variables = nullptr;      // batch mode: the caller's training vector (gamma and beta are read from it at every forward)
+    float *pairs = nullptr, *stats = nullptr;       // batch mode: the handle's own device buffers, pair_floats each
+    int forwarded = 0, has_bh = 0, has_init = 0;    // a forward has been made since create / set_mode, with these optional inputs
+    ~twv_tacotron_cbhg_grad()
+    {
+        if (pairs) (void)hipFree(pairs);
+        if (stats) (void)hipFree(stats);
+    }
 };
 using Cg = twv_tacotron_cbhg_grad;
 
@@ -388,7 +524,7 @@ static long long cg_carve(const twv_tacotron_cbhg_grad* g, float* base, CgCarve&
     const long long nchunk = (rows + kChunk - 1) / kChunk;
     int cmax = 2 * kU;                                  // the widest matrix a column-statistics kernel is run on
     for (int v : {CB, P0, P1, Cin, g->P0, g->F, g->E}) cmax = cmax > v ? cmax : v;
-    c.partial = reinterpret_cast<double*>(take(nchunk * 2 * cmax * 2));      // (every piece starts at a multiple of four floats)
+    c.partial = reinterpret_cast<double*>(take((nchunk * 2 + 2) * cmax * 2));      // (every piece starts at a multiple of four floats; + the batch mode's two coefficient rows)
     return take.off.used;
 }
 
@@ -414,6 +550,22 @@ extern "C" int twv_tacotron_cbhg_grad_create(const twv_tacotron* h, int which, i
         delete g;
         return twv_fail(TWV_E_UNSUPPORTED, std::string("proj_width above 16: ") + kCgBuilt);
     }
+    {
+        long long ahead = 0, poff = 0;
+        if (which == TWV_CBHG_POST) {       // the encoder's batch norms lie in front of the post net's in the training vector
+            TacoCbhgBlob e;
+            taco_cbhg_blob(h, TWV_CBHG_ENCODER, e);
+            ahead = 2LL * ((long long)e.bank * e.bch + e.proj[0] + e.proj[1]);
+        }
+        g->n_bn = w.bank + 2;
+        for (int i = 0; i < g->n_bn; ++i) {
+            g->bn_ch[i] = i < w.bank ? w.bch : w.proj[i - w.bank];
+            g->bn_blob[i] = i < w.bank ? w.bn[i + 1] : w.pbn[i - w.bank];
+            g->bn_var[i] = g->bn_blob[i] + ahead; ahead += 2LL * g->bn_ch[i];
+            g->bn_pair[i] = poff; poff += 2LL * g->bn_ch[i];
+        }
+        g->pair_floats = poff;
+    }
     g->E = which ? 0 : d.embedding_size; g->P0 = which ? 0 : d.enc_prenet_sizes[0]; g->F = which ? d.num_freq : 0;
     const int CB = w.bank * w.bch;
     long long wt = 0;
@@ -435,6 +587,26 @@ extern "C" void twv_tacotron_cbhg_grad_destroy(twv_tacotron_cbhg_grad* g) { dele
 extern "C" int twv_tacotron_cbhg_grad_set_timing(twv_tacotron_cbhg_grad* g, int on) { return g ? g->set_timing(on) : twv_fail(TWV_E_INVALID, "null argument"); }
 extern "C" size_t twv_tacotron_cbhg_grad_workspace_bytes(const twv_tacotron_cbhg_grad* g) { return g ? (size_t)g->ws_floats * 4 : 0; }
 extern "C" const char* twv_tacotron_cbhg_grad_route(const twv_tacotron_cbhg_grad* g) { return g ? g->route.c_str() : ""; }
+extern "C" int twv_tacotron_cbhg_grad_set_mode(twv_tacotron_cbhg_grad* g, int mode, const float* variables)
+{
+    if (!g) return twv_fail(TWV_E_INVALID, "null argument");
+    if (mode != TWV_BN_INFERENCE && mode != TWV_BN_BATCH) return twv_fail(TWV_E_INVALID, "mode must be TWV_BN_INFERENCE (0) or TWV_BN_BATCH (1)");
+    if (mode == TWV_BN_BATCH && !variables) return twv_fail(TWV_E_INVALID, "batch mode needs the training vector (gamma and beta are read from it)");
+    if (mode == TWV_BN_BATCH && !g->pairs) {
+        GRAD_HIPCHK(hipMalloc(&g->pairs, (size_t)g->pair_floats * 4));
+        GRAD_HIPCHK(hipMalloc(&g->stats, (size_t)g->pair_floats * 4));
+    }
+    g->mode = mode; g->variables = mode == TWV_BN_BATCH ? variables : nullptr; g->forwarded = 0;
+    return TWV_OK;
+}
+extern "C" size_t twv_tacotron_cbhg_grad_batch_stats_floats(const twv_tacotron_cbhg_grad* g) { return g ? (size_t)g->pair_floats : 0; }
+extern "C" int twv_tacotron_cbhg_grad_batch_stats(const twv_tacotron_cbhg_grad* g, float* out, void* stream)
+{
+    if (!g || !out) return twv_fail(TWV_E_INVALID, "null argument");
+    if (g->mode != TWV_BN_BATCH || !g->forwarded) return twv_fail(TWV_E_INVALID, "batch statistics: no forward in batch mode has been made on this handle");
+    GRAD_HIPCHK(hipMemcpyAsync(out, g->stats, (size_t)g->pair_floats * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return TWV_OK;
+}
 
 namespace {
 
@@ -492,10 +664,52 @@ struct CgRun {
         f.off[0][0] = off; f.gs = Nc; f.nstat = 1; f.Cn = Nc; f.nchunk = nchunk;
         hipLaunchKernelGGL(cg_finish_kernel, dim3((Nc + 63) / 64), dim3(64), 0, st, c.partial, f, grad);
     }
-    // dZ = batch norm / relu (/ max pool) backward of dY against the tape A; the (d_inv, d_shift) pairs land in the groups' blob slots
-    void bn_bwd(const float* dY, int ldy, const float* A, int lda, const Groups& gr, int Cn, int pool, int relu, float* dZ, int ldz) const
+    bool batch() const { return g->mode == TWV_BN_BATCH; }
+    // the handle's batch norms first .. first + n - 1 (gs channels each) as the groups of one launch: their pairs in the blob (and so in
+    // the gradient), or, in_pairs, in the handle's own `pairs`
+    Groups groups(int first, int n, int gs, bool in_pairs) const
+    {
+        Groups gr;
+        memset(&gr, 0, sizeof(gr));
+        gr.gs = gs;
+        for (int q = 0; q < n; ++q) { gr.inv[q] = in_pairs ? g->bn_pair[first + q] : g->bn_blob[first + q]; gr.shift[q] = gr.inv[q] + gs; }
+        return gr;
+    }
+    BatchGroups batch_groups(int first, int n, int gs) const
+    {
+        BatchGroups b;
+        memset(&b, 0, sizeof(b));
+        b.gs = gs;
+        for (int q = 0; q < n; ++q) { b.pair[q] = g->bn_pair[first + q]; b.var[q] = g->bn_var[first + q]; }
+        return b;
+    }
+    // what a kernel reads a batch norm's (inv, shift) from: the blob, or the batch pairs
+    const float* bn_base() const { return batch() ? g->pairs : blob; }
+    Groups bn_read(int first, int n, int gs) const { return groups(first, n, gs, batch()); }
+    // batch mode: the statistics of A's columns over all rows and the pairs derived from them
+    void batch_stats(const float* A, int lda, int first, int n, int gs, int Cn) const
     {
         const int nchunk = (rows + kChunk - 1) / kChunk;
+        hipLaunchKernelGGL(cg_stats_kernel, dim3((Cn + 63) / 64, nchunk), dim3(256), 0, st, A, lda, rows, Cn, c.partial);
+        hipLaunchKernelGGL(cg_stats_finish_kernel, dim3((Cn + 63) / 64), dim3(64), 0, st, c.partial, batch_groups(first, n, gs), Cn, nchunk, rows,
+                           g->variables, g->stats, g->pairs);
+    }
+    // dZ = batch norm / relu (/ max pool) backward of dY against the tape A.  Inference mode: the (d_inv, d_shift) pairs land in the groups'
+    // blob slots; batch mode: (d_gamma, d_beta) do, and dZ is the backward through the statistics too
+    void bn_bwd(const float* dY, int ldy, const float* A, int lda, int first, int n, int gs, int Cn, int pool, int relu, float* dZ, int ldz) const
+    {
+        const int nchunk = (rows + kChunk - 1) / kChunk;
+        const Groups gr = groups(first, n, gs, false);
+        if (batch()) {
+            const BatchGroups b = batch_groups(first, n, gs);
+            double* coef = c.partial + (long long)nchunk * 2 * Cn;
+            hipLaunchKernelGGL(cg_bn_batch_sums_kernel, dim3((Cn + 63) / 64, nchunk), dim3(256), 0, st, dY, ldy, A, lda, g->pairs, groups(first, n, gs, true),
+                               rows, T, Cn, pool, dZ, ldz, c.partial);
+            hipLaunchKernelGGL(cg_bn_batch_finish_kernel, dim3((Cn + 63) / 64), dim3(64), 0, st, c.partial, b, gr, Cn, nchunk, rows, g->stats, coef, grad);
+            hipLaunchKernelGGL(cg_bn_batch_bwd_kernel, dim3(grid_for((long long)rows * Cn)), dim3(256), 0, st, dZ, ldz, A, lda, g->pairs, g->stats, b, coef,
+                               rows, Cn, relu);
+            return;
+        }
         hipLaunchKernelGGL(cg_bn_bwd_kernel, dim3((Cn + 63) / 64, nchunk), dim3(256), 0, st, dY, ldy, A, lda, blob, gr, rows, T, Cn, pool, relu, dZ, ldz, c.partial);
         FinishArgs f;
         memset(&f, 0, sizeof(f));
@@ -505,14 +719,6 @@ struct CgRun {
     }
 };
 
-Groups one_group(long long bn, int Cn)
-{
-    Groups gr;
-    memset(&gr, 0, sizeof(gr));
-    gr.inv[0] = bn; gr.shift[0] = bn + Cn; gr.gs = Cn;
-    return gr;
-}
-
 // the CBHG forward from r.c.X-or-`x` (rows x Cin) to r.c.out, recording; `bh` (N, proj[1]) and `init` (N, 2 kU) may be null
 int cbhg_forward(CgRun& r, const float* x, const float* bh, const float* init, const int32_t* lengths)
 {
@@ -521,26 +727,40 @@ int cbhg_forward(CgRun& r, const float* x, const float* bh, const float* init, c
     const float* B = r.blob;
     const int Cin = w.Cin, CB = w.bank * w.bch, P0 = w.proj[0], P1 = w.proj[1], pl = (w.pw - 1) / 2;
     const long long rows = r.rows;
-    Groups bank;
-    memset(&bank, 0, sizeof(bank));
-    bank.gs = w.bch;
+    const bool batch = r.batch();
     for (int k = 1; k <= w.bank; ++k) {
-        bank.inv[k - 1] = w.bn[k]; bank.shift[k - 1] = w.bn[k] + w.bch;
         RowsArgs a = r.rows_args(x, Cin, Cin, k, (k - 1) / 2, B + w.W[k], w.bch, w.bch, B + w.b[k]);
         a.act = 1; a.C = c.bankA + (long long)(k - 1) * w.bch; a.ldc = CB;
         r.launch(a);
     }
-    hipLaunchKernelGGL(cg_pool_kernel, dim3(grid_for(rows * CB)), dim3(256), 0, r.st, c.bankA, B, bank, r.rows, r.T, CB, c.pool);
+    if (batch) r.batch_stats(c.bankA, CB, 0, w.bank, w.bch, CB);
+    hipLaunchKernelGGL(cg_pool_kernel, dim3(grid_for(rows * CB)), dim3(256), 0, r.st, c.bankA, r.bn_base(), r.bn_read(0, w.bank, w.bch), r.rows, r.T, CB, c.pool);
+    // In batch mode a projection's batch norm cannot ride in the row kernel (the statistics need all of A): rows, statistics, apply
     {
         RowsArgs a = r.rows_args(c.pool, CB, CB, w.pw, pl, B + w.pW[0], P0, P0, B + w.pb[0]);
-        a.act = 1; a.C = c.A1; a.ldc = P0; a.Y = c.Y1; a.ldy = P0; a.inv = B + w.pbn[0]; a.shift = B + w.pbn[0] + P0;
+        a.act = 1; a.C = c.A1; a.ldc = P0;
+        if (!batch) { a.Y = c.Y1; a.ldy = P0; a.inv = B + w.pbn[0]; a.shift = B + w.pbn[0] + P0; }
         r.launch(a);
+        if (batch) {
+            r.batch_stats(c.A1, P0, w.bank, 1, P0, P0);
+            const float* pr = r.g->pairs + r.g->bn_pair[w.bank];
+            hipLaunchKernelGGL(cg_bn_apply_kernel, dim3(grid_for(rows * P0)), dim3(256), 0, r.st, c.A1, pr, pr + P0, (const float*)nullptr, 0,
+                               (const float*)nullptr, 0, r.rows, r.T, P0, c.Y1);
+        }
     }
     {   // second projection + residual: (proj + inputs) + before_highway
         RowsArgs a = r.rows_args(c.Y1, P0, P0, w.pw, pl, B + w.pW[1], P1, P1, B + w.pb[1]);
-        a.C = c.A2; a.ldc = P1; a.Y = c.HW0; a.ldy = P1; a.inv = B + w.pbn[1]; a.shift = B + w.pbn[1] + P1;
-        a.add1 = x; a.ld1 = Cin; a.add2 = bh; a.ld2 = P1;
+        a.C = c.A2; a.ldc = P1;
+        if (!batch) {
+            a.Y = c.HW0; a.ldy = P1; a.inv = B + w.pbn[1]; a.shift = B + w.pbn[1] + P1;
+            a.add1 = x; a.ld1 = Cin; a.add2 = bh; a.ld2 = P1;
+        }
         r.launch(a);
+        if (batch) {
+            r.batch_stats(c.A2, P1, w.bank + 1, 1, P1, P1);
+            const float* pr = r.g->pairs + r.g->bn_pair[w.bank + 1];
+            hipLaunchKernelGGL(cg_bn_apply_kernel, dim3(grid_for(rows * P1)), dim3(256), 0, r.st, c.A2, pr, pr + P1, x, Cin, bh, P1, r.rows, r.T, P1, c.HW0);
+        }
     }
     if (w.has_dense) {
         RowsArgs a = r.rows_args(c.HW0, P1, P1, 1, 0, B + w.dW, kU, kU, B + w.db);
@@ -611,15 +831,11 @@ int cbhg_backward_data(CgRun& r, const int32_t* lengths, float* d_bh, float* d_i
     const float* dHW0 = c.dhw;
     if (w.has_dense) { r.data_grad(c.dhw, kU, kU, B + w.dW, kU, P1, 1, c.dHW0, P1, 0); dHW0 = c.dHW0; }
     if (d_bh) hipLaunchKernelGGL(cg_utterance_sum_kernel, dim3((r.g->N * P1 + 255) / 256), dim3(256), 0, r.st, dHW0, r.g->N, r.T, P1, d_bh);
-    r.bn_bwd(dHW0, P1, c.A2, P1, one_group(w.pbn[1], P1), P1, 0, 0, c.dZ2, P1);
+    r.bn_bwd(dHW0, P1, c.A2, P1, w.bank + 1, 1, P1, P1, 0, 0, c.dZ2, P1);
     r.data_grad(c.dZ2, P1, P1, B + w.pW[1], P1, P0, w.pw, c.dY1, P0, 0);
-    r.bn_bwd(c.dY1, P0, c.A1, P0, one_group(w.pbn[0], P0), P0, 0, 1, c.dZ1, P0);
+    r.bn_bwd(c.dY1, P0, c.A1, P0, w.bank, 1, P0, P0, 0, 1, c.dZ1, P0);
     r.data_grad(c.dZ1, P0, P0, B + w.pW[0], P0, CB, w.pw, c.dpool, CB, 0);
-    Groups bank;
-    memset(&bank, 0, sizeof(bank));
-    bank.gs = w.bch;
-    for (int k = 1; k <= w.bank; ++k) { bank.inv[k - 1] = w.bn[k]; bank.shift[k - 1] = w.bn[k] + w.bch; }
-    r.bn_bwd(c.dpool, CB, c.bankA, CB, bank, CB, 1, 1, c.dZb, CB);
+    r.bn_bwd(c.dpool, CB, c.bankA, CB, 0, w.bank, w.bch, CB, 1, 1, c.dZb, CB);
     // d_x: the residual's share, then the bank's convolutions in order
     GRAD_HIPCHK(hipMemcpy2DAsync(c.dX, (size_t)Cin * 4, dHW0, (size_t)P1 * 4, (size_t)Cin * 4, (size_t)rows, hipMemcpyDeviceToDevice, r.st));
     for (int k = 1; k <= w.bank; ++k) r.data_grad(c.dZb + (long long)(k - 1) * w.bch, CB, w.bch, B + w.W[k], w.bch, Cin, k, c.dX, Cin, 1);
@@ -661,7 +877,8 @@ int cbhg_weight_grads(CgRun& r, const float* x)
 int cg_begin(twv_tacotron_cbhg_grad* g, CgRun& r, const float* blob, void* workspace, int32_t* status, void* stream, float* grad_blob)
 {
     r.g = g; r.st = (hipStream_t)stream; r.blob = blob; r.grad = grad_blob; r.rows = g->N * g->T; r.T = g->T;
-    GRAD_CHK(g->begin(r.st, status, grad_blob, g->w.blob_floats));
+    if (g->mode == TWV_BN_BATCH && (!g->variables || !g->pairs)) return twv_fail(TWV_E_INVALID, "batch mode without a training vector (twv_tacotron_cbhg_grad_set_mode)");
+    GRAD_CHK(g->begin(r.st, status, grad_blob, g->w.blob_floats));       // (a forward has no gradient to zero: grad_blob null)
     cg_carve(g, (float*)workspace, r.c);
     GRAD_HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(cg_gru_forward_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, g->lds));
     GRAD_HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(cg_gru_backward_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, g->lds));
@@ -670,16 +887,16 @@ int cg_begin(twv_tacotron_cbhg_grad* g, CgRun& r, const float* blob, void* works
 
 }  // namespace
 
-extern "C" int twv_tacotron_encoder_grad_run(twv_tacotron_cbhg_grad* g, const float* blob, const int32_t* tokens, const int32_t* lengths,
-                                             const float* before_highway, const float* rnn_init, const float* mask1, const float* mask2,
-                                             const float* d_memory, void* workspace, int32_t* status, void* stream, float* memory_out,
-                                             float* grad_blob, float* d_before_highway, float* d_rnn_init)
+// ---- the two halves of a pass.  The tape of a forward stays in the caller's workspace until the handle's next forward; a backward reads
+// it, so it is given the same workspace (and the same blob and inputs).
+extern "C" int twv_tacotron_encoder_grad_forward(twv_tacotron_cbhg_grad* g, const float* blob, const int32_t* tokens, const int32_t* lengths,
+                                                 const float* before_highway, const float* rnn_init, const float* mask1, const float* mask2,
+                                                 void* workspace, int32_t* status, void* stream, float* memory_out)
 {
-    if (!g || !blob || !tokens || !lengths || !d_memory || !workspace || !status || !memory_out || !grad_blob) return twv_fail(TWV_E_INVALID, "null argument");
+    if (!g || !blob || !tokens || !lengths || !workspace || !status || !memory_out) return twv_fail(TWV_E_INVALID, "null argument");
     if (g->which != TWV_CBHG_ENCODER) return twv_fail(TWV_E_INVALID, "the handle was created for the post net");
-    if ((before_highway && !d_before_highway) || (rnn_init && !d_rnn_init)) return twv_fail(TWV_E_INVALID, "null argument: before_highway / rnn_init need their d_ outputs");
     CgRun r;
-    GRAD_CHK(cg_begin(g, r, blob, workspace, status, stream, grad_blob));
+    GRAD_CHK(cg_begin(g, r, blob, workspace, status, stream, nullptr));
     const TacoCbhgBlob& w = g->w;
     const CgCarve& c = r.c;
     const int E = g->E, P0 = g->P0, P1 = w.Cin, rows = r.rows;
@@ -697,10 +914,27 @@ extern "C" int twv_tacotron_encoder_grad_run(twv_tacotron_cbhg_grad* g, const fl
     GRAD_CHK(cbhg_forward(r, c.X, before_highway, rnn_init, lengths));
     GRAD_HIPCHK(hipMemcpyAsync(memory_out, c.out, (size_t)rows * 2 * kU * 4, hipMemcpyDeviceToDevice, r.st));
     GRAD_HIPCHK(hipGetLastError());
+    g->forwarded = 1; g->has_bh = before_highway ? 1 : 0; g->has_init = rnn_init ? 1 : 0;
+    return TWV_OK;
+}
+
+extern "C" int twv_tacotron_encoder_grad_backward(twv_tacotron_cbhg_grad* g, const float* blob, const int32_t* tokens, const int32_t* lengths,
+                                                  const float* d_memory, void* workspace, int32_t* status, void* stream, float* grad_blob,
+                                                  float* d_before_highway, float* d_rnn_init)
+{
+    if (!g || !blob || !tokens || !lengths || !d_memory || !workspace || !status || !grad_blob) return twv_fail(TWV_E_INVALID, "null argument");
+    if (g->which != TWV_CBHG_ENCODER) return twv_fail(TWV_E_INVALID, "the handle was created for the post net");
+    if (!g->forwarded) return twv_fail(TWV_E_INVALID, "backward: no forward has been made on this handle (twv_tacotron_encoder_grad_forward)");
+    if ((g->has_bh && !d_before_highway) || (g->has_init && !d_rnn_init)) return twv_fail(TWV_E_INVALID, "null argument: before_highway / rnn_init need their d_ outputs");
+    CgRun r;
+    GRAD_CHK(cg_begin(g, r, blob, workspace, status, stream, grad_blob));
+    const TacoCbhgBlob& w = g->w;
+    const CgCarve& c = r.c;
+    const int E = g->E, P0 = g->P0, P1 = w.Cin, rows = r.rows;
     // ---- (b) the GRUs backward through time, (c) the row-wise backward
     GRAD_CHK(r.g->mark(1));
     GRAD_HIPCHK(hipMemcpyAsync(c.dOut, d_memory, (size_t)rows * 2 * kU * 4, hipMemcpyDeviceToDevice, r.st));
-    GRAD_CHK(cbhg_backward_data(r, lengths, before_highway ? d_before_highway : nullptr, rnn_init ? d_rnn_init : nullptr));
+    GRAD_CHK(cbhg_backward_data(r, lengths, g->has_bh ? d_before_highway : nullptr, g->has_init ? d_rnn_init : nullptr));
     launch_mul<Cg>(r.st, c.dX, c.G2, (long long)rows * P1);
     r.data_grad(c.dX, P1, P1, blob + w.pW2, P1, P0, 1, c.dH1, P0, 0, c.G1);
     r.data_grad(c.dH1, P0, P0, blob + w.pW1, P0, E, 1, c.dE, E, 0);
@@ -716,16 +950,29 @@ extern "C" int twv_tacotron_encoder_grad_run(twv_tacotron_cbhg_grad* g, const fl
     return TWV_OK;
 }
 
-extern "C" int twv_tacotron_postnet_grad_run(twv_tacotron_cbhg_grad* g, const float* blob, const float* mel, const float* d_linear, void* workspace,
-                                             int32_t* status, void* stream, float* linear_out, float* grad_blob, float* d_mel)
+// forward, then backward, in the handle's mode
+extern "C" int twv_tacotron_encoder_grad_run(twv_tacotron_cbhg_grad* g, const float* blob, const int32_t* tokens, const int32_t* lengths,
+                                             const float* before_highway, const float* rnn_init, const float* mask1, const float* mask2,
+                                             const float* d_memory, void* workspace, int32_t* status, void* stream, float* memory_out,
+                                             float* grad_blob, float* d_before_highway, float* d_rnn_init)
 {
-    if (!g || !blob || !mel || !d_linear || !workspace || !status || !linear_out || !grad_blob || !d_mel) return twv_fail(TWV_E_INVALID, "null argument");
+    if (!g || !blob || !tokens || !lengths || !d_memory || !workspace || !status || !memory_out || !grad_blob) return twv_fail(TWV_E_INVALID, "null argument");
+    if (g->which != TWV_CBHG_ENCODER) return twv_fail(TWV_E_INVALID, "the handle was created for the post net");
+    if ((before_highway && !d_before_highway) || (rnn_init && !d_rnn_init)) return twv_fail(TWV_E_INVALID, "null argument: before_highway / rnn_init need their d_ outputs");
+    GRAD_CHK(twv_tacotron_encoder_grad_forward(g, blob, tokens, lengths, before_highway, rnn_init, mask1, mask2, workspace, status, stream, memory_out));
+    return twv_tacotron_encoder_grad_backward(g, blob, tokens, lengths, d_memory, workspace, status, stream, grad_blob, d_before_highway, d_rnn_init);
+}
+
+extern "C" int twv_tacotron_postnet_grad_forward(twv_tacotron_cbhg_grad* g, const float* blob, const float* mel, void* workspace, int32_t* status,
+                                                 void* stream, float* linear_out)
+{
+    if (!g || !blob || !mel || !workspace || !status || !linear_out) return twv_fail(TWV_E_INVALID, "null argument");
     if (g->which != TWV_CBHG_POST) return twv_fail(TWV_E_INVALID, "the handle was created for the encoder");
     CgRun r;
-    GRAD_CHK(cg_begin(g, r, blob, workspace, status, stream, grad_blob));
+    GRAD_CHK(cg_begin(g, r, blob, workspace, status, stream, nullptr));
     const TacoCbhgBlob& w = g->w;
     const CgCarve& c = r.c;
-    const int F = g->F, M = w.Cin, rows = r.rows;
+    const int F = g->F;
     GRAD_CHK(r.g->mark(0));
     GRAD_CHK(cbhg_forward(r, mel, nullptr, nullptr, nullptr));
     {
@@ -734,6 +981,22 @@ extern "C" int twv_tacotron_postnet_grad_run(twv_tacotron_cbhg_grad* g, const fl
         r.launch(a);
     }
     GRAD_HIPCHK(hipGetLastError());
+    g->forwarded = 1; g->has_bh = 0; g->has_init = 0;
+    return TWV_OK;
+}
+
+// (mel: the forward's input once more -- the bank's kernel gradients are products with it)
+extern "C" int twv_tacotron_postnet_grad_backward(twv_tacotron_cbhg_grad* g, const float* blob, const float* mel, const float* d_linear, void* workspace,
+                                                  int32_t* status, void* stream, float* grad_blob, float* d_mel)
+{
+    if (!g || !blob || !mel || !d_linear || !workspace || !status || !grad_blob || !d_mel) return twv_fail(TWV_E_INVALID, "null argument");
+    if (g->which != TWV_CBHG_POST) return twv_fail(TWV_E_INVALID, "the handle was created for the encoder");
+    if (!g->forwarded) return twv_fail(TWV_E_INVALID, "backward: no forward has been made on this handle (twv_tacotron_postnet_grad_forward)");
+    CgRun r;
+    GRAD_CHK(cg_begin(g, r, blob, workspace, status, stream, grad_blob));
+    const TacoCbhgBlob& w = g->w;
+    const CgCarve& c = r.c;
+    const int F = g->F, M = w.Cin, rows = r.rows;
     GRAD_CHK(r.g->mark(1));
     r.data_grad(d_linear, F, F, blob + w.lW, F, 2 * kU, 1, c.dOut, 2 * kU, 0);
     GRAD_CHK(cbhg_backward_data(r, nullptr, nullptr, nullptr));
@@ -744,6 +1007,15 @@ extern "C" int twv_tacotron_postnet_grad_run(twv_tacotron_cbhg_grad* g, const fl
     GRAD_HIPCHK(hipGetLastError());
     GRAD_CHK(r.g->mark(4));
     return TWV_OK;
+}
+
+extern "C" int twv_tacotron_postnet_grad_run(twv_tacotron_cbhg_grad* g, const float* blob, const float* mel, const float* d_linear, void* workspace,
+                                             int32_t* status, void* stream, float* linear_out, float* grad_blob, float* d_mel)
+{
+    if (!g || !blob || !mel || !d_linear || !workspace || !status || !linear_out || !grad_blob || !d_mel) return twv_fail(TWV_E_INVALID, "null argument");
+    if (g->which != TWV_CBHG_POST) return twv_fail(TWV_E_INVALID, "the handle was created for the encoder");
+    GRAD_CHK(twv_tacotron_postnet_grad_forward(g, blob, mel, workspace, status, stream, linear_out));
+    return twv_tacotron_postnet_grad_backward(g, blob, mel, d_linear, workspace, status, stream, grad_blob, d_mel);
 }
 
 // after a run with timing on: waits for it and gives the milliseconds of (a) the recording forward, (b) the GRUs' backward through time,

@@ -543,6 +543,7 @@ struct twv_tacotron_decoder_grad : Handle {
     TacoDecoderBlob w;
     int N, T, steps;
     int lds_fwd, lds_bwd;          // bytes
+    int forwarded = 0;             // a forward has been made since create
 };
 using Tg = twv_tacotron_decoder_grad;
 
@@ -618,22 +619,38 @@ static RowsArgs tg_nt(const float* X, int rows, int K, const float* W, int ncols
 }
 static void tg_launch_nt(hipStream_t st, const RowsArgs& a) { hipLaunchKernelGGL(tg_rows_nt_kernel, dim3((a.rows + kRB - 1) / kRB), dim3(256), 0, st, a); }
 
-extern "C" int twv_tacotron_decoder_grad_run(twv_tacotron_decoder_grad* g, const float* blob, const float* memory, const float* decoder_init,
-                                             const int32_t* lengths, const float* mel_targets, const float* d_mel, const float* mask1,
-                                             const float* mask2, void* workspace, int32_t* status, void* stream, float* mel_out,
-                                             float* grad_blob, float* d_memory, float* d_init)
+namespace {
+// the arguments of the two recurrent kernels: the tape and the deltas are pieces of the workspace
+TgArgs tg_args(const Tg* g, const float* blob, const float* memory, const float* decoder_init, const int32_t* lengths, const TgCarve& c, float* d_memory,
+               float* d_init)
 {
-    if (!g || !blob || !memory || !decoder_init || !lengths || !mel_targets || !d_mel || !workspace || !status || !mel_out || !grad_blob ||
-        !d_memory || !d_init)
-        return twv_fail(TWV_E_INVALID, "null argument");
+    const twv_tacotron_dims& d = g->d;
+    TgArgs a;
+    memset(&a, 0, sizeof(a));
+    a.blob = blob; a.memory = memory; a.init = decoder_init; a.keys = c.keys; a.lengths = lengths; a.w = g->w;
+    a.N = g->N; a.T = g->T; a.steps = g->steps; a.D1 = d.dec_prenet_sizes[1]; a.ENC = 2 * d.enc_rnn_size; a.A = d.attention_size; a.AS = d.attention_state_size;
+    a.DR = d.dec_rnn_size; a.L = d.dec_layer_num; a.norm = d.attention_type == TWV_ATT_BAH_MON_NORM ? 1 : 0;
+    a.P = c.P; a.XA = c.XA; a.GA = c.GA; a.XC = c.XC; a.QB = c.QB; a.PCH = c.PCH; a.CP = c.CP; a.S = c.S; a.AL = c.AL; a.YF = c.YF;
+    for (int l = 0; l < 4; ++l) { a.XR[l] = c.XR[l]; a.GR[l] = c.GR[l]; a.DRg[l] = c.DRg[l]; a.DRc[l] = c.DRc[l]; }
+    a.dYF = c.dYF; a.DAg = c.DAg; a.DAc = c.DAc; a.DQ = c.DQ; a.DY0 = c.DY0; a.DP = c.DP; a.dkeys = c.dkeys; a.dmem = d_memory; a.dinit = d_init;
+    a.pv = c.pv; a.pb = c.pb; a.psb = c.psb;
+    return a;
+}
+}  // namespace
+
+// ---- the two halves of a pass: the tape of a forward stays in the caller's workspace until the handle's next forward
+extern "C" int twv_tacotron_decoder_grad_forward(twv_tacotron_decoder_grad* g, const float* blob, const float* memory, const float* decoder_init,
+                                                 const int32_t* lengths, const float* mel_targets, const float* mask1, const float* mask2,
+                                                 void* workspace, int32_t* status, void* stream, float* mel_out)
+{
+    if (!g || !blob || !memory || !decoder_init || !lengths || !mel_targets || !workspace || !status || !mel_out) return twv_fail(TWV_E_INVALID, "null argument");
     const twv_tacotron_dims& d = g->d;
     const TacoDecoderBlob& w = g->w;
     hipStream_t st = (hipStream_t)stream;
     const int N = g->N, T = g->T, steps = g->steps, rows = N * steps, rowsE = N * T;
-    const int D0 = d.dec_prenet_sizes[0], D1 = d.dec_prenet_sizes[1], ENC = 2 * d.enc_rnn_size, A = d.attention_size, AS = d.attention_state_size,
-              DR = d.dec_rnn_size, M = d.num_mels, R = d.reduction_factor, L = d.dec_layer_num, MR = M * R, ain = D1 + ENC, XW = ain + 2 * AS;
-    const int norm = d.attention_type == TWV_ATT_BAH_MON_NORM ? 1 : 0;
-    GRAD_CHK(g->begin(st, status, grad_blob, w.blob_floats));
+    const int D0 = d.dec_prenet_sizes[0], D1 = d.dec_prenet_sizes[1], ENC = 2 * d.enc_rnn_size, A = d.attention_size, DR = d.dec_rnn_size, M = d.num_mels,
+              R = d.reduction_factor, MR = M * R;
+    GRAD_CHK(g->begin(st, status, nullptr, w.blob_floats));
     TgCarve c;
     tg_carve(g, (float*)workspace, c);
     // ---- (a) recording forward
@@ -648,18 +665,34 @@ extern "C" int twv_tacotron_decoder_grad_run(twv_tacotron_decoder_grad* g, const
         launch_rows<Tg>(st, p);
         launch_rows<Tg>(st, tg_nn(memory, rowsE, ENC, blob + w.Wm, A, nullptr, c.keys));
     }
-    TgArgs a;
-    memset(&a, 0, sizeof(a));
-    a.blob = blob; a.memory = memory; a.init = decoder_init; a.keys = c.keys; a.lengths = lengths; a.w = w;
-    a.N = N; a.T = T; a.steps = steps; a.D1 = D1; a.ENC = ENC; a.A = A; a.AS = AS; a.DR = DR; a.L = L; a.norm = norm;
-    a.P = c.P; a.XA = c.XA; a.GA = c.GA; a.XC = c.XC; a.QB = c.QB; a.PCH = c.PCH; a.CP = c.CP; a.S = c.S; a.AL = c.AL; a.YF = c.YF;
-    for (int l = 0; l < 4; ++l) { a.XR[l] = c.XR[l]; a.GR[l] = c.GR[l]; a.DRg[l] = c.DRg[l]; a.DRc[l] = c.DRc[l]; }
-    a.dYF = c.dYF; a.DAg = c.DAg; a.DAc = c.DAc; a.DQ = c.DQ; a.DY0 = c.DY0; a.DP = c.DP; a.dkeys = c.dkeys; a.dmem = d_memory; a.dinit = d_init;
-    a.pv = c.pv; a.pb = c.pb; a.psb = c.psb;
+    const TgArgs a = tg_args(g, blob, memory, decoder_init, lengths, c, nullptr, nullptr);
     GRAD_HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(tg_forward_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, g->lds_fwd));
-    GRAD_HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(tg_backward_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, g->lds_bwd));
     hipLaunchKernelGGL(tg_forward_kernel, dim3(N), dim3(kThreads), (size_t)g->lds_fwd, st, a);
     launch_rows<Tg>(st, tg_nn(c.YF, rows, DR, blob + w.oW, MR, blob + w.ob, mel_out));
+    GRAD_HIPCHK(hipGetLastError());
+    g->forwarded = 1;
+    return TWV_OK;
+}
+
+extern "C" int twv_tacotron_decoder_grad_backward(twv_tacotron_decoder_grad* g, const float* blob, const float* memory, const float* decoder_init,
+                                                  const int32_t* lengths, const float* d_mel, void* workspace, int32_t* status, void* stream,
+                                                  float* grad_blob, float* d_memory, float* d_init)
+{
+    if (!g || !blob || !memory || !decoder_init || !lengths || !d_mel || !workspace || !status || !grad_blob || !d_memory || !d_init)
+        return twv_fail(TWV_E_INVALID, "null argument");
+    if (!g->forwarded) return twv_fail(TWV_E_INVALID, "backward: no forward has been made on this handle (twv_tacotron_decoder_grad_forward)");
+    const twv_tacotron_dims& d = g->d;
+    const TacoDecoderBlob& w = g->w;
+    hipStream_t st = (hipStream_t)stream;
+    const int N = g->N, T = g->T, steps = g->steps, rows = N * steps, rowsE = N * T;
+    const int D0 = d.dec_prenet_sizes[0], D1 = d.dec_prenet_sizes[1], ENC = 2 * d.enc_rnn_size, A = d.attention_size, AS = d.attention_state_size,
+              DR = d.dec_rnn_size, M = d.num_mels, R = d.reduction_factor, L = d.dec_layer_num, MR = M * R, ain = D1 + ENC, XW = ain + 2 * AS;
+    const int norm = d.attention_type == TWV_ATT_BAH_MON_NORM ? 1 : 0;
+    GRAD_CHK(g->begin(st, status, grad_blob, w.blob_floats));
+    TgCarve c;
+    tg_carve(g, (float*)workspace, c);
+    const TgArgs a = tg_args(g, blob, memory, decoder_init, lengths, c, d_memory, d_init);
+    GRAD_HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(tg_backward_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, g->lds_bwd));
     // ---- (b) backward through time
     GRAD_CHK(g->mark(1));
     tg_launch_nt(st, tg_nt(d_mel, rows, MR, blob + w.oW, DR, c.dYF));
@@ -699,6 +732,19 @@ extern "C" int twv_tacotron_decoder_grad_run(twv_tacotron_decoder_grad* g, const
     GRAD_HIPCHK(hipGetLastError());
     GRAD_CHK(g->mark(3));
     return TWV_OK;
+}
+
+// forward, then backward
+extern "C" int twv_tacotron_decoder_grad_run(twv_tacotron_decoder_grad* g, const float* blob, const float* memory, const float* decoder_init,
+                                             const int32_t* lengths, const float* mel_targets, const float* d_mel, const float* mask1,
+                                             const float* mask2, void* workspace, int32_t* status, void* stream, float* mel_out,
+                                             float* grad_blob, float* d_memory, float* d_init)
+{
+    if (!g || !blob || !memory || !decoder_init || !lengths || !mel_targets || !d_mel || !workspace || !status || !mel_out || !grad_blob ||
+        !d_memory || !d_init)
+        return twv_fail(TWV_E_INVALID, "null argument");
+    GRAD_CHK(twv_tacotron_decoder_grad_forward(g, blob, memory, decoder_init, lengths, mel_targets, mask1, mask2, workspace, status, stream, mel_out));
+    return twv_tacotron_decoder_grad_backward(g, blob, memory, decoder_init, lengths, d_mel, workspace, status, stream, grad_blob, d_memory, d_init);
 }
 
 // after a run with timing on: waits for it and gives the milliseconds of (a) the recording forward, (b) the backward through time (with the

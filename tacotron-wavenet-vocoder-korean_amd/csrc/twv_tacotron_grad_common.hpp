@@ -159,7 +159,7 @@ struct Handle {
         if (blas) rocblas_destroy_handle(blas);
         for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
     }
-    // the start of every run: rocBLAS on the run's stream, status cleared, the whole gradient blob zeroed
+    // the start of every run: rocBLAS on the run's stream, status cleared, the whole gradient blob (if the run writes one) zeroed
     int begin(hipStream_t stream, int32_t* status, float* grad_blob, long long blob_floats)
     {
         st = stream; grad = grad_blob;
@@ -170,7 +170,7 @@ struct Handle {
         GRAD_BLASCHK(rocblas_set_stream(blas, st));
         GRAD_BLASCHK(rocblas_set_pointer_mode(blas, rocblas_pointer_mode_host));
         GRAD_HIPCHK(hipMemsetAsync(status, 0, 16, st));
-        GRAD_HIPCHK(hipMemsetAsync(grad_blob, 0, (size_t)blob_floats * 4, st));
+        if (grad_blob) GRAD_HIPCHK(hipMemsetAsync(grad_blob, 0, (size_t)blob_floats * 4, st));
         return TWV_OK;
     }
     int mark(int i)

@@ -161,7 +161,8 @@ __global__ void tt_refold_kernel(const float* var, BnMap m, long long blob_float
 }
 // tacotron.bn_grad_from_inference_pair: d_gamma = rsqrt(var + eps) (d_inv - mean d_shift), d_beta = d_shift, float64 inside; exact zeros for
 // the moving statistics; every other range copied
-__global__ void tt_grad_convert_kernel(const float* var, const float* gblob, BnMap m, long long train_floats, float* gvar)
+// (batch: the pair's slots already hold (d_gamma, d_beta) of a pass in batch-statistics mode, which are copied)
+__global__ void tt_grad_convert_kernel(const float* var, const float* gblob, BnMap m, long long train_floats, int batch, float* gvar)
 {
     for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < train_floats; t += (long long)gridDim.x * blockDim.x) {
         long long ahead = 0;
@@ -171,12 +172,45 @@ __global__ void tt_grad_convert_kernel(const float* var, const float* gblob, BnM
         const int C = m.channels[i], row = (int)((t - m.off[i] - ahead) / C), c = (int)(t - m.off[i] - ahead) - row * C;
         const float* pair = gblob + m.off[i] + c;
         float out = 0.0f;
-        if (row == 0) {
+        if (batch) out = row < 2 ? pair[row * C] : 0.0f;
+        else if (row == 0) {
             const float* raw = var + m.off[i] + ahead + c;
             const double rs = 1.0 / sqrt((double)raw[3 * C] + (double)kBnEps);
             out = (float)(rs * ((double)pair[0] - (double)raw[2 * C] * (double)pair[C]));
         } else if (row == 1) out = pair[C];
         gvar[t] = out;
+    }
+}
+
+// tf's assign_moving_average without zero-debias on the moving mean and variance of every batch norm: m <- m - (m - batch) * decay, each
+// operation rounded to float32.  stats: per batch norm in BnMap order a (2, C) piece = (mean, variance) of the batch
+__global__ void tt_moving_update_kernel(float* var, BnMap m, const float* stats, long long total, float decay)
+{
+    for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (long long)gridDim.x * blockDim.x) {
+        long long ahead = 0;
+        int i = 0;
+        while (p >= ahead + 2LL * m.channels[i]) { ahead += 2LL * m.channels[i]; ++i; }
+        float* t = var + m.off[i] + ahead + 2LL * m.channels[i] + (p - ahead);       // rows 2, 3 of the (4, C) tensor
+        const float v = *t;
+        *t = __fsub_rn(v, __fmul_rn(__fsub_rn(v, stats[p]), decay));
+    }
+}
+
+// dropout multipliers from a counter-based generator: element i of site `site` at step `step` under `seed` depends on those four alone.
+//   key = mix(seed + G * (4 * step + site)),  z = mix(key + G * (i + 1)),  u = (z >> 40) * 2^-24   (mix: the splitmix64 finaliser, G its increment)
+// kept where u >= rate: out = scale (1 / (1 - rate)) or 0
+__device__ __host__ inline unsigned long long tt_mix(unsigned long long z)
+{
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+    return z ^ (z >> 31);
+}
+__global__ void tt_dropout_mask_kernel(unsigned long long key, long long total, float rate, float scale, float* out)
+{
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const unsigned long long z = tt_mix(key + 0x9E3779B97F4A7C15ULL * (unsigned long long)(i + 1));
+        const float u = (float)(z >> 40) * 5.9604644775390625e-08f;
+        out[i] = u >= rate ? scale : 0.0f;
     }
 }
 
@@ -293,7 +327,53 @@ extern "C" int twv_tacotron_grad_convert(const twv_tacotron* h, const float* var
     if (!h || !variables || !grad_blob || !grad_variables) return twv_fail(TWV_E_INVALID, "null argument");
     BnMap m;
     const long long n = (long long)twv_tacotron_blob_floats(h) + bn_map(h, m);
-    hipLaunchKernelGGL(tt_grad_convert_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, variables, grad_blob, m, n, grad_variables);
+    hipLaunchKernelGGL(tt_grad_convert_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, variables, grad_blob, m, n, 0, grad_variables);
+    GRAD_HIPCHK(hipGetLastError());
+    return TWV_OK;
+}
+
+extern "C" int twv_tacotron_grad_convert_batch(const twv_tacotron* h, const float* grad_blob, float* grad_variables, void* stream)
+{
+    if (!h || !grad_blob || !grad_variables) return twv_fail(TWV_E_INVALID, "null argument");
+    BnMap m;
+    const long long n = (long long)twv_tacotron_blob_floats(h) + bn_map(h, m);
+    hipLaunchKernelGGL(tt_grad_convert_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, (const float*)nullptr, grad_blob, m, n, 1, grad_variables);
+    GRAD_HIPCHK(hipGetLastError());
+    return TWV_OK;
+}
+
+extern "C" int twv_tacotron_moving_update(const twv_tacotron* h, float* variables, const float* encoder_stats, const float* post_stats, double momentum,
+                                          void* stream)
+{
+    if (!h || !variables || !encoder_stats || !post_stats) return twv_fail(TWV_E_INVALID, "null argument");
+    if (!(momentum >= 0.0 && momentum <= 1.0)) return twv_fail(TWV_E_INVALID, "momentum must lie in [0, 1]");
+    BnMap m, part;
+    bn_map(h, m);
+    const float decay = (float)(1.0 - momentum);
+    int first = 0;
+    for (int which = 0; which < 2; ++which) {           // one launch per CBHG: its statistics are one buffer, its batch norms a run of the map
+        TacoCbhgBlob c;
+        taco_cbhg_blob(h, which, c);
+        const int n = c.bank + 2;
+        long long total = 0, ahead = 0;
+        for (int i = 0; i < first; ++i) ahead += 2LL * m.channels[i];
+        part.n = n;
+        for (int i = 0; i < n; ++i) { part.channels[i] = m.channels[first + i]; part.off[i] = m.off[first + i] + ahead; total += 2LL * part.channels[i]; }
+        hipLaunchKernelGGL(tt_moving_update_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, variables, part, which ? post_stats : encoder_stats,
+                           total, decay);
+        first += n;
+    }
+    GRAD_HIPCHK(hipGetLastError());
+    return TWV_OK;
+}
+
+extern "C" int twv_dropout_mask(float* out, int64_t n, uint64_t seed, int64_t step, int site, double rate, void* stream)
+{
+    if (!out) return twv_fail(TWV_E_INVALID, "null argument");
+    if (n < 1 || step < 0 || site < 0 || site > 3) return twv_fail(TWV_E_INVALID, "n >= 1, step >= 0 and a site 0 .. 3 required");
+    if (!(rate >= 0.0 && rate < 1.0)) return twv_fail(TWV_E_INVALID, "rate must lie in [0, 1)");
+    const unsigned long long key = tt_mix((unsigned long long)seed + 0x9E3779B97F4A7C15ULL * (4ULL * (unsigned long long)step + (unsigned long long)site));
+    hipLaunchKernelGGL(tt_dropout_mask_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, key, (long long)n, (float)rate, (float)(1.0 / (1.0 - rate)), out);
     GRAD_HIPCHK(hipGetLastError());
     return TWV_OK;
 }

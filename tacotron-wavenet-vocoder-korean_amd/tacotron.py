@@ -222,6 +222,34 @@ def bn_grad_from_inference_pair(pair, raw):
     return np.stack([rs * (pair[0] - raw[2] * pair[1]), pair[1]]).astype(np.float32)
 
 
+# batch norm of the encoder / post-net passes (include/twv_amd.h TWV_BN_*): "inference" = the moving statistics (the evaluation graph),
+# "batch" = tf.layers.batch_normalization(training=True), the statistics of the batch over all N * T rows
+BN_MODES = {"inference": 0, "batch": 1}
+DROPOUT_SITES = {"encoder_prenet_1": 0, "encoder_prenet_2": 1, "decoder_prenet_1": 2, "decoder_prenet_2": 3}
+BN_MOMENTUM = 0.99             # tf.layers.batch_normalization's default momentum (modules.py:92-96 passes none)
+
+
+def dropout_mask_numpy(n, seed, step, site, rate=0.5):
+    """twv_dropout_mask restated on the host: n multipliers (float32), element i from (seed, step, site, i) alone"""
+    G = np.uint64(0x9E3779B97F4A7C15)
+
+    def mix(z):
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        return z ^ (z >> np.uint64(31))
+    with np.errstate(over="ignore"):
+        key = mix(np.asarray([seed], np.uint64) + G * np.asarray([4 * int(step) + int(site)], np.uint64))
+        z = mix(key + G * np.arange(1, int(n) + 1, dtype=np.uint64))
+    u = (z >> np.uint64(40)).astype(np.float32) * np.float32(2.0 ** -24)
+    return np.where(u >= np.float32(rate), np.float32(1.0 / (1.0 - rate)), np.float32(0.0)).astype(np.float32)
+
+
+def moving_average_update(moving, batch, momentum=BN_MOMENTUM):
+    """twv_tacotron_moving_update restated on the host, float32: m - (m - batch) * (float32)(1 - momentum)"""
+    m, b = np.asarray(moving, np.float32), np.asarray(batch, np.float32)
+    return (m - ((m - b).astype(np.float32) * np.float32(1.0 - momentum)).astype(np.float32)).astype(np.float32)
+
+
 # kind of gradient handle -> (prefix of its C entries, leading arguments of *_create after the model)
 _GRAD_KINDS = {"decoder": ("twv_tacotron_decoder_grad", ()), "encoder": ("twv_tacotron_cbhg_grad", (0,)), "post": ("twv_tacotron_cbhg_grad", (1,))}
 
@@ -303,6 +331,8 @@ class Tacotron(object):
         # the raw (4, C) batch norm tensors: encoder_grad / postnet_grad turn the derived pair's gradient into (d_gamma, d_beta) with them
         self._bn_raw = {n: np.asarray(tensors[n], np.float64) for n, _ in self.specs if n.endswith("batch_normalization")}
         assert blob.size == self._L.twv_tacotron_blob_floats(self._h), (blob.size, self._L.twv_tacotron_blob_floats(self._h))
+        self._train_vec = None                              # (training_vector builds it from the tensors below when a batch-mode pass asks)
+        self._train_src = {n: np.asarray(tensors[n], np.float32) for n, _ in self.specs}
         with torch.cuda.device(self.device):
             dblob = self._blob = torch.from_numpy(blob).to(self.device)     # kept: decoder_grad differentiates the canonical tensors
             self._packed = torch.empty(self._L.twv_tacotron_packed_bytes(self._h) // 4, dtype=torch.float32, device=self.device)
@@ -485,15 +515,183 @@ class Tacotron(object):
             raise ValueError("loss_coeff must hold one factor per utterance (%d), got shape %s" % (N, co.shape))
         return torch.from_numpy(co).to(self.device)
 
-    def _named_grads(self, grad, layout):
-        """the blob-shaped gradient as a dict by checkpoint name, a batch norm's slot as (d_gamma, d_beta)"""
+    def _named_grads(self, grad, layout, mode="inference"):
+        """the blob-shaped gradient as a dict by checkpoint name, a batch norm's slot as (d_gamma, d_beta): what a batch-mode pass wrote
+        there, or the inference mode's (d_inv, d_shift) through bn_grad_from_inference_pair"""
         out = {}
         for name, off, shp in layout:
             t = grad[off:off + int(np.prod(shp))].view(*shp)
-            if name.endswith("batch_normalization"):
+            if name.endswith("batch_normalization") and mode != "batch":
                 t = torch.from_numpy(bn_grad_from_inference_pair(t.cpu().numpy(), self._bn_raw[name])).to(self.device)
             out[name] = t
         return out
+
+    # ---- batch-statistics mode and the passes' halves (DESIGN 3b-j)
+    def training_vector(self):
+        """the training vector (flatten_variables: batch norms as their (4, C) tensors) on the device: what a batch-mode pass reads gamma and
+        beta from.  Built from the tensors of load_weights; a TacotronTrainer puts its own vector here, which its steps update."""
+        if getattr(self, "_train_vec", None) is None:
+            if getattr(self, "_train_src", None) is None:
+                raise ValueError("batch mode needs load_weights first")
+            with torch.cuda.device(self.device):
+                self._train_vec = torch.from_numpy(flatten_variables(self.specs, self._train_src)).to(self.device)
+        return self._train_vec
+
+    def _cbhg_handle(self, kind, sizes, mode):
+        """_grad_handle of "encoder" / "post" put into `mode`"""
+        if mode not in BN_MODES:
+            raise ValueError("mode must be one of %s, got %r" % (sorted(BN_MODES), mode))
+        g, ws = self._grad_handle(kind, sizes)
+        _lib.check(self._L.twv_tacotron_cbhg_grad_set_mode(g, BN_MODES[mode], _ptr(self.training_vector()) if mode == "batch" else None))
+        self.__dict__.setdefault("_bn_mode", {})[kind] = mode
+        return g, ws
+
+    def batch_statistics(self, which):
+        """the statistics of the last batch-mode pass of `which` ("encoder" / "post"): {batch_normalization name: (2, C) device tensor =
+        (mean, biased variance) over all N * T rows of that batch norm's input}"""
+        if which not in ("encoder", "post"):
+            raise KeyError(which)
+        return self._split_stats(self._batch_stats_flat(which), which)
+
+    def _batch_stats_flat(self, which):
+        entry = getattr(self, "_grad_cache", {}).get(which)
+        if entry is None:
+            raise ValueError("batch_statistics needs a batch-mode pass first")
+        with torch.cuda.device(self.device):
+            out = torch.empty(self._L.twv_tacotron_cbhg_grad_batch_stats_floats(entry[1]), dtype=torch.float32, device=self.device)
+            _lib.check(self._L.twv_tacotron_cbhg_grad_batch_stats(entry[1], _ptr(out), _stream()))
+        return out
+
+    def _split_stats(self, flat, which):
+        scope = "encoder_cbhg/" if which == "encoder" else "post_cbhg/"
+        out, off = {}, 0
+        for n, shp in self.specs:
+            if n.startswith(scope) and n.endswith("batch_normalization"):
+                out[n] = flat[off:off + 2 * shp[1]].view(2, shp[1])
+                off += 2 * shp[1]
+        assert off == flat.numel(), (off, flat.numel())
+        return out
+
+    def dropout_mask(self, shape, seed, step, site, rate=0.5):
+        """dropout multipliers of `shape` on the device (twv_dropout_mask): 1 / (1 - rate) where kept, 0 where dropped; an element depends
+        on (seed, step, site, its index) alone.  site: a key of DROPOUT_SITES or 0 .. 3.  dropout_mask_numpy gives the same bits."""
+        site = DROPOUT_SITES.get(site, site)
+        with torch.cuda.device(self.device):
+            out = torch.empty(tuple(int(v) for v in shape), dtype=torch.float32, device=self.device)
+            _lib.check(self._L.twv_dropout_mask(_ptr(out), out.numel(), int(seed), int(step), int(site), float(rate), _stream()))
+        return out
+
+    def encoder_grad_forward(self, prenet_masks=None, mode="inference"):
+        """the recording forward of encoder_grad alone, on the tokens of the last forward_targets(teacher_forced=True) pass: returns memory
+        (N, T_in, 2 * enc_rnn_size).  encoder_grad_backward(d_memory) finishes the pass."""
+        hp = self._hparams
+        self._forced_pass("encoder_grad_forward")
+        if getattr(self, "_blob", None) is None:
+            raise ValueError("encoder_grad_forward needs load_weights first")
+        N, T = (int(v) for v in self.inputs.shape)
+        with torch.cuda.device(self.device):
+            masks = self._prenet_masks(prenet_masks, (N, T), hp.enc_prenet_sizes)
+            g, ws = self._cbhg_handle("encoder", (N, T), mode)      # (first: a model the pass is not built for is refused in the library's words)
+            bh = init = None
+            if self.num_speakers > 1:
+                bh, init = self.workspace_view(N, T, "before_highway"), self.workspace_view(N, T, "encoder_rnn_init")
+            memory = torch.empty((N, T, 2 * hp.enc_rnn_size), dtype=torch.float32, device=self.device)
+            status = torch.zeros(4, dtype=torch.int32, device=self.device)
+            _lib.check(self._L.twv_tacotron_encoder_grad_forward(g, _ptr(self._blob), _ptr(self.inputs), _ptr(self.input_lengths), _ptr(bh), _ptr(init),
+                                                                 _ptr(masks[0]), _ptr(masks[1]), _ptr(ws), _ptr(status), _stream(), _ptr(memory)))
+        self._enc_half = (N, T, bh is not None)
+        return memory
+
+    def encoder_grad_backward(self, d_memory):
+        """the backward of the last encoder_grad_forward: (blob-shaped gradient, d_before_highway, d_encoder_rnn_init); in batch mode a batch
+        norm's slot of the gradient holds (d_gamma, d_beta), in inference mode (d_inv, d_shift)"""
+        hp = self._hparams
+        if getattr(self, "_enc_half", None) is None:
+            raise ValueError("encoder_grad_backward needs encoder_grad_forward first")
+        N, T, spk = self._enc_half
+        ENC = 2 * hp.enc_rnn_size
+        with torch.cuda.device(self.device):
+            dm = self._device_f32(d_memory, (N, T, ENC), "d_memory must be %s, got %s")
+            g, ws = self._grad_handle("encoder", (N, T))
+            d_bh = torch.empty((N, hp.enc_prenet_sizes[1]), dtype=torch.float32, device=self.device) if spk else None
+            d_init = torch.empty((N, ENC), dtype=torch.float32, device=self.device) if spk else None
+            grad = torch.empty_like(self._blob)
+            status = torch.zeros(4, dtype=torch.int32, device=self.device)
+            _lib.check(self._L.twv_tacotron_encoder_grad_backward(g, _ptr(self._blob), _ptr(self.inputs), _ptr(self.input_lengths), _ptr(dm), _ptr(ws),
+                                                                  _ptr(status), _stream(), _ptr(grad), _ptr(d_bh), _ptr(d_init)))
+        return grad, d_bh, d_init
+
+    def postnet_grad_forward(self, mel, mode="inference"):
+        """the recording forward of postnet_grad alone: mel (N, T_out, num_mels) -> linear (N, T_out, num_freq)"""
+        hp = self._hparams
+        if getattr(self, "_blob", None) is None:
+            raise ValueError("postnet_grad_forward needs load_weights first")
+        with torch.cuda.device(self.device):
+            mel = self._device_f32(mel, None, "")
+            if mel.dim() != 3 or int(mel.shape[2]) != hp.num_mels:
+                raise ValueError("mel must be (N, T_out, %d), got %s" % (hp.num_mels, tuple(mel.shape)))
+            N, TO, _ = (int(v) for v in mel.shape)
+            g, ws = self._cbhg_handle("post", (N, TO), mode)
+            lin = torch.empty((N, TO, hp.num_freq), dtype=torch.float32, device=self.device)
+            status = torch.zeros(4, dtype=torch.int32, device=self.device)
+            _lib.check(self._L.twv_tacotron_postnet_grad_forward(g, _ptr(self._blob), _ptr(mel), _ptr(ws), _ptr(status), _stream(), _ptr(lin)))
+        self._post_half = mel
+        return lin
+
+    def postnet_grad_backward(self, d_linear):
+        """the backward of the last postnet_grad_forward: (blob-shaped gradient, d_mel)"""
+        hp = self._hparams
+        mel = getattr(self, "_post_half", None)
+        if mel is None:
+            raise ValueError("postnet_grad_backward needs postnet_grad_forward first")
+        N, TO, _ = (int(v) for v in mel.shape)
+        with torch.cuda.device(self.device):
+            dl = self._device_f32(d_linear, (N, TO, hp.num_freq), "d_linear must be %s, got %s")
+            g, ws = self._grad_handle("post", (N, TO))
+            grad, d_mel = torch.empty_like(self._blob), torch.empty_like(mel)
+            status = torch.zeros(4, dtype=torch.int32, device=self.device)
+            _lib.check(self._L.twv_tacotron_postnet_grad_backward(g, _ptr(self._blob), _ptr(mel), _ptr(dl), _ptr(ws), _ptr(status), _stream(),
+                                                                  _ptr(grad), _ptr(d_mel)))
+        return grad, d_mel
+
+    def decoder_grad_forward(self, memory=None, prenet_masks=None):
+        """the recording forward of decoder_grad alone, teacher-forced on the targets of the last forward_targets(teacher_forced=True) pass:
+        memory (N, T_in, 2 * enc_rnn_size), by default that pass's; the initial states are that pass's.  Returns mel (N, T_out, num_mels)."""
+        hp = self._hparams
+        _, tgt = self._forced_pass("decoder_grad_forward")
+        if getattr(self, "_blob", None) is None:
+            raise ValueError("decoder_grad_forward needs load_weights first")
+        N, TO, M = (int(v) for v in tgt.shape)
+        T = int(self.inputs.shape[1])
+        steps = TO // hp.reduction_factor
+        with torch.cuda.device(self.device):
+            masks = self._prenet_masks(prenet_masks, (N, steps), hp.dec_prenet_sizes)
+            g, ws = self._grad_handle("decoder", (N, T, steps))
+            mem = self.workspace_view(N, T, "memory") if memory is None else self._device_f32(memory, (N, T, 2 * hp.enc_rnn_size), "memory must be %s, got %s")
+            init = self.workspace_view(N, T, "decoder_init").clone()
+            mel_out = torch.empty((N, TO, M), dtype=torch.float32, device=self.device)
+            status = torch.zeros(4, dtype=torch.int32, device=self.device)
+            _lib.check(self._L.twv_tacotron_decoder_grad_forward(g, _ptr(self._blob), _ptr(mem), _ptr(init), _ptr(self.input_lengths), _ptr(tgt),
+                                                                 _ptr(masks[0]), _ptr(masks[1]), _ptr(ws), _ptr(status), _stream(), _ptr(mel_out)))
+        self._dec_half = (N, T, steps, mem, init)
+        return mel_out
+
+    def decoder_grad_backward(self, d_mel):
+        """the backward of the last decoder_grad_forward: (blob-shaped gradient, d_memory, d_init)"""
+        hp = self._hparams
+        if getattr(self, "_dec_half", None) is None:
+            raise ValueError("decoder_grad_backward needs decoder_grad_forward first")
+        N, T, steps, mem, init = self._dec_half
+        with torch.cuda.device(self.device):
+            dm = self._device_f32(d_mel, (N, steps * hp.reduction_factor, hp.num_mels), "d_mel must be %s, got %s")
+            g, ws = self._grad_handle("decoder", (N, T, steps))
+            grad = torch.empty_like(self._blob)
+            d_memory = torch.empty((N, T, 2 * hp.enc_rnn_size), dtype=torch.float32, device=self.device)
+            d_init = torch.empty((N, hp.attention_state_size + hp.dec_layer_num * hp.dec_rnn_size), dtype=torch.float32, device=self.device)
+            status = torch.zeros(4, dtype=torch.int32, device=self.device)
+            _lib.check(self._L.twv_tacotron_decoder_grad_backward(g, _ptr(self._blob), _ptr(mem), _ptr(init), _ptr(self.input_lengths), _ptr(dm), _ptr(ws),
+                                                                  _ptr(status), _stream(), _ptr(grad), _ptr(d_memory), _ptr(d_init)))
+        return grad, d_memory, d_init
 
     def linear_loss_cotangent(self, linear_targets, loss_coeff=None):
         """d(linear term of add_loss) / d linear_outputs on the last teacher-forced forward_targets pass (tacotron.py:258-282), a
@@ -513,18 +711,19 @@ class Tacotron(object):
                                                              float(hp.sample_rate), _ptr(out), _stream()))
         return out
 
-    def postnet_grad(self, d_linear, mel=None):
+    def postnet_grad(self, d_linear, mel=None, mode="inference"):
         """The vector-Jacobian product of the post net (post CBHG + the linear-spectrogram layer): d_linear (N, T_out, num_freq) is the
         cotangent on linear_outputs; mel (N, T_out, num_mels) the post net's input, by default the mel_outputs of the last teacher-forced
         forward_targets pass.  Returns a dict: the gradient of every post_cbhg/* tensor and of the linear layer by name (batch norms as
-        (2, C) = d_gamma, d_beta), "d_mel" (the cotangent on mel) and "linear", the recorded forward's output."""
-        grad, d_mel, lin = self._postnet_grad_blob(d_linear, mel)
+        (2, C) = d_gamma, d_beta), "d_mel" (the cotangent on mel) and "linear", the recorded forward's output.  mode: a key of BN_MODES;
+        "batch" = batch-statistics batch norm over all N * T_out rows (batch_statistics("post") then gives the statistics)."""
+        grad, d_mel, lin = self._postnet_grad_blob(d_linear, mel, mode)
         with torch.cuda.device(self.device):
-            out = self._named_grads(grad, postnet_grad_layout(self.specs))
+            out = self._named_grads(grad, postnet_grad_layout(self.specs), mode)
         out["d_mel"], out["linear"] = d_mel, lin
         return out
 
-    def _postnet_grad_blob(self, d_linear, mel=None):
+    def _postnet_grad_blob(self, d_linear, mel=None, mode="inference"):
         """postnet_grad's pass with the gradient as the C entry leaves it: (blob-shaped gradient, d_mel, linear)"""
         hp = self._hparams
         mel0, _ = self._forced_pass("postnet_grad")
@@ -536,7 +735,7 @@ class Tacotron(object):
             dl = self._device_f32(d_linear, None, "")
             if M != hp.num_mels or tuple(dl.shape) != (N, TO, hp.num_freq):
                 raise ValueError("mel must be (N, T_out, %d) and d_linear (N, T_out, %d), got %s and %s" % (hp.num_mels, hp.num_freq, tuple(mel.shape), tuple(dl.shape)))
-            g, ws = self._grad_handle("post", (N, TO))
+            g, ws = self._cbhg_handle("post", (N, TO), mode)
             lin = torch.empty((N, TO, hp.num_freq), dtype=torch.float32, device=self.device)
             grad = torch.empty_like(self._blob)
             d_mel = torch.empty_like(mel)
@@ -545,22 +744,23 @@ class Tacotron(object):
                                                              _ptr(lin), _ptr(grad), _ptr(d_mel)))
         return grad, d_mel, lin
 
-    def encoder_grad(self, d_memory, prenet_masks=None):
+    def encoder_grad(self, d_memory, prenet_masks=None, mode="inference"):
         """The vector-Jacobian product of the encoder (embedding, prenet, encoder CBHG) of the last forward_targets(teacher_forced=True)
         pass: d_memory (N, T_in, 2 * enc_rnn_size) is the cotangent on the encoder output (decoder_grad's "d_memory"); tokens, lengths and,
         for a multi-speaker model, before_highway and the GRUs' initial states are read from that pass.  prenet_masks: None (the evaluation
         graph) or two (N, T_in, enc_prenet_sizes[i]) arrays of multipliers after the prenet's relus.  Returns a dict: the gradient of
         embedding, prenet/* and encoder_cbhg/* by name (batch norms as (2, C) = d_gamma, d_beta), "memory" (the recorded output) and, for a
-        multi-speaker model, "d_before_highway" (N, enc_prenet_sizes[1]) and "d_encoder_rnn_init" (N, 2 * enc_rnn_size)."""
-        grad, memory, d_bh, d_init = self._encoder_grad_blob(d_memory, prenet_masks)
+        multi-speaker model, "d_before_highway" (N, enc_prenet_sizes[1]) and "d_encoder_rnn_init" (N, 2 * enc_rnn_size).  mode: a key of
+        BN_MODES; "batch" = batch-statistics batch norm over all N * T_in rows, padded ones included."""
+        grad, memory, d_bh, d_init = self._encoder_grad_blob(d_memory, prenet_masks, mode)
         with torch.cuda.device(self.device):
-            out = self._named_grads(grad, encoder_grad_layout(self.specs))
+            out = self._named_grads(grad, encoder_grad_layout(self.specs), mode)
         out["memory"] = memory
         if d_bh is not None:
             out["d_before_highway"], out["d_encoder_rnn_init"] = d_bh, d_init
         return out
 
-    def _encoder_grad_blob(self, d_memory, prenet_masks=None):
+    def _encoder_grad_blob(self, d_memory, prenet_masks=None, mode="inference"):
         """encoder_grad's pass with the gradient as the C entry leaves it: (blob-shaped gradient, memory, d_before_highway, d_encoder_rnn_init)"""
         hp = self._hparams
         self._forced_pass("encoder_grad")
@@ -576,7 +776,7 @@ class Tacotron(object):
                 bh, init = self.workspace_view(N, T, "before_highway"), self.workspace_view(N, T, "encoder_rnn_init")
                 d_bh = torch.empty((N, P[1]), dtype=torch.float32, device=self.device)
                 d_init = torch.empty((N, ENC), dtype=torch.float32, device=self.device)
-            g, ws = self._grad_handle("encoder", (N, T))
+            g, ws = self._cbhg_handle("encoder", (N, T), mode)
             memory = torch.empty((N, T, ENC), dtype=torch.float32, device=self.device)
             grad = torch.empty_like(self._blob)
             status = torch.zeros(4, dtype=torch.int32, device=self.device)

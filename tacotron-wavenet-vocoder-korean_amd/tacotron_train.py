@@ -9,11 +9,19 @@ One step is forward_targets(teacher_forced=True) -> add_loss -> the three gradie
 training vector -> tf.clip_by_global_norm(gradients, 1.0) -> AdamOptimizer(lr, adam_beta1, adam_beta2) -> the new inference blob, all on
 the device; the only device -> host traffic is add_loss's four numbers.
 
-What this is NOT: the reference trains with batch-statistics batch norm and dropout (is_training=True).  Those change the forward graph
-of all three gradient passes and are not built; here the moving statistics are frozen and there is no dropout -- a fine-tuning step with
+That is TacotronTrainer(training=False), the default: the moving statistics are frozen and there is no dropout -- a fine-tuning step with
 frozen batch norm.  The moving statistics ride along in the flat Adam call with a zero gradient and zero moments, which leaves them
-untouched bit for bit (TensorFlow does not hand non-trainable variables to the optimiser at all).  A data feeder, a `train_tacotron`
-command line and the gradient all-reduce are not built either.
+untouched bit for bit (TensorFlow does not hand non-trainable variables to the optimiser at all).
+
+TacotronTrainer(training=True, seed=s) is the reference's is_training=True graph: batch-statistics batch norm after every
+convolution of both CBHGs, dropout 0.5 after both relus of the encoder prenet and of the decoder prenet (masks from a counter-based
+generator keyed by (seed, global_step, site): TensorFlow's random stream is not reproduced), and the moving-average update of every moving
+mean and variance (momentum 0.99, the biased batch variance) run with the optimiser.  One step is forward_targets(teacher_forced=True) for
+the speaker side's values -> the recording forwards of the encoder, the decoder and the post net in that mode -> add_loss on their outputs
+-> the three backwards -> the speaker side -> clip -> Adam -> the moving update -> the new inference blob.  The seed is a constructor
+argument and is not stored in a checkpoint: restore into a trainer made with the same seed to continue the same mask sequence.
+
+A data feeder, a `train_tacotron` command line and the gradient all-reduce are not built.
 PyTorch is used for device memory and streams only."""
 import os
 
@@ -22,8 +30,9 @@ import torch
 
 from . import _lib
 from . import checkpoint as ckpt
-from .tacotron import _ptr, _stream, flatten_variables, training_layout
+from .tacotron import BN_MOMENTUM, _ptr, _stream, flatten_variables, training_layout
 
+DROPOUT_RATE = 0.5       # modules.py:15-23 prenet: tf.layers.dropout(rate=0.5, training=is_training)
 CLIP_NORM = 1.0          # tacotron.py:306 tf.clip_by_global_norm(gradients, 1.0)
 ADAM_EPSILON = 1e-8      # tf.train.AdamOptimizer's default
 SCOPE = "model/inference/"
@@ -56,13 +65,15 @@ def _copy_runs(specs, picks):
 
 
 class TacotronTrainer(object):
-    def __init__(self, model, randomly_initialized=True):
+    def __init__(self, model, randomly_initialized=True, training=False, seed=0):
         """model: a Tacotron, with weights loaded or to be given its weights by `restore`; the trainer updates the model's blob in place, so
         `infer` and `forward_targets` see the new weights after every step.  randomly_initialized: tacotron.py:296-299, the warm-up of
-        learning-rate mode 0."""
+        learning-rate mode 0.  training: False = the evaluation graph (frozen batch norm, no dropout), True = the reference's
+        is_training=True graph; seed: of the dropout masks (not stored by `save`)."""
         hp = model._hparams
         self.model, self.device, self._L = model, model.device, model._L
         self.randomly_initialized = bool(randomly_initialized)
+        self.training, self.seed = bool(training), int(seed)
         self.lr0, self.mode = hp.tacotron_initial_learning_rate, hp.decay_learning_rate_mode
         learning_rate(self.lr0, 1, self.mode, self.randomly_initialized)         # (refuses another mode here, not at the first step)
         self.beta1, self.beta2, self.epsilon = hp.adam_beta1, hp.adam_beta2, ADAM_EPSILON
@@ -104,6 +115,7 @@ class TacotronTrainer(object):
         assert flat.size == self.n_variables, (flat.size, self.n_variables)
         with torch.cuda.device(self.device):
             self.vars = torch.from_numpy(flat).to(self.device)
+            self.model._train_vec = self.vars               # (batch-mode passes read gamma and beta from the vector the steps update)
             self.m = torch.zeros_like(self.vars) if m is None else torch.from_numpy(m).to(self.device)
             self.v = torch.zeros_like(self.vars) if v is None else torch.from_numpy(v).to(self.device)
             self._shadow = self.vars.clone()                # twv_adam_ema_step's shadow: written, never read
@@ -133,6 +145,8 @@ class TacotronTrainer(object):
         m = self.model
         if self.vars is None:
             raise RuntimeError("no weights: give the model its weights (load_weights) before the trainer is made, or call restore")
+        if self.training:
+            return self._training_loss_and_gradients(inputs, input_lengths, speaker_id, mel_targets, linear_targets, loss_coeff)
         m.forward_targets(inputs, input_lengths, speaker_id, mel_targets, teacher_forced=True)
         out = m.add_loss(linear_targets, loss_coeff)
         self._forward_done()
@@ -149,6 +163,45 @@ class TacotronTrainer(object):
                 m._speaker_grad_blob(d_bh, d_ei, d_init, grad=g)
             self._speaker_done()
             _lib.check(self._L.twv_tacotron_grad_convert(m._h, _ptr(self.vars), _ptr(g), _ptr(self.grads), _stream()))
+        return out
+
+    def dropout_masks(self, N, T, steps, step=None):
+        """the four masks of a step (global_step by default): encoder prenet 1, 2 (N, T, enc_prenet_sizes[i]), decoder prenet 1, 2
+        (N, steps, dec_prenet_sizes[i])"""
+        hp, m = self.model._hparams, self.model
+        step = self.global_step if step is None else int(step)
+        shapes = [(N, T, hp.enc_prenet_sizes[0]), (N, T, hp.enc_prenet_sizes[1]), (N, steps, hp.dec_prenet_sizes[0]), (N, steps, hp.dec_prenet_sizes[1])]
+        return [m.dropout_mask(shp, self.seed, step, site, DROPOUT_RATE) for site, shp in enumerate(shapes)]
+
+    def _training_loss_and_gradients(self, inputs, input_lengths, speaker_id, mel_targets, linear_targets, loss_coeff):
+        """the training-mode chain: every recording forward before any backward, add_loss on the training-mode outputs"""
+        m = self.model
+        # the speaker side's values (before_highway, the GRUs' and the decoder's initial states: no batch norm, no dropout in them), the
+        # tokens and the targets on the device
+        m.forward_targets(inputs, input_lengths, speaker_id, mel_targets, teacher_forced=True)
+        N, T = (int(v) for v in m.inputs.shape)
+        steps = int(m.mel_targets.shape[1]) // m._hparams.reduction_factor
+        with torch.cuda.device(self.device):
+            masks = self.last_masks = self.dropout_masks(N, T, steps)
+            memory = m.encoder_grad_forward(masks[:2], mode="batch")
+            mel = m.decoder_grad_forward(memory, masks[2:])
+            lin = m.postnet_grad_forward(mel, mode="batch")
+            m.mel_outputs, m.linear_outputs = mel, lin       # (add_loss and the two loss cotangents read the pass's outputs from here)
+            out = m.add_loss(linear_targets, loss_coeff)
+            self._forward_done()
+            g = self._gblob
+            post, d_mel_post = m.postnet_grad_backward(m.linear_loss_cotangent(linear_targets, loss_coeff))
+            self._collect(g, post, "post")
+            dec, d_memory, d_init = m.decoder_grad_backward(m.mel_loss_cotangent(loss_coeff) + d_mel_post)
+            self._collect(g, dec, "decoder")
+            enc, d_bh, d_ei = m.encoder_grad_backward(d_memory)
+            self._collect(g, enc, "encoder")
+            self._passes_done()
+            if self._speaker:
+                m._speaker_grad_blob(d_bh, d_ei, d_init, grad=g)
+            self._speaker_done()
+            _lib.check(self._L.twv_tacotron_grad_convert_batch(m._h, _ptr(g), _ptr(self.grads), _stream()))
+            self._stats = (m._batch_stats_flat("encoder"), m._batch_stats_flat("post"))
         return out
 
     def _collect(self, grad, part, which):
@@ -174,7 +227,13 @@ class TacotronTrainer(object):
             _lib.check(self._L.twv_adam_ema_step(_ptr(self.vars), _ptr(self.grads), _ptr(self.m), _ptr(self.v), _ptr(self._shadow),
                                                 self.n_variables, lr, self.beta1, self.beta2, self.epsilon, self.global_step + 1, 0.0, 1.0,
                                                 _stream()))
+            if self.training:
+                # tacotron.py:310-313: the moving-average updates run with the optimiser.  Adam leaves the moving slots bit for bit, so the
+                # order of the two is free
+                _lib.check(self._L.twv_tacotron_moving_update(m._h, _ptr(self.vars), _ptr(self._stats[0]), _ptr(self._stats[1]), BN_MOMENTUM, _stream()))
             self._refold()
+            if self.training:
+                self._refresh_bn_raw()
         self.global_step += 1
         return lr
 
@@ -185,8 +244,20 @@ class TacotronTrainer(object):
         _lib.check(self._L.twv_tacotron_refold(m._h, _ptr(self.vars), _ptr(m._blob), _stream()))
         _lib.check(self._L.twv_tacotron_pack(m._h, _ptr(m._blob), _ptr(m._packed), _stream()))
 
+    def _refresh_bn_raw(self):
+        """after a training-mode step the moving statistics have moved: the (4, C) tensors the model keeps on the host for
+        bn_grad_from_inference_pair (loss_gradients on the evaluation graph) are read back from the training vector"""
+        m = self.model
+        bns = [(n, off, shp) for n, off, shp in self.layout if n.endswith("batch_normalization")]
+        host = torch.cat([self.vars[off:off + int(np.prod(shp))] for _, off, shp in bns]).cpu().numpy().astype(np.float64)      # (one copy)
+        at = 0
+        for n, _, shp in bns:
+            size = int(np.prod(shp))
+            m._bn_raw[n] = host[at:at + size].reshape(shp).copy()
+            at += size
+
     def step(self, inputs, input_lengths, speaker_id, mel_targets, linear_targets, loss_coeff=None):
-        """one sess.run([model.loss, model.optimize]) on the evaluation graph; returns add_loss's dict (the loss BEFORE the update) and
+        """one sess.run([model.loss, model.optimize]) on the evaluation graph (training=False) or the training graph (training=True); returns add_loss's dict (the loss BEFORE the update) and
         advances global_step.  `last_learning_rate` is the rate the update used."""
         out = self.loss_and_gradients(inputs, input_lengths, speaker_id, mel_targets, linear_targets, loss_coeff)
         self.last_learning_rate = self.apply_gradients()
