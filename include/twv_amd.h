@@ -266,6 +266,25 @@ int twv_tacotron_loss(const float* mel, const float* linear, const float* mel_ta
                       const float* loss_coeff, int batch, int t_out, int num_mels, int num_freq, int prioritize_loss,
                       double sample_rate, double* out, void* stream);
 
+/* ---- Tacotron batch staging: a batch's ragged arrays, packed, -> the padded arrays of a training step ----
+ * `packed` (device, 16-byte aligned) is packed_words 32-bit words with four sections, each given by its first word: the tokens of every
+ * utterance one after the other (int32, total_tokens), their mel rows (total_frames, num_mels) and linear rows (total_frames, num_freq) as
+ * float32, and a table of `batch` twv_tacotron_feed_row at an even word.  table_host is the same table in host memory: every check is made on
+ * it before anything is launched.  TWV_E_INVALID: a null argument, a size < 1 or above 2^20, an output above 2^38 words, a section or a
+ * row's tokens / frames outside the buffer, a row with more tokens than t_in or more frames than t_out, a misaligned `packed`, table or
+ * target.  Out, every element written (the padding is stored): inputs (batch, t_in) int32 and mel_targets (batch, t_out, num_mels) /
+ * linear_targets (batch, t_out, num_freq), padded with 0; input_lengths, loss_coeff, speaker_id (batch) -- what datafeeder_tacotron.py:
+ * 269-309 `_prepare_batch` builds on the host, bit for bit.  The targets must be 16-byte aligned.  No atomics. */
+typedef struct twv_tacotron_feed_row {
+    int64_t token_offset, frame_offset;   /* in tokens / frames from the start of the section */
+    int32_t n_tokens, n_frames, speaker_id;
+    float loss_coeff;
+} twv_tacotron_feed_row;
+int twv_tacotron_batch_stage(const void* packed, const twv_tacotron_feed_row* table_host, long long packed_words, long long tokens_at,
+                             long long mel_at, long long linear_at, long long table_at, long long total_tokens, long long total_frames,
+                             int batch, int t_in, int t_out, int num_mels, int num_freq, int32_t* inputs, int32_t* input_lengths,
+                             float* mel_targets, float* linear_targets, float* loss_coeff, int32_t* speaker_id, void* stream);
+
 /* ---- Tacotron decoder gradients: the vector-Jacobian product of the teacher-forced decoder ----
  * Host only: where a twv_tacotron_infer / twv_tacotron_forward_targets call of (batch, t_in) left the pieces the decoder reads from the
  * encoder side, as (offset, count) in floats from the start of its workspace.  which = "memory" (batch, t_in, 2 * enc_rnn_size; zero past
@@ -282,6 +301,12 @@ int twv_tacotron_decoder_grad_create(const twv_tacotron* h, int batch, int t_in,
 void twv_tacotron_decoder_grad_destroy(twv_tacotron_decoder_grad* g);
 size_t twv_tacotron_decoder_grad_workspace_bytes(const twv_tacotron_decoder_grad* g);
 const char* twv_tacotron_decoder_grad_route(const twv_tacotron_decoder_grad* g);
+/* The handle at other sizes: accepts exactly what twv_tacotron_decoder_grad_create accepts for the handle's model and refuses the rest with
+ * the same codes and words (the LDS bound on t_in included).  Host only.  Kept: the rocBLAS handle, the events, the timing flag.  Follows the
+ * sizes: twv_tacotron_decoder_grad_workspace_bytes, the label's LDS sizes.  The backward is refused until a forward at the new sizes, as
+ * after _create.  A refused call leaves the handle unchanged.  A reshaped handle's runs give the bits of a newly created handle's,
+ * whatever the handle ran before and whatever the workspace holds. */
+int twv_tacotron_decoder_grad_reshape(twv_tacotron_decoder_grad* g, int batch, int t_in, int steps);
 /* The teacher-forced decoder forward (recorded) and its backward through time.
  * In:  blob          the canonical weights on the device (twv_tacotron_blob_floats floats, the order of tacotron_specs)
  *      memory        (batch, t_in, 2 * enc_rnn_size), decoder_init (batch, AS + layers * DR), lengths (batch) int32
@@ -334,6 +359,10 @@ int twv_tacotron_cbhg_grad_create(const twv_tacotron* h, int which, int batch, i
 void twv_tacotron_cbhg_grad_destroy(twv_tacotron_cbhg_grad* g);
 size_t twv_tacotron_cbhg_grad_workspace_bytes(const twv_tacotron_cbhg_grad* g);
 const char* twv_tacotron_cbhg_grad_route(const twv_tacotron_cbhg_grad* g);
+/* The handle at another (batch, t), as twv_tacotron_decoder_grad_reshape: what twv_tacotron_cbhg_grad_create accepts for the handle's model
+ * and side, the same refusals; the batch-norm mode, its variables pointer and the handle's device buffers (their sizes are sums of channel
+ * counts) are kept with the rocBLAS handle, the events and the timing flag. */
+int twv_tacotron_cbhg_grad_reshape(twv_tacotron_cbhg_grad* g, int batch, int t);
 /* The encoder (embedding, prenet, encoder CBHG), recorded, and its backward.
  * In:  blob            the canonical weights on the device; tokens (batch, t_in) int32, lengths (batch) int32
  *      before_highway  (batch, enc_prenet_sizes[1]) and rnn_init (batch, 2 * enc_rnn_size), or NULL each (a single-speaker model)

@@ -530,10 +530,9 @@ static long long cg_carve(const twv_tacotron_cbhg_grad* g, float* base, CgCarve&
 
 static const char* const kCgBuilt = "the CBHG gradient is built for single-speaker and 'deepvoice' models, enc_rnn_size = post_rnn_size = 128 and projection widths up to 16";
 
-extern "C" int twv_tacotron_cbhg_grad_create(const twv_tacotron* h, int which, int batch, int t, twv_tacotron_cbhg_grad** out)
+// what _create and _reshape accept of (which, batch, t) for the model `d`: one validation, the same codes and words from both
+static int cg_check_sizes(const twv_tacotron_dims& d, int which, int batch, int t)
 {
-    if (!h || !out) return twv_fail(TWV_E_INVALID, "null argument");
-    const twv_tacotron_dims& d = taco_dims(h);
     if (which != TWV_CBHG_ENCODER && which != TWV_CBHG_POST) return twv_fail(TWV_E_INVALID, "which must be TWV_CBHG_ENCODER (0) or TWV_CBHG_POST (1)");
     if (batch < 1) return twv_fail(TWV_E_INVALID, "batch >= 1 required");
     if (which == TWV_CBHG_ENCODER && (t < 1 || t > 1024)) return twv_fail(TWV_E_INVALID, "encoder: 1 <= t_in <= 1024 required");
@@ -541,6 +540,14 @@ extern "C" int twv_tacotron_cbhg_grad_create(const twv_tacotron* h, int which, i
     if ((long long)batch * t > (1LL << 24)) return twv_fail(TWV_E_INVALID, "batch * t above 2^24 rows");
     if (d.num_speakers > 1 && d.model_simple && d.speaker_embedding_size != 1)
         return twv_fail(TWV_E_UNSUPPORTED, std::string("model_type 'simple': ") + kCgBuilt);
+    return TWV_OK;
+}
+
+extern "C" int twv_tacotron_cbhg_grad_create(const twv_tacotron* h, int which, int batch, int t, twv_tacotron_cbhg_grad** out)
+{
+    if (!h || !out) return twv_fail(TWV_E_INVALID, "null argument");
+    const twv_tacotron_dims& d = taco_dims(h);
+    GRAD_CHK(cg_check_sizes(d, which, batch, t));
     twv_tacotron_cbhg_grad* g = new twv_tacotron_cbhg_grad();
     g->d = d; g->which = which; g->N = batch; g->T = t;
     taco_cbhg_blob(h, which, g->w);
@@ -581,6 +588,20 @@ extern "C" int twv_tacotron_cbhg_grad_create(const twv_tacotron* h, int which, i
                std::to_string(w.bank) + " bank_channels=" + std::to_string(w.bch) + " highway=" + std::to_string(w.depth) + " dense=" +
                std::to_string(w.has_dense) + " lds=" + std::to_string(g->lds) + " wgrad=rocblas";
     *out = g;
+    return TWV_OK;
+}
+// The handle at another (batch, t): what a _create at these sizes followed by the handle's set_mode would give.  Kept: the rocBLAS handle,
+// the events and the timing flag, the batch-norm mode and its variables pointer, and `pairs` / `stats` -- pair_floats is a sum of channel
+// counts (bank * bank channels + the two projection widths, twice), as is wT_floats, so neither follows the sizes; every forward in batch
+// mode writes all of `pairs` and `stats` before it reads them.  The label carries no sizes.  A refused call leaves the handle as it was.
+extern "C" int twv_tacotron_cbhg_grad_reshape(twv_tacotron_cbhg_grad* g, int batch, int t)
+{
+    if (!g) return twv_fail(TWV_E_INVALID, "null argument");
+    GRAD_CHK(cg_check_sizes(g->d, g->which, batch, t));
+    g->N = batch; g->T = t;
+    CgCarve c;
+    g->ws_floats = cg_carve(g, nullptr, c);
+    g->forwarded = 0; g->has_bh = 0; g->has_init = 0;
     return TWV_OK;
 }
 extern "C" void twv_tacotron_cbhg_grad_destroy(twv_tacotron_cbhg_grad* g) { delete g; }

@@ -569,10 +569,10 @@ static long long tg_carve(const twv_tacotron_decoder_grad* g, float* base, TgCar
 
 static const char* const kTgBuilt = "the decoder gradient is built for attention_type 'bah_mon_norm' and 'bah_mon', single-speaker and 'deepvoice' models";
 
-extern "C" int twv_tacotron_decoder_grad_create(const twv_tacotron* h, int batch, int t_in, int steps, twv_tacotron_decoder_grad** out)
+// what _create and _reshape accept of (batch, t_in, steps) for the model `d`: one validation, so both answer with the same codes and words.
+// Gives the LDS bytes of the two recurrent kernels at t_in.
+static int tg_check_sizes(const twv_tacotron_dims& d, int batch, int t_in, int steps, int& lf, int& lb)
 {
-    if (!h || !out) return twv_fail(TWV_E_INVALID, "null argument");
-    const twv_tacotron_dims& d = taco_dims(h);
     if (batch < 1 || t_in < 1 || t_in > 1024) return twv_fail(TWV_E_INVALID, "batch >= 1 and 1 <= t_in <= 1024 required");
     if (steps < 1 || steps > d.max_iters) return twv_fail(TWV_E_INVALID, "steps must satisfy 1 <= steps <= max_iters");
     if (d.attention_type != TWV_ATT_BAH_MON_NORM && d.attention_type != TWV_ATT_BAH_MON)
@@ -584,17 +584,48 @@ extern "C" int twv_tacotron_decoder_grad_create(const twv_tacotron* h, int batch
     // twv_tacotron_create has bounded everything else (attention_size, attention_state_size = dec_rnn_size <= 256, dec_prenet_sizes[0] and
     // num_mels * r <= 512, 1 .. 4 layers); the row kernels hold rows of up to 512 floats
     if (D1 > kRowsK || D0 > kRowsK || d.num_mels > kRowsK) return twv_fail(TWV_E_UNSUPPORTED, "decoder gradient: dec_prenet_sizes and num_mels above 512 are not built");
-    const int lf = tg_fwd_lds(t_in, D1, ENC, A, AS, DR, L).total * 4, lb = tg_bwd_lds(t_in, D1, ENC, A, AS, DR, L).total * 4;
+    // Of each carve only the four arrays of Tp = t_in rounded up to 4 floats follow t_in: 16 KB at t_in = 1024.  The rest is bounded by
+    // twv_tacotron_create: at its widest (D1 = 512, ENC = 256, A = AS = DR = 256, L = 4) the forward carve is 43 KB and the backward
+    // carve 66 KB, so no model it accepts reaches the bound below at t_in <= 1024.  The check stays: it is what holds if a bound moves.
+    lf = tg_fwd_lds(t_in, D1, ENC, A, AS, DR, L).total * 4; lb = tg_bwd_lds(t_in, D1, ENC, A, AS, DR, L).total * 4;
     if (lf > 160 * 1024 || lb > 160 * 1024) return twv_fail(TWV_E_UNSUPPORTED, "decoder gradient: the per-utterance state does not fit the LDS of one workgroup");
-    twv_tacotron_decoder_grad* g = new twv_tacotron_decoder_grad();
-    g->d = d; g->N = batch; g->T = t_in; g->steps = steps; g->lds_fwd = lf; g->lds_bwd = lb;
-    taco_decoder_blob(h, g->w);
+    return TWV_OK;
+}
+// everything of a handle that follows (batch, t_in, steps): the sizes, the LDS bytes, the workspace size and the label
+static void tg_set_sizes(twv_tacotron_decoder_grad* g, int batch, int t_in, int steps, int lf, int lb)
+{
+    const twv_tacotron_dims& d = g->d;
+    g->N = batch; g->T = t_in; g->steps = steps; g->lds_fwd = lf; g->lds_bwd = lb;
     TgCarve c;
     g->ws_floats = tg_carve(g, nullptr, c);
     g->route = std::string("kernel=tg_bptt attention=") + (d.attention_type == TWV_ATT_BAH_MON_NORM ? "bah_mon_norm" : "bah_mon") +
-               " workgroups_per_utterance=1 threads=512 layers=" + std::to_string(L) + " lds_forward=" + std::to_string(lf) +
+               " workgroups_per_utterance=1 threads=512 layers=" + std::to_string(d.dec_layer_num) + " lds_forward=" + std::to_string(lf) +
                " lds_backward=" + std::to_string(lb) + " wgrad=rocblas";
+    g->forwarded = 0;
+}
+
+extern "C" int twv_tacotron_decoder_grad_create(const twv_tacotron* h, int batch, int t_in, int steps, twv_tacotron_decoder_grad** out)
+{
+    if (!h || !out) return twv_fail(TWV_E_INVALID, "null argument");
+    const twv_tacotron_dims& d = taco_dims(h);
+    int lf = 0, lb = 0;
+    GRAD_CHK(tg_check_sizes(d, batch, t_in, steps, lf, lb));
+    twv_tacotron_decoder_grad* g = new twv_tacotron_decoder_grad();
+    g->d = d;
+    taco_decoder_blob(h, g->w);
+    tg_set_sizes(g, batch, t_in, steps, lf, lb);
     *out = g;
+    return TWV_OK;
+}
+// The handle at other sizes: what a _create at (batch, t_in, steps) would give, with the rocBLAS handle, the events and the timing flag
+// kept (nothing the handle owns depends on the sizes: the tape lives in the caller's workspace, carved anew by every run).  A refused
+// call leaves the handle as it was.
+extern "C" int twv_tacotron_decoder_grad_reshape(twv_tacotron_decoder_grad* g, int batch, int t_in, int steps)
+{
+    if (!g) return twv_fail(TWV_E_INVALID, "null argument");
+    int lf = 0, lb = 0;
+    GRAD_CHK(tg_check_sizes(g->d, batch, t_in, steps, lf, lb));
+    tg_set_sizes(g, batch, t_in, steps, lf, lb);
     return TWV_OK;
 }
 extern "C" void twv_tacotron_decoder_grad_destroy(twv_tacotron_decoder_grad* g) { delete g; }

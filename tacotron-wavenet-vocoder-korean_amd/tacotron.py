@@ -368,15 +368,17 @@ class Tacotron(object):
         TacoTrainingHelper (helpers.py:44-87) for mel_targets.shape[1] / r steps.  teacher_forced=False is the reference's test_model
         (rnn_decoder_test_mode=True: free-running, the targets give the length only); teacher_forced=True feeds step t >= 1 the target
         frame t*r - 1.  Every layer stays in inference mode in both (no dropout, moving-average batch norm: the reference's training-mode
-        layers belong to a training step).  mel_targets: (N, T_out, num_mels) array or tensor, T_out a multiple of r, T_out / r <= max_iters."""
+        layers belong to a training step).  mel_targets: (N, T_out, num_mels) array or tensor, T_out a multiple of r, T_out / r <= max_iters.
+        inputs, input_lengths and speaker_id: arrays, or int32 tensors -- a batch already on the device (tacotron_feed.BatchStager) is
+        used where it lies, with no host round trip."""
         hp = self._hparams
         with torch.cuda.device(self.device):
-            tok = torch.as_tensor(np.asarray(inputs, np.int32), device=self.device).contiguous()
+            tok = self._device_i32(inputs)
             N, T = tok.shape
-            ln = torch.as_tensor(np.asarray(input_lengths, np.int32), device=self.device).contiguous()
+            ln = self._device_i32(input_lengths)
             sp = None
             if self.num_speakers > 1:
-                sp = torch.as_tensor(np.asarray(speaker_id, np.int32), device=self.device).contiguous()
+                sp = self._device_i32(speaker_id)
             if not torch.is_tensor(mel_targets):
                 mel_targets = torch.from_numpy(np.ascontiguousarray(mel_targets, np.float32))
             tgt = mel_targets.to(device=self.device, dtype=torch.float32).contiguous()
@@ -473,16 +475,37 @@ class Tacotron(object):
 
     # ---- what the gradient methods share
     def _grad_handle(self, kind, sizes):
-        """(handle, workspace) of a kind of _GRAD_KINDS at `sizes` (the arguments of its *_create), kept until that kind's sizes change"""
+        """(handle, workspace) of a kind of _GRAD_KINDS at `sizes` (the arguments of its *_create).  One handle per kind lives as long as
+        the model: when the sizes change it is reshaped (*_reshape keeps its rocBLAS handle, events and device buffers; a refusal leaves
+        it and this cache as they were), and its workspace tensor only ever grows."""
         cache = self.__dict__.setdefault("_grad_cache", {})
-        if kind not in cache or cache[kind][0] != sizes:
-            self._drop_grad_handles(kind)
-            prefix, lead = _GRAD_KINDS[kind]
-            g = C.c_void_p()
+        entry = cache.get(kind)
+        prefix, lead = _GRAD_KINDS[kind]
+        if entry is None:
+            g, ws = C.c_void_p(), None
             _lib.check(getattr(self._L, prefix + "_create")(self._h, *(lead + tuple(sizes) + (C.byref(g),))))
-            ws = torch.empty(getattr(self._L, prefix + "_workspace_bytes")(g) // 4, dtype=torch.float32, device=self.device)
+        else:
+            g, ws = entry[1:]
+            if entry[0] != sizes:
+                _lib.check(getattr(self._L, prefix + "_reshape")(g, *sizes))
+        cache[kind] = (sizes, g, ws)                     # (the cache says what the handle is at, also when the allocation below fails)
+        need = max(getattr(self._L, prefix + "_workspace_bytes")(g) // 4, getattr(self, "_grad_reserve", {}).get(kind, 0))
+        if ws is None or ws.numel() < need:
+            ws = torch.empty(need, dtype=torch.float32, device=self.device)
             cache[kind] = (sizes, g, ws)
-        return cache[kind][1:]
+        return g, ws
+
+    def reserve_gradients(self, batch, t_in, steps):
+        """sizes the three gradient workspaces once for the largest batch a feeder can produce -- (batch, t_in) tokens, steps decoder steps
+        = steps * r target frames: no later pass of at most these sizes allocates (a workspace's size grows with each of its sizes).
+        The reservation outlives the handles."""
+        hp = self._hparams
+        reserve = self.__dict__.setdefault("_grad_reserve", {})
+        batch, t_in, steps = int(batch), int(t_in), int(steps)
+        with torch.cuda.device(self.device):
+            for kind, sizes in (("decoder", (batch, t_in, steps)), ("encoder", (batch, t_in)), ("post", (batch, steps * hp.reduction_factor))):
+                _, ws = self._grad_handle(kind, sizes)
+                reserve[kind] = max(reserve.get(kind, 0), ws.numel())
 
     def _drop_grad_handles(self, kind=None):
         cache = getattr(self, "_grad_cache", {})
@@ -492,6 +515,12 @@ class Tacotron(object):
     def _grad_route(self, kind):
         entry = getattr(self, "_grad_cache", {}).get(kind)
         return getattr(self._L, _GRAD_KINDS[kind][0] + "_route")(entry[1]).decode() if entry else ""
+
+    def _device_i32(self, value):
+        """array or tensor -> contiguous int32 tensor on the device (a device tensor of that kind is returned as it is)"""
+        if torch.is_tensor(value):
+            return value.to(device=self.device, dtype=torch.int32).contiguous()
+        return torch.as_tensor(np.asarray(value, np.int32), device=self.device).contiguous()
 
     def _device_f32(self, value, shape, message):
         """array or tensor -> contiguous float32 tensor on the device; ValueError(message % (shape, its shape)) when a shape is given and is not its shape"""
@@ -510,6 +539,11 @@ class Tacotron(object):
 
     def _loss_coeff(self, loss_coeff, N):
         """add_loss's per-utterance factors on the device (ones when None)"""
+        if torch.is_tensor(loss_coeff):
+            co = loss_coeff.to(device=self.device, dtype=torch.float32).reshape(-1).contiguous()
+            if tuple(co.shape) != (N,):
+                raise ValueError("loss_coeff must hold one factor per utterance (%d), got shape %s" % (N, tuple(co.shape)))
+            return co
         co = np.ones(N, np.float32) if loss_coeff is None else np.asarray(loss_coeff, np.float32).reshape(-1)
         if co.shape != (N,):
             raise ValueError("loss_coeff must hold one factor per utterance (%d), got shape %s" % (N, co.shape))

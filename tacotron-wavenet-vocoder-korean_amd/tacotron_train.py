@@ -21,8 +21,12 @@ the speaker side's values -> the recording forwards of the encoder, the decoder 
 -> the three backwards -> the speaker side -> clip -> Adam -> the moving update -> the new inference blob.  The seed is a constructor
 argument and is not stored in a checkpoint: restore into a trainer made with the same seed to continue the same mask sequence.
 
-A data feeder, a `train_tacotron` command line and the gradient all-reduce are not built.
-PyTorch is used for device memory and streams only."""
+With an initialised torch.distributed process group (or a reduction callable of the caller's) the step is data-parallel: ONE
+all-reduce per step over one flat buffer -- the unclipped gradient, a failure flag and, in training mode, both CBHGs' batch statistics --
+summed and divided by the world size before the clip; `step(..., failed=True)` and `peer_failure()` are WaveNetTrainer's protocol.
+`init_weights(seed)` draws the reference's initial values on the host.  The data feeder and the staging of its batches are
+tacotron_feed.py, the command line is train_tacotron.py.
+PyTorch is used for device memory, streams and the collective only."""
 import os
 
 import numpy as np
@@ -31,6 +35,7 @@ import torch
 from . import _lib
 from . import checkpoint as ckpt
 from .tacotron import BN_MOMENTUM, _ptr, _stream, flatten_variables, training_layout
+from .train import allreduce_sum_
 
 DROPOUT_RATE = 0.5       # modules.py:15-23 prenet: tf.layers.dropout(rate=0.5, training=is_training)
 CLIP_NORM = 1.0          # tacotron.py:306 tf.clip_by_global_norm(gradients, 1.0)
@@ -50,6 +55,90 @@ def learning_rate(lr0, step, mode=0, randomly_initialized=True):
     raise ValueError("decay_learning_rate_mode must be 0 or 1, got %r" % (mode,))
 
 
+TRUNCATED_VARIANCE = 0.7737413      # the variance of a unit normal cut at two standard deviations: 1 - 4 pdf(2) / (2 cdf(2) - 1)
+
+
+def _truncated_normal(rng, shape, stddev):
+    """tf.truncated_normal_initializer(stddev): normal draws further than two standard deviations from 0 are drawn again"""
+    a = rng.standard_normal(int(np.prod(shape)))
+    while True:
+        far = np.abs(a) > 2.0
+        if not far.any():
+            return (a * stddev).reshape(shape).astype(np.float32)
+        a[far] = rng.standard_normal(int(far.sum()))
+
+
+def glorot_limit(shape):
+    """tf.glorot_uniform_initializer's bound sqrt(6 / (fan_in + fan_out)): a dense kernel (in, out) has fans in and out, a conv1d kernel
+    (taps, in, out) taps * in and taps * out, a vector (n) n and n ([RECALLED-TF] init_ops._compute_fans)"""
+    shape = tuple(int(v) for v in shape)
+    if len(shape) == 1:
+        fan_in = fan_out = shape[0]
+    else:
+        taps = int(np.prod(shape[:-2]))
+        fan_in, fan_out = taps * shape[-2], taps * shape[-1]
+    return float(np.sqrt(6.0 / (fan_in + fan_out)))
+
+
+# speaker_embedding_size == 1 (tacotron.py:69-75): the five speaker-dependent vectors are tables made by modules.py:10-12 get_embed
+_SPEAKER_TABLES = ("before_highway", "encoder_rnn_init_state", "attention_rnn_init_state", "decoder_rnn_init_states")
+
+
+def initializer_of(name, shape):
+    """(kind, parameter) of a checkpoint tensor's initial value, the reference's tf.global_variables_initializer() by distribution:
+      "truncated_normal", stddev   embedding and speaker_embedding 0.5 (tacotron.py:51, :65), the tables of speaker_embedding_size 1 0.1
+                                   (modules.py:11)
+      "glorot_uniform", limit      every dense, conv1d and GRU kernel, attention_v and loc_sen's attention_variable: tf.layers' and
+                                   tf.get_variable's default ([RECALLED-TF]; rnn_wrappers.py:719-721 asks for xavier by name)
+      "constant", value            GRU gate biases 1 and candidate biases 0 ([RECALLED-TF] GRUCell's bias_initializer None), highway T biases
+                                   -1 (modules.py:88), attention_g sqrt(1 / units) ([RECALLED-TF] _bahdanau_score; Luong's scale 1), attention_b 0,
+                                   attention_score_bias score_bias_init = 0 ([RECALLED-TF] BahdanauMonotonicAttention's default; tacotron.py:128-130
+                                   does not pass one), every other bias 0
+      "batch_normalization", None  gamma 1, beta 0, moving mean 0, moving variance 1 ([RECALLED-TF] tf.layers.batch_normalization)
+    alignments_bias (rnn_wrappers.py:566, zeros) belongs to 'bah_mon_norm_hccho', which is not built and has no tensor here."""
+    base = name.rsplit("/", 1)[-1]
+    if name.endswith("batch_normalization"):
+        return "batch_normalization", None
+    if name in ("embedding", "speaker_embedding"):
+        return "truncated_normal", 0.5
+    if "/" not in name and name.startswith(_SPEAKER_TABLES):
+        return "truncated_normal", 0.1
+    if base == "attention_g":
+        return "constant", (1.0 if "luong" in name else None)         # (None: sqrt(1 / units), filled in by initial_tensors)
+    if base in ("attention_b", "attention_score_bias", "attention_bias"):
+        return "constant", 0.0
+    if base in ("attention_v", "attention_variable", "kernel"):
+        return "glorot_uniform", glorot_limit(shape)
+    if base == "bias":
+        if name.endswith("gates/bias"):
+            return "constant", 1.0
+        if "/highway_" in name and name.endswith("/T/bias"):
+            return "constant", -1.0
+        return "constant", 0.0
+    raise KeyError("no initializer is known for %s" % name)
+
+
+def initial_tensors(specs, hp, seed=0):
+    """{name: float32 array} for every tensor of `specs`, drawn on the host from RandomState(seed) in the order of the specs: the same
+    seed gives the same bits on every rank.  By distribution, not by TensorFlow's random stream (initializer_of)."""
+    rng = np.random.RandomState(seed)
+    out = {}
+    for name, shape in specs:
+        kind, value = initializer_of(name, shape)
+        if kind == "batch_normalization":
+            C_ = shape[1]
+            out[name] = np.stack([np.ones(C_), np.zeros(C_), np.zeros(C_), np.ones(C_)]).astype(np.float32)
+        elif kind == "truncated_normal":
+            out[name] = _truncated_normal(rng, shape, value)
+        elif kind == "glorot_uniform":
+            out[name] = rng.uniform(-value, value, shape).astype(np.float32)
+        else:
+            if value is None:
+                value = np.sqrt(1.0 / hp.attention_size)
+            out[name] = np.full(shape, value, np.float32)
+    return out
+
+
 def _copy_runs(specs, picks):
     """[(first float, one past the last)] of the maximal runs of blob floats whose tensor satisfies pick(i, name)"""
     runs, off = [], 0
@@ -65,12 +154,15 @@ def _copy_runs(specs, picks):
 
 
 class TacotronTrainer(object):
-    def __init__(self, model, randomly_initialized=True, training=False, seed=0):
+    def __init__(self, model, randomly_initialized=True, training=False, seed=0, group=None, allreduce=None):
         """model: a Tacotron, with weights loaded or to be given its weights by `restore`; the trainer updates the model's blob in place, so
         `infer` and `forward_targets` see the new weights after every step.  randomly_initialized: tacotron.py:296-299, the warm-up of
         learning-rate mode 0.  training: False = the evaluation graph (frozen batch norm, no dropout), True = the reference's
-        is_training=True graph; seed: of the dropout masks (not stored by `save`)."""
+        is_training=True graph; seed: of the dropout masks (not stored by `save`).  group: the torch.distributed group of a data-parallel
+        run (None: the default group, when one is initialised); allreduce: the reduction, `allreduce(flat, group) -> world size` summing
+        `flat` in place over the ranks -- train.allreduce_sum_ by default, which without a process group does nothing and returns 1."""
         hp = model._hparams
+        self.group, self._allreduce = group, (allreduce_sum_ if allreduce is None else allreduce)
         self.model, self.device, self._L = model, model.device, model._L
         self.randomly_initialized = bool(randomly_initialized)
         self.training, self.seed = bool(training), int(seed)
@@ -119,7 +211,14 @@ class TacotronTrainer(object):
             self.m = torch.zeros_like(self.vars) if m is None else torch.from_numpy(m).to(self.device)
             self.v = torch.zeros_like(self.vars) if v is None else torch.from_numpy(v).to(self.device)
             self._shadow = self.vars.clone()                # twv_adam_ema_step's shadow: written, never read
-            self.grads = torch.zeros_like(self.vars)
+            # the step's reduction buffer: the gradient, then ONE word for the failure flag, then (from the next multiple of four floats) both
+            # CBHGs' batch statistics, encoder first -- one all-reduce carries all three
+            self._stat_floats = [sum(2 * shp[1] for n, shp in self.model.specs if n.startswith(scope) and n.endswith("batch_normalization"))
+                                 for scope in ("encoder_cbhg/", "post_cbhg/")]
+            self._stats_at = (self.n_variables + 1 + 3) // 4 * 4
+            self._gbuf = torch.zeros(self._stats_at + sum(self._stat_floats), dtype=torch.float32, device=self.device)
+            self.grads = self._gbuf[:self.n_variables]
+            self._flag = self._gbuf[self.n_variables:self.n_variables + 1]
             self._gblob = torch.zeros_like(self.model._blob)
             self._clip_scratch = torch.empty(self.n_variables + 2048, dtype=torch.float32, device=self.device)
 
@@ -256,12 +355,58 @@ class TacotronTrainer(object):
             m._bn_raw[n] = host[at:at + size].reshape(shp).copy()
             at += size
 
-    def step(self, inputs, input_lengths, speaker_id, mel_targets, linear_targets, loss_coeff=None):
+    def step(self, inputs, input_lengths, speaker_id, mel_targets, linear_targets, loss_coeff=None, failed=False):
         """one sess.run([model.loss, model.optimize]) on the evaluation graph (training=False) or the training graph (training=True); returns add_loss's dict (the loss BEFORE the update) and
-        advances global_step.  `last_learning_rate` is the rate the update used."""
-        out = self.loss_and_gradients(inputs, input_lengths, speaker_id, mel_targets, linear_targets, loss_coeff)
-        self.last_learning_rate = self.apply_gradients()
+        advances global_step.  `last_learning_rate` is the rate the update used.
+
+        Data-parallel (a process group, or the constructor's `allreduce`): the unclipped gradient, the failure flag and, in training
+        mode, both CBHGs' batch statistics are summed over the ranks in ONE all-reduce and divided by the world size before the clip.
+        Each rank has normalised its batch norms with its own statistics, as a tower would; the moving averages move by the ranks' MEAN
+        statistics, so the variables stay identical on every rank (the reference has one GPU: this is an extension).
+        failed=True: this rank has no batch; it joins the collective with zeros and the flag set, applies nothing and returns None.  A
+        rank whose loss / gradient computation raises joins the same way before re-raising.  NO rank applies a step whose reduction
+        carries a failed rank: with more than one rank the flag is read (one host sync) before the clip, Adam and global_step move.
+        With one rank the reduction does nothing and nothing is divided: the step is the single-device step bit for bit."""
+        err, out = None, None
+        if not failed:
+            self._flag.zero_()
+            try:
+                out = self.loss_and_gradients(inputs, input_lengths, speaker_id, mel_targets, linear_targets, loss_coeff)
+                if self.training:
+                    at = self._stats_at
+                    for part in self._stats:
+                        self._gbuf[at:at + part.numel()].copy_(part)
+                        at += part.numel()
+            except Exception as e:                     # noqa: BLE001 -- re-raised below, after the peers have been released
+                err, failed = e, True
+        if failed:
+            self._gbuf.zero_()
+            self._flag.fill_(1.0)
+        world = self._allreduce(self._gbuf, self.group)
+        if err is not None:
+            raise err
+        if world > 1:
+            self._gbuf.div_(world)
+            if self.training and not failed:
+                a, b = self._stats_at, self._stats_at + self._stat_floats[0]
+                self._stats = (self._gbuf[a:b].clone(), self._gbuf[b:b + self._stat_floats[1]].clone())
+        if not failed and (world == 1 or not self.peer_failure()):
+            self.last_learning_rate = self.apply_gradients()
         return out
+
+    def peer_failure(self):
+        """True when some rank joined the last step's all-reduce with failed=True (host sync)"""
+        return bool(float(self._flag.item()) > 0.0)
+
+    # ---- tf.global_variables_initializer
+    def init_weights(self, seed=0):
+        """the reference's initial values (initial_tensors: by distribution, drawn on the host from `seed`, identical on every rank) into
+        the model and the trainer; the optimiser's moments and global_step start from zero.  Returns the tensors."""
+        tensors = initial_tensors(self.model.specs, self.model._hparams, seed)
+        self.model.load_weights(tensors)
+        self._set_variables(tensors)
+        self.global_step = 0
+        return tensors
 
     # ---- saver.save / restore
     def save(self, logdir, step=None, include_optimizer=True, max_to_keep=None):
