@@ -298,6 +298,11 @@ int twv_tacotron_workspace_view(const twv_tacotron* h, int batch, int t_in, cons
  * twv_tacotron_decoder_grad_route: a label of the kernels and sizes in use ("kernel=tg_bptt attention=... workgroups_per_utterance=1 ..."). */
 typedef struct twv_tacotron_decoder_grad twv_tacotron_decoder_grad;
 int twv_tacotron_decoder_grad_create(const twv_tacotron* h, int batch, int t_in, int steps, twv_tacotron_decoder_grad** out);
+/* The same with every attention type twv_tacotron_create accepts (bah_norm, bah, luong, luong_scaled, loc_sen beside the two monotonic
+ * types); model_type 'simple' and the size limits are refused as above.  Host only.  For the monotonic types the handle is the one
+ * twv_tacotron_decoder_grad_create makes (same workspace, label, kernels).  Every other twv_tacotron_decoder_grad_* call takes either kind
+ * of handle; twv_tacotron_decoder_grad_reshape validates as the call that made the handle did. */
+int twv_tacotron_decoder_grad_create_any(const twv_tacotron* h, int batch, int t_in, int steps, twv_tacotron_decoder_grad** out);
 void twv_tacotron_decoder_grad_destroy(twv_tacotron_decoder_grad* g);
 size_t twv_tacotron_decoder_grad_workspace_bytes(const twv_tacotron_decoder_grad* g);
 const char* twv_tacotron_decoder_grad_route(const twv_tacotron_decoder_grad* g);

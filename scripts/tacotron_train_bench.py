@@ -5,7 +5,10 @@ decoder steps (T_out = 1000 frames), the weights of scripts/tacotron_bench.py.  
 refold + re-pack), the whole step from the host, and -- the yardstick -- the PyTorch-ROCm float32 step of the same evaluation graph on the
 same device: forward, autograd backward, clip_grad_norm_(1.0) and torch.optim.Adam over the same trainable tensors.  Medians of --passes
 steps.  `--root DIR` (a checkout of the parent commit WITH its built library) adds `infer` of the two builds, processes alternating
-(scripts/tacotron_targets_bench.py's measurement).  Writes --out (default profiles/tacotron_train_step_bench.txt).  Needs the GPU."""
+(scripts/tacotron_targets_bench.py's measurement).  Writes --out (default profiles/tacotron_train_step_bench.txt).  Needs the GPU.
+`--attention_type a,b,...` runs the step at each of these hparams.attention_type values (TacotronTrainer(attention_gradients="any") for
+all but the monotonic ones; the PyTorch yardstick restates bah_mon_norm only and runs there alone).  `--json` prints, instead, one line
+{"label", "<type> b<N> step_ms" ...}: the per-process record of an A/B of two builds."""
 import argparse, json, os, subprocess, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -164,19 +167,24 @@ def main():
     ap.add_argument("--batches", default="8,32")
     ap.add_argument("--root", default=None, help="a checkout of the parent commit with its built library: adds the infer A/B")
     ap.add_argument("--ab-rounds", type=int, default=3)
+    ap.add_argument("--attention_type", default="bah_mon_norm")
+    ap.add_argument("--json", action="store_true")
+    ap.add_argument("--label", default="")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "a measurement needs the GPU"
     hp = twvk_amd.default_hparams()
     L = _lib.lib()
+    record = {"label": args.label, "library": L.twv_version().decode()}
     lines = ["One Tacotron training step on the evaluation graph (TacotronTrainer.step: frozen moving statistics, no dropout), default geometry:",
              "101 tokens, 200 decoder steps (T_out 1000), every length 101, two speakers, speaker_embedding_size %d" % hp.speaker_embedding_size,
              "(scripts/tacotron_train_bench.py; medians of %d steps, the PyTorch step of %d)" % (args.passes, args.torch_passes),
              "library %s on %s, torch %s" % (L.twv_version().decode(), torch.cuda.get_device_name(0), torch.__version__), ""]
-    for N in [int(b) for b in args.batches.split(",")]:
+    for at, N in [(at, int(b)) for at in args.attention_type.split(",") for b in args.batches.split(",")]:
+        hp.attention_type = at
         m = Tacotron(hp, num_speakers=2)
         tensors = random_tensors(m.specs)
         m.load_weights(tensors)
-        tr = TimedTrainer(m)
+        tr = TimedTrainer(m) if at in ("bah_mon_norm", "bah_mon") else TimedTrainer(m, attention_gradients="any")
         rng = np.random.RandomState(1)
         tok = rng.randint(2, 80, (N, T)).astype(np.int32); tok[:, -1] = 1
         ln = np.full(N, T, np.int32); spk = (np.arange(N) % 2).astype(np.int32)
@@ -191,41 +199,48 @@ def main():
             phases.append(tr.phases())
         ph = np.median(np.asarray(phases[1:]), axis=0)
         wall = float(np.median(walls[1:]))
+        record["%s b%d step_ms" % (at, N)] = float(ph.sum())
+        record["%s b%d gradient_passes_ms" % (at, N)] = float(ph[1])
+        if args.json:
+            del tr, m
+            continue
         # the speaker side alone, its four launches between two events
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         z = [torch.zeros(N, n, device="cuda") for n in (hp.enc_prenet_sizes[1], 2 * hp.enc_rnn_size, hp.attention_state_size + hp.dec_layer_num * hp.dec_rnn_size)]
         spk_us = []
         for i in range(12):
             e0.record(); m._speaker_grad_blob(z[0], z[1], z[2], grad=tr._gblob); e1.record(); torch.cuda.synchronize(); spk_us.append(e0.elapsed_time(e1) * 1e3)
-        # the yardstick: the same graph, float32 autograd, clip and Adam of PyTorch
-        names = [n for n, _ in m.specs]
-        w = {n: torch.from_numpy(np.asarray(tensors[n], np.float32)).cuda() for n in names}
-        train = []
-        for n in names:
-            if n.endswith("batch_normalization"):       # gamma and beta trainable, the moving statistics not
-                gb = w[n][:2].clone().requires_grad_(); train.append(gb); w[n] = torch.cat([gb, w[n][2:]], 0)
-            else:
-                w[n].requires_grad_(); train.append(w[n])
-        opt = torch.optim.Adam(train, lr=tr.learning_rate(1), betas=(hp.adam_beta1, hp.adam_beta2), eps=1e-8)
-        tokd, lnd, spkd = (torch.from_numpy(a.astype(np.int64)).cuda() for a in (tok, ln, spk))
-        first = {}
-
-        def torch_step():
-            ww = dict(w)
+        yard = at == "bah_mon_norm" and args.torch_passes > 0
+        auto, first = None, {}
+        if yard:
+            # the yardstick: the same graph, float32 autograd, clip and Adam of PyTorch
+            names = [n for n, _ in m.specs]
+            w = {n: torch.from_numpy(np.asarray(tensors[n], np.float32)).cuda() for n in names}
+            train = []
             for n in names:
-                if n.endswith("batch_normalization"):
-                    ww[n] = torch.cat([train[names.index(n)], w[n][2:].detach()], 0)
-            opt.zero_grad(set_to_none=True)
-            loss = torch_loss(ww, hp, names, tokd, lnd, spkd, tg, lt)
-            loss.backward()
-            torch.nn.utils.clip_grad_norm_(train, 1.0)
-            opt.step()
-            first.setdefault("loss", float(loss))
-        ts = []
-        for i in range(args.torch_passes + 1):
-            torch.cuda.synchronize(); t0 = time.perf_counter(); torch_step(); torch.cuda.synchronize(); ts.append((time.perf_counter() - t0) * 1e3)
-        auto = float(np.median(ts[1:]))
-        lines += ["B = %d   (decoder gradient: %s)" % (N, m.decoder_grad_route()),
+                if n.endswith("batch_normalization"):       # gamma and beta trainable, the moving statistics not
+                    gb = w[n][:2].clone().requires_grad_(); train.append(gb); w[n] = torch.cat([gb, w[n][2:]], 0)
+                else:
+                    w[n].requires_grad_(); train.append(w[n])
+            opt = torch.optim.Adam(train, lr=tr.learning_rate(1), betas=(hp.adam_beta1, hp.adam_beta2), eps=1e-8)
+            tokd, lnd, spkd = (torch.from_numpy(a.astype(np.int64)).cuda() for a in (tok, ln, spk))
+
+            def torch_step():
+                ww = dict(w)
+                for n in names:
+                    if n.endswith("batch_normalization"):
+                        ww[n] = torch.cat([train[names.index(n)], w[n][2:].detach()], 0)
+                opt.zero_grad(set_to_none=True)
+                loss = torch_loss(ww, hp, names, tokd, lnd, spkd, tg, lt)
+                loss.backward()
+                torch.nn.utils.clip_grad_norm_(train, 1.0)
+                opt.step()
+                first.setdefault("loss", float(loss))
+            ts = []
+            for i in range(args.torch_passes + 1):
+                torch.cuda.synchronize(); t0 = time.perf_counter(); torch_step(); torch.cuda.synchronize(); ts.append((time.perf_counter() - t0) * 1e3)
+            auto = float(np.median(ts[1:]))
+        lines += ["attention_type %s, B = %d   (decoder gradient: %s)" % (at, N, m.decoder_grad_route()),
                   "    forward_targets(teacher_forced) + add_loss            %9.3f ms" % ph[0],
                   "    three gradient passes (post net, decoder, encoder)    %9.3f ms" % ph[1],
                   "    speaker side (twv_tacotron_speaker_grad)              %9.3f ms   (alone, four launches between two events: median %.1f us, min %.1f us)"
@@ -233,9 +248,12 @@ def main():
                   "    gradient conversion + clip + Adam + refold + re-pack  %9.3f ms" % ph[3],
                   "    sum of the phases                                     %9.3f ms   (the step from the host, with its allocations: %.3f ms)" % (float(ph.sum()), wall),
                   "    loss over the timed steps: %s" % " ".join("%.5f" % v for v in losses),
-                  "    PyTorch-ROCm float32: forward + autograd + clip_grad_norm_ + optim.Adam of the same graph: %.3f ms  ->  %.2f x the step (first loss %.5f)"
-                  % (auto, auto / wall, first["loss"]), ""]
+                  ] + (["    PyTorch-ROCm float32: forward + autograd + clip_grad_norm_ + optim.Adam of the same graph: %.3f ms  ->  %.2f x the step (first loss %.5f)"
+                        % (auto, auto / wall, first["loss"])] if yard else []) + [""]
         del tr, m
+    if args.json:
+        print(json.dumps(record))
+        return
     if args.root:
         infer_ab(os.path.abspath(args.root), args.ab_rounds, lines)
     text = "\n".join(lines)

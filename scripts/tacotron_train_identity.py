@@ -1,7 +1,9 @@
 #!/usr/bin/env python
 """Bit identity of what existed before the training step, one build against another: `infer`, `forward_targets` (free-running and
-teacher-forced) and `loss_gradients` on every case of tests/tacotron_cbhg_grad_cases.py, and one `TacotronTrainer.step` with the
-constructor's defaults on the whole-model cases of tests/tacotron_train_cases.py (the losses and every variable after the update).
+teacher-forced) and `loss_gradients` on every case of tests/tacotron_cbhg_grad_cases.py, `decoder_grad` on every case of
+tests/tacotron_grad_cases.py (bah_mon_norm and bah_mon), and one `TacotronTrainer.step` with the
+constructor's defaults, and one in the training graph, on the whole-model cases of tests/tacotron_train_cases.py (the losses and every
+variable after the update).
 
     python scripts/tacotron_train_identity.py --root PARENT_CHECKOUT --dump parent.json      # a checkout WITH its built library
     python scripts/tacotron_train_identity.py --dump new.json
@@ -37,19 +39,29 @@ def dump(root, path):
             out["entries"]["%s %s" % (label, name)] = {k: digest(t) for k, t in zip(("mel", "linear", "alignments"), run())}
         if h.forced:        # (the last pass above is the teacher-forced one)
             out["entries"]["loss_gradients %s" % name] = {k: digest(t) for k, t in sorted(m.loss_gradients(h.lin_tgt, h.coeff).items())}
-    # one TacotronTrainer step with the constructor's defaults (the evaluation graph) on the whole-model cases of tests/tacotron_train_cases.py:
+    # decoder_grad alone on every case of tests/tacotron_grad_cases.py (both monotonic types: G-bah_mon is the other one; masks where the
+    # case has them): every decoder-side gradient, d_memory, d_init and the recorded mel
+    import tacotron_grad_cases as GC
+    for name in sorted(GC.CASES):
+        c = GC.HostCase(name)
+        m = Tacotron(c.hp, num_speakers=2)
+        m.load_weights(c.w)
+        m.forward_targets(c.tok, c.ln, c.spk, c.tgt, teacher_forced=True)
+        out["entries"]["decoder_grad %s (%s)" % (name, c.at)] = {k: digest(t) for k, t in sorted(m.decoder_grad(c.d_mel, c.masks).items())}
+    # one TacotronTrainer step with the constructor's defaults (the evaluation graph) and one with training=True on the whole-model cases of tests/tacotron_train_cases.py:
     # the losses and every variable after the update
     from tacotron_train_cases import WHOLE, whole_case
     from twvk_amd.tacotron_train import TacotronTrainer
     for name in sorted(WHOLE):
         h = whole_case(name)
-        m = Tacotron(h.hp, num_speakers=h.speakers)
-        m.load_weights(h.w)
-        t = TacotronTrainer(m)
-        losses = t.step(h.tok, h.ln, h.spk, h.tgt, h.lin_tgt, h.coeff)
-        entry = {k: digest(torch_of(v)) for k, v in sorted(t.variables().items())}
-        entry["losses"] = (4, hashlib.sha256(repr(sorted(losses.items())).encode()).hexdigest())
-        out["entries"]["TacotronTrainer.step %s" % name] = entry
+        for label, kw in (("TacotronTrainer.step", {}), ("TacotronTrainer(training=True, seed=7).step", dict(training=True, seed=7))):
+            m = Tacotron(h.hp, num_speakers=h.speakers)
+            m.load_weights(h.w)
+            t = TacotronTrainer(m, **kw)
+            losses = t.step(h.tok, h.ln, h.spk, h.tgt, h.lin_tgt, h.coeff)
+            entry = {k: digest(torch_of(v)) for k, v in sorted(t.variables().items())}
+            entry["losses"] = (4, hashlib.sha256(repr(sorted(losses.items())).encode()).hexdigest())
+            out["entries"]["%s %s" % (label, name)] = entry
     with open(path, "w") as fh:
         json.dump(out, fh)
     print("wrote", path, len(out["entries"]), "entries,", out["library"])
@@ -57,8 +69,8 @@ def dump(root, path):
 
 def compare(a_path, b_path, out_path):
     a, b = json.load(open(a_path)), json.load(open(b_path))
-    lines = ["Bit identity of `infer`, `forward_targets`, `loss_gradients` and one `TacotronTrainer.step`, parent build against this tree: every case of",
-             "tests/tacotron_cbhg_grad_cases.py CASES and tests/tacotron_train_cases.py WHOLE (scripts/tacotron_train_identity.py).  Two processes on one MI355X, each the Python package and the",
+    lines = ["Bit identity of `infer`, `forward_targets`, `loss_gradients`, `decoder_grad` and `TacotronTrainer.step` in both graphs, parent build against this tree: every case of",
+             "tests/tacotron_cbhg_grad_cases.py CASES, tests/tacotron_grad_cases.py CASES and tests/tacotron_train_cases.py WHOLE (scripts/tacotron_train_identity.py).  Two processes on one MI355X, each the Python package and the",
              "library of one commit; every output tensor's bytes compared by SHA-256.  The condition: 0 differing tensors everywhere.",
              "parent: %s" % a["library"], "new:    %s" % b["library"], ""]
     tensors = elements = differing = 0

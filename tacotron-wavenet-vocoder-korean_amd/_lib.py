@@ -287,6 +287,7 @@ def lib():
     L.twv_tacotron_moving_update.argtypes = [vp, fp, fp, fp, C.c_double, vp]
     L.twv_dropout_mask.argtypes = [fp, C.c_int64, C.c_uint64, C.c_int64, C.c_int, C.c_double, vp]
     L.twv_tacotron_decoder_grad_reshape.argtypes = [vp, C.c_int, C.c_int, C.c_int]
+    L.twv_tacotron_decoder_grad_create_any.argtypes = L.twv_tacotron_decoder_grad_create.argtypes
     L.twv_tacotron_cbhg_grad_reshape.argtypes = [vp, C.c_int, C.c_int]
     L.twv_tacotron_batch_stage.argtypes = [vp, vp] + [C.c_longlong] * 7 + [C.c_int] * 5 + [ip, ip, fp, fp, fp, ip, vp]
     L.twv_tacotron_set_profile_buffer.argtypes = [vp, vp]
@@ -347,7 +348,8 @@ EXPORTS = ["twv_last_error", "twv_version", "twv_wavenet_create", "twv_wavenet_d
            "twv_tacotron_encoder_grad_forward", "twv_tacotron_encoder_grad_backward", "twv_tacotron_postnet_grad_forward",
            "twv_tacotron_postnet_grad_backward", "twv_tacotron_cbhg_grad_set_mode", "twv_tacotron_cbhg_grad_batch_stats_floats",
            "twv_tacotron_cbhg_grad_batch_stats", "twv_tacotron_grad_convert_batch", "twv_tacotron_moving_update", "twv_dropout_mask",
-           "twv_tacotron_decoder_grad_reshape", "twv_tacotron_cbhg_grad_reshape", "twv_tacotron_batch_stage"]
+           "twv_tacotron_decoder_grad_reshape", "twv_tacotron_cbhg_grad_reshape", "twv_tacotron_batch_stage",
+           "twv_tacotron_decoder_grad_create_any"]
 
 
 class TacoDims(C.Structure):

@@ -2946,7 +2946,10 @@ void taco_decoder_blob(const twv_tacotron* h, TacoDecoderBlob& b)
     };
     const int at = h->d.attention_type;
     const bool bah = at == TWV_ATT_BAH_MON_NORM || at == TWV_ATT_BAH_MON || at == TWV_ATT_BAH_NORM || at == TWV_ATT_BAH, norm = at == TWV_ATT_BAH_MON_NORM || at == TWV_ATT_BAH_NORM;
-    b.Wm = src(h->Wm.off, true); b.Wq = src(h->Wq.off, bah); b.av = src(h->av.off, bah); b.ag = src(h->ag.off, norm); b.ab = src(h->ab.off, norm);
+    const bool loc = at == TWV_ATT_LOC_SEN;
+    b.Wm = src(h->Wm.off, true); b.Wq = src(h->Wq.off, bah || loc); b.av = src(h->av.off, bah || loc);
+    b.ag = src(h->ag.off, norm || at == TWV_ATT_LUONG_SCALED); b.ab = src(h->ab.off, norm || loc);
+    b.lcK = src(h->lcK.off, loc); b.lcb = src(h->lcb.off, loc); b.lcL = src(h->lcL.off, loc);
     b.asb = src(h->asb.off, at == TWV_ATT_BAH_MON_NORM || at == TWV_ATT_BAH_MON);
     b.dpW1 = src(h->dpW1.off, true); b.dpb1 = src(h->dpb1.off, true); b.dpW2 = src(h->dpW2.off, true); b.dpb2 = src(h->dpb2.off, true);
     b.aWg = src(h->aWgm.off, true); b.abg = src(h->abg.off, true); b.aWc = src(h->aWcm.off, true); b.abc = src(h->abc.off, true);

@@ -1,10 +1,12 @@
 // What twv_tacotron_grad.hip needs to know of a twv_tacotron handle (defined in twv_tacotron.hip): its dims and the offsets (floats) of the
 // decoder-side tensors in the CANONICAL blob (tacotron.py tacotron_specs order; every tensor row-major as in the checkpoint).  -1 = the
-// model has no such tensor (attention_g / attention_b of the un-normalised score, layers past dec_layer_num).
+// model has no such tensor (attention_g / attention_b of the un-normalised score, what another attention type owns, layers past
+// dec_layer_num).  loc_sen: av = attention_variable, ab = attention_bias; luong_scaled: ag alone.
 #pragma once
 #include "../../include/twv_amd.h"
 
-struct TacoDecoderBlob {
+// what the recurrent kernels carry by value in their arguments
+struct TacoDecoderBlobCore {
     long long Wm, Wq, av, ag, ab, asb;              // memory_layer/kernel, query_layer/kernel, attention_v / _g / _b / _score_bias
     long long dpW1, dpb1, dpW2, dpb2;               // decoder prenet
     long long aWg, abg, aWc, abc;                   // attention GRU: gates / candidate kernel (rows [x | h]) and bias
@@ -12,6 +14,11 @@ struct TacoDecoderBlob {
     long long rWg[4], rbg[4], rWc[4], rbc[4];       // residual GRUs
     long long oW, ob;                               // output projection
     long long blob_floats;
+};
+// with loc_sen's location features, which only its own small kernels read: location_features_convolution/kernel (31, 1, 32), /bias,
+// location_features_layer/kernel (32, A)
+struct TacoDecoderBlob : TacoDecoderBlobCore {
+    long long lcK, lcb, lcL;
 };
 
 // The same for one CBHG (twv_tacotron_cbhg_grad.hip): which = 0 the encoder's (with the embedding and the encoder prenet in front of it),

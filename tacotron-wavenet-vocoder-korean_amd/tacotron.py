@@ -299,6 +299,24 @@ class Tacotron(object):
         self._h = h
         self._packed = None
         self._ws = None
+        self._attention_gradients = "monotonic"
+
+    @property
+    def attention_gradients(self):
+        """which attention types the decoder gradient (decoder_grad, decoder_grad_forward / _backward, reserve_gradients, loss_gradients,
+        variable_gradients, the trainer's step) is made for: "monotonic" -- twv_tacotron_decoder_grad_create: bah_mon_norm and bah_mon,
+        every other type refused with TWV_E_UNSUPPORTED -- or "any" -- twv_tacotron_decoder_grad_create_any: every type the model can be
+        built with.  "monotonic" is the default only because existing tests pin that refusal.  Setting another value drops the cached
+        decoder handle."""
+        return self._attention_gradients
+
+    @attention_gradients.setter
+    def attention_gradients(self, value):
+        if value not in ("monotonic", "any"):
+            raise ValueError('attention_gradients must be "monotonic" or "any", got %r' % (value,))
+        if value != self._attention_gradients:
+            self._drop_grad_handles("decoder")
+            self._attention_gradients = value
 
     def set_option(self, name, value):
         """launch geometry (performance only, results are bit-identical): "decoder_groups" = workgroups per utterance in the decoder
@@ -483,7 +501,8 @@ class Tacotron(object):
         prefix, lead = _GRAD_KINDS[kind]
         if entry is None:
             g, ws = C.c_void_p(), None
-            _lib.check(getattr(self._L, prefix + "_create")(self._h, *(lead + tuple(sizes) + (C.byref(g),))))
+            create = "_create_any" if kind == "decoder" and self._attention_gradients == "any" else "_create"
+            _lib.check(getattr(self._L, prefix + create)(self._h, *(lead + tuple(sizes) + (C.byref(g),))))
         else:
             g, ws = entry[1:]
             if entry[0] != sizes:

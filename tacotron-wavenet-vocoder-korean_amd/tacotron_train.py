@@ -154,14 +154,19 @@ def _copy_runs(specs, picks):
 
 
 class TacotronTrainer(object):
-    def __init__(self, model, randomly_initialized=True, training=False, seed=0, group=None, allreduce=None):
+    def __init__(self, model, randomly_initialized=True, training=False, seed=0, group=None, allreduce=None, attention_gradients=None):
         """model: a Tacotron, with weights loaded or to be given its weights by `restore`; the trainer updates the model's blob in place, so
         `infer` and `forward_targets` see the new weights after every step.  randomly_initialized: tacotron.py:296-299, the warm-up of
         learning-rate mode 0.  training: False = the evaluation graph (frozen batch norm, no dropout), True = the reference's
         is_training=True graph; seed: of the dropout masks (not stored by `save`).  group: the torch.distributed group of a data-parallel
         run (None: the default group, when one is initialised); allreduce: the reduction, `allreduce(flat, group) -> world size` summing
-        `flat` in place over the ranks -- train.allreduce_sum_ by default, which without a process group does nothing and returns 1."""
+        `flat` in place over the ranks -- train.allreduce_sum_ by default, which without a process group does nothing and returns 1.
+        attention_gradients: None leaves the model's setting (Tacotron.attention_gradients, "monotonic" unless the caller changed it);
+        "monotonic" or "any" sets it on the model -- "any" trains every attention type the model can be built with, "monotonic" refuses
+        all but bah_mon_norm and bah_mon at the first step, and is the model's default only because existing tests pin that."""
         hp = model._hparams
+        if attention_gradients is not None:
+            model.attention_gradients = attention_gradients
         self.group, self._allreduce = group, (allreduce_sum_ if allreduce is None else allreduce)
         self.model, self.device, self._L = model, model.device, model._L
         self.randomly_initialized = bool(randomly_initialized)

@@ -168,7 +168,8 @@ def main(argv=None, hp=None, log=print):
     log(' [*] Loading training data from: %s' % data_dirs)
     device = "cuda:%d" % local_rank
     model = Tacotron(hp, num_speakers, device=device)
-    trainer = TacotronTrainer(model, randomly_initialized=config.initialize_path is None, training=config.training, seed=config.random_seed)
+    trainer = TacotronTrainer(model, randomly_initialized=config.initialize_path is None, training=config.training, seed=config.random_seed,
+                              attention_gradients="any")          # whatever hparams.attention_type the model was built with
     trainer.init_weights(config.random_seed)                        # tf.global_variables_initializer (identical on every rank)
     start_step = start_state(config, trainer, model_dir, log)
     train_feeder = DataFeederTacotron(data_dirs, hp, config.batch_size, BATCHES_PER_GROUP, "train", config.random_seed, config.skip_path_filter,
