@@ -285,6 +285,26 @@ int twv_tacotron_batch_stage(const void* packed, const twv_tacotron_feed_row* ta
                              int batch, int t_in, int t_out, int num_mels, int num_freq, int32_t* inputs, int32_t* input_lengths,
                              float* mel_targets, float* linear_targets, float* loss_coeff, int32_t* speaker_id, void* stream);
 
+/* ---- WaveNet crop staging: a batch's random crops cut from a corpus that lives on the device ----
+ * audio_pool (device, audio_floats float32) holds every example's samples, mel_pool (device, mel_floats float32) every example's mel rows
+ * (n_frames, num_mels) packed densely; row i of the table says where example i starts in each pool (offsets in floats), how many frames it
+ * has (its audio is n_frames * hop_size samples) and its speaker id.  picks is (batch, 2) int32: the example and the crop's first frame.
+ * The table and the picks are given twice, in host and in device memory: every check is made on the host copies before anything is
+ * launched, the kernel reads the device copies.  TWV_E_INVALID: a null argument, a size < 1 or above 2^20, an output above 2^38 words, an
+ * example outside [0, n_examples), start < 0 or start + frames > n_frames, a picked row whose audio or mel range leaves its pool, audio or
+ * local_condition not 16-byte aligned.  Out, every element written by ONE launch: audio (batch, frames * hop_size) =
+ * audio_pool[audio_offset + start * hop_size ...], local_condition (batch, frames, num_mels) = rows start .. start + frames of the
+ * example's mels, gc_ids (batch) = the rows' speaker ids -- what datafeeder_wavenet.py:150-156 cuts on the host, bit for bit.  Nothing
+ * outside the two ranges a picked row names is read.  No atomics. */
+typedef struct twv_wavenet_feed_row {
+    int64_t audio_offset, mel_offset;     /* in floats from the start of the pool */
+    int32_t n_frames, speaker_id;
+} twv_wavenet_feed_row;
+int twv_wavenet_crop_stage(const float* audio_pool, long long audio_floats, const float* mel_pool, long long mel_floats,
+                           const twv_wavenet_feed_row* table_host, const twv_wavenet_feed_row* table_dev, int n_examples,
+                           const int32_t* picks_host, const int32_t* picks_dev, int batch, int frames, int hop_size, int num_mels,
+                           float* audio, float* local_condition, int32_t* gc_ids, void* stream);
+
 /* ---- Tacotron decoder gradients: the vector-Jacobian product of the teacher-forced decoder ----
  * Host only: where a twv_tacotron_infer / twv_tacotron_forward_targets call of (batch, t_in) left the pieces the decoder reads from the
  * encoder side, as (offset, count) in floats from the start of its workspace.  which = "memory" (batch, t_in, 2 * enc_rnn_size; zero past

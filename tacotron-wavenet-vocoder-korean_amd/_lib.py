@@ -290,6 +290,7 @@ def lib():
     L.twv_tacotron_decoder_grad_create_any.argtypes = L.twv_tacotron_decoder_grad_create.argtypes
     L.twv_tacotron_cbhg_grad_reshape.argtypes = [vp, C.c_int, C.c_int]
     L.twv_tacotron_batch_stage.argtypes = [vp, vp] + [C.c_longlong] * 7 + [C.c_int] * 5 + [ip, ip, fp, fp, fp, ip, vp]
+    L.twv_wavenet_crop_stage.argtypes = [fp, C.c_longlong, fp, C.c_longlong, vp, vp, C.c_int, ip, ip] + [C.c_int] * 4 + [fp, fp, ip, vp]
     L.twv_tacotron_set_profile_buffer.argtypes = [vp, vp]
     L.twv_tacotron_set_option.argtypes = [vp, C.c_char_p, C.c_int]
     L.twv_tacotron_gemm_stats.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]
@@ -349,7 +350,7 @@ EXPORTS = ["twv_last_error", "twv_version", "twv_wavenet_create", "twv_wavenet_d
            "twv_tacotron_postnet_grad_backward", "twv_tacotron_cbhg_grad_set_mode", "twv_tacotron_cbhg_grad_batch_stats_floats",
            "twv_tacotron_cbhg_grad_batch_stats", "twv_tacotron_grad_convert_batch", "twv_tacotron_moving_update", "twv_dropout_mask",
            "twv_tacotron_decoder_grad_reshape", "twv_tacotron_cbhg_grad_reshape", "twv_tacotron_batch_stage",
-           "twv_tacotron_decoder_grad_create_any"]
+           "twv_tacotron_decoder_grad_create_any", "twv_wavenet_crop_stage"]
 
 
 class TacoDims(C.Structure):

@@ -8,7 +8,11 @@ The feeder is datafeeder_wavenet.py's batch rule without its thread and TF queue
 'audio' (T,) and 'mel' (T/hop, num_mels); every example is cut to `sample_size` (floored to a hop multiple) at a RANDOM FRAME
 offset, audio and mel in step (datafeeder_wavenet.py:153-156, which draws from the global np.random, not the feeder's rng).
 Those npz files are written from wav files by preprocess.py (`python -m twvk_amd.preprocess --in_dir ... --out_dir ...`); their text side
-is out of scope.  `--synthetic` trains on random data of the right shapes."""
+is out of scope.  `--synthetic` trains on random data of the right shapes.
+
+Where the batches are cut is chosen once per run (choose_feeder, the environment variable TWV_VOCODER_CORPUS = device | host | auto): by
+default the corpus is packed into device memory and a kernel cuts the crops (wavenet_feed.py); the batches are the same bits
+either way."""
 import argparse
 import os
 import time
@@ -115,6 +119,46 @@ class SyntheticFeeder(object):
                 (np.arange(B) % self.num_speakers).astype(np.int32))
 
 
+def free_device_bytes(device):
+    """free memory of `device` as the driver reports it now (what the `auto` route compares the packed corpus with)"""
+    import torch
+    return int(torch.cuda.mem_get_info(device)[0])
+
+
+def choose_feeder(data_dirs, hp, receptive_field, gc_enable, rank, world, device, log=print):
+    """The feeder of a run and its route's name, chosen ONCE by the environment variable TWV_VOCODER_CORPUS:
+      device  the corpus packed and held on the device, crops cut by twv_wavenet_crop_stage (wavenet_feed.DeviceFeederWavenet); a pack
+              that fails, or pools that do not fit, raise
+      host    DataFeederWavenet as it is, no thread
+      auto    (default) `device` when the packed bytes are within TWV_VOCODER_CORPUS_GB (default 32) and within half of the device's free
+              memory as reported now -- call this after the trainer's workspace is allocated; otherwise, or when the pack raises, the
+              host feeder behind a one-batch prefetch thread ("host+prefetch"), with one log line that gives the reason.
+    Every route feeds the same bits in the same order, so the choice changes a run's speed and nothing else."""
+    from .wavenet_feed import CorpusIndex, DeviceFeederWavenet, PrefetchFeeder
+    mode = os.environ.get("TWV_VOCODER_CORPUS", "auto")
+    if mode not in ("device", "host", "auto"):
+        raise ValueError("TWV_VOCODER_CORPUS must be device, host or auto, not %r" % mode)
+
+    def host():
+        return DataFeederWavenet(data_dirs, hp.wavenet_batch_size, receptive_field, gc_enable=gc_enable, hp=hp, rank=rank, world=world)
+    if mode == "host":
+        return host(), "host"
+    limit = None
+    if mode == "auto":
+        limit = min(int(float(os.environ.get("TWV_VOCODER_CORPUS_GB", "32")) * 1e9), free_device_bytes(device) // 2)
+    try:
+        index = CorpusIndex(data_dirs, hp.wavenet_batch_size, receptive_field, gc_enable=gc_enable, hp=hp, rank=rank, world=world, max_bytes=limit)
+    except Exception as e:
+        if mode == "device":
+            raise
+        reader = host()                                             # (an empty directory raises here as it always did)
+        log("vocoder corpus stays on the host, one batch prefetched: {} ({} examples, limit {} bytes)".format(
+            e, sum(len(p) for p in reader.path_dict.values()), limit))
+        return PrefetchFeeder(reader), "host+prefetch"
+    log("vocoder corpus on the device: {} examples, {} bytes packed".format(index.n_examples, index.packed_bytes))
+    return DeviceFeederWavenet(index, device), "device"
+
+
 def get_default_logdir(logdir_root):
     return os.path.join(logdir_root, 'train', datetime.now().strftime('%Y-%m-%dT%H-%M-%S'))
 
@@ -199,11 +243,6 @@ def main(argv=None, log=print):
     num_speakers = len(config.data_dir)
     gc_enable = num_speakers > 1
     rf = WaveNetModel.calculate_receptive_field(hparams.filter_width, hparams.dilations, hparams.scalar_input, hparams.initial_filter_width)
-    if config.synthetic:
-        reader = SyntheticFeeder(hparams.wavenet_batch_size, max(num_speakers, 1), hparams, seed=rank)
-    else:
-        reader = DataFeederWavenet(config.data_dir, hparams.wavenet_batch_size, rf, gc_enable=gc_enable, hp=hparams, rank=rank, world=world)
-        np.random.seed(1234 + rank)                                 # ranks must not draw the same crop offsets
     net = WaveNetModel(batch_size=hparams.wavenet_batch_size, dilations=hparams.dilations, filter_width=hparams.filter_width,
                        residual_channels=hparams.residual_channels, dilation_channels=hparams.dilation_channels,
                        quantization_channels=hparams.quantization_channels, out_channels=hparams.out_channels,
@@ -212,6 +251,11 @@ def main(argv=None, log=print):
                        global_condition_cardinality=num_speakers, local_condition_channels=hparams.num_mels,
                        upsample_factor=hparams.upsample_factor, train_mode=True, device="cuda:%d" % local_rank)
     trainer = WaveNetTrainer(net, hparams)
+    if config.synthetic:
+        reader, route = SyntheticFeeder(hparams.wavenet_batch_size, max(num_speakers, 1), hparams, seed=rank), "synthetic"
+    else:                                                           # (after the trainer: `auto` asks what its workspace left free)
+        reader, route = choose_feeder(config.data_dir, hparams, rf, gc_enable, rank, world, net.device, log)
+        np.random.seed(1234 + rank)                                 # ranks must not draw the same crop offsets
     trainer.init_weights(seed=0)                                    # tf.global_variables_initializer (identical on every rank)
     start_step = None
     if ckpt.latest_checkpoint(restore_from) is not None:            # load(saver, sess, restore_from)
@@ -221,26 +265,30 @@ def main(argv=None, log=print):
         trainer.global_step = 0                                     # train_vocoder.py:141-145
     num_steps = config.num_steps if config.num_steps is not None else hparams.num_steps
     step, loss_value = trainer.global_step, float("nan")
-    while step < num_steps:
-        start_time = time.time()
-        failure = None
-        try:
-            audio, lc, gc = reader.next_batch()
-        except Exception as e:                                      # a rank that cannot feed must not leave the others in the all-reduce
-            failure = e
-        # the failure flag rides in the gradient all-reduce itself (WaveNetTrainer.step): a failing rank still joins the collective
-        loss = trainer.step(None, None, None, failed=True) if failure is not None else trainer.step(audio, lc, gc)
-        if failure is not None:
-            raise failure
-        step = trainer.global_step
-        loss_value = float(loss.item())
-        if dist is not None and trainer.peer_failure():             # read where the loss is read: the stream is drained already
-            raise RuntimeError("another rank's feeder failed at step %d" % step)
-        log('step {:d} - loss = {:.3f}, ({:.3f} sec/step)'.format(step, loss_value, time.time() - start_time))
-        if step % config.checkpoint_every == 0 and rank == 0:
-            log('Storing checkpoint to {} ...'.format(logdir))
-            trainer.save(logdir, step)
-    return {"logdir": logdir, "step": step, "loss": loss_value}
+    try:
+        while step < num_steps:
+            start_time = time.time()
+            failure = None
+            try:
+                audio, lc, gc = reader.next_batch()
+            except Exception as e:                                  # a rank that cannot feed must not leave the others in the all-reduce
+                failure = e
+            # the failure flag rides in the gradient all-reduce itself (WaveNetTrainer.step): a failing rank still joins the collective
+            loss = trainer.step(None, None, None, failed=True) if failure is not None else trainer.step(audio, lc, gc)
+            if failure is not None:
+                raise failure
+            step = trainer.global_step
+            loss_value = float(loss.item())
+            if dist is not None and trainer.peer_failure():         # read where the loss is read: the stream is drained already
+                raise RuntimeError("another rank's feeder failed at step %d" % step)
+            log('step {:d} - loss = {:.3f}, ({:.3f} sec/step)'.format(step, loss_value, time.time() - start_time))
+            if step % config.checkpoint_every == 0 and rank == 0:
+                log('Storing checkpoint to {} ...'.format(logdir))
+                trainer.save(logdir, step)
+    finally:
+        if hasattr(reader, "close"):
+            reader.close()                                          # (the prefetch thread of the host+prefetch route)
+    return {"logdir": logdir, "step": step, "loss": loss_value, "feeder": route}
 
 
 if __name__ == '__main__':
