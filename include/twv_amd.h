@@ -217,7 +217,8 @@ typedef struct {
     int32_t attention_type; /* hparams.attention_type (tacotron.py:127-144), TWV_ATT_*: 0 = 'bah_mon_norm' (hparams.py:145, the default).  The
                              * others run on the split decoder kernel only (decoder_groups 0, 1, 2, 4, 8, 16); 'luong' / 'luong_scaled'
                              * need attention_state_size == attention_size.  Appended last: callers of the older layout that zero the
-                             * struct get the default. */
+                             * struct get the default.  A pass with caller-supplied alignments (twv_tacotron_infer_manual) runs none of the
+                             * mechanisms: every type is served there at decoder_groups -1, 0, 1, 2, 4, 8 and 16. */
 } twv_tacotron_dims;
 enum { TWV_ATT_BAH_MON_NORM = 0, TWV_ATT_BAH_MON = 1, TWV_ATT_BAH_NORM = 2, TWV_ATT_BAH = 3, TWV_ATT_LUONG = 4, TWV_ATT_LUONG_SCALED = 5,
        TWV_ATT_LOC_SEN = 6 };
@@ -256,6 +257,38 @@ int twv_tacotron_forward_targets(const twv_tacotron* h, const void* packed, cons
                                  const int32_t* speaker_ids, int batch, int t_in, const float* mel_targets, int t_out,
                                  int teacher_forced, void* workspace, float* mel, float* linear, float* alignments,
                                  int32_t* status, void* stream);
+/* A pass with caller-supplied alignments: the inference graph's is_manual_attention / manual_alignments feeds (tacotron/tacotron.py:122-123),
+ * under which AttentionWrapper's _compute_attention replaces the mechanism's alignments by manual_alignments[:, time, :] at every decoder
+ * step (tacotron/rnn_wrappers.py:369-374); synthesizer.py:136-148 feeds saved alignments this way, :165-195 edited ones.
+ * manual_alignments: device float[batch][steps][t_in] (the reference's [N, D, E]), 1 <= steps <= max_iters.  At step `it` the alignments used
+ * for the context and carried as previous_alignments are manual_alignments[n][it][0 .. t_in) exactly as given: no mask past input_lengths,
+ * no normalisation, no clipping.  The decoder runs free (the zero go-frame, then its own last frame) for exactly `steps` steps; everything
+ * else is twv_tacotron_infer's pass, the post net and the linear projection on steps * r frames.  Outputs: mel (B, steps * r, num_mels),
+ * linear (B, steps * r, num_freq) or NULL, alignments (B, t_in, steps) or NULL = the manual values transposed, bit for bit.  The mechanism is
+ * not run and none of its tensors is read, whatever the attention_type (loc_sen's cumulative state included), so feeding a pass its own
+ * alignments gives that pass's bits.  The values must be finite; that is not checked.
+ * Kernels: tc_decoder_g_kernel (split) at decoder_groups 0, 1, 2, 4, 8, 16 with either decoder_local and decoder_split_all, tc_decoder_kernel
+ * at -1, for every attention type and model_type.  The XCD-local kernel takes no manual alignments: decoder_groups = 0 goes the split route
+ * here even where twv_tacotron_infer takes the resident kernel, and decoder_groups = 32 is TWV_E_UNSUPPORTED.  The workspace is
+ * twv_tacotron_workspace_bytes', the same buffer serves both kinds of pass.
+ * Refused before the device is looked at -- TWV_E_INVALID: a null handle, a null buffer other than linear / alignments, steps outside
+ * 1 .. max_iters, batch < 1, t_in outside 1 .. 1024, no speaker_ids on a multi-speaker model; TWV_E_UNSUPPORTED: decoder_groups = 32.
+ * TWV_E_UNSUPPORTED with the device's size known: the split kernel's geometry limits (LDS above 160 KiB, more than 512 workgroups).
+ * twv_tacotron_manual_kernel_name: the kernel such a call launches, static strings as twv_tacotron_decoder_kernel_name's ("" where refused). */
+int twv_tacotron_infer_manual(const twv_tacotron* h, const void* packed, const int32_t* tokens, const int32_t* lengths,
+                              const int32_t* speaker_ids, int batch, int t_in, const float* manual_alignments, int steps,
+                              void* workspace, float* mel, float* linear, float* alignments, int32_t* status, void* stream);
+const char* twv_tacotron_manual_kernel_name(const twv_tacotron* h, int batch, int t_in);
+/* The alignment edits of synthesizer.py:165-190 on the device, one launch: alignments (batch, t_in, steps) as a pass emits them ->
+ * manual_out (batch, steps, t_in) as twv_tacotron_infer_manual reads them.  With d* = the first argmax over the steps of
+ * alignments[n][e][:] for EVERY encoder row e, padded rows included (an all-zero row gives d* = 0):
+ *   mode 0  the transpose (what saved alignments, --base_alignment_path, need)
+ *   mode 1  synthesizer.py:167-173: zeros, then manual_out[n][d*][e] = 1
+ *   mode 2  :175-183: the transpose squared elementwise (no renormalisation)
+ *   mode 3  :185-190: the transpose, then manual_out[n][d*][e] = 1
+ * Every output element is written.  TWV_E_INVALID: a null pointer, a size < 1, batch above 65535, another mode. */
+int twv_tacotron_alignment_edit(const float* alignments, int batch, int t_in, int steps, int mode, float* manual_out, void* stream);
+
 /* Tacotron.add_loss (tacotron.py:258-282) on device buffers: out = device double[4] = loss, mel_loss, linear_loss, loss_without_coeff.
  * mel / mel_targets (B, t_out, num_mels), linear / linear_targets (B, t_out, num_freq), loss_coeff (B) float (required: pass ones where the
  * examples carry none, datafeeder_tacotron.py:263).  prioritize_loss != 0: the band [int(165 / (sample_rate * 0.5) * num_freq),

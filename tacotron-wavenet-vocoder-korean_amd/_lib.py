@@ -250,6 +250,9 @@ def lib():
     L.twv_tacotron_pack.argtypes = [vp, fp, vp, vp]
     L.twv_tacotron_infer.argtypes = [vp, vp, ip, ip, ip, C.c_int, C.c_int, vp, fp, fp, fp, ip, vp]
     L.twv_tacotron_forward_targets.argtypes = [vp, vp, ip, ip, ip, C.c_int, C.c_int, fp, C.c_int, C.c_int, vp, fp, fp, fp, ip, vp]
+    L.twv_tacotron_infer_manual.argtypes = [vp, vp, ip, ip, ip, C.c_int, C.c_int, fp, C.c_int, vp, fp, fp, fp, ip, vp]
+    L.twv_tacotron_manual_kernel_name.argtypes = [vp, C.c_int, C.c_int]; L.twv_tacotron_manual_kernel_name.restype = C.c_char_p
+    L.twv_tacotron_alignment_edit.argtypes = [fp, C.c_int, C.c_int, C.c_int, C.c_int, fp, vp]
     L.twv_tacotron_loss.argtypes = [fp, fp, fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, dp, vp]
     L.twv_tacotron_workspace_view.argtypes = [vp, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
     L.twv_tacotron_decoder_grad_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
@@ -350,7 +353,8 @@ EXPORTS = ["twv_last_error", "twv_version", "twv_wavenet_create", "twv_wavenet_d
            "twv_tacotron_postnet_grad_backward", "twv_tacotron_cbhg_grad_set_mode", "twv_tacotron_cbhg_grad_batch_stats_floats",
            "twv_tacotron_cbhg_grad_batch_stats", "twv_tacotron_grad_convert_batch", "twv_tacotron_moving_update", "twv_dropout_mask",
            "twv_tacotron_decoder_grad_reshape", "twv_tacotron_cbhg_grad_reshape", "twv_tacotron_batch_stage",
-           "twv_tacotron_decoder_grad_create_any", "twv_wavenet_crop_stage"]
+           "twv_tacotron_decoder_grad_create_any", "twv_wavenet_crop_stage", "twv_tacotron_infer_manual", "twv_tacotron_manual_kernel_name",
+           "twv_tacotron_alignment_edit"]
 
 
 class TacoDims(C.Structure):

@@ -841,9 +841,26 @@ struct DecArgs {
     long long packed_bytes;
     unsigned long long* prof;   // optional [iters][16] s_memtime stamps of workgroup 0 (tuning aid)
     int nbias;                  // total bias floats over the decoder stages
+    union {                     // (one slot: a pass is teacher-forced or fed alignments, never both -- the kernel arguments of the
+                                // existing instantiations keep their layout)
     const float* tgt;           // teacher forcing (helpers.py:86, the kernels' TF instantiations): [N][iters*R][M] ground-truth frames, step
                                 // it + 1 is fed row (it + 1) * R - 1; not read when the decoder runs free (helpers.py:84, TF = false)
+    const float* man;           // caller-supplied alignments (rnn_wrappers.py:369-374, the MAN / AK_MAN instantiations): [N][iters][T], step
+                                // it attends with row it exactly as given
+    };
 };
+// rnn_wrappers.py:374 `alignments = manual_alignments[:, time, :]`: the step's row replaces whatever the mechanism would compute -- into
+// lds[o_al .. o_al + Tp) (zero from T to Tp, as the mechanisms leave it) and, by one workgroup per utterance, into the emitted alignments.
+// No mask past the length, no normalisation: the values are the caller's.  All 512 threads call it; the caller's barrier follows.
+__device__ __forceinline__ void dec_manual_alignments(const DecArgs& a, int n, int it, int T, int Tp, int o_al, bool emit, int tid)
+{
+    const float* row = a.man + ((long long)n * a.iters + it) * T;
+    for (int t = tid; t < Tp; t += 512) {
+        const float al = t < T ? row[t] : 0.0f;
+        lds[o_al + t] = al;
+        if (emit && t < T && a.align) a.align[((long long)n * T + t) * a.iters + it] = al;      // tacotron.py:223
+    }
+}
 // the frame fed to step it + 1, element j of M: the target row when teacher-forced (TF), else the step's own last output frame `v`.  Read
 // straight from global memory by every workgroup that keeps the frame (targets are read-only: no exchange); the last step feeds nothing,
 // so it reads no target.  TF is a template parameter of the three decoder kernels: as a run-time test of a.tgt the feed cost the resident
@@ -952,7 +969,10 @@ __device__ __forceinline__ void dec_gru(rsrc_t rs, const float* P, long long oWg
     __syncthreads();
 }
 
-template <bool TF>
+// MAN: the step attends with the caller's alignments (dec_manual_alignments) and the mechanism -- query layer, score, recurrence -- is not
+// run; that instantiation also takes model_type 'simple' (SEc > 0: the speaker embedding inside the two concatenations, as in the split
+// kernel).  MAN = false is the kernel as it was.
+template <bool TF, bool MAN = false>
 __global__ void __launch_bounds__(512) tc_decoder_kernel(DecArgs a)
 {
     const int tid = threadIdx.x, lane = tid & 63;
@@ -960,6 +980,7 @@ __global__ void __launch_bounds__(512) tc_decoder_kernel(DecArgs a)
     const int n = blockIdx.x;
     const int T = a.T, M = a.M, R = a.R, A = a.A, AS = a.AS, ENC = a.ENC, DR = a.DR, D0 = a.D0, D1 = a.D1;
     const int len = a.lengths[n];
+    const int SEc = MAN ? a.SEc : 0, DE = D1 + SEc;
     const float* P = a.P;
     const rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.P), 0, (int)a.packed_bytes, 0x00020000);
     const float* keys = a.keys + (long long)n * T * A;
@@ -993,82 +1014,88 @@ __global__ void __launch_bounds__(512) tc_decoder_kernel(DecArgs a)
         __syncthreads();
         // ---- rnn_wrappers.py:310-312 cell_inputs = [prenet_out | attention]; attention GRU on state ha
         if (tid < D1) { const float v = dec_combine(o_part, D0, tid) + P[a.w.dp2b + tid]; lds[o_cat + tid] = v > 0.0f ? v : 0.0f; }
-        for (int i = tid; i < ENC; i += 512) lds[o_cat + D1 + i] = lds[o_ctx + i];
-        for (int i = tid; i < AS; i += 512) lds[o_cat + D1 + ENC + i] = lds[o_ha + i];
+        for (int i = tid; i < SEc; i += 512) lds[o_cat + D1 + i] = a.semb[(long long)n * SEc + i];      // rnn_wrappers.py:429-430
+        for (int i = tid; i < ENC; i += 512) lds[o_cat + DE + i] = lds[o_ctx + i];
+        for (int i = tid; i < AS; i += 512) lds[o_cat + DE + ENC + i] = lds[o_ha + i];
         __syncthreads();
         TWV_STAMP(1)
-        dec_gru(rs, P, a.w.aWg, a.w.abg, a.w.aWc, a.w.abc, D1 + ENC, AS, o_cat, o_ha, o_part, o_vec, tid, wave, lane);
+        dec_gru(rs, P, a.w.aWg, a.w.abg, a.w.aWc, a.w.abc, DE + ENC, AS, o_cat, o_ha, o_part, o_vec, tid, wave, lane);
         TWV_STAMP(2)
-        // ---- attention [RECALLED-TF BahdanauMonotonicAttention.__call__]: query layer
-        dec_gemv_partials(rs, (int)((a.w.Wq) * 4), AS, A, o_ha, o_part, wave, lane);
-        __syncthreads();
-        if (tid < A) lds[o_pq + tid] = dec_combine(o_part, AS, tid);
-        __syncthreads();
-        TWV_STAMP(3)
-        // score[t] = cdot_j normed_v[j] * tanh((keys[t][j] + pq[j]) + b[j]) + score_bias ; one (t, chunk) per thread
-        for (int task = tid; task < T * nAch; task += 512) {
-            const int t = task / nAch, ch = task - t * nAch;
-            float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-            const float* kr = keys + (long long)t * A + ch * 32;
+        if constexpr (MAN) {
+            dec_manual_alignments(a, n, it, T, Tp, o_al, true, tid);
+            __syncthreads();
+        } else {
+            // ---- attention [RECALLED-TF BahdanauMonotonicAttention.__call__]: query layer
+            dec_gemv_partials(rs, (int)((a.w.Wq) * 4), AS, A, o_ha, o_part, wave, lane);
+            __syncthreads();
+            if (tid < A) lds[o_pq + tid] = dec_combine(o_part, AS, tid);
+            __syncthreads();
+            TWV_STAMP(3)
+            // score[t] = cdot_j normed_v[j] * tanh((keys[t][j] + pq[j]) + b[j]) + score_bias ; one (t, chunk) per thread
+            for (int task = tid; task < T * nAch; task += 512) {
+                const int t = task / nAch, ch = task - t * nAch;
+                float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+                const float* kr = keys + (long long)t * A + ch * 32;
 #pragma unroll
-            for (int j = 0; j < 32; j += 4) {
-                const int jj = ch * 32 + j;
-                s0 = fma_(P[a.w.nv + jj + 0], tanh_e((kr[j + 0] + lds[o_pq + jj + 0]) + P[a.w.ab + jj + 0]), s0);
-                s1 = fma_(P[a.w.nv + jj + 1], tanh_e((kr[j + 1] + lds[o_pq + jj + 1]) + P[a.w.ab + jj + 1]), s1);
-                s2 = fma_(P[a.w.nv + jj + 2], tanh_e((kr[j + 2] + lds[o_pq + jj + 2]) + P[a.w.ab + jj + 2]), s2);
-                s3 = fma_(P[a.w.nv + jj + 3], tanh_e((kr[j + 3] + lds[o_pq + jj + 3]) + P[a.w.ab + jj + 3]), s3);
+                for (int j = 0; j < 32; j += 4) {
+                    const int jj = ch * 32 + j;
+                    s0 = fma_(P[a.w.nv + jj + 0], tanh_e((kr[j + 0] + lds[o_pq + jj + 0]) + P[a.w.ab + jj + 0]), s0);
+                    s1 = fma_(P[a.w.nv + jj + 1], tanh_e((kr[j + 1] + lds[o_pq + jj + 1]) + P[a.w.ab + jj + 1]), s1);
+                    s2 = fma_(P[a.w.nv + jj + 2], tanh_e((kr[j + 2] + lds[o_pq + jj + 2]) + P[a.w.ab + jj + 2]), s2);
+                    s3 = fma_(P[a.w.nv + jj + 3], tanh_e((kr[j + 3] + lds[o_pq + jj + 3]) + P[a.w.ab + jj + 3]), s3);
+                }
+                lds[o_scp + t * 8 + ch] = (s0 + s1) + (s2 + s3);
             }
-            lds[o_scp + t * 8 + ch] = (s0 + s1) + (s2 + s3);
-        }
-        __syncthreads();
-        TWV_STAMP(4)
-        // p = sigmoid(score) (0 past the length: _maybe_mask_score(-inf)); safe_cumprod pieces
-        for (int t = tid; t < T; t += 512) {
-            float sc = 0.0f;
-            for (int ch = 0; ch < nAch; ++ch) { const float c = lds[o_scp + t * 8 + ch]; sc = ch == 0 ? c : sc + c; }
-            sc = sc + P[a.w.asb];
-            const float pv = t < len ? sigmoid_e(sc) : 0.0f;
-            lds[o_p + t] = pv;
-            float om = 1.0f - pv;
-            const float tiny = 1.17549435e-38f;
-            om = om < tiny ? tiny : (om > 1.0f ? 1.0f : om);
-            lds[o_q + t] = log_e(om);
-        }
-        __syncthreads();
-        if (wave == 0) {  // exclusive cumsum of the logs (AC-6: blocks of 64, scan64 tree)
-            float run = 0.0f;
-            for (int base = 0; base < T; base += 64) {
-                const int t = base + lane;
-                const float r = decg_scan_block(t < T ? lds[o_q + t] : 0.0f, run, base == 0, lane, false);
-                if (t < T) lds[o_q + t] = r;
+            __syncthreads();
+            TWV_STAMP(4)
+            // p = sigmoid(score) (0 past the length: _maybe_mask_score(-inf)); safe_cumprod pieces
+            for (int t = tid; t < T; t += 512) {
+                float sc = 0.0f;
+                for (int ch = 0; ch < nAch; ++ch) { const float c = lds[o_scp + t * 8 + ch]; sc = ch == 0 ? c : sc + c; }
+                sc = sc + P[a.w.asb];
+                const float pv = t < len ? sigmoid_e(sc) : 0.0f;
+                lds[o_p + t] = pv;
+                float om = 1.0f - pv;
+                const float tiny = 1.17549435e-38f;
+                om = om < tiny ? tiny : (om > 1.0f ? 1.0f : om);
+                lds[o_q + t] = log_e(om);
             }
-        }
-        __syncthreads();
-        for (int t = tid; t < T; t += 512) {
-            const float cpv = exp_e(lds[o_q + t]);
-            lds[o_cp + t] = cpv;
-            float den = cpv;
-            den = den < 1e-10f ? 1e-10f : (den > 1.0f ? 1.0f : den);
-            lds[o_q + t] = div_(lds[o_al + t], den);
-        }
-        __syncthreads();
-        if (wave == 0) {  // inclusive cumsum (AC-6)
-            float cs = 0.0f;
-            for (int base = 0; base < T; base += 64) {
-                const int t = base + lane;
-                const float r = decg_scan_block(t < T ? lds[o_q + t] : 0.0f, cs, base == 0, lane, true);
-                if (t < T) lds[o_q + t] = r;
+            __syncthreads();
+            if (wave == 0) {  // exclusive cumsum of the logs (AC-6: blocks of 64, scan64 tree)
+                float run = 0.0f;
+                for (int base = 0; base < T; base += 64) {
+                    const int t = base + lane;
+                    const float r = decg_scan_block(t < T ? lds[o_q + t] : 0.0f, run, base == 0, lane, false);
+                    if (t < T) lds[o_q + t] = r;
+                }
             }
+            __syncthreads();
+            for (int t = tid; t < T; t += 512) {
+                const float cpv = exp_e(lds[o_q + t]);
+                lds[o_cp + t] = cpv;
+                float den = cpv;
+                den = den < 1e-10f ? 1e-10f : (den > 1.0f ? 1.0f : den);
+                lds[o_q + t] = div_(lds[o_al + t], den);
+            }
+            __syncthreads();
+            if (wave == 0) {  // inclusive cumsum (AC-6)
+                float cs = 0.0f;
+                for (int base = 0; base < T; base += 64) {
+                    const int t = base + lane;
+                    const float r = decg_scan_block(t < T ? lds[o_q + t] : 0.0f, cs, base == 0, lane, true);
+                    if (t < T) lds[o_q + t] = r;
+                }
+            }
+            __syncthreads();
+            for (int t = tid; t < T; t += 512) {
+                const float pc = lds[o_p + t] * lds[o_cp + t];
+                const float al = pc * lds[o_q + t];
+                lds[o_al + t] = al;
+                if (a.align) a.align[((long long)n * T + t) * a.iters + it] = al;      // tacotron.py:223
+            }
+            for (int t = T + tid; t < Tp; t += 512) lds[o_al + t] = 0.0f;
+            __syncthreads();
         }
-        __syncthreads();
-        for (int t = tid; t < T; t += 512) {
-            const float pc = lds[o_p + t] * lds[o_cp + t];
-            const float al = pc * lds[o_q + t];
-            lds[o_al + t] = al;
-            if (a.align) a.align[((long long)n * T + t) * a.iters + it] = al;      // tacotron.py:223
-        }
-        for (int t = T + tid; t < Tp; t += 512) lds[o_al + t] = 0.0f;
-        __syncthreads();
         TWV_STAMP(5)
         // ---- rnn_wrappers.py:390 context = alignments . values : cdot over t (AC-1 chunks of 32 time steps)
         if (tid < ENC) {
@@ -1087,10 +1114,11 @@ __global__ void __launch_bounds__(512) tc_decoder_kernel(DecArgs a)
         // ---- rnn_wrappers.py:463 concat(output, attention) -> OutputProjectionWrapper(dec_rnn)
         for (int i = tid; i < AS; i += 512) lds[o_cat + i] = lds[o_ha + i];
         for (int i = tid; i < ENC; i += 512) lds[o_cat + AS + i] = lds[o_ctx + i];
+        for (int i = tid; i < SEc; i += 512) lds[o_cat + AS + ENC + i] = a.semb[(long long)n * SEc + i];  // rnn_wrappers.py:458-460
         __syncthreads();
-        dec_gemv_partials(rs, (int)((a.w.cW) * 4), AS + ENC, DR, o_cat, o_part, wave, lane);
+        dec_gemv_partials(rs, (int)((a.w.cW) * 4), AS + ENC + SEc, DR, o_cat, o_part, wave, lane);
         __syncthreads();
-        if (tid < DR) lds[o_y + tid] = dec_combine(o_part, AS + ENC, tid) + P[a.w.cb + tid];
+        if (tid < DR) lds[o_y + tid] = dec_combine(o_part, AS + ENC + SEc, tid) + P[a.w.cb + tid];
         __syncthreads();
         TWV_STAMP(7)
         // ---- tacotron.py:167 ResidualWrapper(GRUCell(dec_rnn)): y <- y + GRU(y, h_l)
@@ -1157,7 +1185,10 @@ struct DecGArgs {
 //   AK_SOFT  BahdanauAttention (bah_norm: nv = g v / |v|, ab = b; bah: nv = v, ab = 0), masked softmax
 //   AK_LUONG LuongAttention: score = s * (query . keys), no query layer (s = attention_g for luong_scaled, 1 for luong), masked softmax
 //   AK_LOC   LocationSensitiveAttention: the Bahdanau score with location features of the cumulative alignments inside the tanh, softmax
-enum { AK_MON = 0, AK_SOFT = 1, AK_LUONG = 2, AK_LOC = 3 };
+//   AK_MAN   no mechanism: every step attends with the caller's alignments (rnn_wrappers.py:369-374, DecArgs::man).  The query stage has
+//            no tiles and no exchange (as AK_LUONG's), and there is no score exchange either: each workgroup reads the step's row itself.
+//            One kind serves all seven attention types -- none of their tensors is read -- so nothing of the mechanism can reach an output.
+enum { AK_MON = 0, AK_SOFT = 1, AK_LUONG = 2, AK_LOC = 3, AK_MAN = 4 };
 constexpr int kLocTaps = 31;        // location_features_convolution kernel_size (rnn_wrappers.py:662)
 
 struct DecgPos { int m, ch; };
@@ -1395,7 +1426,7 @@ __host__ __device__ __forceinline__ DecgCarve decg_carve(int M, int R, int D1, i
     c.lf = o; o += ak == AK_LOC ? kLocTaps * (A + A / 8) : 0;
     c.cum = o; o += ak == AK_LOC ? c.Tp + 32 : 0;
     // kv: this workgroup's key rows / memory columns held in LDS
-    c.keys = o; o += kv ? ((T + G - 1) >> lg) * (A + A / 8) : 0;
+    c.keys = o; o += kv && ak != AK_MAN ? ((T + G - 1) >> lg) * (A + A / 8) : 0;     // (AK_MAN reads no keys)
     c.memo = o; o += kv ? T * ((ENC >> lg) + 8) : 0;      // rows 8 words apart in the banks: the context's chains k = t mod 4 read four rows at once
     c.part = o; o += partials;                            // GEMV chunk partials (dec_partials)
     c.total = o + 3;                                      // (+ 3: the most c.tab's alignment can take; the launch has always asked for it)
@@ -1471,7 +1502,8 @@ __global__ void __launch_bounds__(512) tc_decoder_g_kernel(DecGArgs ga)
     if (kv) {
         // (every 32-word chunk of the attention tables is skewed by 4 words: the score's threads -- one per (t, chunk, chain) -- read
         // addresses 32 and 128 words apart, i.e. all in four of the 32 LDS banks without the skew: the phase was these reads)
-        for (int i = tid; i < nt_all * A; i += 512) { const int tl = i / A, j = i - tl * A; lds[o_keys + i + ((i >> 5) << 2)] = keys[(long long)((tl << lg) + g) * A + j]; }
+        if constexpr (AK != AK_MAN)
+            for (int i = tid; i < nt_all * A; i += 512) { const int tl = i / A, j = i - tl * A; lds[o_keys + i + ((i >> 5) << 2)] = keys[(long long)((tl << lg) + g) * A + j]; }
         const int ncol = ENC >> lg;
         for (int i = tid; i < T * ncol; i += 512) { const int t = i / ncol, cl = i - t * ncol; lds[o_memo + t * (ncol + 8) + cl] = memo[(long long)t * ENC + g * ncol + cl]; }
     }
@@ -1495,8 +1527,8 @@ __global__ void __launch_bounds__(512) tc_decoder_g_kernel(DecGArgs ga)
         put(a.w.aWg, a.w.abg, DE + ENC + AS, 2 * AS, o_cat2, o_vec, DA_SIGMOID, 1, DP_GATES, DE + ENC, AS, 0);
         put(a.w.aWc, a.w.abc, DE + ENC + AS, AS, o_cat2, o_cand, DA_TANH, 1, DP_CAND, AS, o_ha, -1);
         // attention query layer (redundant: 32 tiles), then score / recurrence / context
-        put(a.w.Wq, -1, AS, A, o_ha, o_pq, DA_NONE, AK == AK_LUONG ? 0 : ga.split_all, DP_QUERY, 0, 0, 0);
-        if (AK == AK_LUONG) {                             // LuongAttention has no query layer: a stage without tiles and without exchange
+        put(a.w.Wq, -1, AS, A, o_ha, o_pq, DA_NONE, AK == AK_LUONG || AK == AK_MAN ? 0 : ga.split_all, DP_QUERY, 0, 0, 0);
+        if (AK == AK_LUONG || AK == AK_MAN) {             // LuongAttention has no query layer: a stage without tiles and without exchange
             const int q = o_tab + (s - 1) * DS_STRIDE;
             LDSI(q + DS_NTILE) = 0; LDSI(q + DS_GEO) = LDSI(q + DS_GEO) & ((1 << 13) - 1);
         }
@@ -1696,171 +1728,176 @@ __global__ void __launch_bounds__(512) tc_decoder_g_kernel(DecGArgs ga)
                 __syncthreads();
                 TWV_STAMP(53)
             } else if (post == DP_QUERY) {
-                // [RECALLED-TF BahdanauMonotonicAttention.__call__] score for the time steps t = g, g+G, ...: one (t, chunk) per thread
-                const int nt = T > g ? (T - g + G - 1) >> lg : 0;
-                if constexpr (AK == AK_LUONG) {           // [RECALLED-TF LuongAttention.__call__] the query is the cell output itself
-                    for (int j = tid; j < A; j += 512) lds[o_pq + j + ((j >> 5) << 2)] = lds[o_ha + j];
-                    __syncthreads();
-                }
-                // one thread per (t, chunk, chain k): s_k = fma chain over j = k, k+4, ..., k+28; the four chains of a chunk sit in
-                // adjacent lanes and are combined as (s0+s1)+(s2+s3)
-                for (int task0 = 0; task0 < nt * nAch * 4; task0 += 512) {
-                    const int task = task0 + tid;
-                    const bool live = task < nt * nAch * 4;
-                    const int k = task & 3, tc = task >> 2;
-                    const int tl = live ? tc / nAch : 0, ch = live ? tc - tl * nAch : 0, t = (tl << lg) + g;
-                    float sk = 0.f;
-                    const float* kr = keys + (long long)t * A + ch * 32 + k;
-                    const int jb = ch * 32 + k, js = jb + 4 * ch, kl = o_keys + tl * A + jb + 4 * (tl * nAch + ch);      // js, kl: skewed
-                    TWV_STAMP(54)
-                    if constexpr (AK == AK_LUONG) {       // [RECALLED-TF _luong_score] query . keys
-                        if (kv) {
-#pragma unroll
-                            for (int j = 0; j < 32; j += 4) sk = fma_(lds[o_pq + js + j], lds[kl + j], sk);
-                        } else {
-#pragma unroll
-                            for (int j = 0; j < 32; j += 4) sk = fma_(lds[o_pq + js + j], kr[j], sk);
-                        }
-                    } else if constexpr (AK == AK_LOC) {
-                        // rnn_wrappers.py:697-727: location features of the cumulative alignments, through the combined 31 x A filter
-                        // (loc_j = cdot_k F[k][j] * cum[t + k - 15], one fma chain in tap order), inside the tanh:
-                        // v . tanh(((keys + pq) + loc) + (attention_bias + the convolution bias through location_features_layer))
-                        float win[kLocTaps];
-#pragma unroll
-                        for (int k2 = 0; k2 < kLocTaps; ++k2) win[k2] = lds[o_cum + 1 + t + k2];
-#pragma unroll
-                        for (int j = 0; j < 32; j += 4) {
-                            float lv = 0.f;
-#pragma unroll
-                            for (int k2 = 0; k2 < kLocTaps; ++k2) lv = fma_(lds[o_lf + k2 * (A + A / 8) + js + j], win[k2], lv);
-                            const float kj = kv ? lds[kl + j] : kr[j];
-                            sk = fma_(lds[o_nv + js + j], tanh_e(((kj + lds[o_pq + js + j]) + lv) + lds[o_ab + js + j]), sk);
-                        }
-                    } else {
-                        if (kv) {
-#pragma unroll
-                            for (int j = 0; j < 32; j += 4) sk = fma_(lds[o_nv + js + j], tanh_e((lds[kl + j] + lds[o_pq + js + j]) + lds[o_ab + js + j]), sk);
-                        } else {
-#pragma unroll
-                            for (int j = 0; j < 32; j += 4) sk = fma_(lds[o_nv + js + j], tanh_e((kr[j] + lds[o_pq + js + j]) + lds[o_ab + js + j]), sk);
-                        }
-                    }
-                    TWV_STAMP(55)
-                    const float s1 = __shfl_xor(sk, 1);
-                    const float pr = (k & 1) ? s1 + sk : sk + s1;       // lanes k=0,1 hold s0+s1 ; k=2,3 hold s2+s3 (operand order as written)
-                    const float p2 = __shfl_xor(pr, 2);
-                    if (live && k == 0) lds[o_scp + tl * 8 + ch] = pr + p2;
-                }
-                TWV_STAMP(56)
-                __syncthreads();
-                TWV_STAMP(48)
-                {
-                    ++ep;
-                    unsigned long long* Xb = X + (ep & 1) * kExN;
-                    for (int tl = tid; tl < nt; tl += 512) {
-                        const int t = (tl << lg) + g;
-                        float sc = 0.0f;
-                        for (int ch = 0; ch < nAch; ++ch) { const float c = lds[o_scp + tl * 8 + ch]; sc = ch == 0 ? c : sc + c; }
-                        float pv;
-                        if constexpr (AK == AK_MON) {
-                            sc = sc + P[a.w.asb];
-                            pv = t < len ? sigmoid_e(sc) : 0.0f;               // _maybe_mask_score(-inf) -> p = 0
-                        } else {                                               // the masked score itself: the softmax follows
-                            if constexpr (AK == AK_LUONG) sc = P[ga.att_g] * sc;   // [RECALLED-TF _luong_score(scale=True)] g * score
-                            pv = t < len ? sc : -INFINITY;
-                        }
-                        if (G == 1) lds[o_p + t] = pv; else decg_store(Xb + t, ep, pv, loc);
-                    }
-                    if (G > 1) decg_gather(Xb, T, ep, o_p, tid, o_abort);
-                    __syncthreads();
-                    ok = LDSI(o_abort) == 0;
-                }
-                TWV_STAMP(49)
-                // monotonic attention recurrence (redundant in every workgroup), all in wave 0 and in registers:
-                // cumprod(1 - p) as exp(exclusive cumsum(log(clip(1 - p)))) [RECALLED-TF safe_cumprod], then
-                // alignments = p * cumprod * inclusive cumsum(previous / clip(cumprod, 1e-10, 1))
-                // The 64-step blocks of AC-6 run side by side, one wave each (eight blocks per round): a block needs from its
-                // predecessors only the running total in front of its own scan, and that is the same chain of adds -- total of block
-                // 0, + block 1's own total, ... -- whether the blocks are scanned one after the other or their totals are summed
-                // afterwards.  (One wave walking the blocks: 1.02 us at T = 101, most of it the log / exp / division of block 2 waiting
-                // behind block 1's.)
-                if constexpr (AK == AK_MON) {
-                    const int o_tot = o_scp;                               // block totals (the score chunk values are consumed)
-                    float run = 0.0f, run2 = 0.0f;                         // totals in front of this round's first block
-                    for (int base0 = 0; base0 < T; base0 += 512) {
-                        const int base = base0 + wave * 64, t = base + lane;
-                        const bool mine = base < T, live = t < T;
-                        const int nblk = (T - base0 + 63) >> 6 < 8 ? (T - base0 + 63) >> 6 : 8;
-                        const float pv = live ? lds[o_p + t] : 0.0f;
-                        float om = 1.0f - pv;
-                        const float tiny = 1.17549435e-38f;
-                        om = om < tiny ? tiny : (om > 1.0f ? 1.0f : om);
-                        const float lq = live ? log_e(om) : 0.0f;
-                        const float sc = scan64_f32_wave(lq);
-                        if (mine && lane == 63) lds[o_tot + wave] = sc;
-                        __syncthreads();
-                        float carry = run, all = run;                      // this block's carry; the total after the round's last block
-                        for (int b = 0; b < nblk; ++b) {
-                            const float tb = lds[o_tot + b];
-                            const float nx = (base0 == 0 && b == 0) ? tb : all + tb;
-                            if (b < wave) carry = nx;
-                            all = nx;
-                        }
-                        run = all;
-                        const bool first = base0 == 0 && wave == 0;
-                        const float incl = first ? sc : carry + sc;
-                        const float up = __shfl_up(incl, 1);
-                        const float ex = lane == 0 ? (first ? 0.0f : carry) : up;
-                        const float cpv = exp_e(ex);
-                        float den = cpv;
-                        den = den < 1e-10f ? 1e-10f : (den > 1.0f ? 1.0f : den);
-                        const float q2 = live ? div_(lds[o_al + t], den) : 0.0f;
-                        const float sc2 = scan64_f32_wave(q2);
-                        __syncthreads();                                   // (the first totals have been read)
-                        if (mine && lane == 63) lds[o_tot + wave] = sc2;
-                        __syncthreads();
-                        float carry2 = run2, all2 = run2;
-                        for (int b = 0; b < nblk; ++b) {
-                            const float tb = lds[o_tot + b];
-                            const float nx = (base0 == 0 && b == 0) ? tb : all2 + tb;
-                            if (b < wave) carry2 = nx;
-                            all2 = nx;
-                        }
-                        run2 = all2;
-                        const float cs = first ? sc2 : carry2 + sc2;
-                        if (live) {
-                            const float pc = pv * cpv;
-                            const float al = pc * cs;
-                            lds[o_al + t] = al;
-                            if (a.align && g == 0) a.align[((long long)n * T + t) * a.iters + it] = al;      // tacotron.py:223
-                        }
-                        __syncthreads();                                   // (the second totals have been read)
-                    }
-                    for (int t = T + tid; t < Tp; t += 512) lds[o_al + t] = 0.0f;
+                if constexpr (AK == AK_MAN) {
+                    // no score, no exchange of it, no recurrence: the row is the same for every workgroup of the utterance
+                    dec_manual_alignments(a, n, it, T, Tp, o_al, g == 0, tid);
                 } else {
-                    // [RECALLED-TF _maybe_mask_score(-inf) + nn_ops.softmax] over the valid positions, wave 0 (redundant in every
-                    // workgroup): max, exp(s - max), sum, quotient.  Each lane sums its positions t = lane, lane + 64, ... in order, the
-                    // 64 lane sums meet in an xor butterfly (every lane ends with the same bits).  Past the length the alignments are 0.
-                    if (wave == 0) {
-                        const int lim = len < T ? len : T;
-                        float mx = -INFINITY;
-                        for (int t = lane; t < lim; t += 64) mx = fmaxf(mx, lds[o_p + t]);
-#pragma unroll
-                        for (int d = 32; d >= 1; d >>= 1) mx = fmaxf(mx, __shfl_xor(mx, d));
-                        float sm = 0.0f;
-                        for (int t = lane; t < lim; t += 64) { const float e = exp_e(lds[o_p + t] - mx); lds[o_cp + t] = e; sm = sm + e; }
-#pragma unroll
-                        for (int d = 32; d >= 1; d >>= 1) sm = sm + __shfl_xor(sm, d);
-                        for (int t = lane; t < T; t += 64) {
-                            const float al = t < lim ? div_(lds[o_cp + t], sm) : 0.0f;
-                            lds[o_al + t] = al;
-                            // LocationSensitiveAttention(cumulate_weights=True): next state = alignments + state; the alignments
-                            // themselves are what the wrapper emits and attends with (rnn_wrappers.py:718-725)
-                            if constexpr (AK == AK_LOC) lds[o_cum + 16 + t] = al + lds[o_cum + 16 + t];
-                            if (a.align && g == 0) a.align[((long long)n * T + t) * a.iters + it] = al;      // tacotron.py:223
-                        }
+                    // [RECALLED-TF BahdanauMonotonicAttention.__call__] score for the time steps t = g, g+G, ...: one (t, chunk) per thread
+                    const int nt = T > g ? (T - g + G - 1) >> lg : 0;
+                    if constexpr (AK == AK_LUONG) {           // [RECALLED-TF LuongAttention.__call__] the query is the cell output itself
+                        for (int j = tid; j < A; j += 512) lds[o_pq + j + ((j >> 5) << 2)] = lds[o_ha + j];
+                        __syncthreads();
                     }
-                    for (int t = T + tid; t < Tp; t += 512) lds[o_al + t] = 0.0f;
+                    // one thread per (t, chunk, chain k): s_k = fma chain over j = k, k+4, ..., k+28; the four chains of a chunk sit in
+                    // adjacent lanes and are combined as (s0+s1)+(s2+s3)
+                    for (int task0 = 0; task0 < nt * nAch * 4; task0 += 512) {
+                        const int task = task0 + tid;
+                        const bool live = task < nt * nAch * 4;
+                        const int k = task & 3, tc = task >> 2;
+                        const int tl = live ? tc / nAch : 0, ch = live ? tc - tl * nAch : 0, t = (tl << lg) + g;
+                        float sk = 0.f;
+                        const float* kr = keys + (long long)t * A + ch * 32 + k;
+                        const int jb = ch * 32 + k, js = jb + 4 * ch, kl = o_keys + tl * A + jb + 4 * (tl * nAch + ch);      // js, kl: skewed
+                        TWV_STAMP(54)
+                        if constexpr (AK == AK_LUONG) {       // [RECALLED-TF _luong_score] query . keys
+                            if (kv) {
+#pragma unroll
+                                for (int j = 0; j < 32; j += 4) sk = fma_(lds[o_pq + js + j], lds[kl + j], sk);
+                            } else {
+#pragma unroll
+                                for (int j = 0; j < 32; j += 4) sk = fma_(lds[o_pq + js + j], kr[j], sk);
+                            }
+                        } else if constexpr (AK == AK_LOC) {
+                            // rnn_wrappers.py:697-727: location features of the cumulative alignments, through the combined 31 x A filter
+                            // (loc_j = cdot_k F[k][j] * cum[t + k - 15], one fma chain in tap order), inside the tanh:
+                            // v . tanh(((keys + pq) + loc) + (attention_bias + the convolution bias through location_features_layer))
+                            float win[kLocTaps];
+#pragma unroll
+                            for (int k2 = 0; k2 < kLocTaps; ++k2) win[k2] = lds[o_cum + 1 + t + k2];
+#pragma unroll
+                            for (int j = 0; j < 32; j += 4) {
+                                float lv = 0.f;
+#pragma unroll
+                                for (int k2 = 0; k2 < kLocTaps; ++k2) lv = fma_(lds[o_lf + k2 * (A + A / 8) + js + j], win[k2], lv);
+                                const float kj = kv ? lds[kl + j] : kr[j];
+                                sk = fma_(lds[o_nv + js + j], tanh_e(((kj + lds[o_pq + js + j]) + lv) + lds[o_ab + js + j]), sk);
+                            }
+                        } else {
+                            if (kv) {
+#pragma unroll
+                                for (int j = 0; j < 32; j += 4) sk = fma_(lds[o_nv + js + j], tanh_e((lds[kl + j] + lds[o_pq + js + j]) + lds[o_ab + js + j]), sk);
+                            } else {
+#pragma unroll
+                                for (int j = 0; j < 32; j += 4) sk = fma_(lds[o_nv + js + j], tanh_e((kr[j] + lds[o_pq + js + j]) + lds[o_ab + js + j]), sk);
+                            }
+                        }
+                        TWV_STAMP(55)
+                        const float s1 = __shfl_xor(sk, 1);
+                        const float pr = (k & 1) ? s1 + sk : sk + s1;       // lanes k=0,1 hold s0+s1 ; k=2,3 hold s2+s3 (operand order as written)
+                        const float p2 = __shfl_xor(pr, 2);
+                        if (live && k == 0) lds[o_scp + tl * 8 + ch] = pr + p2;
+                    }
+                    TWV_STAMP(56)
+                    __syncthreads();
+                    TWV_STAMP(48)
+                    {
+                        ++ep;
+                        unsigned long long* Xb = X + (ep & 1) * kExN;
+                        for (int tl = tid; tl < nt; tl += 512) {
+                            const int t = (tl << lg) + g;
+                            float sc = 0.0f;
+                            for (int ch = 0; ch < nAch; ++ch) { const float c = lds[o_scp + tl * 8 + ch]; sc = ch == 0 ? c : sc + c; }
+                            float pv;
+                            if constexpr (AK == AK_MON) {
+                                sc = sc + P[a.w.asb];
+                                pv = t < len ? sigmoid_e(sc) : 0.0f;               // _maybe_mask_score(-inf) -> p = 0
+                            } else {                                               // the masked score itself: the softmax follows
+                                if constexpr (AK == AK_LUONG) sc = P[ga.att_g] * sc;   // [RECALLED-TF _luong_score(scale=True)] g * score
+                                pv = t < len ? sc : -INFINITY;
+                            }
+                            if (G == 1) lds[o_p + t] = pv; else decg_store(Xb + t, ep, pv, loc);
+                        }
+                        if (G > 1) decg_gather(Xb, T, ep, o_p, tid, o_abort);
+                        __syncthreads();
+                        ok = LDSI(o_abort) == 0;
+                    }
+                    TWV_STAMP(49)
+                    // monotonic attention recurrence (redundant in every workgroup), all in wave 0 and in registers:
+                    // cumprod(1 - p) as exp(exclusive cumsum(log(clip(1 - p)))) [RECALLED-TF safe_cumprod], then
+                    // alignments = p * cumprod * inclusive cumsum(previous / clip(cumprod, 1e-10, 1))
+                    // The 64-step blocks of AC-6 run side by side, one wave each (eight blocks per round): a block needs from its
+                    // predecessors only the running total in front of its own scan, and that is the same chain of adds -- total of block
+                    // 0, + block 1's own total, ... -- whether the blocks are scanned one after the other or their totals are summed
+                    // afterwards.  (One wave walking the blocks: 1.02 us at T = 101, most of it the log / exp / division of block 2 waiting
+                    // behind block 1's.)
+                    if constexpr (AK == AK_MON) {
+                        const int o_tot = o_scp;                               // block totals (the score chunk values are consumed)
+                        float run = 0.0f, run2 = 0.0f;                         // totals in front of this round's first block
+                        for (int base0 = 0; base0 < T; base0 += 512) {
+                            const int base = base0 + wave * 64, t = base + lane;
+                            const bool mine = base < T, live = t < T;
+                            const int nblk = (T - base0 + 63) >> 6 < 8 ? (T - base0 + 63) >> 6 : 8;
+                            const float pv = live ? lds[o_p + t] : 0.0f;
+                            float om = 1.0f - pv;
+                            const float tiny = 1.17549435e-38f;
+                            om = om < tiny ? tiny : (om > 1.0f ? 1.0f : om);
+                            const float lq = live ? log_e(om) : 0.0f;
+                            const float sc = scan64_f32_wave(lq);
+                            if (mine && lane == 63) lds[o_tot + wave] = sc;
+                            __syncthreads();
+                            float carry = run, all = run;                      // this block's carry; the total after the round's last block
+                            for (int b = 0; b < nblk; ++b) {
+                                const float tb = lds[o_tot + b];
+                                const float nx = (base0 == 0 && b == 0) ? tb : all + tb;
+                                if (b < wave) carry = nx;
+                                all = nx;
+                            }
+                            run = all;
+                            const bool first = base0 == 0 && wave == 0;
+                            const float incl = first ? sc : carry + sc;
+                            const float up = __shfl_up(incl, 1);
+                            const float ex = lane == 0 ? (first ? 0.0f : carry) : up;
+                            const float cpv = exp_e(ex);
+                            float den = cpv;
+                            den = den < 1e-10f ? 1e-10f : (den > 1.0f ? 1.0f : den);
+                            const float q2 = live ? div_(lds[o_al + t], den) : 0.0f;
+                            const float sc2 = scan64_f32_wave(q2);
+                            __syncthreads();                                   // (the first totals have been read)
+                            if (mine && lane == 63) lds[o_tot + wave] = sc2;
+                            __syncthreads();
+                            float carry2 = run2, all2 = run2;
+                            for (int b = 0; b < nblk; ++b) {
+                                const float tb = lds[o_tot + b];
+                                const float nx = (base0 == 0 && b == 0) ? tb : all2 + tb;
+                                if (b < wave) carry2 = nx;
+                                all2 = nx;
+                            }
+                            run2 = all2;
+                            const float cs = first ? sc2 : carry2 + sc2;
+                            if (live) {
+                                const float pc = pv * cpv;
+                                const float al = pc * cs;
+                                lds[o_al + t] = al;
+                                if (a.align && g == 0) a.align[((long long)n * T + t) * a.iters + it] = al;      // tacotron.py:223
+                            }
+                            __syncthreads();                                   // (the second totals have been read)
+                        }
+                        for (int t = T + tid; t < Tp; t += 512) lds[o_al + t] = 0.0f;
+                    } else {
+                        // [RECALLED-TF _maybe_mask_score(-inf) + nn_ops.softmax] over the valid positions, wave 0 (redundant in every
+                        // workgroup): max, exp(s - max), sum, quotient.  Each lane sums its positions t = lane, lane + 64, ... in order, the
+                        // 64 lane sums meet in an xor butterfly (every lane ends with the same bits).  Past the length the alignments are 0.
+                        if (wave == 0) {
+                            const int lim = len < T ? len : T;
+                            float mx = -INFINITY;
+                            for (int t = lane; t < lim; t += 64) mx = fmaxf(mx, lds[o_p + t]);
+#pragma unroll
+                            for (int d = 32; d >= 1; d >>= 1) mx = fmaxf(mx, __shfl_xor(mx, d));
+                            float sm = 0.0f;
+                            for (int t = lane; t < lim; t += 64) { const float e = exp_e(lds[o_p + t] - mx); lds[o_cp + t] = e; sm = sm + e; }
+#pragma unroll
+                            for (int d = 32; d >= 1; d >>= 1) sm = sm + __shfl_xor(sm, d);
+                            for (int t = lane; t < T; t += 64) {
+                                const float al = t < lim ? div_(lds[o_cp + t], sm) : 0.0f;
+                                lds[o_al + t] = al;
+                                // LocationSensitiveAttention(cumulate_weights=True): next state = alignments + state; the alignments
+                                // themselves are what the wrapper emits and attends with (rnn_wrappers.py:718-725)
+                                if constexpr (AK == AK_LOC) lds[o_cum + 16 + t] = al + lds[o_cum + 16 + t];
+                                if (a.align && g == 0) a.align[((long long)n * T + t) * a.iters + it] = al;      // tacotron.py:223
+                            }
+                        }
+                        for (int t = T + tid; t < Tp; t += 512) lds[o_al + t] = 0.0f;
+                    }
                 }
                 __syncthreads();
                 TWV_STAMP(50)
@@ -3169,7 +3206,12 @@ struct TacoRoute {
     bool def;                           // TK_X / TK_G: the instantiation with the hparams-default sizes folded in
     long long lds_floats; int wgs;      // dynamic LDS and workgroups of the launch
 };
-static TacoRoute taco_route(const twv_tacotron* h, int N, int T, int cus)
+static const char kManualNoX[] = "decoder_groups = 32: the XCD-local decoder kernel takes no caller-supplied alignments (decoder_groups 0, 1, 2, 4, 8, 16 or -1)";
+// manual: a pass with caller-supplied alignments (twv_tacotron_infer_manual).  It is served by the split kernel's AK_MAN instantiations at
+// decoder_groups 0, 1, 2, 4, 8, 16 -- with the geometry code below, the same as a mechanism's pass gets -- and by tc_decoder_kernel<false, true>
+// at -1, for every attention type and model_type; the XCD-resident kernel has no such instantiation (decoder_groups = 32 is refused, 0 never
+// chooses it).  The device is not looked at for the choice of kernel.
+static TacoRoute taco_route(const twv_tacotron* h, int N, int T, int cus, bool manual = false)
 {
     const twv_tacotron_dims& d = h->d;
     const int M = d.num_mels, R = d.reduction_factor, D0 = d.dec_prenet_sizes[0], D1 = d.dec_prenet_sizes[1], A = d.attention_size,
@@ -3181,6 +3223,10 @@ static TacoRoute taco_route(const twv_tacotron* h, int N, int T, int cus)
     taco_xstages(h, r.xt);
     const int SEc = r.simple ? d.speaker_embedding_size : 0;
     auto refuse = [&](const char* msg) { r.err = TWV_E_UNSUPPORTED; r.msg = msg; return r; };
+    if (manual) {
+        r.ak = AK_MAN;
+        if (h->dec_groups == 32) return refuse(kManualNoX);
+    }
     // Which kernel (round 6, scripts/tacotron_bench.py --batch 8 / 16 / 24 / 32): the XCD-resident kernel is the default wherever it fits
     // (up to four utterances per XCD = batch 32); pass times against the split kernel are in profiles/r06_tacotron_decoder_ab.txt.
     // (Until its scratch spills and per-utterance branch chains were removed it tied the split kernel at four utterances per XCD.)
@@ -3188,10 +3234,10 @@ static TacoRoute taco_route(const twv_tacotron* h, int N, int T, int cus)
     const int nu = r.upx < N ? r.upx : N;
     const long long xfl = xdec_carve(M, D1, ENC, AS, NL, DR, A, T, nu < 1 ? 1 : nu, r.xt.nst).total + 64;
     const bool xok = taco_xdec_ok(h, r.xt) && cus >= 256 && r.upx <= kXU && T <= 512 && xfl * 4 <= kLdsBudget && !r.simple;
-    const bool one_or_x = h->dec_groups == -1 || h->dec_groups == 32, other_att = at != TWV_ATT_BAH_MON_NORM;
+    const bool one_or_x = h->dec_groups == -1 || h->dec_groups == 32, other_att = !manual && at != TWV_ATT_BAH_MON_NORM;
     r.kind = other_att && one_or_x ? TK_NONE : h->dec_groups == -1 ? TK_ONE
-           : xok && !other_att && (h->dec_groups == 32 || h->dec_groups == 0) ? TK_X : TK_G;
-    if (r.simple && one_or_x) return refuse("model_type 'simple' runs on the split decoder kernel only (decoder_groups 0, 1, 2, 4, 8 or 16)");
+           : !manual && xok && !other_att && (h->dec_groups == 32 || h->dec_groups == 0) ? TK_X : TK_G;
+    if (!manual && r.simple && one_or_x) return refuse("model_type 'simple' runs on the split decoder kernel only (decoder_groups 0, 1, 2, 4, 8 or 16)");
     if (other_att && one_or_x) return refuse("attention_type other than bah_mon_norm runs on the split decoder kernel only (decoder_groups 0, 1, 2, 4, 8 or 16)");
     if (h->dec_groups == 32 && r.kind != TK_X)
         return refuse("decoder_groups = 32 (XCD-local decoder) needs 256 CUs, batch <= 32, t_in <= 512 and the default decoder sizes");
@@ -3201,7 +3247,7 @@ static TacoRoute taco_route(const twv_tacotron* h, int N, int T, int cus)
         r.def = M == 80 && R == 5 && A == 256 && AS == 256 && ENC == 256 && DR == 256 && D1 == 128 && NL == 2 && r.xt.nst == 11;
     } else if (r.kind == TK_ONE) {      // the single-workgroup kernel (kept as a cross-check of the split one)
         int hr[4];
-        r.lds_floats = dec1_carve(M, ENC, AS, NL, DR, A, T, dec_partials(M, R, D1, 0, ENC, AS, DR, T), hr).total; r.wgs = N;
+        r.lds_floats = dec1_carve(M, ENC, AS, NL, DR, A, T, dec_partials(M, R, D1, manual ? SEc : 0, ENC, AS, DR, T), hr).total; r.wgs = N;
     } else {
         // G workgroups per utterance, all N*G co-resident (they exchange through polled granules)
         int G = h->dec_groups > 0 ? h->dec_groups : 16;        // 16 workgroups per utterance up to batch 16, 8 up to 32, 4 up to 64, ...
@@ -3247,6 +3293,9 @@ static const void* taco_decoder_fn_tf(const TacoRoute& r)
 static const void* taco_decoder_fn(const TacoRoute& r, bool prof, bool tf)
 {
     const bool def = r.def, mm = r.mm;
+    if (r.ak == AK_MAN)                 // (a manual route is TK_ONE or TK_G, free-running, without an instrumented build)
+        return r.kind == TK_ONE ? (const void*)tc_decoder_kernel<false, true>
+             : def ? (const void*)tc_decoder_g_kernel<false, true, AK_MAN> : (const void*)tc_decoder_g_kernel<false, false, AK_MAN>;
     if (tf) return taco_decoder_fn_tf<true>(r);
     if (prof && r.kind == TK_X)
         return def ? (mm ? (const void*)tc_decoder_x_kernel<true, true, true> : (const void*)tc_decoder_x_kernel<true, true, false>)
@@ -3257,10 +3306,11 @@ static const void* taco_decoder_fn(const TacoRoute& r, bool prof, bool tf)
 
 // One pass of the graph for `steps` decoder steps (t_out = steps * r output frames): the body of twv_tacotron_infer (steps = max_iters, no
 // targets) and of twv_tacotron_forward_targets (steps = t_out / r; `targets` non-null = teacher forcing).  The workspace is carved for
-// max_iters steps, so any 1 <= steps <= max_iters fits it; the callers have checked their arguments.
+// max_iters steps, so any 1 <= steps <= max_iters fits it; the callers have checked their arguments.  `manual` non-null (and no targets) =
+// twv_tacotron_infer_manual's pass: the decoder attends with those alignments [batch][steps][t_in].
 static int taco_forward(const twv_tacotron* h, const void* packed, const int32_t* tokens, const int32_t* lengths,
                         const int32_t* speaker_ids, int batch, int t_in, int steps, const float* targets, void* workspace, float* mel,
-                        float* linear, float* alignments, int32_t* status, void* stream)
+                        float* linear, float* alignments, int32_t* status, void* stream, const float* manual = nullptr)
 {
     if (!speaker_ids && h->d.num_speakers > 1) return twv_fail(TWV_E_INVALID, "speaker_ids is required for a multi-speaker model");
     if (batch < 1 || t_in < 1 || t_in > 1024) return twv_fail(TWV_E_INVALID, "batch >= 1 and 1 <= t_in <= 1024 required");
@@ -3274,7 +3324,7 @@ static int taco_forward(const twv_tacotron* h, const void* packed, const int32_t
     // the decoder kernel of this call, or its refusal -- before anything is launched
     const int cus = taco_cus();
     if (cus < 0) return twv_fail(TWV_E_HIP, "hipDeviceGetAttribute(hipDeviceAttributeMultiprocessorCount) failed");
-    const TacoRoute r = taco_route(h, N, T, cus);
+    const TacoRoute r = taco_route(h, N, T, cus, manual != nullptr);
     if (r.err) return twv_fail(r.err, r.msg);
     HIPCHK(hipMemsetAsync(status, 0, 16, st));
     TacoCarve w;
@@ -3335,6 +3385,7 @@ static int taco_forward(const twv_tacotron* h, const void* packed, const int32_t
     da.DR = DR; da.layers = d.dec_layer_num; da.iters = steps; da.tgt = targets; da.mel = mel; da.align = alignments; da.status = status;
     da.SEc = simple ? SE : 0; da.semb = simple ? w.semb : nullptr;
     da.packed_bytes = (long long)h->packed_floats * 4; da.prof = h->prof; da.nbias = r.nbias;
+    if (manual) da.man = manual;
     DecXArgs xa; DecGArgs ga; void* kargs[1] = {&da};
     if (r.kind == TK_X) {
         xa.d = da; xa.tab = r.xt; xa.upx = r.upx; xa.xt_off = h->xt_off; xa.stab = reinterpret_cast<int*>(w.stabf);
@@ -3390,6 +3441,33 @@ extern "C" int twv_tacotron_forward_targets(const twv_tacotron* h, const void* p
     if (teacher_forced && !mel_targets) return twv_fail(TWV_E_INVALID, "teacher_forced needs mel_targets");
     return taco_forward(h, packed, tokens, lengths, speaker_ids, batch, t_in, t_out / R, teacher_forced ? mel_targets : nullptr, workspace, mel,
                         linear, alignments, status, stream);
+}
+
+// rnn_wrappers.py:369-374 / tacotron.py:122-123 (is_manual_attention, manual_alignments): the free-running pass of `steps` steps whose decoder
+// attends with the caller's alignments.  Every refusal but the launch geometry's comes before the device is looked at.
+extern "C" int twv_tacotron_infer_manual(const twv_tacotron* h, const void* packed, const int32_t* tokens, const int32_t* lengths,
+                                         const int32_t* speaker_ids, int batch, int t_in, const float* manual_alignments, int steps,
+                                         void* workspace, float* mel, float* linear, float* alignments, int32_t* status, void* stream)
+{
+    if (!h) return twv_fail(TWV_E_INVALID, "null handle");
+    if (!packed || !tokens || !lengths || !manual_alignments || !workspace || !mel || !status) return twv_fail(TWV_E_INVALID, "null argument");
+    if (steps < 1 || steps > h->d.max_iters)
+        return twv_fail(TWV_E_INVALID, "steps must satisfy 1 <= steps <= max_iters (dynamic_decode and the workspace stop there)");
+    if (batch < 1 || t_in < 1 || t_in > 1024) return twv_fail(TWV_E_INVALID, "batch >= 1 and 1 <= t_in <= 1024 required");
+    if (!speaker_ids && h->d.num_speakers > 1) return twv_fail(TWV_E_INVALID, "speaker_ids is required for a multi-speaker model");
+    if (h->dec_groups == 32) return twv_fail(TWV_E_UNSUPPORTED, kManualNoX);       // (taco_route's refusal, before the device is looked at)
+    return taco_forward(h, packed, tokens, lengths, speaker_ids, batch, t_in, steps, nullptr, workspace, mel, linear, alignments, status, stream,
+                        manual_alignments);
+}
+
+// the kernel twv_tacotron_infer_manual launches for (handle, batch, t_in, options): static strings as twv_tacotron_decoder_kernel_name's, ""
+// where the call is refused for its decoder_groups.  A manual route's kernel does not depend on the device.
+extern "C" const char* twv_tacotron_manual_kernel_name(const twv_tacotron* h, int batch, int t_in)
+{
+    if (!h || batch < 1 || t_in < 1) return "";
+    const TacoRoute r = taco_route(h, batch, t_in, 0, true);       // (no device: only the kind is read)
+    if (r.msg == kManualNoX) return "";
+    return r.kind == TK_G ? "tc_decoder_g_kernel" : r.kind == TK_ONE ? "tc_decoder_kernel" : "";
 }
 
 // taco_route's answer for (handle, batch, t_in, options) on the current device as a measurement label (bench.py's `tacotron.roofline.kernel`,

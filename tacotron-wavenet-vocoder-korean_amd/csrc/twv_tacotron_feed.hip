@@ -1,4 +1,4 @@
-// Tacotron batch staging (gfx950): one packed buffer of a batch's ragged arrays -> the padded arrays a training step reads.
+// Tacotron feeds (gfx950).  Batch staging: one packed buffer of a batch's ragged arrays -> the padded arrays a training step reads.
 //
 // The packed buffer is an array of 32-bit words with four sections, each given by its first word:
 //   tokens   every utterance's tokens one after the other (int32)
@@ -84,8 +84,77 @@ __global__ void __launch_bounds__(256) tf_stage_tokens_kernel(const uint32_t* __
     }
 }
 
+// ---- alignment edits (synthesizer.py:165-190): a pass's alignments (N, T_in, steps) -> the manual_alignments feed (N, steps, T_in) ----
+//   mode 0  the transpose
+//   mode 1  zeros, then 1 at (argmax_d in[n][e][:], e) for EVERY encoder row e (padded rows too: an all-zero row puts its 1 at step 0)
+//   mode 2  the transpose, squared
+//   mode 3  the transpose, then that same 1
+// A workgroup takes 32 encoder rows of one utterance.  First (modes 1, 3) each of its four waves finds the argmax of eight rows: the lanes
+// read a row's `steps` contiguous floats 64 at a time, each keeps the first maximum of its own positions, and a butterfly picks the larger
+// value and, of equal values, the smaller step -- numpy's argmax on finite values.  Then 32 x 32 tiles go through LDS: read with the step
+// index running along the lanes, written with the encoder row running along them, so both sides move 128-byte pieces.  Every output
+// element is stored exactly once; no atomics.
+constexpr int kEditRows = 32;
+__global__ void __launch_bounds__(256) tf_alignment_edit_kernel(const float* __restrict__ in, int T_in, int steps, int mode, float* __restrict__ out)
+{
+    __shared__ float tile[kEditRows][kEditRows + 1];
+    __shared__ int arg[kEditRows];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = blockIdx.y, e0 = blockIdx.x * kEditRows;
+    const float* src = in + (long long)n * T_in * steps;
+    float* dst = out + (long long)n * steps * T_in;
+    if (mode == 1 || mode == 3) {
+        for (int r = wave * 8; r < wave * 8 + 8; ++r) {
+            const int e = e0 + r;
+            float best = -INFINITY; int at = 0x7fffffff;
+            if (e < T_in)
+                for (int d = lane; d < steps; d += 64) {
+                    const float v = src[(long long)e * steps + d];
+                    if (v > best) { best = v; at = d; }
+                }
+#pragma unroll
+            for (int k = 32; k >= 1; k >>= 1) {
+                const float ob = __shfl_xor(best, k); const int oa = __shfl_xor(at, k);
+                if (ob > best || (ob == best && oa < at)) { best = ob; at = oa; }
+            }
+            if (lane == 0) arg[r] = at;
+        }
+    }
+    __syncthreads();
+    const int tx = tid & 31, ty = tid >> 5;
+    for (int d0 = 0; d0 < steps; d0 += kEditRows) {
+        if (mode != 1)
+            for (int r = ty; r < kEditRows; r += 8)
+                if (e0 + r < T_in && d0 + tx < steps) tile[r][tx] = src[(long long)(e0 + r) * steps + d0 + tx];
+        __syncthreads();
+        for (int c = ty; c < kEditRows; c += 8) {
+            const int d = d0 + c, e = e0 + tx;
+            if (d < steps && e < T_in) {
+                float v = mode == 1 ? 0.0f : tile[tx][c];
+                if (mode == 2) v = v * v;
+                else if ((mode == 1 || mode == 3) && arg[tx] == d) v = 1.0f;
+                dst[(long long)d * T_in + e] = v;
+            }
+        }
+        __syncthreads();
+    }
+}
+
 }  // namespace tf
 using namespace tf;
+
+extern "C" int twv_tacotron_alignment_edit(const float* alignments, int batch, int t_in, int steps, int mode, float* manual_out, void* stream)
+{
+    if (!alignments || !manual_out) return twv_fail(TWV_E_INVALID, "null argument");
+    if (batch < 1 || t_in < 1 || steps < 1) return twv_fail(TWV_E_INVALID, "batch, t_in and steps must be >= 1");
+    if (mode < 0 || mode > 3) return twv_fail(TWV_E_INVALID, "mode must be 0 (transpose), 1 (argmax one-hot), 2 (squared) or 3 (argmax set to 1)");
+    if (batch > 65535) return twv_fail(TWV_E_INVALID, "batch above 65535");
+    hipLaunchKernelGGL(tf_alignment_edit_kernel, dim3((unsigned)((t_in + kEditRows - 1) / kEditRows), (unsigned)batch), dim3(256), 0, (hipStream_t)stream,
+                       alignments, t_in, steps, mode, manual_out);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return twv_fail(TWV_E_HIP, std::string("twv_tacotron_alignment_edit: ") + hipGetErrorString(e));
+    return TWV_OK;
+}
 
 extern "C" int twv_tacotron_batch_stage(const void* packed, const twv_tacotron_feed_row* table_host, long long packed_words, long long tokens_at,
                                         long long mel_at, long long linear_at, long long table_at, long long total_tokens, long long total_frames,

@@ -244,6 +244,31 @@ def dropout_mask_numpy(n, seed, step, site, rate=0.5):
     return np.where(u >= np.float32(rate), np.float32(1.0 / (1.0 - rate)), np.float32(0.0)).astype(np.float32)
 
 
+ALIGNMENT_EDITS = {0: "transpose", 1: "argmax one-hot", 2: "squared", 3: "argmax set to 1"}
+
+
+def alignment_edit_numpy(alignments, mode):
+    """twv_tacotron_alignment_edit restated on the host: (B, T_in, steps) alignments as a pass emits them -> the (B, steps, T_in) float32
+    feed of infer_manual.  mode 0: the transpose.  With d* = the first step at which encoder row e has its maximum -- every row, the padded
+    ones too, so an all-zero row gives step 0 -- mode 1: zeros with a 1 at (d*, e); mode 2: the transpose squared elementwise, not
+    renormalised; mode 3: the transpose with a 1 at (d*, e)."""
+    if mode not in ALIGNMENT_EDITS:
+        raise ValueError("mode must be one of %s, got %r" % (sorted(ALIGNMENT_EDITS), mode))
+    a = np.asarray(alignments, np.float32)
+    if a.ndim != 3 or 0 in a.shape:
+        raise ValueError("alignments must be (B, T_in, steps) with no empty axis, got %s" % (a.shape,))
+    t = a.transpose(0, 2, 1).copy()                          # (a copy in any case: with one step the transpose is contiguous as it stands)
+    if mode == 0:
+        return t
+    if mode == 2:
+        return t * t
+    out = np.zeros_like(t) if mode == 1 else t
+    first = a.argmax(axis=2)                                 # (B, T_in): numpy takes the first of equal maxima
+    b, e = np.meshgrid(np.arange(a.shape[0]), np.arange(a.shape[1]), indexing="ij")
+    out[b, first, e] = np.float32(1.0)
+    return out
+
+
 def moving_average_update(moving, batch, momentum=BN_MOMENTUM):
     """twv_tacotron_moving_update restated on the host, float32: m - (m - batch) * (float32)(1 - momentum)"""
     m, b = np.asarray(moving, np.float32), np.asarray(batch, np.float32)
@@ -329,6 +354,10 @@ class Tacotron(object):
         """the decoder kernel infer() launches for this batch and input length with the options set (a measurement label)"""
         return self._L.twv_tacotron_decoder_kernel_name(self._h, int(batch), int(t_in)).decode()
 
+    def manual_kernel_name(self, batch, t_in):
+        """the decoder kernel infer_manual() launches for this batch and input length with the options set ("" where it refuses them)"""
+        return self._L.twv_tacotron_manual_kernel_name(self._h, int(batch), int(t_in)).decode()
+
     def gemm_stats(self):
         """after set_option("gemm_timing", 1): (useful FLOPs, summed kernel milliseconds, launches) of the dense contractions since then"""
         f, ms, n = C.c_double(), C.c_double(), C.c_int64()
@@ -380,6 +409,57 @@ class Tacotron(object):
         self.mel_outputs, self.linear_outputs, self.alignments = mel, lin, al
         self.mel_targets = None                              # (the outputs no longer belong to a pass with targets: add_loss refuses)
         return mel, lin, al
+
+    def infer_manual(self, inputs, input_lengths, speaker_id, manual_alignments, want_linear=True, want_alignments=True):
+        """the inference graph fed `is_manual_attention: True, manual_alignments: ...` (tacotron.py:122-123, synthesizer.py:146-147): at
+        decoder step t the attention wrapper uses manual_alignments[:, t, :] in place of what its mechanism computes (rnn_wrappers.py:
+        369-374), exactly as given -- no mask past the lengths, no normalisation.  manual_alignments: (B, steps, T_in) array or device
+        tensor, 1 <= steps <= max_iters; the decoder runs free for `steps` steps.  Returns what infer returns, at `steps`: mel
+        (B, steps * r, num_mels), linear (B, steps * r, num_freq), alignments (B, T_in, steps) = the manual values transposed.  Runs on the
+        split kernel or (decoder_groups = -1) the single-workgroup kernel, never the XCD-local one: decoder_groups = 32 raises."""
+        hp = self._hparams
+        with torch.cuda.device(self.device):
+            tok = self._device_i32(inputs)
+            N, T = tok.shape
+            ln = self._device_i32(input_lengths)
+            sp = None
+            if self.num_speakers > 1:
+                sp = self._device_i32(speaker_id)
+            if not torch.is_tensor(manual_alignments):
+                manual_alignments = torch.from_numpy(np.ascontiguousarray(manual_alignments, np.float32))
+            man = manual_alignments.to(device=self.device, dtype=torch.float32).contiguous()
+            if man.dim() != 3 or man.shape[0] != N or man.shape[2] != T or man.shape[1] < 1:
+                raise ValueError("manual_alignments must be (%d, steps >= 1, %d), got %s" % (N, T, tuple(man.shape)))
+            steps = int(man.shape[1])                            # (steps above max_iters are refused by the library)
+            need = self._L.twv_tacotron_workspace_bytes(self._h, N, T) // 4
+            if self._ws is None or self._ws.numel() < need:
+                self._ws = torch.empty(need, dtype=torch.float32, device=self.device)
+            TO = steps * hp.reduction_factor
+            mel = torch.empty((N, TO, hp.num_mels), dtype=torch.float32, device=self.device)
+            lin = torch.empty((N, TO, hp.num_freq), dtype=torch.float32, device=self.device) if want_linear else None
+            al = torch.empty((N, T, steps), dtype=torch.float32, device=self.device) if want_alignments else None
+            status = torch.zeros(4, dtype=torch.int32, device=self.device)
+            _lib.check(self._L.twv_tacotron_infer_manual(self._h, _ptr(self._packed), _ptr(tok), _ptr(ln), _ptr(sp), N, T, _ptr(man), steps,
+                                                         _ptr(self._ws), _ptr(mel), _ptr(lin), _ptr(al), _ptr(status), _stream()))
+        self.inputs, self.input_lengths, self.speaker_id = tok, ln, sp
+        self.mel_outputs, self.linear_outputs, self.alignments = mel, lin, al
+        self.mel_targets = None
+        return mel, lin, al
+
+    def edit_alignments(self, alignments, mode):
+        """synthesizer.py:165-190 on the device (twv_tacotron_alignment_edit; alignment_edit_numpy is the same on the host): the (B, T_in,
+        steps) alignments of a pass, array or device tensor -> the (B, steps, T_in) device tensor infer_manual takes.  mode 0 transposes,
+        1 = one-hot at every encoder row's argmax over the steps, 2 = squared ("sharpening"), 3 = that argmax set to 1."""
+        with torch.cuda.device(self.device):
+            if not torch.is_tensor(alignments):
+                alignments = torch.from_numpy(np.ascontiguousarray(alignments, np.float32))
+            al = alignments.to(device=self.device, dtype=torch.float32).contiguous()
+            if al.dim() != 3:
+                raise ValueError("alignments must be (B, T_in, steps), got %s" % (tuple(al.shape),))
+            N, T, steps = (int(v) for v in al.shape)
+            out = torch.empty((N, steps, T), dtype=torch.float32, device=self.device)
+            _lib.check(self._L.twv_tacotron_alignment_edit(_ptr(al), N, T, steps, int(mode), _ptr(out), _stream()))
+        return out
 
     def forward_targets(self, inputs, input_lengths, speaker_id, mel_targets, teacher_forced=False, want_linear=True, want_alignments=True):
         """`.initialize(inputs, input_lengths, num_speakers, speaker_id, mel_targets, ...)` (tacotron.py:36-37): the decoder under
