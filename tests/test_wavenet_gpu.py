@@ -175,6 +175,8 @@ def test_mu_law_codec(torch_cuda, oracle):
 
 
 def test_upsample(torch_cuda, oracle):
+    """the default width and upsampling list; other widths and one to four stages: tests/conditioning_cases.py, run by
+    tests/test_wavenet_conditioning_gpu.py::test_create_upsample"""
     dil = [1, 2, 4]
     d, tensors, blob = make_case(oracle, dil, S=64, scale=0.3)
     m = make_model(2, dil, tensors, S=64)
@@ -289,6 +291,8 @@ def test_generate_past_longest_delay_line(torch_cuda, oracle):
 @pytest.mark.parametrize("kw", [dict(use_bias=False), dict(G=0), dict(L=0), dict(ifw=8), dict(S=64), dict(S=1024), dict(S=1024, groups=16), dict(S=128, groups=2), dict(groups=1),
                                 dict(up=(3, 4))])
 def test_generate_variants(torch_cuda, oracle, kw):
+    """one departure from the default shape at a time; the conditioning geometries (lc / gc widths, upsampling lists) have a table of their
+    own, tests/conditioning_cases.py, held on every generation kernel by tests/test_wavenet_conditioning_gpu.py"""
     dil = [1, 2, 4, 8, 16, 1, 2]
     d, blob, m, want, got, _ = _run_mol(oracle, torch_cuda, dil, 3, 6, T=70 if kw.get("L", 80) else 70, **kw)
     assert first_mismatch(got.cpu().numpy(), want) is None, kw
